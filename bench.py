@@ -6,7 +6,7 @@ whole predict_action computation: DINOv2+SigLIP towers → projector → splice 
 decode steps with on-device greedy argmax → 7 action-token ids per sequence. Nothing is skipped or cached between
 steps; weights are seeded-synthetic bf16 (no checkpoint exists offline).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...     (N > 1: one replica per GPU)
     python bench.py --mode train --stage vla-full-train|vla-train|lora [--gpus N]     (BASELINE configs[2] / [3])
 
@@ -19,8 +19,14 @@ timed region is bracketed by barrier + synchronize, the elapsed time is the MAX 
 by rank with the optimizer state partitioned (training/sharding.py: reduce-scatter of gradient buckets overlapped with
 the backward, all-gather of updated weights) — RCCL over xGMI.
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel = the tiled MFMA GEMM, measured live with HIP events on the
-launch stream) and `cpu_baseline` (the CPU oracle timed on this host's cores on a bounded, stated sample).
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, …) and nothing else. `--full` adds, after the timed region, `roofline` (dominant kernel = the tiled MFMA
+GEMM, measured live with HIP events on the launch stream), `end_to_end` (per-kernel figures, the one-batch engine and,
+on the default 1-GPU openvla-7b run, the training legs) and `cpu_baseline` (the CPU oracle timed on this host's cores on
+a bounded, stated sample).
+
+`--dump-outputs DIR` writes what the last timed step returned (rank 0) as DIR/<name>.npy; inputs and weights are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -84,10 +90,18 @@ def parse() -> argparse.Namespace:
                     help="--mode infer: after the inference measurement (engines freed) also time 3 steps each of BASELINE "
                          "configs[2]'s per-GPU shape (vla-full-train, B = 32) and configs[3] (LoRA r = 32, B = 16) and report them "
                          "under end_to_end.train_cfg2_n1 / train_cfg3_lora_n1 of the same JSON line; auto = the default 1-GPU "
-                         "openvla-7b run only")
+                         "openvla-7b --full run only")
     ap.add_argument("--pipeline", type=int, default=7, choices=[1, 2, 7, 8],
                     help="2 = overlap batch i's decode with batch i+1's vision+prefill (TwoStagePipeline); 7 = StaggeredDecodePipeline "
                          "(one merged decode iteration over the 6 older batches per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else the line reports: roofline and per-kernel figures "
+                         "(an instrumented eager pass), the one-batch engine, the training legs and the CPU baseline; "
+                         "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned on its last timed step as DIR/<name>.npy (float32 / float64, "
+                         "64 MB at most): rank 0's action ids and the logits that chose the first and last of them "
+                         "(--mode train: loss and gradient norm)")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 32 if (args.mode == "train" and args.stage != "lora") else 16
@@ -128,6 +142,27 @@ def make_inputs(B: int, L: int, seed: int, device):
     ids = torch.randint(3, 31743, (B, L), generator=g)
     ids[:, 0], ids[:, -1] = 1, 29871
     return ids.to(device), pv.to(device)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: DIR/<name>.npy for each {name: tensor}, as float32 (float64 stays float64; token ids < 2^24 are
+    exact). Over 64 MB in all, every array larger than its share keeps a fixed, seeded sample of its rows (sorted)."""
+    import numpy as np
+    arrays = {k: v.detach().cpu().double().numpy() if v.dtype == torch.float64 else v.detach().cpu().float().numpy()
+              for k, v in arrays.items()}
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        for k, a in arrays.items():
+            if a.nbytes > share and a.ndim >= 1:
+                keep = max(1, share // max(a.nbytes // a.shape[0], 1))
+                rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=min(keep, a.shape[0]), replace=False))
+                arrays[k] = a[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def per_kernel_profile(eng) -> dict:
@@ -330,11 +365,33 @@ def train_line(args, rank: int, world: int, dev) -> dict:
     replicas.fence(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = ts.step(lr, graph=graph)
+        loss, norm = ts.step(lr, graph=graph)
     replicas.fence(dev)
     elapsed = replicas.max_over_ranks(time.perf_counter() - t0, dev)
     losses.append(float(loss.item()))
+    if rank == 0 and args.dump_outputs:                  # what ts.step() returned on the last timed step
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "grad_norm": norm.reshape(1)})
     if rank == 0:
+        ms = elapsed / args.steps * 1e3
+        cfg_no = 4 if args.model == "prism-13b" else 3 if args.stage == "lora" else 2
+        line = {
+            "metric": f"samples/sec {dims.name} {args.stage} bf16", "value": round(world * B * args.steps / elapsed, 3), "unit": "samples/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+            "config": {"workload": (f"{dims.name} {args.stage} (BASELINE configs[{cfg_no}]): per-GPU batch {B} x S={ts.S} "
+                                    f"DummyDataset-shaped samples (32 prompt ids + 7 action ids + EOS, 224px frame), forward + "
+                                    f"backward + global-norm clip + AdamW" + (" on LoRA r=32 adapters" if lora is not None else "")
+                                    + (f"; optimizer state sharded over {world} ranks, {args.reduce} gradient reduce-scatter "
+                                       f"per bucket overlapped with backward, bf16 weight all-gather" if world > 1 else "")),
+                       "batch_per_gpu": B, "global_batch": B * world, "seq_len": ts.S, "stage": args.stage,
+                       "parallelism": (f"dp{world} sharded-optimizer ({'full-shard: parameters and gradients of all FSDP units sharded' if args.shard_params else 'shard-grad-op'})"
+                                       if world > 1 else "single GPU"),
+                       "hip_graph": graph, "recompute_activations": bool(args.recompute), "shard_params": bool(args.shard_params), "fp8_fwd_dgrad": bool(args.fp8),
+                       "fp8_wgrad": bool(getattr(args, "fp8_wgrad", False)),
+                       "fp8_wgrad_gemms": {"e4m3": ts.fp8_wgrad_gemms[0], "bf16_fallback": ts.fp8_wgrad_gemms[1]}},
+        }
+        if not args.full:
+            return line
         # per-phase and GEMM-family timing: one instrumented eager step outside the timed region (HIP events on the
         # launch stream); roofline = the tiled MFMA GEMM family (forward, dgrad, wgrad) per bl_gemm_bf16 call
         ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -366,29 +423,13 @@ def train_line(args, rank: int, world: int, dev) -> dict:
         gemm = {f: sum(a[f] for a in fam) for f in ("ms", "flops", "launches")}
         achieved = gemm["flops"] / (gemm["ms"] * 1e-3) / 1e12
         model_flops = sum(op.flops for op in plan)
-        ms = elapsed / args.steps * 1e3
         train_traffic = None          # HBM bytes per forward GEMM call from the committed PMC passes (same M as this run only)
         pmc = newest_pmc("gemm_traffic_train.json")
         pmc_src = None
         if pmc is not None and args.model == "openvla-7b" and ts.T == 9472 and not args.fp8:
             pj = json.loads(pmc.read_text())
             train_traffic, pmc_src = round(pj["avg_hbm_bytes_per_call_llama_layer"]), pmc_provenance(pmc, pj)
-        cfg_no = 4 if args.model == "prism-13b" else 3 if args.stage == "lora" else 2
-        line = {
-            "metric": f"samples/sec {dims.name} {args.stage} bf16", "value": round(world * B * args.steps / elapsed, 3), "unit": "samples/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": (f"{dims.name} {args.stage} (BASELINE configs[{cfg_no}]): per-GPU batch {B} x S={ts.S} "
-                                    f"DummyDataset-shaped samples (32 prompt ids + 7 action ids + EOS, 224px frame), forward + "
-                                    f"backward + global-norm clip + AdamW" + (" on LoRA r=32 adapters" if lora is not None else "")
-                                    + (f"; optimizer state sharded over {world} ranks, {args.reduce} gradient reduce-scatter "
-                                       f"per bucket overlapped with backward, bf16 weight all-gather" if world > 1 else "")),
-                       "batch_per_gpu": B, "global_batch": B * world, "seq_len": ts.S, "stage": args.stage,
-                       "parallelism": (f"dp{world} sharded-optimizer ({'full-shard: parameters and gradients of all FSDP units sharded' if args.shard_params else 'shard-grad-op'})"
-                                       if world > 1 else "single GPU"),
-                       "hip_graph": graph, "recompute_activations": bool(args.recompute), "shard_params": bool(args.shard_params), "fp8_fwd_dgrad": bool(args.fp8),
-                       "fp8_wgrad": bool(getattr(args, "fp8_wgrad", False)),
-                       "fp8_wgrad_gemms": {"e4m3": ts.fp8_wgrad_gemms[0], "bf16_fallback": ts.fp8_wgrad_gemms[1]}},
+        line.update({
             "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(achieved / BF16_MFMA_PEAK_TFLOPS, 4), "traffic": train_traffic,
                          "traffic_note": "avg HBM+Infinity-Cache bytes per forward bl_gemm_bf16 call over the 4 decoder-layer GEMM shapes at "
@@ -407,7 +448,7 @@ def train_line(args, rank: int, world: int, dev) -> dict:
                            "trainable_params_B": round(ts.store.n_params / 1e9, 3),
                            "hbm_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
                            "loss_first_last": [round(losses[0], 4), round(losses[-1], 4)]},
-        }
+        })
         return line
     return None
 
@@ -425,6 +466,7 @@ def train_legs(args, dev) -> dict:
         a.mode, a.stage, a.batch, a.steps, a.warmup = "train", stage, batch, 3, 1
         a.recompute = a.shard_params = a.fp8 = a.fp8_wgrad = False
         a.reduce = "fp32"
+        a.full, a.dump_outputs = True, None          # the leg's roofline / end_to_end are read below; the dump is the headline's
         gc.collect()
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats()
@@ -454,6 +496,8 @@ def main() -> None:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: launch one rank per GPU "
                          f"(python bench.py --gpus N starts them itself)")
     if args.dry_run:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dry-run computes nothing to dump (--dump-outputs)")
         return dry_run(args, rank, world)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
@@ -470,25 +514,41 @@ def main() -> None:
     ids, pv = make_inputs(args.batch, args.prompt_len, seed=rank, device=dev)
 
     def timed(replay, steps):
-        """EXACTLY `steps` steps bracketed by barrier + synchronize; elapsed = MAX over ranks."""
+        """EXACTLY `steps` steps bracketed by barrier + synchronize; elapsed = MAX over ranks. Also returns what the last
+        step returned."""
         replicas.fence(dev)
+        last = None
         t0 = time.perf_counter()
         for _ in range(steps):
-            replay()
+            last = replay()
         replicas.fence(dev)
-        return replicas.max_over_ranks(time.perf_counter() - t0, dev)
+        return replicas.max_over_ranks(time.perf_counter() - t0, dev), last
 
-    # ---- one batch in flight (the latency-oriented predict_action path) ----
-    eng = OpenVLAEngine(w, args.batch, args.prompt_len, fp8=args.fp8)
-    eng.set_inputs(ids, pv)                      # inputs resident in HBM before the timed region
-    if args.no_graph:
-        eng.run_eager()
-    else:
-        eng.capture()
-    for _ in range(args.warmup):
-        eng.replay()
-    elapsed_single = timed(eng.replay, args.steps)
-    elapsed = elapsed_single
+    def dump(done, last_logits, returned=None):
+        """--dump-outputs, right after the headline's timed region: the batch the last timed step completed — its 7 action
+        ids (what step() / generate() hand the caller) and the fp32 logits that chose the first and the last of them."""
+        if rank != 0 or not args.dump_outputs:
+            return
+        ids_done = done.gen_ids.t()
+        assert returned is None or returned.data_ptr() == ids_done.data_ptr(), "dump: not the batch the last step returned"
+        dump_outputs(args.dump_outputs, {"action_ids": ids_done, "logits_first": done.logits[0], "logits_last": last_logits})
+
+    # ---- one batch in flight (the latency-oriented predict_action path): the headline of --pipeline 1; --full times it
+    # beside the pipelines as `one_batch_in_flight` ----
+    eng = None
+    if args.pipeline == 1 or args.full:
+        eng = OpenVLAEngine(w, args.batch, args.prompt_len, fp8=args.fp8)
+        eng.set_inputs(ids, pv)                      # inputs resident in HBM before the timed region
+        if args.no_graph:
+            eng.run_eager()
+        else:
+            eng.capture()
+        for _ in range(args.warmup):
+            eng.replay()
+        elapsed_single, _ = timed(eng.replay, args.steps)
+        elapsed = elapsed_single
+        if args.pipeline == 1:
+            dump(eng, eng.logits[eng.n_new - 1])
     # ---- two batches in flight: batch i's decode overlaps batch i+1's vision + prefill (throughput serving) ----
     if args.pipeline == 2:
         from bridgelang_amd.pipeline import TwoStagePipeline
@@ -499,7 +559,9 @@ def main() -> None:
             pipe.capture()
         for _ in range(max(args.warmup, 2)):     # also fills the pipeline
             pipe.step()
-        elapsed = timed(pipe.step, args.steps)   # every step completes one batch (submitted one step earlier)
+        elapsed, ret = timed(pipe.step, args.steps)   # every step completes one batch (submitted one step earlier)
+        done = pipe.engines[pipe._tick & 1]
+        dump(done, done.logits[done.n_new - 1], ret)
     elif args.pipeline >= 7:
         from bridgelang_amd.pipeline import StaggeredDecodePipeline
         pipe = StaggeredDecodePipeline(w, args.batch, args.prompt_len, split_vision=args.pipeline == 8, fp8=args.fp8)
@@ -509,30 +571,21 @@ def main() -> None:
             pipe.capture()
         for _ in range(max(args.warmup, pipe.slots)):     # also fills the pipeline
             pipe.step()
-        elapsed = timed(pipe.step, args.steps)   # every step submits one batch and completes the one submitted 6 steps earlier
-        ids_pipe = pipe.step().clone().cpu()
-    ids_out = eng.gen_ids.t().cpu()
-    ids_cpu0, pv_cpu0 = ids[:1].cpu(), pv[:1].cpu()
-    if args.pipeline >= 7 and rank == 0:
-        pipe_agree = float((ids_pipe == ids_out).all(dim=1).float().mean())
+        elapsed, ret = timed(pipe.step, args.steps)   # every step submits one batch and completes the one submitted 6 steps earlier
+        # the completed batch's last decode iteration ran in the merged pass: its logits are rows (n_new-2)·B … (n_new-1)·B
+        dump(pipe.engines[pipe._tick % pipe.slots], pipe.logits[(pipe.n_new - 2) * pipe.B:(pipe.n_new - 1) * pipe.B], ret)
+        if args.full:
+            ids_pipe = pipe.step().clone().cpu()
+    if args.full:
+        ids_out = eng.gen_ids.t().cpu()
+        ids_cpu0, pv_cpu0 = ids[:1].cpu(), pv[:1].cpu()
+        if args.pipeline >= 7 and rank == 0:
+            pipe_agree = float((ids_pipe == ids_out).all(dim=1).float().mean())
 
     if rank == 0:
         seqs = world * args.batch * args.steps
         value = seqs / elapsed
-        prof = per_kernel_profile(eng)
-        gemm = prof["bl_gemm_fp8" if args.fp8 else "bl_gemm_bf16"]     # the dominant kernel of the mode measured
-        peak = FP8_MFMA_PEAK_TFLOPS if args.fp8 else BF16_MFMA_PEAK_TFLOPS
-        achieved = gemm["flops"] / (gemm["ms"] * 1e-3) / 1e12
-        skinny = prof.get("bl_gemm_skinny_bf16")
-        kern_ms = sum(a["ms"] for a in prof.values())
-        traffic = None      # HBM bytes per GEMM call from the committed PMC passes (bench.py cannot run rocprofv3 itself)
-        pmc = newest_pmc("gemm_traffic.json")
-        pmc_src = None
-        if pmc is not None and args.model == "openvla-7b" and args.batch == 16 and args.prompt_len == 32 and not args.fp8:
-            pj = json.loads(pmc.read_text())
-            traffic, pmc_src = round(pj["avg_hbm_bytes_per_call_llama_layer"]), pmc_provenance(pmc, pj)
-        # algorithmic work per sequence: the SURVEY figure for the BASELINE model, the plan's own GEMM + attention FLOPs otherwise
-        algo = ALGO_TFLOP_PER_SEQ if args.model == "openvla-7b" else sum(op.flops for op in eng.all_ops()) / args.batch / 1e12
+        S = (eng if eng is not None else pipe.engines[0]).S
         line = {
             "metric": f"action-seqs/sec (7-DoF, 224px) {dims.name} {'fp8' if args.fp8 else 'bf16'}", "value": round(value, 3), "unit": "action-seqs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -540,50 +593,66 @@ def main() -> None:
             "vs_baseline": None, "dtype": "fp8-e4m3 (W8A8 Llama prefill projections) + bf16" if args.fp8 else "bf16", "data": "synthetic",
             "config": {"workload": (f"{dims.name} bf16 inference (BASELINE configs[1]): batch {args.batch} synthetic 224px "
                                     f"frames + {args.prompt_len}-token prompts per GPU, predict_action = vision towers + "
-                                    f"projector + Llama prefill S={eng.S} + 6 cached decode steps, greedy"
+                                    f"projector + Llama prefill S={S} + 6 cached decode steps, greedy"
                                     + {1: "", 2: "; 2 batches in flight (batch i decode overlaps batch i+1 vision+prefill), one "
                                                  "batch completes per step",
                                        7: "; 7 batches in flight: per step one batch is submitted (vision+prefill) while decode "
                                           "iteration g of the batch submitted g steps earlier, g = 1..6, runs as ONE merged 96-row "
                                           "pass over the weights (bit-identical to per-batch decode); one batch completes per step"}.get(args.pipeline, "8 in flight")),
-                       "batch_per_gpu": args.batch, "prompt_len": args.prompt_len, "seq_len": eng.S,
+                       "batch_per_gpu": args.batch, "prompt_len": args.prompt_len, "seq_len": S,
                        "replicas": world, "hip_graph": not args.no_graph, "pipeline_depth": args.pipeline},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "traffic_note": "avg HBM+Infinity-Cache bytes per bl_gemm_bf16 call over the 4 Llama prefill GEMMs, separate --pmc passes: "
-                                         "read from a COMMITTED summary (bench.py cannot run rocprofv3 on itself), see traffic_source",
-                         "traffic_source": pmc_src,
-                         "kernel": ("gemm256s_fp8_kernel (per bl_gemm_fp8 call)" if args.fp8 else
-                                    "tiled MFMA GEMM family: gemm256s_kernel / gemm288s_kernel + gemm_tail_kernel (per bl_gemm_bf16 call)"), "launches_per_step": gemm["launches"],
-                         "avg_launch_us": round(gemm["ms"] * 1e3 / gemm["launches"], 2),
-                         "algorithmic_gflop_per_launch": round(gemm["flops"] / gemm["launches"] / 1e9, 3),
-                         "sustained_mfma_note": ("`peak` is the dense bf16 spec figure; a register-only stream of the same MFMA on "
-                                                 "N(0,1) operands sustains 1611 TFLOP/s on this pool (power cap; tools/micro/"
-                                                 "w4_ceiling.hip, DESIGN §3)" if not args.fp8 else None)},
-            "end_to_end": {"algorithmic_tflop_per_seq": round(algo, 3),
-                           "mfma_util_whole_step": round(value / world * algo / BF16_MFMA_PEAK_TFLOPS, 4),
-                           "kernel_ms_per_step_eager_events": round(kern_ms, 3),
-                           "per_kernel_ms": {k: round(v["ms"], 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])},
-                           "decode_weight_stream_GBs": (round(skinny["bytes"] / (skinny["ms"] * 1e-3) / 1e9, 1) if skinny else None),
-                           "decode_hbm_frac": (round(skinny["bytes"] / (skinny["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if skinny else None),
-                           "one_batch_in_flight": {"value": round(seqs / elapsed_single, 3),
-                                                   "ms_per_step": round(elapsed_single / args.steps * 1e3, 3)},
-                           "first_ids": ids_out[0].tolist()},
         }
-        if args.pipeline >= 7:   # same inputs in every slot: fraction of sequences whose 7 ids equal the one-batch engine's
-            line["end_to_end"]["staggered_ids_equal_one_batch_engine"] = round(pipe_agree, 4)
-            line["end_to_end"]["staggered_ids_note"] = ("the merged 96-row decode pass runs bl_gemm_skinny_rows_bf16 + bl_rmsnorm_skinny_bf16, "
-                                                       "which reproduce the per-batch weight-streaming kernels' fp32 summation order: ids "
-                                                       "and logits are bit-identical to the one-batch engine "
-                                                       "(tests/test_full_size_gpu.py::test_staggered_pipeline_full_size)")
-        legs = args.train_legs == "on" or (args.train_legs == "auto" and world == 1 and args.model == "openvla-7b"
+        prof = None
+        if args.full:          # everything below is measured after the headline, outside its timed region
+            prof = per_kernel_profile(eng)
+            gemm = prof["bl_gemm_fp8" if args.fp8 else "bl_gemm_bf16"]     # the dominant kernel of the mode measured
+            peak = FP8_MFMA_PEAK_TFLOPS if args.fp8 else BF16_MFMA_PEAK_TFLOPS
+            achieved = gemm["flops"] / (gemm["ms"] * 1e-3) / 1e12
+            skinny = prof.get("bl_gemm_skinny_bf16")
+            kern_ms = sum(a["ms"] for a in prof.values())
+            traffic = None      # HBM bytes per GEMM call from the committed PMC passes (bench.py cannot run rocprofv3 itself)
+            pmc = newest_pmc("gemm_traffic.json")
+            pmc_src = None
+            if pmc is not None and args.model == "openvla-7b" and args.batch == 16 and args.prompt_len == 32 and not args.fp8:
+                pj = json.loads(pmc.read_text())
+                traffic, pmc_src = round(pj["avg_hbm_bytes_per_call_llama_layer"]), pmc_provenance(pmc, pj)
+            # algorithmic work per sequence: the SURVEY figure for the BASELINE model, the plan's own GEMM + attention FLOPs otherwise
+            algo = ALGO_TFLOP_PER_SEQ if args.model == "openvla-7b" else sum(op.flops for op in eng.all_ops()) / args.batch / 1e12
+            line["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                                "frac": round(achieved / peak, 4), "traffic": traffic,
+                                "traffic_note": "avg HBM+Infinity-Cache bytes per bl_gemm_bf16 call over the 4 Llama prefill GEMMs, separate --pmc passes: "
+                                                "read from a COMMITTED summary (bench.py cannot run rocprofv3 on itself), see traffic_source",
+                                "traffic_source": pmc_src,
+                                "kernel": ("gemm256s_fp8_kernel (per bl_gemm_fp8 call)" if args.fp8 else
+                                           "tiled MFMA GEMM family: gemm256s_kernel / gemm288s_kernel + gemm_tail_kernel (per bl_gemm_bf16 call)"), "launches_per_step": gemm["launches"],
+                                "avg_launch_us": round(gemm["ms"] * 1e3 / gemm["launches"], 2),
+                                "algorithmic_gflop_per_launch": round(gemm["flops"] / gemm["launches"] / 1e9, 3),
+                                "sustained_mfma_note": ("`peak` is the dense bf16 spec figure; a register-only stream of the same MFMA on "
+                                                        "N(0,1) operands sustains 1611 TFLOP/s on this pool (power cap; tools/micro/"
+                                                        "w4_ceiling.hip, DESIGN §3)" if not args.fp8 else None)}
+            line["end_to_end"] = {"algorithmic_tflop_per_seq": round(algo, 3),
+                                  "mfma_util_whole_step": round(value / world * algo / BF16_MFMA_PEAK_TFLOPS, 4),
+                                  "kernel_ms_per_step_eager_events": round(kern_ms, 3),
+                                  "per_kernel_ms": {k: round(v["ms"], 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])},
+                                  "decode_weight_stream_GBs": (round(skinny["bytes"] / (skinny["ms"] * 1e-3) / 1e9, 1) if skinny else None),
+                                  "decode_hbm_frac": (round(skinny["bytes"] / (skinny["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if skinny else None),
+                                  "one_batch_in_flight": {"value": round(seqs / elapsed_single, 3),
+                                                          "ms_per_step": round(elapsed_single / args.steps * 1e3, 3)},
+                                  "first_ids": ids_out[0].tolist()}
+            if args.pipeline >= 7:   # same inputs in every slot: fraction of sequences whose 7 ids equal the one-batch engine's
+                line["end_to_end"]["staggered_ids_equal_one_batch_engine"] = round(pipe_agree, 4)
+                line["end_to_end"]["staggered_ids_note"] = ("the merged 96-row decode pass runs bl_gemm_skinny_rows_bf16 + bl_rmsnorm_skinny_bf16, "
+                                                           "which reproduce the per-batch weight-streaming kernels' fp32 summation order: ids "
+                                                           "and logits are bit-identical to the one-batch engine "
+                                                           "(tests/test_full_size_gpu.py::test_staggered_pipeline_full_size)")
+        legs = args.train_legs == "on" or (args.train_legs == "auto" and args.full and world == 1 and args.model == "openvla-7b"
                                            and not args.fp8 and args.pipeline == 7 and args.batch == 16)
         if legs and world == 1:          # training on the same clock: free the inference state first
             if args.pipeline != 1:
                 del pipe
             del eng, w, prof
-            line["end_to_end"].update(train_legs(args, dev))
-        if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks would wait at the barrier)
+            line.setdefault("end_to_end", {}).update(train_legs(args, dev))
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks would wait at the barrier)
             big_host = (os.cpu_count() or 1) >= 64 and os.sysconf("SC_AVPHYS_PAGES") * os.sysconf("SC_PAGE_SIZE") > (64 << 30)
             if big_host and args.model == "openvla-7b":
                 line["cpu_baseline"] = cpu_baseline_whole(dims, ids_cpu0, pv_cpu0, ids_out[0].tolist())

@@ -275,6 +275,29 @@ def test_bench_launcher_starts_one_rank_per_gpu(tmp_path):
     assert p.returncode != 0 and "WORLD_SIZE" in p.stderr
 
 
+def test_bench_dump_outputs_format_and_budget(tmp_path):
+    """bench.py --dump-outputs writes DIR/<name>.npy as float32 (float64 kept), ids exactly; over 64 MB in all, a large
+    array keeps a seeded row sample, the same one every time."""
+    import numpy as np
+    import torch
+    import bench
+    ids = torch.tensor([[31744, 31999, 3], [1, 2, 29871]], dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path / "a"), {"action_ids": ids, "loss": torch.tensor([0.5], dtype=torch.float64),
+                                             "logits": torch.randn(2, 5, dtype=torch.bfloat16)})
+    got = np.load(tmp_path / "a" / "action_ids.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, ids.numpy().astype(np.float32))
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64 and np.load(tmp_path / "a" / "logits.npy").dtype == np.float32
+    big = torch.arange(80 * (1 << 18), dtype=torch.float32).view(80, 1 << 18)          # 80 MB
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "ids": ids})
+    b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(b, c) and 0 < b.shape[0] < 80 and b.shape[1] == 1 << 18
+    rows = b[:, 0] / (1 << 18)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(b, big.numpy()[rows.astype(int)])
+    assert np.array_equal(np.load(tmp_path / "b" / "ids.npy"), ids.numpy().astype(np.float32))
+
+
 def test_registries_and_checkpoint_naming():
     """Reference ids resolve (models/materialize.py:29-73), unknown ids raise its ValueError; native ↔ HF key maps are
     inverse bijections over every tensor of the model (convert_openvla_weights_to_hf.py:73-115)."""
