@@ -718,9 +718,8 @@ static int attention_launch(const bl_attn_desc* d, float* lse, void* stream) {
   if (d->causal && d->Skv < d->Sq) return BL_E_SHAPE;
   a.lse = lse; a.lse_rs = (d->Sq + 31) / 32 * 32;
   hipStream_t s = (hipStream_t)stream;
-  static const bool chunked_only = getenv("BL_ATTN_CHUNKED") != nullptr;   // A/B aid
   // short sequences (the whole OpenVLA path): K and V of a head fit in LDS → whole-sequence kernel
-  if (d->Skv <= 320 && d->Sq <= 320 && !chunked_only) {
+  if (d->Skv <= 320 && d->Sq <= 320) {
     int r = BL_E_SHAPE;
 #define BL_SEQ_CASE(HD) case HD: r = d->causal ? launch_seq<HD, true>(a, d, s) : launch_seq<HD, false>(a, d, s); break;
     switch (d->head_dim) { BL_SEQ_CASE(64) BL_SEQ_CASE(72) BL_SEQ_CASE(128) default: return BL_E_SHAPE; }

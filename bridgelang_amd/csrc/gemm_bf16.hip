@@ -14,16 +14,13 @@
 //   * 1-D grid remapped so that each XCD (private L2) receives a contiguous run of tiles, walked in groups of
 //     GROUP_M row-tiles so concurrently resident tiles share weight panels.
 //
-// Two kernels:
-//   gemm128_kernel — 128×128×64 tile, 4 waves (64×64 each), 2 workgroups/CU, one vmcnt(0)+barrier per K-step. Small or
-//                    skinny problems, and the ragged tail of big ones.
-//   gemm256_kernel — 256×256×64 tile, 8 waves (128(m)×64(n) each), 128 KiB LDS = 2 stages, 1 workgroup/CU. Each K-tile
-//                    is staged as four 16-KiB HALF-TILES (X0/X1 = the two 64-row halves of every wave's activation
-//                    rows, Y0/Y1 = the two 32-row halves of every wave's weight rows) and consumed in four PHASES of 16
-//                    MFMAs (output quadrants (0,0) (0,1) (1,1) (1,0)). Per phase: issue one half-tile of LDS-DMA for a
-//                    later K-tile, prefetch the NEXT phase's fragments LDS→VGPR, run this phase's MFMAs, counted
-//                    `s_waitcnt vmcnt(4)` (two half-tiles stay in flight across the barrier — never 0 in the loop),
-//                    ONE raw s_barrier. Every half-tile is issued ≥ 3 phases before its first read.
+// Kernels (launch_gemm picks one per shape):
+//   gemm256s_kernel   — 256×256×64 tile, 8 waves in two staggered groups, 1 workgroup/CU; whole rounds of big problems.
+//   gemm288s_kernel   — the same on 288-row tiles (one 288-token sequence per row tile) where they remove a leftover round.
+//   gemm_ring8_kernel — 4-stage LDS-DMA ring, 8 waves: the sub-tiles of a leftover round, one round of 160×128 tiles for
+//                       narrow layers, K-sliced few-tile problems.
+//   gemm128_kernel    — 128×128×64 tile, 4 waves, 2 workgroups/CU: the remaining small problems.
+//   gemm_mid_kernel / gemm_mid2_kernel — weight streaming for M ≤ 640 rows.
 #include "gemm_common.h"
 #include <stdlib.h>
 
@@ -44,7 +41,7 @@ __device__ __forceinline__ void lin_to_tile(const GemmArgs& p, int lin, int& tm,
 
 __device__ __forceinline__ void tile_coords(const GemmArgs& p, int& tm, int& tn) {
   // XCD-contiguous ordering over the LAUNCHED blocks (speed only; any bijective mapping is correct). The grid may
-  // cover only the first gridDim.x tiles of the tiles_m x tiles_n grid (whole rounds; the tail goes to gemm128).
+  // cover only the first gridDim.x tiles of the tiles_m x tiles_n grid (whole rounds; a leftover round goes to gemm_ring8_kernel).
   const int nwg = gridDim.x;
   const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
   const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
@@ -77,15 +74,9 @@ __global__ __launch_bounds__(256) void gemm128_kernel(GemmArgs p) {
   constexpr int A_BYTES = BM * ROW_BYTES, BUF_BYTES = A_BYTES + BN * ROW_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 × BUF_BYTES
 
-  int tm, tn, m0, n0;
-  if (p.tail_base >= 0) {   // tail mode: 4 small tiles per leftover 256x256 tile of the big kernel's grid
-    lin_to_tile(p, p.tail_base + (blockIdx.x >> 2), tm, tn);
-    m0 = tm * 256 + ((blockIdx.x >> 1) & 1) * 128;
-    n0 = tn * 256 + (blockIdx.x & 1) * 128;
-  } else {
-    tile_coords(p, tm, tn);
-    m0 = tm * BM, n0 = tn * BN;
-  }
+  int tm, tn;
+  tile_coords(p, tm, tn);
+  const int m0 = tm * BM, n0 = tn * BN;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
@@ -125,17 +116,10 @@ __global__ __launch_bounds__(256) void gemm128_kernel(GemmArgs p) {
 #pragma unroll
     for (int j = 0; j < MT; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-  // few-tile problems (tall-skinny: LoRA rank projections, small ViT shapes): grid.y slices K; every slice writes an fp32
-  // partial [M, N] to the slab, gemm128_splitk_reduce_kernel sums them in slice order and applies the epilogue
-  const int nk_all = p.K / BK;
-  int kt0 = 0, nk = nk_all;
-  if (p.splitk > 1 && p.tail_base < 0) {
-    kt0 = (int)(((long)blockIdx.y * nk_all) / p.splitk);
-    nk = (int)(((long)(blockIdx.y + 1) * nk_all) / p.splitk);
-  }
-  BL_STAGE(kt0 & 1, kt0);
+  const int nk = p.K / BK;
+  BL_STAGE(0, 0);
   __syncthreads();
-  for (int kt = kt0; kt < nk; ++kt) {
+  for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
     if (kt + 1 < nk) BL_STAGE(cur ^ 1, kt + 1);
     const char* base = smem + cur * BUF_BYTES;
@@ -156,17 +140,6 @@ __global__ __launch_bounds__(256) void gemm128_kernel(GemmArgs p) {
     __syncthreads();
   }
 #undef BL_STAGE
-  if (p.splitk > 1 && p.tail_base < 0) {
-    float* slab = p.slab + (long)blockIdx.y * p.M * p.N;
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-#pragma unroll
-      for (int j = 0; j < MT; ++j) {
-        const int m = m0 + wm * TM + j * 16 + l15, n = n0 + wn * TN + i * 16 + lg * 4;
-        if (m < p.M && n < p.N) *(f32x4_t*)(slab + (long)m * p.N + n) = acc[i][j];
-      }
-    return;
-  }
 #pragma unroll
   for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -176,139 +149,18 @@ __global__ __launch_bounds__(256) void gemm128_kernel(GemmArgs p) {
 }
 
 // ======================================================================================================================
-// tail kernel: BM × BN sub-tiles (128×128, 128×64 or 64×64) of the big kernel's leftover 256×256 tiles, 4 waves (2 × 2),
-// NST-stage LDS-DMA ring with NST-1 K-tiles in flight behind a counted vmcnt and ONE barrier per K-step. The leftover
-// round has at most one workgroup per CU, so nothing else hides the HBM/L2 latency — the two-stage gemm128 loop spent
-// ≈ 3/4 of every K-step waiting there. K order per output = the big kernel's (bit-identical results).
-// Stand-alone mode (p.tail_base < 0): the same loop as the main kernel of problems whose 160 × 128 tiles fit ONE round of
-// 256 CUs — the narrow ViT layers at 16 images (attn.proj / mlp.fc2 / patch embed: M = 4176 or 4096, N = 1024 or 1152:
-// 216 / 234 tiles; 160 divides the ragged M with 1.5–3.4 % waste where 128-row tiles need 264 / 288 > 256 workgroups) —
-// where gemm128's one-stage prefetch left a lone workgroup per CU waiting on every K-step (fc2: 65 µs → see DESIGN).
-// ======================================================================================================================
-template <int EPI, int BM, int BN, int NST, int WM = 2>
-__global__ __launch_bounds__(WM * 128) void gemm_tail_kernel(GemmArgs p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int NWAVE = WM * 2, TM = BM / WM, TN = BN / 2, MT = TM / 16, NT = TN / 16;
-  constexpr int APW = BM / 8 / NWAVE, WPW = BN / 8 / NWAVE, LPS = APW + WPW;   // LDS-DMA pieces per wave and stage
-  constexpr int A_BYTES = BM * ROW_BYTES, BUF_BYTES = A_BYTES + BN * ROW_BYTES;
-  constexpr int SUB_N = 256 / BN, SUBS = (256 / BM) * SUB_N;
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // NST × BUF_BYTES
-
-  // workgroups go to XCDs round-robin: give each XCD (private L2) a contiguous run of sub-tiles, i.e. WHOLE leftover tiles —
-  // with the plain order the SUBS pieces of a tile land on SUBS different L2s and every one of them fetches the same rows
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, q = nwg >> 3, r = nwg & 7;
-  const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-  int m0, n0;
-  if (p.tail_base >= 0) {
-    int tm, tn;
-    lin_to_tile(p, p.tail_base + lin / SUBS, tm, tn);
-    const int sub = lin % SUBS;
-    m0 = tm * 256 + (sub / SUB_N) * BM, n0 = tn * 256 + (sub % SUB_N) * BN;
-  } else {
-    // stand-alone mode: the whole problem as BM × BN tiles (p.tiles_n of them per row panel), one tile per workgroup and —
-    // the launcher's condition — at most one workgroup per CU. Column tiles of a row panel are neighbours in `lin`, so an
-    // XCD's contiguous run re-uses its activation panels from L2.
-    m0 = (lin / p.tiles_n) * BM, n0 = (lin % p.tiles_n) * BN;
-  }
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int kt32 = p.K >> 5;
-
-  const unsigned a_bytes = (unsigned)min((long)p.M * p.lda * 2, 0xffffffffL);
-  const unsigned w_bytes = (unsigned)min((long)p.N * p.K * 2, 0xffffffffL);
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, w_bytes, 0x00020000);
-
-  const int prow = lane >> 3, pchunk = (lane & 7) ^ prow;
-  static_assert(APW >= 1 && WPW >= 1, "tile too small for the wave count");
-  unsigned voffA[APW], voffW[WPW];
-#pragma unroll
-  for (int j = 0; j < APW; ++j) voffA[j] = (unsigned)(((long)(m0 + (j * NWAVE + wave) * 8 + prow) * p.lda) * 2 + pchunk * 16);
-#pragma unroll
-  for (int j = 0; j < WPW; ++j) {   // weight block b = j*NWAVE + wave: n-tile b >> 1, k-step b & 1
-    const int blk = j * NWAVE + wave;
-    voffW[j] = (unsigned)(((long)(n0 / 16 + (blk >> 1)) * kt32 + (blk & 1)) * 1024 + lane * 16);
-  }
-
-#define BL_STAGE(BUF, KT)                                                                                   \
-  do {                                                                                                      \
-    char* base__ = smem + (BUF) * BUF_BYTES;                                                                \
-    _Pragma("unroll") for (int j = 0; j < APW; ++j) BL_GLDS(rsA, base__ + (j * NWAVE + wave) * 1024, voffA[j], (KT) * 128); \
-    _Pragma("unroll") for (int j = 0; j < WPW; ++j)                                                         \
-        BL_GLDS(rsW, base__ + A_BYTES + (j * NWAVE + wave) * 1024, voffW[j], (KT) * 2048);                  \
-  } while (0)
-
-  const int l15 = lane & 15, lg = lane >> 4;
-  const int c0 = lg ^ (lane & 7);
-  const int offA = (wm * TM + l15) * ROW_BYTES;
-  const int offW = A_BYTES + (wn * NT) * 2048 + lane * 16;   // block (wn*NT + i)*2 + ks
-
-  f32x4_t acc[NT][MT];
-#pragma unroll
-  for (int i = 0; i < NT; ++i)
-#pragma unroll
-    for (int j = 0; j < MT; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-  // Branch-free ring: every iteration issues one stage — past the end of K it re-fetches the last K-tile into a slot nobody
-  // reads again — so exactly NST-1 stages are in flight at every wait and the loop body has no control flow (with branches
-  // between the MFMAs the compiler parks the accumulators in VGPRs and copies them to AGPRs around every MFMA).
-  const int nk = p.K / BK;
-#pragma unroll
-  for (int s2 = 0; s2 < NST - 1; ++s2) BL_STAGE(s2, min(s2, nk - 1));
-  static_assert((NST - 2) * LPS <= 63, "counted vmcnt range");
-  for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * LPS) : "memory");   // K-tile kt landed (this wave's pieces)
-    __builtin_amdgcn_s_barrier();      // K-tile kt landed for every wave; every wave is done reading K-tile kt-1
-    const char* base = smem + (kt % NST) * BUF_BYTES;
-    // one wave per SIMD: nothing else covers this wave's issue slots — the next ring slot's LDS-DMA pieces are issued in
-    // the shadow of the MFMAs (sched_group_barrier order below)
-    char* nbase = smem + ((kt + NST - 1) % NST) * BUF_BYTES;     // the slot of K-tile kt-1
-    const int nkt = min(kt + NST - 1, nk - 1);
-#pragma unroll
-    for (int pc = 0; pc < APW; ++pc) BL_GLDS(rsA, nbase + (pc * NWAVE + wave) * 1024, voffA[pc], nkt * 128);
-#pragma unroll
-    for (int jw = 0; jw < WPW; ++jw) BL_GLDS(rsW, nbase + A_BYTES + (jw * NWAVE + wave) * 1024, voffW[jw], nkt * 2048);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int cb = (c0 ^ (ks * 4)) << 4;
-      bf16x8_t wf[NT], af[MT];
-#pragma unroll
-      for (int i = 0; i < NT; ++i) wf[i] = *(const bf16x8_t*)(base + offW + i * 2048 + ks * 1024);
-#pragma unroll
-      for (int j = 0; j < MT; ++j) af[j] = *(const bf16x8_t*)(base + offA + j * 16 * ROW_BYTES + cb);
-#pragma unroll
-      for (int i = 0; i < NT; ++i)
-#pragma unroll
-        for (int j = 0; j < MT; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[j], acc[i][j], 0, 0, 0);
-    }
-    constexpr int NMF = 2 * NT * MT, EVERY = NMF / LPS;          // one piece every EVERY MFMAs
-    static_assert(EVERY >= 1, "more DMA pieces than MFMAs");
-    __builtin_amdgcn_sched_group_barrier(0x100, 2 * (NT + MT), 0);   // all DS reads first
-#pragma unroll
-    for (int pc = 0; pc < LPS; ++pc) {
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);             // VMEM read (one LDS-DMA piece)
-      __builtin_amdgcn_sched_group_barrier(0x008, EVERY, 0);         // MFMA
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, NMF - EVERY * LPS, 0);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the surplus stages must not outlive the workgroup's LDS allocation
-#undef BL_STAGE
-#pragma unroll
-  for (int i = 0; i < NT; ++i)
-#pragma unroll
-    for (int j = 0; j < MT; ++j)
-      epilogue_store4<EPI>(p, m0 + wm * TM + j * 16 + l15, n0 + wn * TN + i * 16 + lg * 4, acc[i][j]);
-#endif
-}
-
-// ======================================================================================================================
-// ring kernel with TWO waves per SIMD (round 4): the tail kernel's stand-alone mode (one round of BM × BN = 160 × 128 tiles,
-// NST-stage LDS-DMA ring, counted vmcnt, one barrier per K-step) run by 8 waves — 2 along m × 4 along n, 80 × 32 outputs
-// each. With one wave per SIMD the wave that issues a ring slot's LDS-DMA pieces (≈ 60 issue cycles per 1-KiB piece) is the
-// only one that could issue MFMAs there, so a K-step took pieces + fragment reads + MFMAs back to back (ISA: 9 pieces, 18
-// ds_read_b128, lgkmcnt(0), 40 MFMAs: ≈ 0.82 µs for 640 cycles of matrix work). Here every wave carries half the MFMAs and
+// ring kernel: BM × BN tiles, NST-stage LDS-DMA ring behind a counted vmcnt, ONE barrier per K-step, 8 waves (two per SIMD)
+// — 2 along m × 4 along n. Three uses, all with at most one workgroup per CU, where nothing else hides the HBM/L2 latency
+// (a two-stage loop spent ≈ 3/4 of every K-step waiting there):
+//   * tail mode (p.tail_base >= 0): 128×128, 128×64 or 64×64 sub-tiles of the big kernel's leftover 256×256 tiles;
+//   * one round of 160 × 128 tiles for the narrow ViT layers at 16 images (attn.proj / mlp.fc2 / patch embed: M = 4176 or
+//     4096, N = 1024 or 1152: 216 / 234 tiles; 160 divides the ragged M with 1.5–3.4 % waste where 128-row tiles need
+//     264 / 288 > 256 workgroups);
+//   * K-sliced (grid.y > 1): few-tile, long-K problems, partial sums to the slab.
+// Two waves per SIMD (round 4, replacing a one-wave-per-SIMD form): with one wave per SIMD the wave that issues
+// a ring slot's LDS-DMA pieces (≈ 60 issue cycles per 1-KiB piece) is the only one that could issue MFMAs there, so a
+// K-step took pieces + fragment reads + MFMAs back to back (ISA: 9 pieces, 18 ds_read_b128, lgkmcnt(0), 40 MFMAs: ≈ 0.82 µs
+// for 640 cycles of matrix work). Here every wave carries half the MFMAs and
 // half the pieces of its SIMD, the pieces are spread through the wave's MFMAs (sched_barrier-pinned groups), and the
 // partner wave's MFMAs issue while this wave sits in a piece's issue. The 20 activation pieces do not divide by 8 waves:
 // waves 4–7 issue a third, out-of-range piece (zero-fill, no memory request) into a dump KiB behind the ring, which keeps
@@ -324,10 +176,14 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
   constexpr int A_BYTES = BM * ROW_BYTES, BUF_BYTES = A_BYTES + BN * ROW_BYTES, DUMP = NST * BUF_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // NST × BUF_BYTES + 1 KiB dump
 
+  // workgroups go to XCDs round-robin: give each XCD (private L2) a contiguous run of tiles. In tail mode that is a run of
+  // WHOLE leftover tiles — with the plain order the SUBS pieces of a tile land on SUBS different L2s and every one of them
+  // fetches the same rows; otherwise the column tiles of a row panel are neighbours in `lin`, so an XCD's run re-uses its
+  // activation panels from L2.
   const int nwg = gridDim.x, xcd = blockIdx.x & 7, q = nwg >> 3, r = nwg & 7;
   const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
   int m0, n0;
-  if (p.tail_base >= 0) {   // tail mode (as gemm_tail_kernel): SUBS sub-tiles per leftover 256 × 256 tile of the big kernel's grid
+  if (p.tail_base >= 0) {   // tail mode: SUBS sub-tiles per leftover 256 × 256 tile, row-major within the tile
     constexpr int SUB_N = 256 / BN, SUBS = (256 / BM) * SUB_N;
     int tm, tn;
     lin_to_tile(p, p.tail_base + lin / SUBS, tm, tn);
@@ -467,7 +323,7 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
 #endif
 }
 
-// out(m, n..n+3) = epilogue(Σ_slices slab[slice][m][n..n+3]) for the split-K form of the 128 kernel
+// out(m, n..n+3) = epilogue(Σ_slices slab[slice][m][n..n+3]): the K-sliced forms of gemm_ring8_kernel and gemm_mid_kernel
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm128_splitk_reduce_kernel(GemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -959,156 +815,11 @@ __global__ __launch_bounds__(256) void gemm_mid2_kernel(GemmArgs p) {
 // = one round + a 32-tile tail on sub-tiles at a third of the efficiency (+ 45 % time for 12.5 % of the work), qkv gets
 // 864 = 3.375 rounds (a quarter-filled fourth round). With 288 rows per tile the same GEMMs are exactly 256 tiles
 // (o / down) and 768 = 3 rounds (qkv): no tail, no partial round.
-// 8 waves as 2 (m) × 4 (n): a wave owns 144 rows × 64 columns = 9 × 4 accumulator tiles (144 VGPRs); per K-tile six
-// phases (row third t ∈ 0..2 × column half h ∈ 0..1, 12 MFMAs each, order (0,0) (0,1) (1,1) (1,0) (2,0) (2,1)) on two
-// fragment register sets per operand, so a phase's MFMAs run over the next phase's ds_reads. LDS: 2 stages × 72 KiB
-// (288 rows × 128 B + 4 KiB landing area for the dummy pieces + 32 KiB weights). A wave issues 9 LDS-DMA pieces per
-// K-tile (5 activation — 36 real ones over 8 waves, the 4 surplus ones hit a zero-record descriptor: no traffic — and
-// 4 weight) for K-tile t+1 during phases 6 (of t-1), 1, 2, 3 (of t); ONE `vmcnt(0)` + barrier per K-tile, at the end of
-// phase 5, two phases after the last issue: it publishes K-tile t+1 (first read in phase 6) and retires every read of
-// K-tile t-1's stage before phase 6 re-fills it. No other barrier: the two waves of a SIMD drift apart inside a
-// K-tile and overlap one's LDS reads / DMA issue with the other's MFMAs.
-// K order per output = every other kernel's (K-tile by K-tile, two 32-steps each): bit-identical results.
-// ======================================================================================================================
-template <int EPI>
-__global__ __launch_bounds__(512) void gemm288_kernel(GemmArgs p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int BM = 288, BN = 256;
-  constexpr int A_BYTES = BM * ROW_BYTES, DUMMY = A_BYTES, W_OFF = A_BYTES + 4096, STAGE = W_OFF + 32768;
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 × STAGE
-  int tm, tn;
-  tile_coords(p, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  const int l15 = lane & 15, lg = lane >> 4;
-  const int kt32 = p.K >> 5, nk = p.K / BK;
-
-  const unsigned a_bytes = (unsigned)min((long)p.M * p.lda * 2, 0xffffffffL);
-  const unsigned w_bytes = (unsigned)min((long)p.N * p.K * 2, 0xffffffffL);
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, w_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsA0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsW0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0, 0x00020000);
-
-  // activation pieces (8 rows × 128 B): wave takes pieces wave, wave + 8, …, wave + 32; pieces ≥ 36 do not exist
-  const int prow = lane >> 3, pchunk = (lane & 7) ^ prow;
-  unsigned voffA[5];
-  int ldsA[5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const int pi = wave + 8 * j;
-    voffA[j] = (unsigned)(((long)(m0 + pi * 8 + prow) * p.lda) * 2 + pchunk * 16);
-    ldsA[j] = pi < 36 ? pi * 1024 : DUMMY + (pi - 36) * 1024;
-  }
-  const bool a4_real = wave < 4;                       // piece wave + 32 exists only for waves 0..3
-  // weight pieces: n-tiles 2·wave and 2·wave + 1, both k-steps (2 KiB contiguous per n-tile and K-tile)
-  unsigned voffW[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) voffW[q] = (unsigned)((long)(n0 / 16 + 2 * wave + q) * kt32 * 1024 + lane * 16);
-  const int ldsW = W_OFF + 2 * wave * 2048;
-
-#define ISSUE_A(J, TILE)                                                                                  \
-  do {                                                                                                    \
-    const int t__ = (TILE);                                                                               \
-    /* no branch here: control flow inside the K loop makes hipcc shuttle the accumulators between VGPRs and AGPRs   \
-       around every MFMA (measured 1.8x slower); the surplus fifth piece of waves 4..7 goes to a zero-record descriptor */ \
-    const __amdgpu_buffer_rsrc_t rs__ = (t__ < nk && ((J) < 4 || a4_real)) ? rsA : rsA0;                  \
-    BL_GLDS(rs__, smem + (t__ & 1) * STAGE + ldsA[J], voffA[J], t__ * 128);                               \
-  } while (0)
-#define ISSUE_W(Q, KS, TILE)                                                                              \
-  do {                                                                                                    \
-    const int t__ = (TILE);                                                                               \
-    const __amdgpu_buffer_rsrc_t rs__ = t__ < nk ? rsW : rsW0;                                            \
-    BL_GLDS(rs__, smem + (t__ & 1) * STAGE + ldsW + (Q) * 2048 + (KS) * 1024, voffW[Q] + (KS) * 1024, t__ * 2048); \
-  } while (0)
-
-  const int cb0 = (lg ^ (lane & 7)) << 4;                       // swizzled chunk of k-step 0; k-step 1 = cb0 ^ 64
-  const int offX = (wm * 144 + l15) * ROW_BYTES;                // + (3·t + i)·2048
-  const int offY = W_OFF + wn * 8192 + lane * 16;               // + (2·h + j)·2048 + ks·1024
-#define READ_X(DST, T3, SB)                                                                               \
-  _Pragma("unroll") for (int i = 0; i < 3; ++i) {                                                         \
-    DST[i * 2] = *(const bf16x8_t*)((SB) + offX + (3 * (T3) + i) * 2048 + cb0);                           \
-    DST[i * 2 + 1] = *(const bf16x8_t*)((SB) + offX + (3 * (T3) + i) * 2048 + (cb0 ^ 64));                \
-  }
-#define READ_Y(DST, NH, SB)                                                                               \
-  _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                         \
-    DST[j * 2] = *(const bf16x8_t*)((SB) + offY + (2 * (NH) + j) * 2048);                                 \
-    DST[j * 2 + 1] = *(const bf16x8_t*)((SB) + offY + (2 * (NH) + j) * 2048 + 1024);                      \
-  }
-#define MMA(XR, YR, T3, NH)                                                                               \
-  do {                                                                                                    \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                      \
-      _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                       \
-        _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                     \
-          acc[2 * (NH) + j][3 * (T3) + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                      \
-              YR[j * 2 + ks], XR[i * 2 + ks], acc[2 * (NH) + j][3 * (T3) + i], 0, 0, 0);                  \
-  } while (0)
-#define PHASE_SYNC()                                                                                      \
-  do {                                                                                                    \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                           \
-    __builtin_amdgcn_s_barrier();                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-  } while (0)
-  // one K-tile: XC holds row third 0 and YC column half 0 of stage SC (K-tile T) on entry; YO takes half 1 and both stay
-  // for the whole K-tile, the thirds alternate between XC and XO; phase 6 loads third 0 / half 0 of K-tile T+1 (stage SN)
-  // into XO / YC, so the next K-tile runs with the X sets swapped
-  // (measured and rejected on this loop: s_setprio(1) around the MFMAs −8 %; sched_group_barrier placement of reads / pieces
-  // −5 % and 8 spilled registers; a wave-uniform branch around the surplus piece −77 % — control flow inside the K loop makes
-  // hipcc shuttle the accumulators through AGPRs around every MFMA. The compiler's own interleave below is the fastest.)
-#define KTILE(XC, XO, YC, YO, SC, SN, T)                                                                  \
-  do {                                                                                                    \
-    ISSUE_A(2, (T) + 1); ISSUE_A(3, (T) + 1); READ_Y(YO, 1, SC);                 MMA(XC, YC, 0, 0);       \
-    ISSUE_A(4, (T) + 1); ISSUE_W(0, 0, (T) + 1); READ_X(XO, 1, SC);              MMA(XC, YO, 0, 1);       \
-    ISSUE_W(0, 1, (T) + 1); ISSUE_W(1, 0, (T) + 1); ISSUE_W(1, 1, (T) + 1);      MMA(XO, YO, 1, 1);       \
-    READ_X(XC, 2, SC);                                                           MMA(XO, YC, 1, 0);       \
-                                                                                 MMA(XC, YC, 2, 0);       \
-    PHASE_SYNC();                                                                                         \
-    ISSUE_A(0, (T) + 2); ISSUE_A(1, (T) + 2); READ_X(XO, 0, SN); READ_Y(YC, 0, SN); MMA(XC, YO, 2, 1);    \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-  } while (0)
-
-  f32x4_t acc[4][9];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 9; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  bf16x8_t Xa[6], Xb[6], Ya[4], Yb[4];
-  char* const S0 = smem;
-  char* const S1 = smem + STAGE;
-
-  // prologue: all of K-tile 0, then the first two activation pieces of K-tile 1 (what phase 6 of the previous tile issues)
-  ISSUE_A(0, 0); ISSUE_A(1, 0); ISSUE_A(2, 0); ISSUE_A(3, 0); ISSUE_A(4, 0);
-  ISSUE_W(0, 0, 0); ISSUE_W(0, 1, 0); ISSUE_W(1, 0, 0); ISSUE_W(1, 1, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  ISSUE_A(0, 1); ISSUE_A(1, 1);
-  READ_X(Xa, 0, S0);
-  READ_Y(Ya, 0, S0);
-  for (int t = 0; t < nk; t += 2) {        // nk is even (launcher: K % 128 == 0)
-    KTILE(Xa, Xb, Ya, Yb, S0, S1, t);
-    KTILE(Xb, Xa, Ya, Yb, S1, S0, t + 1);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the out-of-range issues past the last K-tile
-#undef ISSUE_A
-#undef ISSUE_W
-#undef READ_X
-#undef READ_Y
-#undef MMA
-#undef PHASE_SYNC
-#undef KTILE
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 9; ++j)
-      epilogue_store4<EPI>(p, m0 + wm * 144 + j * 16 + l15, n0 + wn * 64 + i * 16 + lg * 4, acc[i][j]);
-#endif
-}
-
-// ======================================================================================================================
-// 288 × 256 tile, staggered wave groups (the structure of gemm256s_kernel on the 288-row tile): the two 4-wave groups that
+// 8 waves as 2 (m) × 4 (n): a wave owns 144 rows × 64 columns = 9 × 4 accumulator tiles (144 VGPRs). LDS: 2 stages × 72 KiB
+// (288 rows × 128 B + 4 KiB landing area for the surplus pieces + 32 KiB weights). A wave issues 9 LDS-DMA pieces per
+// K-tile: 5 activation — 36 real ones over 8 waves, the 4 surplus ones hit a zero-size descriptor: no traffic — and 4
+// weight. K order per output = every other kernel's (K-tile by K-tile, two 32-steps each): bit-identical results.
+// Staggered wave groups (the structure of gemm256s_kernel on the 288-row tile): the two 4-wave groups that
 // share each SIMD alternate roles segment by segment — one runs a 12-MFMA block while the other issues its LDS-DMA pieces
 // and reads the fragments of its next block — with one raw s_barrier per segment. A single X register set suffices (a
 // group's fragment reads happen while its MFMAs are not running): 9 × 4 accumulator tiles (144 VGPRs) + 6 + 4 + 4 fragments.
@@ -1279,168 +990,10 @@ __global__ __launch_bounds__(512) void gemm288s_kernel(GemmArgs p) {
 }
 
 // ======================================================================================================================
-// 256 × 256 tile, half-tile LDS-DMA ring, 4 phases per K-tile
-// ======================================================================================================================
-template <int EPI>
-__global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int BM = 256, BN = 256;
-  constexpr int STAGE = 65536, W_OFF = 32768;
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 stages × (32 KiB activations + 32 KiB weights)
-
-  int tm, tn;
-  const int nk_all = p.K / BK;
-  int kt_begin = 0, nk = nk_all;        // this workgroup's K-tile range [kt_begin, nk)
-  if (p.splitk > 1) {                   // split-K tail: blockIdx = leftover tile * splitk + slice; even slice starts
-    lin_to_tile(p, p.tail_base + blockIdx.x / p.splitk, tm, tn);
-    const int slice = blockIdx.x % p.splitk;
-    kt_begin = (int)(((long)slice * nk_all) / p.splitk) & ~1;
-    nk = slice + 1 == p.splitk ? nk_all : ((int)(((long)(slice + 1) * nk_all) / p.splitk) & ~1);
-  } else {
-    tile_coords(p, tm, tn);
-  }
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  const int l15 = lane & 15, lg = lane >> 4;
-  const int kt32 = p.K >> 5;
-
-  const unsigned a_bytes = (unsigned)min((long)p.M * p.lda * 2, 0xffffffffL);
-  const unsigned w_bytes = (unsigned)min((long)p.N * p.K * 2, 0xffffffffL);
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, w_bytes, 0x00020000);
-  // zero-record descriptors: every access is out of range → LDS gets zeros, no memory traffic (K-tiles past the end)
-  const __amdgpu_buffer_rsrc_t rsA0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsW0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0, 0x00020000);
-
-  // ---- LDS-DMA source offsets. Half-tile X<mh>: rows {wm'*128 + mh*64 + 0..63}, wm' = 0,1 → 16 pieces of 8 rows;
-  //      this wave takes pieces 2*wave, 2*wave+1. Half-tile Y<nh>: for wn' = 0..3 the weight n-tiles wn'*4 + 2*nh + {0,1},
-  //      both k-steps → 16 KiB; this wave takes (wn' = wave>>1, n-tile 2*nh + (wave&1)), k-steps 0 and 1. ----
-  const int prow = lane >> 3, pchunk = (lane & 7) ^ prow;
-  unsigned voffX[2][2], voffY[2][2];
-  int ldsX[2][2], ldsY[2];
-#pragma unroll
-  for (int mh = 0; mh < 2; ++mh)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int pi = 2 * wave + j, row0 = (pi >> 3) * 128 + mh * 64 + (pi & 7) * 8;
-      voffX[mh][j] = (unsigned)(((long)(m0 + row0 + prow) * p.lda) * 2 + pchunk * 16);
-      ldsX[mh][j] = row0 * ROW_BYTES;
-    }
-#pragma unroll
-  for (int nh = 0; nh < 2; ++nh) {
-    const int nt = (wave >> 1) * 4 + 2 * nh + (wave & 1);
-    voffY[nh][0] = (unsigned)((long)(n0 / 16 + nt) * kt32 * 1024 + lane * 16);
-    voffY[nh][1] = voffY[nh][0] + 1024;
-    ldsY[nh] = W_OFF + nt * 2048;
-  }
-#define ISSUE_X(MH, TILE)                                                                   \
-  do {                                                                                      \
-    const int t__ = (TILE);                                                                 \
-    const __amdgpu_buffer_rsrc_t rs__ = t__ < nk ? rsA : rsA0;                              \
-    char* b__ = smem + (t__ & 1) * STAGE;                                                   \
-    BL_GLDS(rs__, b__ + ldsX[MH][0], voffX[MH][0], t__ * 128);                              \
-    BL_GLDS(rs__, b__ + ldsX[MH][1], voffX[MH][1], t__ * 128);                              \
-  } while (0)
-#define ISSUE_Y(NH, TILE)                                                                   \
-  do {                                                                                      \
-    const int t__ = (TILE);                                                                 \
-    const __amdgpu_buffer_rsrc_t rs__ = t__ < nk ? rsW : rsW0;                              \
-    char* b__ = smem + (t__ & 1) * STAGE;                                                   \
-    BL_GLDS(rs__, b__ + ldsY[NH], voffY[NH][0], t__ * 2048);                                \
-    BL_GLDS(rs__, b__ + ldsY[NH] + 1024, voffY[NH][1], t__ * 2048);                         \
-  } while (0)
-
-  // ---- fragment reads ----
-  const int cb0 = (lg ^ (lane & 7)) << 4;                       // swizzled chunk of k-step 0; k-step 1 = cb0 ^ 64
-  const int offX = (wm * 128 + l15) * ROW_BYTES;                // + mh*8192 + i*2048
-  const int offY = W_OFF + wn * 8192 + lane * 16;               // + (2*nh + j)*2048 + ks*1024
-#define READ_X(DST, MH, SB)                                                                             \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                       \
-    DST[i * 2] = *(const bf16x8_t*)((SB) + offX + (MH) * 8192 + i * 2048 + cb0);                        \
-    DST[i * 2 + 1] = *(const bf16x8_t*)((SB) + offX + (MH) * 8192 + i * 2048 + (cb0 ^ 64));            \
-  }
-#define READ_Y(DST, NH, SB)                                                                             \
-  _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                       \
-    DST[j * 2] = *(const bf16x8_t*)((SB) + offY + (2 * (NH) + j) * 2048);                               \
-    DST[j * 2 + 1] = *(const bf16x8_t*)((SB) + offY + (2 * (NH) + j) * 2048 + 1024);                    \
-  }
-#define MMA(XR, YR, MH, NH)                                                                             \
-  do {                                                                                                  \
-    __builtin_amdgcn_s_setprio(1);                                                                      \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                    \
-      _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                     \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                   \
-          acc[2 * (NH) + j][4 * (MH) + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                    \
-              YR[j * 2 + ks], XR[i * 2 + ks], acc[2 * (NH) + j][4 * (MH) + i], 0, 0, 0);                \
-    __builtin_amdgcn_s_setprio(0);                                                                      \
-  } while (0)
-  // lgkmcnt(0): this phase's prefetch reads have returned (so a later LDS-DMA into the same half-tile cannot overtake
-  // them); vmcnt(4): all but the two youngest half-tiles have landed; the barrier publishes them to the other waves.
-#define PHASE_END(WAITVM)                                                         \
-  do {                                                                            \
-    if (WAITVM) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");       \
-    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                       \
-    __builtin_amdgcn_s_barrier();                                                 \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-  } while (0)
-
-  f32x4_t acc[4][8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  bf16x8_t Xa[8], Xb[8], Ya[4], Yb[4];
-  char* const S0 = smem;
-  char* const S1 = smem + STAGE;
-
-  // ---- prologue: X0 Y0 Y1 X1 of tile 0 and X0 of tile 1; the first three must have landed ----
-  ISSUE_X(0, kt_begin); ISSUE_Y(0, kt_begin); ISSUE_Y(1, kt_begin); ISSUE_X(1, kt_begin); ISSUE_X(0, kt_begin + 1);
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  READ_X(Xa, 0, S0);
-  READ_Y(Ya, 0, S0);
-
-  for (int t = kt_begin; t < nk; t += 2) {
-    // ---- K-tile t (stage 0; kt_begin is even) ----
-    ISSUE_Y(0, t + 1); READ_Y(Yb, 1, S0);                    MMA(Xa, Ya, 0, 0); PHASE_END(1);
-    ISSUE_Y(1, t + 1); READ_X(Xb, 1, S0);                    MMA(Xa, Yb, 0, 1); PHASE_END(0);
-    ISSUE_X(1, t + 1); READ_Y(Ya, 0, S0);                    MMA(Xb, Yb, 1, 1); PHASE_END(1);
-    ISSUE_X(0, t + 2); READ_X(Xa, 0, S1); READ_Y(Yb, 0, S1); MMA(Xb, Ya, 1, 0); PHASE_END(1);
-    // ---- K-tile t+1 (stage 1); the two weight register sets have swapped roles ----
-    ISSUE_Y(0, t + 2); READ_Y(Ya, 1, S1);                    MMA(Xa, Yb, 0, 0); PHASE_END(1);
-    ISSUE_Y(1, t + 2); READ_X(Xb, 1, S1);                    MMA(Xa, Ya, 0, 1); PHASE_END(0);
-    ISSUE_X(1, t + 2); READ_Y(Yb, 0, S1);                    MMA(Xb, Ya, 1, 1); PHASE_END(1);
-    ISSUE_X(0, t + 3); READ_X(Xa, 0, S0); READ_Y(Ya, 0, S0); MMA(Xb, Yb, 1, 0); PHASE_END(1);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // out-of-range tail loads must not outlive the wave's LDS
-#undef ISSUE_X
-#undef ISSUE_Y
-#undef READ_X
-#undef READ_Y
-#undef MMA
-#undef PHASE_END
-
-  if (p.splitk > 1) {   // fp32 partial tile → slab[blockIdx][i*8+j][thread] (16 B per lane, fully coalesced)
-    float* dst = p.slab + ((long)blockIdx.x * 32 * 512 + tid) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) *(f32x4_t*)(dst + (long)(i * 8 + j) * 512 * 4) = acc[i][j];
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      epilogue_store4<EPI>(p, m0 + wm * 128 + j * 16 + l15, n0 + wn * 64 + i * 16 + lg * 4, acc[i][j]);
-#endif
-}
-
-// ======================================================================================================================
-// 256 × 256 tile, STAGGERED wave groups: waves 0-3 (group A, wm = 0) and waves 4-7 (group B, wm = 1) share each SIMD
+// 256 × 256 tile, 8 waves (128(m) × 64(n) each), 128 KiB LDS = 2 stages, 1 workgroup per CU. Each K-tile is staged as four
+// 16-KiB HALF-TILES (X0/X1 = the two 64-row halves of every wave's activation rows, Y0/Y1 = the two 32-row halves of every
+// wave's weight rows) and consumed in four PHASES of 16 MFMAs (output quadrants (0,0) (0,1) (1,1) (1,0)).
+// STAGGERED wave groups: waves 0-3 (group A, wm = 0) and waves 4-7 (group B, wm = 1) share each SIMD
 // pairwise; running them half a phase apart lets one group's 16 MFMAs cover the other group's LDS-DMA issue and
 // fragment reads, so the matrix pipe no longer idles while both waves of a SIMD load in lockstep
 // (square 8k: 1328 → 1430 TFLOP/s; Llama layer GEMMs 1719 → 1594 µs).
@@ -1819,23 +1372,27 @@ __global__ __launch_bounds__(512) void gemm_splitk_reduce_kernel(GemmArgs p) {
                        TN ? tn * 256 + (i >> 1) * 128 + wn * 32 + (i & 1) * 16 + lg * 4 : tn * 256 + wn * 64 + i * 16 + lg * 4, sum);
 }
 
+constexpr int CUS = 256;   // MI355X compute units: the 256-row tile kernels run one workgroup per CU, a round is CUS tiles
+constexpr int LDS128 = 2 * 256 * ROW_BYTES, LDS256 = 2 * 65536, LDS288 = 2 * 73728;
+// gemm_ring8_kernel<EPI, BM, BN, 4>: four ring slots of BM activation + BN weight rows, and the 1-KiB dump
+constexpr int ring8_lds_bytes(int bm, int bn) { return 4 * (bm + bn) * ROW_BYTES + 1024; }
+
+template <typename Kernel>
+bool lds_attr(Kernel* kernel, int bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) ==
+         hipSuccess;
+}
+
 template <int MB, int NB>
 constexpr int mid_lds_bytes() { return 3 * (64 * MB * ROW_BYTES + NB * 2048); }
 template <int EPI, int MB, int NB, int SK = 0>
-bool mid_attr() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mid_kernel<EPI, MB, NB, SK>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, mid_lds_bytes<MB, NB>()) == hipSuccess;
-}
+bool mid_attr() { return lds_attr(&gemm_mid_kernel<EPI, MB, NB, SK>, mid_lds_bytes<MB, NB>()); }
 
 constexpr int RS_LDS_BYTES = 4 * 2 * 6 * 16 * ROW_BYTES;   // gemm_rows_stream_kernel: NWB chunks of 96 rows × 2 K-tiles
 template <int EPI, int NWV, int SK>
 int launch_rs(const GemmArgs& p, hipStream_t s, int n_tiles) {
-  static bool done = false;
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_rows_stream_kernel<EPI, NWV, SK>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS_BYTES) != hipSuccess) return BL_E_LAUNCH;
-    done = true;
-  }
+  static const int attr_rc = lds_attr(&gemm_rows_stream_kernel<EPI, NWV, SK>, RS_LDS_BYTES) ? BL_OK : BL_E_LAUNCH;
+  if (attr_rc != BL_OK) return attr_rc;
   hipLaunchKernelGGL((gemm_rows_stream_kernel<EPI, NWV, SK>), dim3((n_tiles + NWV - 1) / NWV, 8 / SK), dim3(NWV * 64),
                      RS_LDS_BYTES, s, p, n_tiles);
   return BL_OK;
@@ -1845,11 +1402,8 @@ int launch_rs(const GemmArgs& p, hipStream_t s, int n_tiles) {
 // layers at M <= 96 (qkv, gate/up, lm_head), gemm_mid_kernel<SK> otherwise
 template <int EPI>
 int launch_rows_sk(const GemmArgs& a, hipStream_t s) {
-  static bool done = false;
-  if (!done) {
-    if (!mid_attr<EPI, 2, 4, 8>() || !mid_attr<EPI, 2, 4, 2>()) return BL_E_LAUNCH;
-    done = true;
-  }
+  static const int attr_rc = mid_attr<EPI, 2, 4, 8>() && mid_attr<EPI, 2, 4, 2>() ? BL_OK : BL_E_LAUNCH;
+  if (attr_rc != BL_OK) return attr_rc;
   GemmArgs p = a;
   p.fold_ks = p.K / 256;                       // 8 slices of K/8 columns = K/256 MFMA k-steps each
   // Rows-stream form: slices that end on its 4-k-step chunks (K a multiple of 1024), more than 256 weight tiles (the narrow
@@ -1897,76 +1451,59 @@ int launch_rows_sk(const GemmArgs& a, hipStream_t s) {
 
 template <int EPI>
 int set_lds_attr() {
-  static bool done = false;   // idempotent; a benign race only repeats the same calls
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 65536) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 65536) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm288_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 73728) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm288s_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 73728) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm128_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * ROW_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tail_kernel<EPI, 128, 128, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 256 * ROW_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tail_kernel<EPI, 128, 64, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 192 * ROW_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tail_kernel<EPI, 64, 64, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * ROW_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tail_kernel<EPI, 160, 128, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 288 * ROW_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ring8_kernel<EPI, 160, 128, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 288 * ROW_BYTES + 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ring8_kernel<EPI, 128, 128, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 256 * ROW_BYTES + 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ring8_kernel<EPI, 128, 64, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 192 * ROW_BYTES + 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ring8_kernel<EPI, 64, 64, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * ROW_BYTES + 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mid2_kernel<EPI, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            3 * (160 * ROW_BYTES + 4096)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mid2_kernel<EPI, 4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            3 * (160 * ROW_BYTES + 4 * 4096)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mid2_kernel<EPI, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * (160 * ROW_BYTES + 2 * 4096)) != hipSuccess ||
-        !mid_attr<EPI, 2, 4>() || !mid_attr<EPI, 4, 4>() || !mid_attr<EPI, 5, 4>() || !mid_attr<EPI, 2, 1>() ||
-        !mid_attr<EPI, 4, 1>() || !mid_attr<EPI, 5, 1>())
-      return BL_E_LAUNCH;
-    done = true;
-  }
-  return BL_OK;
+  static const int rc = [] {
+    const bool ok =
+        lds_attr(&gemm256s_kernel<EPI>, LDS256) && lds_attr(&gemm288s_kernel<EPI>, LDS288) &&
+        lds_attr(&gemm128_kernel<EPI>, LDS128) &&
+        lds_attr(&gemm_ring8_kernel<EPI, 160, 128, 4>, ring8_lds_bytes(160, 128)) &&
+        lds_attr(&gemm_ring8_kernel<EPI, 128, 128, 4>, ring8_lds_bytes(128, 128)) &&
+        lds_attr(&gemm_ring8_kernel<EPI, 128, 64, 4>, ring8_lds_bytes(128, 64)) &&
+        lds_attr(&gemm_ring8_kernel<EPI, 64, 64, 4>, ring8_lds_bytes(64, 64)) &&
+        lds_attr(&gemm_mid2_kernel<EPI, 1>, 3 * (160 * ROW_BYTES + 4096)) &&
+        lds_attr(&gemm_mid2_kernel<EPI, 4>, 3 * (160 * ROW_BYTES + 4 * 4096)) &&
+        lds_attr(&gemm_mid2_kernel<EPI, 2, 2>, 2 * (160 * ROW_BYTES + 2 * 4096)) &&
+        mid_attr<EPI, 2, 4>() && mid_attr<EPI, 4, 4>() && mid_attr<EPI, 5, 4>() && mid_attr<EPI, 2, 1>() &&
+        mid_attr<EPI, 4, 1>() && mid_attr<EPI, 5, 1>();
+    return ok ? BL_OK : BL_E_LAUNCH;
+  }();
+  return rc;
+}
+
+// K-sliced forms: slices write fp32 partials [M, N] to the slab, gemm128_splitk_reduce_kernel sums them in slice order and
+// applies the epilogue
+template <int EPI>
+void launch_slab_reduce(const GemmArgs& p, hipStream_t s) {
+  const long work = (long)p.M * (p.N / 4);
+  hipLaunchKernelGGL((gemm128_splitk_reduce_kernel<EPI>), dim3((int)min((work + 255) / 256, 2048L)), dim3(256), 0, s, p);
+}
+
+// gemm_mid_kernel for M ≤ 64·MB rows: 64-column slabs (wide) or 16-column slabs
+template <int EPI, int MB>
+void launch_mid(const GemmArgs& p, hipStream_t s, bool wide, dim3 grid) {
+  if (wide) hipLaunchKernelGGL((gemm_mid_kernel<EPI, MB, 4>), grid, dim3(256), (mid_lds_bytes<MB, 4>()), s, p);
+  else hipLaunchKernelGGL((gemm_mid_kernel<EPI, MB, 1>), grid, dim3(256), (mid_lds_bytes<MB, 1>()), s, p);
 }
 
 template <int EPI>
 int launch_gemm(const GemmArgs& a, hipStream_t s) {
-  constexpr int CUS = 256;              // MI355X: the 256x256 kernel runs one workgroup per CU
-  constexpr int LDS128 = 2 * 256 * ROW_BYTES, LDS256 = 2 * 65536;
   if (set_lds_attr<EPI>() != BL_OK) return BL_E_LAUNCH;
   GemmArgs p = a;
-  static const char* force = getenv("BL_GEMM_TILE");   // "128" / "256": benchmarking aid
   const int bm = (p.M + 255) / 256, bn = (p.N + 255) / 256, big_tiles = bm * bn;
   // one (partial) round of big tiles beats 1.5+ rounds of the 128 kernel once about half of the CUs get a tile (ViT qkv at
   // B = 16: 204 / 224 tiles, 45 → 39 µs; round 3, the narrow ViT layers at the training batch of 32 images — 132 / 160 tiles
   // for M = 8352 / 8192, N = 1024 / 1152 — where the 128 kernel needs 528 / 576 > 512 workgroup slots: 104 → 82 µs at
   // K = 4096, 35 → 30 µs at K = 1024)
-  static const int big_min = getenv("BL_GEMM_BIG_MIN") ? atoi(getenv("BL_GEMM_BIG_MIN")) : 128;   // A/B aid
-  bool big = big_tiles >= big_min && p.K >= 512;
-  if (force) big = force[0] == '2';
-  static const bool no_mid = getenv("BL_GEMM_NO_MID") != nullptr;      // A/B aid
+  const bool big = big_tiles >= 128 && p.K >= 512;
   // M <= 320: the weight-streaming mid kernels; up to 640 rows (B = 2 prefill) the 160-row mid2 kernel still beats the
   // tile kernels (38.2 -> 36.4 ms per batch), beyond that it loses (B = 4: 42.7 vs 48.2 ms)
-  static const bool no_mid2 = getenv("BL_GEMM_NO_MID2") != nullptr;      // A/B aid
   const bool mid2_only = p.M > 320;
-  if (p.M <= 640 && p.M > 32 && p.K >= 512 && !force && !no_mid && !(mid2_only && (no_mid2 || p.slab || (p.N % 32)))) {
+  if (p.M <= 640 && p.M > 32 && p.K >= 512 && !(mid2_only && (p.slab || (p.N % 32)))) {
     // every weight byte once: one workgroup per column slab, all rows; 64-column slabs when that already gives ≥ 160
     // workgroups, else 16-column slabs. grid.y slices K only with a workspace (opt-in).
     const int slabs64 = (p.N + 63) / 64, nkm = p.K / BK;
     bool wide = slabs64 >= 160;   // measured: 64-column slabs for N = 4096 without K slicing (64 workgroups) cost +2.2 ms at B = 1
     int S = 1;
-    static const bool no_split_mid = getenv("BL_GEMM_NO_SPLITK") != nullptr;
-    if (!wide && p.slab && !no_split_mid && slabs64 * 2 <= CUS) {
+    if (!wide && p.slab && slabs64 * 2 <= CUS) {
       // Every workgroup re-reads ALL M rows of A from L2, so the L2 traffic is (N / slab width) · M · K · 2 B: with a
       // workspace, narrow layers (N = 4096: 64 slabs of 64 columns) keep the 64-column slabs — a quarter of the activation
       // traffic of 16-column slabs — and fill the chip by slicing K instead (same slicing for every row: slot-invariant)
@@ -1974,7 +1511,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
       while (S2 > 1 && (nkm / S2 < 8 || p.slab_bytes < (long)S2 * p.M * p.N * 4)) --S2;
       if (S2 > 1) { wide = true; S = S2; }
     }
-    if (S == 1 && p.M > 128 && (p.N % 32) == 0 && !no_mid2) {
+    if (S == 1 && p.M > 128 && (p.N % 32) == 0) {
       // 160-row workgroups (gemm_mid2_kernel): narrow layers 32 columns (3-stage ring, 2 workgroups per CU); wide layers
       // 64 columns on a 2-stage ring so that two workgroups share a CU and one's LDS-DMA issue runs under the other's
       // MFMAs (qkv 59 -> 44 us, gate/up 112 -> 83 us at M = 288); the widest (lm_head) 128 columns.
@@ -1989,39 +1526,27 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
       return BL_OK;
     }
     const int slabs = wide ? slabs64 : (p.N + 15) / 16;
-    if (S == 1 && !wide && p.slab && !no_split_mid && slabs < CUS) {
+    if (S == 1 && !wide && p.slab && slabs < CUS) {
       S = min(8, (CUS + CUS / 2 + slabs - 1) / slabs);
       while (S > 1 && (nkm / S < 8 || p.slab_bytes < (long)S * p.M * p.N * 4)) --S;
     }
     p.splitk = S;
-    const dim3 grid(slabs, S), block(256);
-#define BL_MID(MBV)                                                                                            \
-  do {                                                                                                         \
-    if (wide) hipLaunchKernelGGL((gemm_mid_kernel<EPI, MBV, 4>), grid, block, (mid_lds_bytes<MBV, 4>()), s, p);  \
-    else hipLaunchKernelGGL((gemm_mid_kernel<EPI, MBV, 1>), grid, block, (mid_lds_bytes<MBV, 1>()), s, p);       \
-  } while (0)
-    if (p.M <= 128) BL_MID(2);
-    else if (p.M <= 256) BL_MID(4);
-    else BL_MID(5);
-#undef BL_MID
-    if (S > 1) {
-      const long work = (long)p.M * (p.N / 4);
-      hipLaunchKernelGGL((gemm128_splitk_reduce_kernel<EPI>), dim3((int)min((work + 255) / 256, 2048L)), dim3(256), 0, s, p);
-    }
+    const dim3 grid(slabs, S);
+    if (p.M <= 128) launch_mid<EPI, 2>(p, s, wide, grid);
+    else if (p.M <= 256) launch_mid<EPI, 4>(p, s, wide, grid);
+    else launch_mid<EPI, 5>(p, s, wide, grid);
+    if (S > 1) launch_slab_reduce<EPI>(p, s);
     BL_CHECK_LAUNCH();
     return BL_OK;
   }
-  static const bool no_ring160 = getenv("BL_GEMM_NO_RING160") != nullptr;      // A/B aid
-  if (!big && !force && !no_ring160 && p.K >= 512) {
+  if (!big && p.K >= 512) {
     // one round of 160 × 128 tiles on the ring-buffered kernel when that covers the problem with ≥ 3/4 of the CUs busy
     const int t160 = ((p.M + 159) / 160) * ((p.N + 127) / 128);
     if (t160 <= CUS && t160 >= (3 * CUS) / 4) {
       p.tiles_m = (p.M + 159) / 160;
       p.tiles_n = (p.N + 127) / 128;
       p.tail_base = -1;
-      static const bool ring_w4 = getenv("BL_GEMM_RING160_W4") != nullptr;      // A/B aid: the one-wave-per-SIMD form
-      if (ring_w4) hipLaunchKernelGGL((gemm_tail_kernel<EPI, 160, 128, 4>), dim3(t160), dim3(256), 4 * 288 * ROW_BYTES, s, p);
-      else hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 160, 128, 4>), dim3(t160), dim3(512), 4 * 288 * ROW_BYTES + 1024, s, p);
+      hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 160, 128, 4>), dim3(t160), dim3(512), ring8_lds_bytes(160, 128), s, p);
       BL_CHECK_LAUNCH();
       return BL_OK;
     }
@@ -2030,25 +1555,17 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
     p.tiles_m = (p.M + 127) / 128;
     p.tiles_n = (p.N + 127) / 128;
     const int tiles = p.tiles_m * p.tiles_n, nk128 = p.K / BK;
-    // few tiles, long K (tall-skinny): slice K over grid.y when the caller gave a workspace (opt-in, as for the 256
-    // kernel: sliced sums are not batch-slot invariant)
+    // few tiles, long K (tall-skinny): slice K over grid.y on the ring kernel (one workgroup per CU: 129 KiB of LDS) when
+    // the caller gave a workspace (opt-in, as for the 256 kernel: sliced sums are not batch-slot invariant)
     int S128 = 1;
-    static const bool ring_split = getenv("BL_GEMM_SPLITK_128") == nullptr;   // A/B aid: set → gemm128's split-K form
-    if (p.slab && tiles <= CUS / 2 && !force && !getenv("BL_GEMM_NO_SPLITK")) {
-      // the ring kernel holds one workgroup per CU (129 KiB of LDS), gemm128 two
-      S128 = min(8, ((ring_split ? 1 : 2) * CUS) / tiles);
+    if (p.slab && tiles <= CUS / 2) {
+      S128 = min(8, CUS / tiles);
       while (S128 > 1 && (nk128 / S128 < 8 || p.slab_bytes < (long)S128 * p.M * p.N * 4)) --S128;
     }
-    if (S128 > 1 && ring_split) {
+    if (S128 > 1) {
       p.splitk = S128;
-      hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 128, 128, 4>), dim3(tiles, S128), dim3(512), 4 * 256 * ROW_BYTES + 1024, s, p);
-      const long work = (long)p.M * (p.N / 4);
-      hipLaunchKernelGGL((gemm128_splitk_reduce_kernel<EPI>), dim3((int)min((work + 255) / 256, 2048L)), dim3(256), 0, s, p);
-    } else if (S128 > 1) {
-      p.splitk = S128;
-      hipLaunchKernelGGL((gemm128_kernel<EPI>), dim3(tiles, S128), dim3(256), LDS128, s, p);
-      const long work = (long)p.M * (p.N / 4);
-      hipLaunchKernelGGL((gemm128_splitk_reduce_kernel<EPI>), dim3((int)min((work + 255) / 256, 2048L)), dim3(256), 0, s, p);
+      hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 128, 128, 4>), dim3(tiles, S128), dim3(512), ring8_lds_bytes(128, 128), s, p);
+      launch_slab_reduce<EPI>(p, s);
     } else {
       hipLaunchKernelGGL((gemm128_kernel<EPI>), dim3(tiles), dim3(256), LDS128, s, p);
     }
@@ -2058,8 +1575,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
   // 288-row tiles (one 288-token sequence per row tile) where they remove the leftover round: estimated cost in units of
   // one round of 256 × 256 tiles — 256-row tiling: full rounds + 0.45 for a ≤ 64-tile tail on sub-tiles, 1 for a larger
   // partial round; 288-row tiling: rounds × 1.12 (12.5 % more MFMA work and 6 % more staging per tile).
-  static const bool no_288 = getenv("BL_GEMM_NO_288") != nullptr;      // A/B aid
-  if (!force && !no_288 && (p.K % 128) == 0) {
+  if ((p.K % 128) == 0) {
     const int t256 = big_tiles, r256 = t256 % CUS;
     const float cost256 = (float)(t256 / CUS) + (r256 == 0 ? 0.f : (r256 <= 64 && t256 > CUS) ? 0.45f : 1.0f);
     const int bm288 = (p.M + 287) / 288, t288 = bm288 * bn;
@@ -2067,15 +1583,13 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
     if (cost288 < 0.97f * cost256) {
       p.tiles_m = bm288;
       p.tiles_n = bn;
-      static const bool lockstep288 = getenv("BL_GEMM_288_LOCKSTEP") != nullptr;      // A/B aid
-      if (lockstep288) hipLaunchKernelGGL((gemm288_kernel<EPI>), dim3(t288), dim3(512), 2 * 73728, s, p);
-      else hipLaunchKernelGGL((gemm288s_kernel<EPI>), dim3(t288), dim3(512), 2 * 73728, s, p);
+      hipLaunchKernelGGL((gemm288s_kernel<EPI>), dim3(t288), dim3(512), LDS288, s, p);
       BL_CHECK_LAUNCH();
       return BL_OK;
     }
   }
   // Whole rounds of 256 tiles on the pipelined kernel; a partial last round would leave most CUs idle for a full tile
-  // time, so its tiles are cut into 128x128 quarters and run by the small kernel (2 workgroups per CU) instead.
+  // time, so its tiles are cut into sub-tiles and run by the ring kernel instead.
   p.tiles_m = bm;
   p.tiles_n = bn;
   // The last round of 256-tile launches is usually partial (e.g. 288 tiles = 1.125 rounds). Measured cost of the
@@ -2087,59 +1601,42 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
   int S = tail ? CUS / tail : 1;
   if (S > 16) S = 16;
   while (S > 1 && nk / S < 4) --S;
-  static const bool no_split = getenv("BL_GEMM_NO_SPLITK") != nullptr;
-  static const bool lockstep = getenv("BL_GEMM_LOCKSTEP") != nullptr;   // A/B aid: the non-staggered 256 kernel
   // more than one round of tiles: the persistent form (one workgroup per CU walks its tiles, the next tile's first K-tiles
   // land behind this tile's epilogue); needs an even number of K-tiles (stage parity carries over) and 32-bit extents
-  static const bool no_persist = getenv("BL_GEMM_NO_PERSIST") != nullptr;      // A/B aid
-  const bool persist_ok = !no_persist && !lockstep && (nk % 2) == 0 && (long)p.M * p.lda * 2 < (1L << 32) &&
-                          (long)p.N * p.K * 2 < (1L << 32);
-#define BL_LAUNCH256(GRID)                                                                              \
-  do {                                                                                                  \
-    if (lockstep) hipLaunchKernelGGL((gemm256_kernel<EPI>), dim3(GRID), dim3(512), LDS256, s, p);       \
-    else if (persist_ok && p.splitk <= 1 && (GRID) > CUS) {                                             \
-      GemmArgs pp = p;                                                                                  \
-      pp.ptiles = (GRID);                                                                               \
-      hipLaunchKernelGGL((gemm256s_kernel<EPI>), dim3(CUS), dim3(512), LDS256, s, pp);                  \
-    } else hipLaunchKernelGGL((gemm256s_kernel<EPI>), dim3(GRID), dim3(512), LDS256, s, p);             \
-  } while (0)
-  const bool can_split = tail && S >= 2 && p.K >= 8192 && p.slab &&
-                         p.slab_bytes >= (long)tail * S * 256 * 256 * 4 && !no_split && !force;
+  const bool persist_ok = (nk % 2) == 0 && (long)p.M * p.lda * 2 < (1L << 32) && (long)p.N * p.K * 2 < (1L << 32);
+  auto launch256 = [&](int grid) {
+    if (persist_ok && p.splitk <= 1 && grid > CUS) {
+      GemmArgs pp = p;
+      pp.ptiles = grid;
+      hipLaunchKernelGGL((gemm256s_kernel<EPI>), dim3(CUS), dim3(512), LDS256, s, pp);
+    } else {
+      hipLaunchKernelGGL((gemm256s_kernel<EPI>), dim3(grid), dim3(512), LDS256, s, p);
+    }
+  };
+  const bool can_split = tail && S >= 2 && p.K >= 8192 && p.slab && p.slab_bytes >= (long)tail * S * 256 * 256 * 4;
   if (can_split) {
     main_tiles = big_tiles - tail;
-    if (main_tiles) BL_LAUNCH256(main_tiles);
+    if (main_tiles) launch256(main_tiles);
     p.tail_base = main_tiles;
     p.splitk = S;
-    BL_LAUNCH256(tail * S);
+    launch256(tail * S);
     hipLaunchKernelGGL((gemm_splitk_reduce_kernel<EPI>), dim3(tail * 32), dim3(512), 0, s, p);
   } else {
     // (65 … 128 leftover tiles — Llama qkv at B = 16: 96 — as 256 × 128 half tiles instead of a quarter-filled fourth round
     // was measured at −0.6 % end to end: the half tiles stage 3/4 of a full tile's bytes for half its FLOPs)
-    if (tail != 0 && tail <= 64 && main_tiles > tail && !force) main_tiles = big_tiles - tail; else tail = 0;
-    BL_LAUNCH256(main_tiles);
+    if (tail != 0 && tail <= 64 && main_tiles > tail) main_tiles = big_tiles - tail; else tail = 0;
+    launch256(main_tiles);
     if (tail) {
-      // leftover 256x256 tiles, cut so that the sub-tiles cover (up to) every CU once
+      // leftover 256x256 tiles on gemm_ring8_kernel's tail mode, cut so that the sub-tiles cover (up to) every CU once
       p.tail_base = main_tiles;
-      static const bool old_tail = getenv("BL_GEMM_OLD_TAIL") != nullptr;   // A/B aid
-      static const bool tail_w4 = getenv("BL_GEMM_TAIL_W4") != nullptr;     // A/B aid: the one-wave-per-SIMD tail kernels
-      if (old_tail) hipLaunchKernelGGL((gemm128_kernel<EPI>), dim3(tail * 4), dim3(256), LDS128, s, p);
-      else if (tail_w4 && tail <= 16)
-        hipLaunchKernelGGL((gemm_tail_kernel<EPI, 64, 64, 4>), dim3(tail * 16), dim3(256), 4 * 128 * ROW_BYTES, s, p);
-      else if (tail_w4 && tail <= 32)
-        hipLaunchKernelGGL((gemm_tail_kernel<EPI, 128, 64, 4>), dim3(tail * 8), dim3(256), 4 * 192 * ROW_BYTES, s, p);
-      else if (tail_w4)
-        hipLaunchKernelGGL((gemm_tail_kernel<EPI, 128, 128, 4>), dim3(tail * 4), dim3(256), 4 * 256 * ROW_BYTES, s, p);
-      // two waves per SIMD (gemm_ring8_kernel in tail mode): the sub-tiles' K-steps are LDS-DMA issue + fragment reads + MFMAs
-      // of ONE wave per SIMD back to back otherwise
-      else if (tail <= 16)
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 64, 64, 4>), dim3(tail * 16), dim3(512), 4 * 128 * ROW_BYTES + 1024, s, p);
+      if (tail <= 16)
+        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 64, 64, 4>), dim3(tail * 16), dim3(512), ring8_lds_bytes(64, 64), s, p);
       else if (tail <= 32)
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 128, 64, 4>), dim3(tail * 8), dim3(512), 4 * 192 * ROW_BYTES + 1024, s, p);
+        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 128, 64, 4>), dim3(tail * 8), dim3(512), ring8_lds_bytes(128, 64), s, p);
       else
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 128, 128, 4>), dim3(tail * 4), dim3(512), 4 * 256 * ROW_BYTES + 1024, s, p);
+        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 128, 128, 4>), dim3(tail * 4), dim3(512), ring8_lds_bytes(128, 128), s, p);
     }
   }
-#undef BL_LAUNCH256
   BL_CHECK_LAUNCH();
   return BL_OK;
 }
@@ -2148,14 +1645,8 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
 // dW = dyᵀ·x straight from the row-major gradient and activation buffers (no transposed copies). Whole rounds of 256 × 256
 // tiles on the staggered kernel's TN form; a partial last round is split along K when the caller gave a workspace.
 int launch_gemm_tn(const GemmArgs& a, hipStream_t s) {
-  constexpr int CUS = 256, LDS256 = 2 * 65536;
-  static bool done = false;
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_kernel<BL_EPI_F32, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS256) != hipSuccess)
-      return BL_E_LAUNCH;
-    done = true;
-  }
+  static const int attr_rc = lds_attr(&gemm256s_kernel<BL_EPI_F32, true>, LDS256) ? BL_OK : BL_E_LAUNCH;
+  if (attr_rc != BL_OK) return attr_rc;
   GemmArgs p = a;
   p.tiles_m = (p.M + 255) / 256;
   p.tiles_n = (p.N + 255) / 256;
@@ -2166,11 +1657,9 @@ int launch_gemm_tn(const GemmArgs& a, hipStream_t s) {
   if (tiles <= CUS && S > 8) S = 8;
   if (S > 16) S = 16;
   while (S > 1 && nk / S < 4) --S;
-  static const bool no_split = getenv("BL_GEMM_NO_SPLITK") != nullptr;
   const bool can_split = tail && S >= 2 && (nk >= 128 || tiles <= CUS) && p.slab &&
-                         p.slab_bytes >= (long)tail * S * 256 * 256 * 4 && !no_split;
-  static const bool no_persist = getenv("BL_GEMM_NO_PERSIST") != nullptr;      // A/B aid
-  const bool persist_ok = !no_persist && (nk % 2) == 0 && ((long)(p.K - 1) * p.lda + p.M) * 2 < (1L << 32) &&
+                         p.slab_bytes >= (long)tail * S * 256 * 256 * 4;
+  const bool persist_ok = (nk % 2) == 0 && ((long)(p.K - 1) * p.lda + p.M) * 2 < (1L << 32) &&
                           ((long)(p.K - 1) * p.ldw + p.N) * 2 < (1L << 32);
   auto launch_main = [&](int grid) {
     if (persist_ok && grid > CUS) {

@@ -34,8 +34,6 @@ from ..weights import PackedGroup, VLAWeights, _block_view, _unpack
 from .sharding import ShardComm, ShardLayout, bucket_key, comm_order
 
 IGNORE_INDEX = -100
-WGRAD_NT = os.environ.get("BL_WGRAD_NT", "") not in ("", "0")     # A/B aid: weight gradients through transposed copies
-WGRAD_FP8_5PASS = os.environ.get("BL_WGRAD_FP8_5PASS", "") not in ("", "0")   # A/B aid: round 3's five passes per e4m3 wgrad operand pair
 # SwiGLU / GELU forward ("f") and backward ("b") as GEMM epilogues (BL_EPI_*_KEEP / BL_EPI_*_BWD) instead of separate
 # elementwise passes. ON by default since the tile GEMMs' whole-tile epilogue (round 4, gemm_common.h::epilogue_tile): same box,
 # alternating runs at 7B, B = 32: separate passes 409.8 ms / step, forward fused 408.7, backward fused 409.0, both 406.6. With the
@@ -566,10 +564,6 @@ class TrainStep:
             self._wg_sA = torch.zeros(nmx, dtype=torch.float32, device=dev)
             self._wg_sB = torch.zeros(I, dtype=torch.float32, device=dev)
             self._wg_amax = torch.zeros(nmx + I, dtype=torch.float32, device=dev)      # column |max| of dy (first N) and x (next K)
-            if WGRAD_FP8_5PASS:                # A/B aid: the round-3 form through separate transpose / quantise / pack passes
-                self._wg_tA = torch.zeros(nmx * Tq, dtype=torch.bfloat16, device=dev)
-                self._wg_tB = torch.zeros(I * Tq, dtype=torch.bfloat16, device=dev)
-                self._wg_qB = u8(I * Tq)
         self._fp8_scratch()
         if self.shard_params:                  # sharded layers are quantised in their gather (slots carry the e4m3 copies)
             return
@@ -915,7 +909,7 @@ class TrainStep:
 
     def _wgrad_into(self, dy: torch.Tensor, x: torch.Tensor, gview: torch.Tensor, fp8: bool = False) -> List[Op]:
         """gview[N, K] (fp32) = dyᵀ[N, T] · x[T, K]: the TN GEMM reads dy and x where they lie (transposing LDS reads);
-        BL_WGRAD_NT=1 keeps the round-1 form — the NT GEMM over token-padded transposed copies — as the A/B reference.
+        shapes with N % 8 or K % 8 take the round-1 form — the NT GEMM over token-padded transposed copies.
         fp8=True: the e4m3 form (TrainStep(fp8_wgrad=True)) — transpose, quantise per channel, NT GEMM on bl_gemm_fp8."""
         Tn, N = dy.shape
         K = x.shape[1]
@@ -925,19 +919,13 @@ class TrainStep:
             qA = self._wg_qA[:N * Tq].view(N, Tq)
             pB = self._wg_pB[:K * Tq].view(torch.bfloat16).view(K // 16, Tq // 64, 64, 8)
             sA, sB = self._wg_sA[:N], self._wg_sB[:K]
-            if WGRAD_FP8_5PASS:
-                tA, tB = self._wg_tA[:N * Tq].view(N, Tq), self._wg_tB[:K * Tq].view(K, Tq)
-                qB = self._wg_qB[:K * Tq].view(K, Tq)
-                return [T.transpose_pad(dy, tA, Tq, run=False), ops.quantize_rows_fp8(tA, qA, sA, run=False)[2],
-                        T.transpose_pad(x, tB, Tq, run=False), ops.quantize_rows_fp8(tB, qB, sB, run=False)[2],
-                        T.pack(qB.view(torch.bfloat16), pB, run=False), ops.gemm_fp8(qA, sA, pB, sB, gview, EPI_F32, run=False)]
             # two passes per operand: column |max| (2 B read), then one transposing quantise(-and-pack) (2 B read, 1 B written)
             am = self._wg_amax[:N + K]
             return [T.fill_zero(am, run=False), T.colamax(dy, am[:N], run=False), T.colamax(x, am[N:], run=False),
                     T.transpose_quantize_fp8(dy, am[:N], self._wg_qA[:N * Tq], sA, Tq, False, run=False),
                     T.transpose_quantize_fp8(x, am[N:], self._wg_pB[:K * Tq], sB, Tq, True, run=False),
                     ops.gemm_fp8(qA, sA, pB, sB, gview, EPI_F32, run=False)]
-        if not WGRAD_NT and N % 8 == 0 and K % 8 == 0:
+        if N % 8 == 0 and K % 8 == 0:
             return [T.gemm_tn(dy, x, gview, workspace=self.ws, run=False)]
         Tp = (Tn + 63) // 64 * 64
         assert max(N, K) * Tp <= self.tA.numel()

@@ -110,12 +110,14 @@ def test_gemm_none_bias_gelu(dev, M, N, K):
 
 @pytest.mark.parametrize("M,N,K,epi", [(4608, 4096, 512, "res"), (4608, 1024, 1024, "gelu"), (4400, 3584, 768, "swiglu"),
                                        (4608, 12288, 256, "none"),
-                                       # few-tile (tall-skinny) problems: the 128 kernel slices K over grid.y
+                                       # few-tile (tall-skinny) problems: with a workspace the ring or mid kernels slice K
                                        (4608, 64, 4096, "none"), (4176, 192, 3072, "res"), (300, 128, 2048, "gelu"),
                                        (1000, 256, 1536, "swiglu")])
-def test_gemm_splitk_tail(dev, M, N, K, epi):
-    """Shapes whose 256x256 tile count is not a multiple of 256: whole rounds + split-K tail (with a workspace) must
-    equal the oracle, and equal the no-workspace dispatch bit for bit except for fp32 summation order."""
+def test_gemm_workspace_dispatch(dev, M, N, K, epi):
+    """The dispatch with a workspace must equal the oracle, and equal the no-workspace dispatch bit for bit except for
+    fp32 summation order. The shapes take 288-row tiles, one round of 160 × 128 ring tiles, one partial round of 256 × 256
+    tiles and, with the workspace, the K-sliced ring and mid kernels (the few-tile shapes). None reaches the split-K tail
+    of the 256 × 256 kernel, which needs K >= 8192."""
     from bridgelang_amd import ops
     a, w, b, r = rand_bf16((M, K), 1), rand_bf16((N, K), 2, 0.05), rand_bf16((N,), 3, 0.1), rand_bf16((M, N), 4)
     A, Bv, Rr = dv(a, dev), dv(b, dev), dv(r, dev)
@@ -137,8 +139,8 @@ def test_gemm_splitk_tail(dev, M, N, K, epi):
         ops.gemm(A, W, out2, code, **kw)
         lin = R.linear(P, a, w, b if epi == "gelu" else None)
         ref = {"res": lambda: P.rb(r + lin), "gelu": lambda: R.gelu(P, lin), "none": lambda: lin}[epi]()
-    close_bf16(out, ref, f"split-K tail {epi}")
-    close_bf16(out, out2.cpu().float(), "split-K vs 128-tail dispatch", min_exact=0.97)
+    close_bf16(out, ref, f"workspace dispatch {epi}")
+    close_bf16(out, out2.cpu().float(), "workspace vs no-workspace dispatch", min_exact=0.97)
 
 
 @pytest.mark.parametrize("N,K", [(4096, 1024), (1024, 2048), (12288, 512)])   # 12288: 96 leftover tiles = a partial fourth round
@@ -161,10 +163,9 @@ def test_gemm_rows_independent_of_batch(dev, N, K):
 @pytest.mark.parametrize("M,N,K,epi", [(4608, 4096, 1024, "res"), (4591, 4000, 512, "none"), (4608, 12288, 256, "bias"),
                                        (4608, 2048, 384, "swiglu")])
 def test_gemm288_sequence_tiles(dev, M, N, K, epi):
-    """288-row tiles (one 288-token sequence per row tile: gemm288_kernel) where they remove the leftover round of 256-row
+    """288-row tiles (one 288-token sequence per row tile: gemm288s_kernel) where they remove the leftover round of 256-row
     tiling — Llama o_proj / down_proj / qkv at 16 × 288 rows — incl. ragged M and N and every epilogue family, against the
-    oracle on sampled rows and bit-identical to the 256-row tiling (BL_GEMM_NO_288 is read once per process, so the
-    comparison is against the per-sequence call, which takes the mid kernels)."""
+    oracle on sampled rows and bit-identical to the per-sequence call, which takes the mid kernels."""
     from bridgelang_amd import ops
     a, w, b, r = rand_bf16((M, K), 1), rand_bf16((N, K), 2, 0.05), rand_bf16((N,), 3, 0.1), rand_bf16((M, N), 4)
     A, Bv, Rr = dv(a, dev), dv(b, dev), dv(r, dev)
@@ -189,6 +190,58 @@ def test_gemm288_sequence_tiles(dev, M, N, K, epi):
         kw1 = {k: (v[s0:s0 + 288] if k == "res" else v) for k, v in kw.items()}
         ops.gemm(A[s0:s0 + 288], W, one, e, **kw1)
         assert torch.equal(one, out[s0:s0 + 288]), f"rows {s0}..: result depends on the tiling"
+
+
+# (M, N, K): 256 × 256 tiles, leftover tiles of the partial last round, K-tiles → the ring kernel's tail-mode sub-tiles
+RING8_TAILS = {(4608, 22016, 640): "64x64",     # 1548 tiles, 12 left over, 10 K-tiles
+               (4608, 4096, 576): "128x64",     # 288 tiles, 32 left over, 9 K-tiles (K % 128 != 0: no 288-row tiling)
+               (4608, 4352, 1024): "128x128"}   # 306 tiles, 50 left over, 16 K-tiles
+
+
+@pytest.mark.parametrize("M,N,K,epi", [(4608, 22016, 640, "none"), (4608, 22016, 640, "f32"),
+                                       (4608, 4096, 576, "res"), (4608, 4096, 576, "swiglu"),
+                                       (4608, 4352, 1024, "swiglu"), (4608, 4352, 1024, "res")])
+def test_gemm_ring8_tail_modes(dev, M, N, K, epi):
+    """Whole rounds of 256 × 256 tiles plus a leftover round of at most 64 tiles, which gemm_ring8_kernel runs in tail mode
+    as 64×64, 128×64 or 128×128 sub-tiles (RING8_TAILS), without a workspace: against the oracle on sampled rows,
+    including rows of the leftover tiles, and bit-identical to 288-row slices run on their own (mid kernels)."""
+    from bridgelang_amd import ops
+    a, w = rand_bf16((M, K), 1), rand_bf16((N, K), 2, 0.05)
+    A = dv(a, dev)
+    # leftover tiles: the last row tiles (4096 ..) and, for the 128 × 128 case, the right-hand columns of rows 3072 .. 4095
+    sel = torch.cat([torch.arange(0, 128), torch.arange(3500, 3628), torch.arange(M - 300, M)])
+    if epi == "swiglu":
+        I = N // 2
+        W = pk(torch.stack([w[:I], w[I:]], 1).reshape(N, K), dev)
+        out = torch.empty(M, I, dtype=torch.bfloat16, device=dev)
+        kw, e = {}, ops.EPI_SWIGLU
+        g, u = R.linear(P, a[sel], w[:I]), R.linear(P, a[sel], w[I:])
+        ref = P.rb(P.rb(torch.nn.functional.silu(g)) * u)
+    elif epi == "f32":
+        W = pk(w, dev)
+        out = torch.empty(M, N, dtype=torch.float32, device=dev)
+        kw, e = {}, ops.EPI_F32
+        ref = a[sel] @ w.t()
+    else:
+        W = pk(w, dev)
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+        r = rand_bf16((M, N), 4) if epi == "res" else None
+        kw, e = ({"res": dv(r, dev)}, ops.EPI_RES) if epi == "res" else ({}, ops.EPI_NONE)
+        ref = P.rb(r[sel] + R.linear(P, a[sel], w)) if epi == "res" else R.linear(P, a[sel], w)
+    out.fill_(float("nan"))
+    ops.gemm(A, W, out, e, **kw)
+    assert not torch.isnan(out.float()).any(), "an output tile was never written"
+    what = f"ring8 tail {RING8_TAILS[(M, N, K)]} {epi}"
+    if epi == "f32":
+        got = out[sel].cpu()
+        assert torch.allclose(got, ref, rtol=1e-4, atol=1e-4 * ref.abs().max().item()), what
+    else:
+        close_bf16(out[sel], ref, what)
+    for s0 in (0, 288 * 12, M - 288):
+        one = torch.empty(288, out.shape[1], dtype=out.dtype, device=dev)
+        kw1 = {k: v[s0:s0 + 288] for k, v in kw.items()}
+        ops.gemm(A[s0:s0 + 288], W, one, e, **kw1)
+        assert torch.equal(one, out[s0:s0 + 288]), f"{what}: rows {s0}..: result depends on the tiling"
 
 
 @pytest.mark.parametrize("M,N,K,epi", [(2333, 15360, 256, "bias"), (2560, 15344, 384, "none"), (2333, 15360, 256, "swiglu"),
@@ -231,7 +284,7 @@ def test_gemm256_persistent_multi_round(dev, M, N, K, epi):
 @pytest.mark.parametrize("T,N,K", [(261, 1024, 1024), (256, 1152, 4352), (256, 1024, 640), (261, 1024, 1088)])   # last: odd K-tile count (LoRA: K + rank columns)
 def test_gemm_ring160_vit_shapes_and_batch_invariance(dev, T, N, K):
     """The narrow ViT layers at 16 images (attn.proj / mlp.fc2 / patch embed: M = 16·T rows, N ≤ 1152) run as ONE round of
-    160 × 128 tiles on the ring-buffered kernel (gemm_tail_kernel stand-alone mode): vs the oracle with the fused
+    160 × 128 tiles on the ring-buffered kernel (gemm_ring8_kernel): vs the oracle with the fused
     bias + LayerScale + residual epilogue, and bit-identical per image to the one-image call (mid kernels)."""
     from bridgelang_amd import ops
     Bn = 16

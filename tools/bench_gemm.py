@@ -1,5 +1,5 @@
-"""Micro-benchmark of the tiled GEMM on the OpenVLA-7B prefill / ViT shapes (B=16). BL_GEMM_TILE=128|256 forces a kernel."""
-import os, sys, torch
+"""Micro-benchmark of the tiled GEMM on the OpenVLA-7B prefill / ViT shapes (B=16)."""
+import sys, torch
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from bridgelang_amd import ops
@@ -14,7 +14,6 @@ shapes = [("llama qkv", M_LLM, 12288, 4096, ops.EPI_NONE), ("llama o", M_LLM, 40
           ("sig fc1", M_SIG, 4352, 1152, ops.EPI_BIAS_GELU), ("sig fc2", M_SIG, 1152, 4352, ops.EPI_BIAS_RES),
           ("proj fc1", M_SIG, 8704, 2176, ops.EPI_BIAS_GELU), ("proj fc2", M_SIG, 4096, 8704, ops.EPI_BIAS_GELU),
           ("square 8k", 8192, 8192, 8192, ops.EPI_NONE), ("square 4k", 4096, 4096, 4096, ops.EPI_NONE)]
-print("tile =", os.environ.get("BL_GEMM_TILE", "auto"))
 tot = 0.0
 ws = torch.empty(64 << 20, dtype=torch.uint8, device=dev)
 for name, M, N, K, epi in shapes:
