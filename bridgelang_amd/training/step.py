@@ -121,9 +121,9 @@ class ParamStore:
                  shard_params: bool = False, defer_grads: bool = False):
         """`extra`: additional trainable bf16 tensors outside the model's own table — (name, flat live tensor, decayed,
         bucket key), e.g. LoRA adapters. `only`: restrict the stage's trainable set to these HF names (whole fused groups;
-        diagnostics / tests: optimizer state for a handful of tensors instead of the model). `shard_params`: the
-        decoder-layer buckets keep NO full bf16 copy — each rank holds its 1/world slice (`own`), the unit is gathered
-        around its use (FSDP FULL_SHARD, fsdp.py:84-87; TrainStep(shard_params=True))."""
+        diagnostics / tests: optimizer state for a handful of tensors instead of the model). `shard_params`: the buckets
+        of every FSDP unit (param_sharded_key) keep NO full bf16 copy — each rank holds its 1/world slice (`own`), the unit
+        is gathered around its use (FSDP FULL_SHARD, fsdp.py:84-87; TrainStep(shard_params=True))."""
         self.w, self.stage = w, stage
         specs = w._specs()
         names = set(trainable_names(w, stage))
@@ -187,12 +187,12 @@ class ParamStore:
         self.total = lay.total
         self.n_params = sum(u.numel for u in self.units)
         dev = w.embed.device
-        # Parameter-sharded buckets (FSDP FULL_SHARD units = the decoder layers) occupy a contiguous range [lo, hi) of the
+        # Parameter-sharded buckets (FSDP FULL_SHARD units, param_sharded_key) occupy a contiguous range [lo, hi) of the
         # flat space that is CUT OUT of the addressing of the replicated buffers — the bf16 staging copy of the updated
         # parameters and the flat fp32 gradient: for those buckets a rank keeps only its 1/world slice of the parameters
-        # (`own`, bf16) and of the reduced gradient (`gshard`, fp32); the full gradient of ONE layer exists transiently in
-        # one of two slots (`gslots`) between that layer's weight-gradient GEMMs and its reduce-scatter, as FSDP frees a
-        # unit's full gradient after reduce-scatter (fsdp.py:160-168).
+        # (`own`, bf16) and of the reduced gradient (`gshard`, fp32); the full gradient of ONE unit exists transiently in
+        # one of its pool's two slots (`gslots`) between that unit's weight-gradient GEMMs and its reduce-scatter, as FSDP
+        # frees a unit's full gradient after reduce-scatter (fsdp.py:160-168).
         self.shard_params = shard_params
         sh = [b for b in lay.buckets if shard_params and param_sharded_key(b.key)]
         self.sharded_keys = {b.key for b in sh}
@@ -210,9 +210,8 @@ class ParamStore:
             self.own_off[b.key] = n_own
             n_own += lay.shard_numel(b)
             pool = pool_of(b.key)
-            idx = int(b.key[len("llm.layer"):]) if pool == "layers" else seen.get(pool, 0)
+            self.grad_slot_of[b.key] = (pool, seen.get(pool, 0) % 2)
             seen[pool] = seen.get(pool, 0) + 1
-            self.grad_slot_of[b.key] = (pool, idx % 2)
             self._slot_numel[pool] = max(self._slot_numel.get(pool, 0), b.numel)
         self._n_own = n_own
         self.own = torch.zeros(max(n_own, 8), dtype=torch.bfloat16, device=dev) if sh else None
@@ -220,7 +219,7 @@ class ParamStore:
         self.gslots: Dict[str, List[torch.Tensor]] = {}
         self.use_grad_slots = True          # TrainStep clears it when no collective runs (world 1): the "slice" is then the whole
                                             # bucket and the weight-gradient GEMMs write the persistent buffer directly
-        if not defer_grads:                 # TrainStep defers: it first gives the model's own decoder-layer allocation back
+        if not defer_grads:                 # TrainStep defers: it first gives the model's own unit allocations back
             self.alloc_grads()
         f = lambda: torch.zeros(max(lay.local_total, 8), dtype=torch.float32, device=dev)
         self.master, self.m, self.v = f(), f(), f()
@@ -245,8 +244,8 @@ class ParamStore:
         self.step_count = 0
 
     def alloc_grads(self) -> None:
-        """The fp32 gradient buffers: flat for the replicated buckets; this rank's slices + two transient layer slots for
-        the parameter-sharded ones."""
+        """The fp32 gradient buffers: flat for the replicated buckets; this rank's slices + two transient slots per pool
+        for the parameter-sharded ones."""
         if self.grad is not None:
             return
         dev = self.w.embed.device
@@ -302,8 +301,8 @@ class ParamStore:
         return self.grad_range(u.offset, u.numel)
 
     def grad_view(self, name_or_unit) -> torch.Tensor:
-        """fp32 gradient of a unit: [n, k] for a group, flat for a plain tensor (for a parameter-sharded decoder layer:
-        the transient slot the layer's weight-gradient GEMMs write — valid until the slot's next layer overwrites it)."""
+        """fp32 gradient of a unit: [n, k] for a group, flat for a plain tensor (for a parameter-sharded unit: the
+        transient slot its weight-gradient GEMMs write — valid until the slot's next unit overwrites it)."""
         u = name_or_unit if isinstance(name_or_unit, Unit) else self.by_name[name_or_unit]
         sl = self._unit_grad(u)
         return sl.view(u.group.n, u.group.k) if u.group is not None else sl
@@ -369,10 +368,11 @@ class TrainStep:
                  fp8_wgrad: bool = False):
         """`lora`: a training.lora.LoraAdapters → stage "lora": the base model is frozen and only the adapters train.
         `recompute`: keep only each decoder layer's input and replay its forward inside the backward pass.
-        `shard_params`: FSDP FULL_SHARD for the decoder layers (fsdp.py:84-87) — every rank keeps 1/world of each layer's
-        bf16 weights; a layer is all-gathered into one of two slots (and packed into the forward / dgrad layouts there) one
-        layer ahead of its forward and again ahead of its backward, on the communication stream; AdamW updates the
-        rank's slice in place. The model's own decoder-layer allocation is freed (`materialize_params()` brings it back).
+        `shard_params`: FSDP FULL_SHARD for every FSDP unit — decoder layers, ViT blocks and stems, projector, token
+        embeddings, lm_head (fsdp.py:84-87) — every rank keeps 1/world of each unit's bf16 weights; a unit is all-gathered
+        into one of its pool's two slots (and packed into the forward / dgrad layouts there) one unit ahead of its forward
+        and again ahead of its backward, on the communication stream; AdamW updates the rank's slice in place. The model's
+        own allocations of those units are freed (`materialize_params()` brings them back).
         `fp8`: the decoder layers' forward and input-gradient GEMMs (q/k/v, o, gate/up, down: 2/3 of the step's GEMM work)
         run W8A8 on the e4m3 MFMA path (BASELINE configs[4]) — activations / output gradients quantised per token row,
         weights per output channel (forward) and per input channel (the transposed dgrad copy), fp32 accumulation, bf16
@@ -415,12 +415,11 @@ class TrainStep:
         self.device = dev
         self._wT: Dict[int, torch.Tensor] = {}       # transposed packed weights for dgrad
         self._w8: Dict[int, dict] = {}              # packed bf16 weight (data_ptr) → its e4m3 forward / dgrad copies + scales
-        self._cur_layer = -1                   # decoder layer whose ops are being planned (slot tensors are shared by layers)
-        self._cur_unit: Optional[str] = None   # vision / head unit (bucket key) whose ops are being planned
-        self._units: Dict[str, dict] = {}      # parameter-sharded vision / head units (see _setup_unit_pools)
+        self._cur_unit: Optional[str] = None   # unit (bucket key) whose ops are being planned (slot views are shared by a pool's units)
+        self._units: Dict[str, dict] = {}      # parameter-sharded units (see _setup_unit_pools)
+        self._params_updated = torch.cuda.Event()      # end of the last optimizer_step: parameter gathers wait for it
         self._materialized = False
-        if shard_params:                       # first: the model's layer allocation is given back before anything else is reserved
-            self._setup_param_shards()
+        if shard_params:                       # first: the model's unit allocations are given back before anything else is reserved
             self._setup_unit_pools()
         if st.grad is None:
             st.use_grad_slots = self.comm.active
@@ -567,14 +566,12 @@ class TrainStep:
         self._fp8_scratch()
         if self.shard_params:                  # sharded layers are quantised in their gather (slots carry the e4m3 copies)
             return
-        for lw in self.w.layers:
-            for key in self._LAYER_KEYS:
-                p = getattr(lw, key)
-                n, k = p.shape[0] * 16, p.shape[1] * 32
-                self._w8[p.data_ptr()] = e = self._fp8_entry(n, k, dev)
-                rm = ops.unpack_weight(p).contiguous()                   # start-up only; later the optimizer's bf16 copy
-                ops.run_all(self._fp8_weight_ops(rm, e))
-                del rm
+        for _, _, gi, _ in self.w.unit_fields("layers"):
+            g = self.w.groups[gi]
+            self._w8[g.packed.data_ptr()] = e = self._fp8_entry(g.n, g.k, dev)
+            rm = ops.unpack_weight(g.packed).contiguous()                # start-up only; later the optimizer's bf16 copy
+            ops.run_all(self._fp8_weight_ops(rm, e))
+            del rm
 
     def _fp8_scratch(self) -> None:
         if not hasattr(self, "_q_tmp"):
@@ -602,95 +599,39 @@ class TrainStep:
                 T.transpose_pad(rm, t, n, run=False), ops.quantize_rows_fp8(t, qT, e["swT"], run=False)[2],
                 T.pack(as_pairs(qT), e["wT8"], run=False)]
 
-    # ---- parameter sharding (FSDP FULL_SHARD for the decoder layers) ---------------------------------------------------
-    _LAYER_KEYS = ("qkv_w", "o_w", "gu_w", "down_w")
-
-    def _setup_param_shards(self) -> None:
-        """Two gather slots (logical bf16 bucket + the four packed forward weights + their transposed dgrad copies); every
-        decoder layer's weight tensors are re-pointed at slot l % 2 and the model's own layer allocation is freed."""
-        w, st, lay, dev = self.w, self.store, self.store.layout, self.device
-        by_group = {id(u.group): u for u in st.units if u.group is not None}
-        self._layer_units: Dict[Tuple[int, str], Unit] = {
-            (l, key): by_group[id(w.groups[gi])] for l, key, gi, _ in w._layer_views if id(w.groups[gi]) in by_group}
-        self._sharded_layers = sorted({l for l, _ in self._layer_units})
-        sizes = {lay.buckets[self._layer_units[(l, "qkv_w")].bucket].numel for l in self._sharded_layers}
-        assert len(sizes) == 1 and len(self._layer_units) == 4 * len(self._sharded_layers), "decoder layers are uniform units"
-        bucket_numel = next(iter(sizes))
-        L0 = w.layers[0]
-        self._slots: List[dict] = []
-        for _ in range(2):
-            slot = {"flat": torch.zeros(bucket_numel, dtype=torch.bfloat16, device=dev)}
-            for key in self._LAYER_KEYS:
-                p = getattr(L0, key)
-                slot[key] = torch.zeros(tuple(p.shape), dtype=torch.bfloat16, device=dev)
-                if not self.fp8:
-                    slot[key + "T"] = torch.zeros(p.shape[1] * 2, p.shape[0] // 2, 64, 8, dtype=torch.bfloat16, device=dev)
-            slot["ready"], slot["free"] = torch.cuda.Event(), torch.cuda.Event()
-            slot["grads_flushed"] = torch.cuda.Event()     # the gradient slot of the same parity has been reduced and kept
-            self._slots.append(slot)
-        self._slot_key = {slot[k].data_ptr(): k for slot in self._slots for k in self._LAYER_KEYS}
-        if self.fp8:
-            self._fp8_scratch()
-            for slot in self._slots:
-                for k in self._LAYER_KEYS:
-                    p = slot[k]
-                    self._w8[p.data_ptr()] = self._fp8_entry(p.shape[0] * 16, p.shape[1] * 32, dev)
-        for slot in self._slots:
-            for k in self._LAYER_KEYS:
-                if k + "T" in slot:
-                    self._wT[slot[k].data_ptr()] = slot[k + "T"]
-        if len(self._sharded_layers) != self.dims.llm_layers:
-            raise ValueError("parameter sharding needs every decoder layer trainable (vla-full-train / vla-train)")
-        if w.layers_resident:
-            w.release_layer_weights(self._slots)
-        else:                                  # re-planned step over an already sharded model
-            w.repoint_layer_weights(self._slots)
-        # per-layer prepared pack ops: logical [n, k] rows of the gathered bucket → forward and dgrad layouts of the slot
-        self._pack_ops: Dict[int, Tuple[List[Op], List[Op]]] = {}          # layer → (forward pass, backward pass)
-        for l in self._sharded_layers:
-            slot = self._slots[l % 2]
-            b = lay.buckets[self._layer_units[(l, "qkv_w")].bucket]
-            fwd, bwd = [], []
-            for key in self._LAYER_KEYS:
-                u = self._layer_units[(l, key)]
-                rm = slot["flat"][u.offset - b.offset:u.offset - b.offset + u.numel].view(u.group.n, u.group.k)
-                if self.fp8:                   # the slot carries the e4m3 copies (+ scales) instead of the bf16 layouts
-                    q = self._fp8_weight_ops(rm, self._w8[slot[key].data_ptr()])
-                    fwd += q[:2]
-                    bwd += q[2:]
-                    continue
-                fwd.append(T.pack(rm, slot[key], run=False))                              # forward operand layout
-                bwd.append(T.transpose_pack(rm, slot[key + "T"], u.group.n, run=False))   # dgrad operand layout
-            self._pack_ops[l] = (fwd, bwd + fwd if self.recompute else bwd)
-
-
-    # ---- the other FSDP units: ViT blocks + patch embeddings ("vision" pool), projector / token embeddings / lm_head ("head") ----
+    # ---- parameter sharding (FSDP FULL_SHARD): decoder layers ("layers" pool), ViT blocks + patch embeddings ("vision"),
+    #      projector / token embeddings / lm_head ("head") ----
     def _setup_unit_pools(self) -> None:
-        """Same machinery as the decoder layers for the reference's remaining FSDP units (prismatic.py:285-306,
-        dinosiglip_vit.py:136-140, fsdp.py:160-168): per pool TWO gather slots — the logical bf16 bucket + one buffer of
-        forward layouts + one of dgrad layouts, each sized for the pool's largest unit and carved into per-unit views — the
-        model's tensors are re-pointed at the views of slot (unit index % 2) and the pool's own allocation is freed. A unit is
+        """One machinery for every FSDP unit of the reference (prismatic.py:285-306, dinosiglip_vit.py:136-140,
+        fsdp.py:160-168): per pool TWO gather slots — the logical bf16 bucket + one buffer of forward layouts + one of dgrad
+        layouts, each sized for the pool's largest unit and carved into per-unit views — the model's tensors are re-pointed
+        at the views of slot (unit index % 2; decoder layer l: l % 2) and the pool's own allocation is freed. A unit is
         all-gathered (and packed) into its slot one unit ahead of its use, on the communication stream; its weight gradients
         go to one of two transient fp32 slots of the pool and are reduce-scattered into the rank's persistent slice right
         after the unit's last weight-gradient GEMM. The token embeddings are a plain [vocab, D] tensor: read in place from the
-        gathered bucket."""
+        gathered bucket. Under `fp8` a decoder layer's gather quantises instead of packing: the slot carries the e4m3
+        forward / dgrad copies (+ scales, `_w8`) and no bf16 dgrad layouts."""
         w, st, lay, dev = self.w, self.store, self.store.layout, self.device
         by_group = {id(u.group): u for u in st.units if u.group is not None}
         by_key = {b.key: b for b in lay.buckets}
         self._pool_slots: Dict[str, List[dict]] = {}
-        for pool in ("vision", "head"):
+        if self.fp8:
+            self._fp8_scratch()
+        for pool in ("layers", "vision", "head"):
             fields = w.unit_fields(pool)                                   # (unit key, path, group index | None, HF name | None)
             keys = list(dict.fromkeys(k for k, *_ in fields))
             live = [k for k in keys if k in st.sharded_keys]
             if not live:
                 continue
             if len(live) != len(keys):
-                raise ValueError(f"parameter sharding needs every unit of the {pool} pool trainable or none ({set(keys) - set(live)} frozen)")
+                raise ValueError(f"parameter sharding needs every unit of the {pool} pool trainable or none "
+                                 f"({sorted(set(keys) - set(live))} frozen; the decoder layers: vla-full-train / vla-train)")
+            fp8 = self.fp8 and pool == "layers"
             numel = lambda k: sum(w.groups[gi].n * w.groups[gi].k for kk, _, gi, _ in fields if kk == k and gi is not None)
             flat_max, pk_max = max(by_key[k].numel for k in keys), max(max(numel(k) for k in keys), 8)
             slots = [dict(flat=torch.zeros(flat_max, dtype=torch.bfloat16, device=dev),
                           fwd=torch.zeros(pk_max, dtype=torch.bfloat16, device=dev),
-                          bwd=torch.zeros(pk_max, dtype=torch.bfloat16, device=dev),
+                          bwd=None if fp8 else torch.zeros(pk_max, dtype=torch.bfloat16, device=dev),
                           ready=torch.cuda.Event(), free=torch.cuda.Event(), grads_flushed=torch.cuda.Event()) for _ in range(2)]
             self._pool_slots[pool] = slots
             views: Dict[tuple, torch.Tensor] = {}
@@ -706,12 +647,20 @@ class TrainStep:
                         u = by_group[id(w.groups[gi])]
                         n, kd = u.group.n, u.group.k
                         fv = slot["fwd"][off:off + n * kd].view(n // 16, kd // 32, 64, 8)
-                        tv = slot["bwd"][off:off + n * kd].view(kd // 16, n // 32, 64, 8)
-                        off += n * kd
                         rm = slot["flat"][u.offset - b.offset:u.offset - b.offset + u.numel].view(n, kd)
-                        info["fwd_ops"].append(T.pack(rm, fv, run=False))
-                        info["bwd_ops"].append(T.transpose_pack(rm, tv, n, run=False))
-                        info["by_ptr"][fv.data_ptr()], info["T"][fv.data_ptr()] = u, tv
+                        if fp8:                                            # the units of one parity share the slot's e4m3 copies
+                            if fv.data_ptr() not in self._w8:
+                                self._w8[fv.data_ptr()] = self._fp8_entry(n, kd, dev)
+                            q = self._fp8_weight_ops(rm, self._w8[fv.data_ptr()])
+                            info["fwd_ops"] += q[:2]
+                            info["bwd_ops"] += q[2:]
+                        else:
+                            tv = slot["bwd"][off:off + n * kd].view(kd // 16, n // 32, 64, 8)
+                            info["fwd_ops"].append(T.pack(rm, fv, run=False))
+                            info["bwd_ops"].append(T.transpose_pack(rm, tv, n, run=False))
+                            info["T"][fv.data_ptr()] = tv
+                        off += n * kd
+                        info["by_ptr"][fv.data_ptr()] = u
                         views[(k, path)] = fv
                     else:                                                  # token embeddings: used where the gather lands them
                         u = st.by_name[name]
@@ -719,6 +668,8 @@ class TrainStep:
                         views[(k, path)] = slot["flat"][u.offset - b.offset:u.offset - b.offset + u.numel].view(getattr(obj, attr).shape)
                         info["plain"].append((path, u))
                         u.dst = None                                       # the optimizer writes the rank's slice, nothing is copied back
+                if self.recompute and pool == "layers":                    # the backward pass replays the layer's forward
+                    info["bwd_ops"] = info["bwd_ops"] + info["fwd_ops"]
                 self._units[k] = info
             if w.pool_resident(pool):
                 w.release_unit_weights(pool, views)
@@ -733,6 +684,7 @@ class TrainStep:
         """Issue unit `key`'s parameter gather + packing (forward layouts, dgrad layouts, or both) on the communication stream."""
         def fn():
             info, slot, side = self._units[key], self._u_slot(key), self._comm_stream
+            side.wait_event(self._params_updated)             # AdamW (main stream) has written the rank's slice
             side.wait_event(slot["free"])                     # the unit that used this slot before is done with it
             with torch.cuda.stream(side):
                 b = info["bucket"]
@@ -796,88 +748,29 @@ class TrainStep:
             post.append(self._u_gather(nxt, backward))
         return pre + body + post
 
-    def _layer_bucket(self, l: int):
-        return self.store.layout.buckets[self._layer_units[(l, "qkv_w")].bucket]
-
-    def _gather_ops(self, l: int, backward: bool = False) -> Op:
-        """Issue layer l's parameter gather + packing on the communication stream (runs ahead of the compute stream)."""
-        def fn():
-            slot, side = self._slots[l % 2], self._comm_stream
-            side.wait_event(slot["free"])                     # the layer that used this slot before is done with it
-            with torch.cuda.stream(side):
-                b = self._layer_bucket(l)
-                self.comm.all_gather_into(slot["flat"][:b.numel], self.store.own_slice(b))
-                ops.run_all(self._pack_ops[l][1 if backward else 0])
-                slot["ready"].record(side)
-        return ops.glue("gather_layer_params", fn, ())
-
-    def _await_ops(self, l: int) -> Op:
-        return ops.glue("await_layer_params", lambda: torch.cuda.current_stream().wait_event(self._slots[l % 2]["ready"]), ())
-
-    def _release_ops(self, l: int) -> Op:
-        return ops.glue("release_layer_params", lambda: self._slots[l % 2]["free"].record(torch.cuda.current_stream()), ())
-
-    def _await_grad_slot_ops(self, l: int) -> Op:
-        """Before layer l's weight-gradient GEMMs write gradient slot l % 2: the flush of the layer that used it last
-        (l + 2) must be over."""
-        return ops.glue("await_grad_slot", lambda: torch.cuda.current_stream().wait_event(self._slots[l % 2]["grads_flushed"]), ())
-
-    def _flush_grads_ops(self, l: int) -> Op:
-        """After layer l's last weight-gradient GEMM: on the communication stream, reduce-scatter the layer's full fp32
-        gradient (slot l % 2) over the ranks — in place, this rank's slice of the slot receives the sum (bf16 wire copy
-        when reduce_dtype says so) — and keep that slice in the persistent sharded gradient; the slot is then free for
-        layer l - 2. The full gradient of a decoder layer therefore lives for two layers' worth of backward, as under
-        FSDP (fsdp.py:160-168), instead of the whole step."""
-        def fn():
-            st, lay, side = self.store, self.store.layout, self._comm_stream
-            if not st.use_grad_slots:                # nothing to reduce or move: the GEMMs wrote the persistent buffer
-                return
-            b = self._layer_bucket(l)
-            slot = st.grad_slot(b)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                scratch = self._rs_scratch[:b.numel] if self._rs_scratch is not None else None
-                self.comm.reduce_scatter_bucket(slot, b, scratch)
-                n = lay.shard_numel(b)
-                T.copy_f32(slot[lay.rank * n:(lay.rank + 1) * n], st.reduced_grad(b))
-                self._slots[l % 2]["grads_flushed"].record(side)
-        return ops.glue("flush_layer_grads", fn, ())
-
     def _unit_of(self, packed: torch.Tensor) -> Optional[Unit]:
         if self._cur_unit is not None and packed.data_ptr() in self._units[self._cur_unit]["by_ptr"]:
             return self._units[self._cur_unit]["by_ptr"][packed.data_ptr()]     # slot views are shared by the units of a pool
-        if self.shard_params and packed.data_ptr() in self._slot_key:
-            assert self._cur_layer >= 0, "slot weights are only addressed while a decoder layer is being planned"
-            return self._layer_units[(self._cur_layer, self._slot_key[packed.data_ptr()])]
         return self.store.unit_of_packed(packed)
 
     def materialize_params(self) -> None:
-        """Bring the decoder layers back into the model's own allocation (gather every layer, pack) — for inference,
+        """Bring every parameter-sharded unit back into the model's own allocation (gather each unit, pack) — for inference,
         `state_dict()` / `save_pretrained` after parameter-sharded training. The step's plans address the slots, so this
         step object cannot train afterwards."""
         if not self.shard_params or self._materialized:
             return
-        torch.cuda.synchronize()
         w, st = self.w, self.store
-        w.restore_layer_weights()
-        slot = self._slots[0]
-        for l in self._sharded_layers:
-            b = self._layer_bucket(l)
-            self.comm.all_gather_into(slot["flat"][:b.numel], st.own_slice(b))
-            for key in self._LAYER_KEYS:
-                u = self._layer_units[(l, key)]
-                rm = slot["flat"][u.offset - b.offset:u.offset - b.offset + u.numel].view(u.group.n, u.group.k)
-                T.pack(rm, getattr(w.layers[l], key))
-        for pool, slots in getattr(self, "_pool_slots", {}).items():
+        by_group = {id(u.group): u for u in st.units if u.group is not None}
+        for pool, slots in self._pool_slots.items():
             w.restore_unit_weights(pool)
-            by_group = {id(u.group): u for u in st.units if u.group is not None}
+            cur = None
             for key, path, gi, name in w.unit_fields(pool):
                 info = self._units[key]
                 b, slot = info["bucket"], slots[info["parity"]]
-                torch.cuda.synchronize()                    # a slot is re-used by the next unit of its parity
-                self.comm.all_gather_into(slot["flat"][:b.numel], st.own_slice(b))
+                if key != cur:
+                    torch.cuda.synchronize()                # a slot is re-used by the next unit of its parity
+                    self.comm.all_gather_into(slot["flat"][:b.numel], st.own_slice(b))
+                    cur = key
                 obj, attr = w._attr_of(path)
                 u = by_group[id(w.groups[gi])] if gi is not None else st.by_name[name]
                 rm = slot["flat"][u.offset - b.offset:u.offset - b.offset + u.numel]
@@ -1106,17 +999,9 @@ class TrainStep:
         plan.append(ops.embed_splice(self.input_ids, w.embed, self.x[0].view(B, S, D), d.n_patches, run=False))
         if head:
             plan.append(self._u_release("llm.embed"))
-        NL = d.llm_layers
-        if self.shard_params:
-            plan.append(self._gather_ops(0))
-        for l in range(NL):
-            if self.shard_params:          # this layer's weights have landed; the next layer's gather runs under its compute
-                plan.append(self._await_ops(l))
-                if l + 1 < NL:
-                    plan.append(self._gather_ops(l + 1))
-            plan += self._layer_forward(l)
-            if self.shard_params:
-                plan.append(self._release_ops(l))
+        lseq = [f"llm.layer{l:02d}" for l in range(d.llm_layers)]
+        for l in range(d.llm_layers):      # sharded: the next layer's gather runs under this layer's compute
+            plan += self._u_seq(lseq, l, False, self._layer_forward(l))
         if head:
             plan.append(self._u_await("llm.lm_head"))
         plan += [ops.rmsnorm(self.x[-1], w.norm, self.hn, d.rms_eps, run=False),
@@ -1168,37 +1053,30 @@ class TrainStep:
         assert self.dqkv.stride(0) == lq and self.dao.stride(0) == lo
         strides, so = (S * lq, hd, lq), (S * lo, hd, lo)
         stop_layer = self._lowest_needed_layer()
-        if self.shard_params:
-            plan.append(self._gather_ops(d.llm_layers - 1, backward=True))
-        for l in range(d.llm_layers - 1, stop_layer - 1, -1):
+        lseq = [f"llm.layer{l:02d}" for l in range(d.llm_layers - 1, stop_layer - 1, -1)]
+        for j, l in enumerate(range(d.llm_layers - 1, stop_layer - 1, -1)):
             lw, b = w.layers[l], f"{lm}.layers.{l}"
-            self._cur_layer = l
-            if self.shard_params:
-                plan.append(self._await_ops(l))
-                if l - 1 >= stop_layer:
-                    plan.append(self._gather_ops(l - 1, backward=True))
-                plan.append(self._await_grad_slot_ops(l))
+            self._cur_unit = lseq[j] if lseq[j] in self._units else None
+            body: List[Op] = []                # this layer's ops: one parameter-sharded unit
             if self.recompute:         # incl. the top layer: the plan stays idempotent (graph capture runs it twice)
-                plan += self._layer_forward(l, with_down=False)
-            plan += self._lin_bwd_act(dx, self.act[l], lw.down_w, self.gu[l], self.dgu, self.dact, "swiglu")
-            plan += lb(self.dgu, self.h2[l], lw.gu_w, self.dh)
-            plan.append(T.rmsnorm_backward(self.xm[l], lw.ln2, self.dh, dx2, self._gvec(f"{b}.post_attention_layernorm.weight", D),
+                body += self._layer_forward(l, with_down=False)
+            body += self._lin_bwd_act(dx, self.act[l], lw.down_w, self.gu[l], self.dgu, self.dact, "swiglu")
+            body += lb(self.dgu, self.h2[l], lw.gu_w, self.dh)
+            body.append(T.rmsnorm_backward(self.xm[l], lw.ln2, self.dh, dx2, self._gvec(f"{b}.post_attention_layernorm.weight", D),
                                            self.norm_ws, d.rms_eps, dres=dx, run=False))
-            plan += lb(dx2, self.ao[l], lw.o_w, self.dao)
+            body += lb(dx2, self.ao[l], lw.o_w, self.dao)
             qkv, dq = self.qkv[l], self.dqkv
-            plan.append(T.attention_backward(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.dao, self.lse[l], self.delta,
+            body.append(T.attention_backward(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.dao, self.lse[l], self.delta,
                                              dq, dq[:, D:], dq[:, 2 * D:], B=B, H=H, Sq=S, Skv=S, head_dim=hd,
                                              q_strides=strides, k_strides=strides, v_strides=strides,
                                              o_strides=so, causal=True, key_mask=self.key_mask, run=False))
-            plan.append(T.rope_backward(dq, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, run=False))
-            plan += lb(dq, self.h1[l], lw.qkv_w, self.dh)
-            if self.shard_params:
-                plan.append(self._release_ops(l))
-                plan.append(self._flush_grads_ops(l))      # reduce-scatter + keep this rank's slice; frees the gradient slot
-            self._ready.append((len(plan), f"llm.layer{l:02d}"))
+            body.append(T.rope_backward(dq, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, run=False))
+            body += lb(dq, self.h1[l], lw.qkv_w, self.dh)
+            self._cur_unit = None
+            plan += self._u_seq(lseq, j, True, body)             # sharded: the flush reduce-scatters and frees the gradient slot
+            self._ready.append((len(plan), lseq[j]))
             plan.append(T.rmsnorm_backward(self.x[l], lw.ln1, self.dh, dx, self._gvec(f"{b}.input_layernorm.weight", D),
                                            self.norm_ws, d.rms_eps, dres=dx2, run=False))
-        self._cur_layer = -1
         if stop_layer > 0:
             return plan
         # dx = gradient of inputs_embeds [B, S, D]
@@ -1391,7 +1269,7 @@ class TrainStep:
                 entries.append(T.be_copy(st.stage_view(u.offset, u.numel), u.dst))
         for u in st.units:
             if u.group is None or st.layout.buckets[u.bucket].key in st.sharded_keys:
-                continue                                          # parameter-sharded layers are packed when gathered
+                continue                                          # parameter-sharded units are packed when gathered
             n, k = u.group.n, u.group.k
             rm = st.stage_view(u.offset, u.numel).view(n, k)
             key = u.group.packed.data_ptr()
@@ -1583,6 +1461,7 @@ class TrainStep:
         if self.comm.active:
             main.wait_stream(self._comm_stream)
         self._replay("repack", self.repack_ops, graph)
+        self._params_updated.record(main)
 
     def step(self, lr: float, graph: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """forward → backward → clip → AdamW. Returns (loss, grad norm) as device scalars (no host sync here)."""

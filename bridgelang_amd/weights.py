@@ -392,50 +392,18 @@ class VLAWeights:
     placements: Dict[str, Placement] = field(default_factory=dict)
     groups: List[PackedGroup] = field(default_factory=list)
     passthrough: Dict[str, torch.Tensor] = field(default_factory=dict)   # passthrough_specs(): stored, never executed
-    layer_arena: Optional[Arena] = None      # the decoder layers' GEMM weights: a second allocation that parameter-sharded
-                                             # training can give back (release_layer_weights)
-    _layer_views: List[tuple] = field(default_factory=list)             # (layer index, field, group index, arena view index)
-    # the other FSDP units (prismatic.py:285-306: every ViT block, the projector; fsdp.py:160-168: the root's embeddings and
-    # lm_head) in two more releasable allocations: "vision" (patch embeddings + blocks of both towers) and "head"
-    # (projector, token embeddings, lm_head). Parameter-sharded training re-points their tensors at gather slots too.
+    # the FSDP units (prismatic.py:285-306: every decoder layer, every ViT block, the projector; fsdp.py:160-168: the root's
+    # embeddings and lm_head) live in three allocations that parameter-sharded training can give back, re-pointing their
+    # tensors at gather slots: "layers" (the decoder layers' GEMM weights), "vision" (patch embeddings + blocks of both
+    # towers) and "head" (projector, token embeddings, lm_head).
     unit_arenas: Dict[str, Arena] = field(default_factory=dict)
     _unit_views: List[tuple] = field(default_factory=list)  # (pool, unit key, path to the attribute, group index | None, view index, HF name | None)
 
-    # ---- parameter-sharded training (training/step.py, shard_params): decoder-layer GEMM weights leave the device -------
+    # ---- parameter-sharded training (training/step.py, shard_params): the units' weights leave the device ------------------
     @property
     def layers_resident(self) -> bool:
-        return self.layer_arena is not None and self.layer_arena.buf is not None
+        return self.pool_resident("layers")
 
-    def repoint_layer_weights(self, slots: List[Dict[str, torch.Tensor]]) -> None:
-        """Point every decoder layer's packed GEMM weights (and their PackedGroups) at the gather slots: layer l uses
-        slots[l % len(slots)]."""
-        self.__dict__.pop("_fp8_layers", None)
-        for l, key, gi, _ in self._layer_views:
-            t = slots[l % len(slots)][key]
-            assert tuple(t.shape) == tuple(getattr(self.layers[l], key).shape), (l, key)
-            setattr(self.layers[l], key, t)
-            self.groups[gi].packed = t
-
-    def release_layer_weights(self, slots: List[Dict[str, torch.Tensor]]) -> int:
-        """repoint_layer_weights + free the layers' allocation. Returns the bytes given back. Anything that still holds
-        the old views (engine plans built before the call) keeps the storage alive: callers drop those first."""
-        if not self.layers_resident:
-            raise RuntimeError("decoder-layer weights are not resident")
-        self.repoint_layer_weights(slots)
-        self.layer_arena.buf = None
-        return self.layer_arena.nbytes
-
-    def restore_layer_weights(self) -> None:
-        """Re-allocate the decoder layers' GEMM weights (zero-filled; the caller gathers and packs them)."""
-        if self.layers_resident:
-            return
-        self.layer_arena.commit()
-        for l, key, gi, idx in self._layer_views:
-            t = self.layer_arena.view(idx)
-            setattr(self.layers[l], key, t)
-            self.groups[gi].packed = t
-
-    # ---- the same for the vision / head units -----------------------------------------------------------------------------
     def _attr_of(self, path: tuple):
         obj = self
         for q in path[:-1]:
@@ -452,6 +420,8 @@ class VLAWeights:
 
     def repoint_unit_weights(self, pool: str, views: Dict[tuple, torch.Tensor]) -> None:
         """views[(unit key, attribute path)] = the tensor (a gather-slot view of the same shape) that replaces it."""
+        if pool == "layers":
+            self.__dict__.pop("_fp8_layers", None)        # derived e4m3 copies (engine.py) follow the bf16 weights
         for pl, key, path, gi, _, name in self._unit_views:
             if pl != pool or (key, path) not in views:
                 continue
@@ -465,6 +435,8 @@ class VLAWeights:
                 self.placements[name].dst = t
 
     def release_unit_weights(self, pool: str, views: Dict[tuple, torch.Tensor]) -> int:
+        """repoint_unit_weights + free the pool's allocation. Returns the bytes given back. Anything that still holds the
+        old views (engine plans built before the call) keeps the storage alive: callers drop those first."""
         if not self.pool_resident(pool):
             raise RuntimeError(f"the {pool} weights are not resident")
         self.repoint_unit_weights(pool, views)
@@ -564,13 +536,10 @@ def allocate(dims: VLADims, device: torch.device | str = "cuda") -> VLAWeights:
     """Reserve the arena and build the name → placement table. Tensors are zero until filled."""
     device = torch.device(device)
     arena = Arena(device)
-    layer_arena = Arena(device)                  # decoder-layer GEMM weights (see VLAWeights.release_layer_weights)
-    unit_arenas = {"vision": Arena(device), "head": Arena(device)}   # the other FSDP units (see VLAWeights.release_unit_weights)
+    unit_arenas = {pool: Arena(device) for pool in ("layers", "vision", "head")}   # the FSDP units (see VLAWeights.release_unit_weights)
     unit_views: List[tuple] = []
     pending_units: List[Tuple[str, int, Callable[[torch.Tensor], None]]] = []
-    layer_views: List[tuple] = []
     pending: List[Tuple[int, Callable[[torch.Tensor], None]]] = []
-    pending_layers: List[Tuple[int, Callable[[torch.Tensor], None]]] = []
     plain: Dict[str, tuple] = {}                 # name → (holder, key, offset, rows, cols, ld)
     grouped: Dict[str, tuple] = {}               # name → (group id, offset, rows, cols, ld)
     group_defs: List[tuple] = []                 # (holder, key, n, k)
@@ -578,20 +547,13 @@ def allocate(dims: VLADims, device: torch.device | str = "cuda") -> VLAWeights:
     def dense(holder, key, shape):
         pending.append((arena.reserve(tuple(shape)), lambda x, h=holder, k=key: h.__setitem__(k, x)))
 
-    def gemm_w(holder, key, n, k, layer: Optional[int] = None, unit: Optional[tuple] = None) -> int:
-        """`unit` = (pool, bucket key, attribute path on the finished VLAWeights) for the vision / head units."""
+    def gemm_w(holder, key, n, k, unit: tuple) -> int:
+        """`unit` = (pool, bucket key, attribute path on the finished VLAWeights)."""
         assert n % 16 == 0 and k % 64 == 0, (key, n, k)
         setter = lambda x, h=holder, kk=key: h.__setitem__(kk, x)
-        if unit is not None:
-            idx = unit_arenas[unit[0]].reserve((n // 16, k // 32, 64, 8))
-            pending_units.append((unit[0], idx, setter))
-            unit_views.append((unit[0], unit[1], unit[2], len(group_defs), idx, None))
-        elif layer is None:
-            pending.append((arena.reserve((n // 16, k // 32, 64, 8)), setter))
-        else:
-            idx = layer_arena.reserve((n // 16, k // 32, 64, 8))
-            pending_layers.append((idx, setter))
-            layer_views.append((layer, key, len(group_defs), idx))
+        idx = unit_arenas[unit[0]].reserve((n // 16, k // 32, 64, 8))
+        pending_units.append((unit[0], idx, setter))
+        unit_views.append((unit[0], unit[1], unit[2], len(group_defs), idx, None))
         group_defs.append((holder, key, n, k))
         return len(group_defs) - 1
 
@@ -646,30 +608,28 @@ def allocate(dims: VLADims, device: torch.device | str = "cuda") -> VLAWeights:
     layer_h = [dict() for _ in range(dims.llm_layers)]
     for i, lh in enumerate(layer_h):
         bn = f"{lm}.layers.{i}"
+        un = lambda f: ("layers", f"llm.layer{i:02d}", ("layers", i, f))
         dense(lh, "ln1", (L,)); plain[f"{bn}.input_layernorm.weight"] = (lh, "ln1", 0, 1, L, L)
         dense(lh, "ln2", (L,)); plain[f"{bn}.post_attention_layernorm.weight"] = (lh, "ln2", 0, 1, L, L)
-        g = gemm_w(lh, "qkv_w", 3 * L, L, layer=i)
+        g = gemm_w(lh, "qkv_w", 3 * L, L, unit=un("qkv_w"))
         for j, n in enumerate(("q_proj", "k_proj", "v_proj")):
             grouped[f"{bn}.self_attn.{n}.weight"] = (g, j * L * L, L, L, L)
-        g = gemm_w(lh, "o_w", L, L, layer=i); grouped[f"{bn}.self_attn.o_proj.weight"] = (g, 0, L, L, L)
-        g = gemm_w(lh, "gu_w", 2 * I, L, layer=i)
+        g = gemm_w(lh, "o_w", L, L, unit=un("o_w")); grouped[f"{bn}.self_attn.o_proj.weight"] = (g, 0, L, L, L)
+        g = gemm_w(lh, "gu_w", 2 * I, L, unit=un("gu_w"))
         grouped[f"{bn}.mlp.gate_proj.weight"] = (g, 0, I, L, 2 * L)      # row 2j   = gate_j
         grouped[f"{bn}.mlp.up_proj.weight"] = (g, L, I, L, 2 * L)        # row 2j+1 = up_j
-        g = gemm_w(lh, "down_w", L, I, layer=i); grouped[f"{bn}.mlp.down_proj.weight"] = (g, 0, L, I, I)
+        g = gemm_w(lh, "down_w", L, I, unit=un("down_w")); grouped[f"{bn}.mlp.down_proj.weight"] = (g, 0, L, I, I)
     dense(top, "norm", (L,)); plain[f"{lm}.norm.weight"] = (top, "norm", 0, 1, L, L)
     g = gemm_w(top, "lm_head", dims.vocab, L, unit=("head", "llm.lm_head", ("lm_head",)))
     grouped["language_model.lm_head.weight"] = (g, 0, dims.vocab, L, L)
 
     arena.commit()
-    layer_arena.commit()
     for a in unit_arenas.values():
         a.commit()
     for pool, idx, setter in pending_units:
         setter(unit_arenas[pool].view(idx))
     for idx, setter in pending:
         setter(arena.view(idx))
-    for idx, setter in pending_layers:
-        setter(layer_arena.view(idx))
 
     def mk_tower(t: TowerDims, h: dict) -> TowerW:
         return TowerW(t, h["patch_w"], h["patch_b"], h["pos"], h["prefix"], [BlockW(**b) for b in h["blocks"]])
@@ -677,7 +637,6 @@ def allocate(dims: VLADims, device: torch.device | str = "cuda") -> VLAWeights:
     w = VLAWeights(dims, arena, mk_tower(dims.dino, hd), mk_tower(dims.siglip, hs),
                    top["fc1_w"], top["fc1_b"], top["fc2_w"], top["fc2_b"], top["fc3_w"], top["fc3_b"], top["embed"],
                    [LayerW(**lh) for lh in layer_h], top["norm"], top["lm_head"])
-    w.layer_arena, w._layer_views = layer_arena, layer_views
     w.unit_arenas, w._unit_views = unit_arenas, unit_views
     w.groups = [PackedGroup(holder[key], n, k) for holder, key, n, k in group_defs]
     for name, (holder, key, off, rows, cols, ld) in plain.items():

@@ -277,7 +277,8 @@ def test_cfg5_full_depth_13b_full_shard_fp8_recompute(dev):
     lw = w.layers[39]
     from bridgelang_amd import ops
     got = ops.unpack_weight(lw.o_w).float()
-    u = ts._layer_units[(39, "o_w")]                     # world 1: the rank's master slice is the whole flat space
+    u = ts.store.by_name["language_model.model.layers.39.self_attn.o_proj.weight"]     # world 1: the rank's master slice is the whole flat space
+    assert u in ts._units["llm.layer39"]["by_ptr"].values()
     want = ts.store.master[u.offset:u.offset + u.numel].view(u.group.n, u.group.k).to(torch.bfloat16).float()
     assert torch.equal(got, want), "materialised layer weights must be the bf16 rounding of the fp32 masters"
     del ts, w

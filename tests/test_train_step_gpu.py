@@ -214,7 +214,8 @@ def test_parameter_sharding_equals_replicated_weights(dev, stage, recompute):
             loss, norm = ts.step(1e-3, graph=(step == 2))
             log.append((loss.item(), norm.item()))
         if sp:
-            assert all(w.layers[l].qkv_w.data_ptr() == ts._slots[l % 2]["qkv_w"].data_ptr() for l in range(dims.llm_layers))
+            slots = ts._pool_slots["layers"]              # qkv_w is the first view carved from the slot's forward layouts
+            assert all(w.layers[l].qkv_w.data_ptr() == slots[l % 2]["fwd"].data_ptr() for l in range(dims.llm_layers))
             from bridgelang_amd.engine import OpenVLAEngine
             with pytest.raises(RuntimeError):               # no inference over a model whose layers are sharded out
                 OpenVLAEngine(w, 2, 18)
@@ -231,6 +232,28 @@ def test_parameter_sharding_equals_replicated_weights(dev, stage, recompute):
         assert torch.equal(v, out[True][2][k]), k
     for n, v in out[True][3].items():                   # the materialised live weights are the rounded masters
         assert torch.equal(out[True][2][n], v), n
+
+
+def test_parameter_sharding_without_host_syncs_equals_replicated_weights(dev):
+    """Steps issued back to back with no host sync in between: the first parameter gathers of step n + 1 run on the
+    communication stream and must wait for step n's AdamW (main stream) to have written the rank's slices. Losses, norms
+    and masters are read only at the end and must be bit-identical to the replicated run."""
+    from bridgelang_amd.training.step import TrainStep
+    from bridgelang_amd.weights import allocate, tiny_dims
+    dims = tiny_dims()
+    ids, mask, labels, pv = make_batch(dims, 2, 18, seed=30)
+    out = {}
+    for sp in (False, True):
+        w = allocate(dims, dev).fill_synthetic(seed=5)
+        ts = TrainStep(w, "vla-full-train", 2, 18, max_grad_norm=1.0, weight_decay=0.1, shard_params=sp)
+        ts.set_batch(ids, mask, pv, labels)
+        log = []
+        for step in range(6):                               # nothing below reads a value or synchronises until the loop is over
+            loss, norm = ts.step(1e-3)
+            log += [loss.clone(), norm.clone()]
+        out[sp] = (torch.stack(log).cpu(), ts.store.full_master().cpu())
+    assert torch.equal(out[False][0], out[True][0])
+    assert torch.equal(out[False][1], out[True][1])
 
 
 def test_fp8_under_parameter_sharding_equals_fp8_replicated(dev):
