@@ -333,6 +333,229 @@ __global__ void crop_resize_bilinear_kernel(const uint8_t* src, uint8_t* dst, in
   }
 }
 
+// ---- OpenVLA's training-time image augmentation (prismatic/vla/datasets/datasets.py:121-136 → dlimp augment_image) ----
+// random_resized_crop → random_brightness → random_contrast → random_saturation → random_hue on float32 in [0, 1], each
+// followed by clip(·, 0, 1), uint8 in and uint8 out as around bl_crop_resize_bilinear_u8. The random numbers are a host
+// table params[b] = (y1, x1, side_y, side_x, brightness δ, contrast f, saturation f, hue δ), so the kernels are a pure
+// function of (frames, params). Specification: vla/image_augment.py::augment_frame, op for op; every fp32 operation below
+// is a separate, individually rounded instruction (contraction off in every body, plain operators: see
+// crop_resize_bilinear_kernel), the contrast mean is an integer sum — results are bit-identical to the host restatement.
+struct AugGeom { float yb, ys, xb, xs; };
+
+// the four sampling constants of eval_preprocess.sampling_constants for the box (y1, x1, y1 + side_y, x1 + side_x), H×W → H×W
+__device__ __forceinline__ AugGeom augment_geom(const float* p, int H, int W) {
+#pragma clang fp contract(off)
+  const float y1 = p[0], x1 = p[1];
+  const float y2 = y1 + p[2], x2 = x1 + p[3];
+  const float hm = (float)(H - 1), wm = (float)(W - 1);
+  AugGeom g;
+  g.yb = y1 * hm;
+  g.ys = (y2 - y1) * hm / hm;
+  g.xb = x1 * wm;
+  g.xs = (x2 - x1) * wm / wm;
+  return g;
+}
+
+__device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+
+// steps 0-2 for output pixel (i, j): u8 · (1/255), the bilinear sample of crop_resize_bilinear_kernel, clip, + δ, clip
+__device__ __forceinline__ void augment_sample(const uint8_t* img, int H, int W, int i, int j, const AugGeom& g, float bright,
+                                               float v[3]) {
+#pragma clang fp contract(off)
+  const float iy = (float)i * g.ys, jx = (float)j * g.xs;
+  const float ys = g.yb + iy, xs = g.xb + jx;
+  if (!(ys >= 0.0f && ys <= (float)(H - 1) && xs >= 0.0f && xs <= (float)(W - 1))) {
+    v[0] = v[1] = v[2] = 0.0f;                                     // the extrapolation value
+  } else {
+    const float fy = floorf(ys), fx = floorf(xs);
+    const float wy = ys - fy, wx = xs - fx;
+    const int y0 = min(max((int)fy, 0), H - 1), y1 = min(max((int)ceilf(ys), 0), H - 1);
+    const int x0 = min(max((int)fx, 0), W - 1), x1 = min(max((int)ceilf(xs), 0), W - 1);
+    const uint8_t* r0 = img + (long)y0 * W * 3;
+    const uint8_t* r1 = img + (long)y1 * W * 3;
+    const float k = 1.0f / 255.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float p00 = (float)r0[x0 * 3 + c] * k, p01 = (float)r0[x1 * 3 + c] * k;
+      const float p10 = (float)r1[x0 * 3 + c] * k, p11 = (float)r1[x1 * 3 + c] * k;
+      const float dt = p01 - p00, db = p11 - p10;
+      const float et = dt * wx, eb = db * wx;
+      const float top = p00 + et, bot = p10 + eb;
+      const float dv = bot - top;
+      const float ev = dv * wy;
+      v[c] = top + ev;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float a = clip01(v[c]);
+    const float s = a + bright;
+    v[c] = clip01(s);
+  }
+}
+
+// TF's RGB → HSV functor (adjust_saturation / adjust_hue): h in [0, 1)
+__device__ __forceinline__ void rgb_to_hsv(const float v[3], float& h, float& s, float& val) {
+#pragma clang fp contract(off)
+  const float r = v[0], g = v[1], b = v[2];
+  const float mx = fmaxf(fmaxf(r, g), b), mn = fminf(fminf(r, g), b);
+  const float range = mx - mn;
+  const float q = range / mx;
+  s = mx > 0.0f ? q : 0.0f;
+  const float six = 6.0f * range;
+  const float norm = 1.0f / six;
+  const float d0 = g - b, d1 = b - r, d2 = r - g;
+  const float h0 = norm * d0, m1 = norm * d1, m2 = norm * d2;
+  const float h1 = m1 + (2.0f / 6.0f), h2 = m2 + (4.0f / 6.0f);
+  float hh = (r == mx) ? h0 : ((g == mx) ? h1 : h2);
+  if (range == 0.0f) hh = 0.0f;
+  const float hp = hh + 1.0f;
+  h = hh < 0.0f ? hp : hh;
+  val = mx;
+}
+
+// TF's HSV → RGB functor
+__device__ __forceinline__ void hsv_to_rgb(float h, float s, float val, float v[3]) {
+#pragma clang fp contract(off)
+  const float c = s * val;
+  const float m = val - c;
+  const float dh = 6.0f * h;
+  const float a0 = dh - 3.0f, a1 = dh - 2.0f, a2 = dh - 4.0f;
+  const float b0 = fabsf(a0) - 1.0f, b1 = 2.0f - fabsf(a1), b2 = 2.0f - fabsf(a2);
+  const float e0 = clip01(b0) * c, e1 = clip01(b1) * c, e2 = clip01(b2) * c;
+  v[0] = e0 + m;
+  v[1] = e1 + m;
+  v[2] = e2 + m;
+}
+
+// steps 3-6 on one pixel: contrast about the channel means, saturation, hue, saturating convert to uint8
+__device__ __forceinline__ void augment_colour(float v[3], const float mean[3], float contrast, float sat, float hue,
+                                               uint32_t out[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float d = v[c] - mean[c];
+    const float e = d * contrast;
+    const float f = e + mean[c];
+    v[c] = clip01(f);
+  }
+  float h, s, val;
+  rgb_to_hsv(v, h, s, val);
+  const float s2 = s * sat;
+  hsv_to_rgb(h, clip01(s2), val, v);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = clip01(v[c]);
+  rgb_to_hsv(v, h, s, val);
+  const float h2 = h + hue;
+  const float h3 = h2 - floorf(h2);
+  hsv_to_rgb(h3, s, val, v);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float a = clip01(v[c]);
+    const float q = a * 255.5f;
+    out[c] = (uint32_t)fminf(q, 255.0f);                           // q >= 0: truncation, saturated at 255
+  }
+}
+
+__global__ void augment_zero_sums_kernel(long long* sums, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) sums[i] = 0;
+}
+
+// Pass 1: sums[b][c] += Σ rint(x · 2^24) over the pixels of image b after steps 0-2 (x in [0, 1]: every term is an exact
+// integer ≤ 2^24, so the int64 total does not depend on the order of the adds). `bpi` workgroups per image, each
+// grid-strides its image's pixels, reduces through shuffles and LDS, then adds 3 values with 64-bit vector atomics.
+__global__ __launch_bounds__(256) void augment_sums_kernel(const uint8_t* src, int H, int W, int bpi, const float* params,
+                                                           long long* sums) {
+  __shared__ long long red[4][3];
+  const int b = blockIdx.x / bpi, blk = blockIdx.x - b * bpi;
+  const long hw = (long)H * W;
+  const float* p = params + (long)b * 8;
+  const AugGeom g = augment_geom(p, H, W);
+  const float bright = p[4];
+  const uint8_t* img = src + (long)b * hw * 3;
+  long long acc[3] = {0, 0, 0};
+  for (long t = (long)blk * 256 + threadIdx.x; t < hw; t += (long)bpi * 256) {
+    const int i = (int)(t / W), j = (int)(t - (long)i * W);
+    float v[3];
+    augment_sample(img, H, W, i, j, g, bright, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += (long long)rintf(v[c] * 16777216.0f);
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[wave][0] = acc[0]; red[wave][1] = acc[1]; red[wave][2] = acc[2]; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const long long s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    atomicAdd((unsigned long long*)(sums + (long)b * 3 + threadIdx.x), (unsigned long long)s);
+  }
+}
+
+// Pass 2: steps 0-2 again (the source image stays in L2; no fp32 intermediate goes to HBM), then 3-6. One thread = 8
+// consecutive pixels of an image (the last group of an image may be shorter): 24 output bytes as 6 dwords where the
+// address allows, and / or — fused, H·W % 8 == 0 — the 6 × 16-byte bf16 plane stores of preprocess_u8_kernel on the
+// quantised bytes (same expression, so pixel_values equals bl_preprocess_u8_bf16 of the uint8 output bit for bit).
+__global__ __launch_bounds__(256) void augment_apply_kernel(const uint8_t* src, int B, int H, int W, const float* params,
+                                                            const long long* sums, uint8_t* dst, uint16_t* pv,
+                                                            const float* mean_std) {
+  const long hw = (long)H * W, gpi = (hw + 7) >> 3, total = (long)B * gpi;
+  const double den = (double)hw * 16777216.0;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    const long b = t / gpi, p0 = (t - b * gpi) * 8;
+    const int n = (int)(hw - p0 < 8 ? hw - p0 : 8);
+    const float* p = params + b * 8;
+    const AugGeom g = augment_geom(p, H, W);
+    const float bright = p[4], contrast = p[5], sat = p[6], hue = p[7];
+    float mean[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) mean[c] = (float)((double)sums[b * 3 + c] / den);
+    const uint8_t* img = src + b * hw * 3;
+    uint32_t px[24];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      px[e * 3] = px[e * 3 + 1] = px[e * 3 + 2] = 0u;
+      if (e < n) {
+        const long q = p0 + e;
+        const int i = (int)(q / W), j = (int)(q - (long)i * W);
+        float v[3];
+        augment_sample(img, H, W, i, j, g, bright, v);
+        augment_colour(v, mean, contrast, sat, hue, px + e * 3);
+      }
+    }
+    if (dst) {
+      uint8_t* q = dst + (b * hw + p0) * 3;
+      if (n == 8 && (((uintptr_t)q) & 3) == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+          *(uint32_t*)(q + 4 * k) = px[4 * k] | (px[4 * k + 1] << 8) | (px[4 * k + 2] << 16) | (px[4 * k + 3] << 24);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 24; ++e)
+          if (e < n * 3) q[e] = (uint8_t)px[e];
+      }
+    }
+    if (pv) {                                                     // host checked hw % 8 == 0: n == 8 here
+#pragma unroll
+      for (int c6 = 0; c6 < 6; ++c6) {
+        const int c = c6 % 3;
+        const float mu = mean_std[c6], sd = mean_std[6 + c6];
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)px[e * 3 + c], 255.0f), mu), sd);
+        u32x4_t o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = pack2bf(v[2 * e], v[2 * e + 1]);
+        *(u32x4_t*)(pv + ((b * 6 + c6) * hw + p0)) = o;
+      }
+    }
+  }
+}
+
 inline int grid_for(long total, int block) {
   long g = (total + block - 1) / block;
   return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));   // cap at 256 CUs × 8 and grid-stride the rest
@@ -460,6 +683,26 @@ extern "C" int bl_crop_resize_bilinear_u8(const uint8_t* src, uint8_t* dst, int3
   if (B <= 0 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0) return BL_E_SHAPE;
   hipLaunchKernelGGL(crop_resize_bilinear_kernel, dim3(grid_for((long)B * out_h * out_w, 256)), dim3(256), 0, (hipStream_t)stream,
                      src, dst, B, H, W, out_h, out_w, y_base, y_step, x_base, x_step);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
+extern "C" int bl_augment_frames_u8(const uint8_t* src, int32_t B, int32_t H, int32_t W, const float* params, int64_t* workspace,
+                                    uint8_t* dst, bl_bf16* pixel_values, const float* mean_std, void* stream) {
+  if (!src || !params || !workspace || (!dst && !pixel_values) || (pixel_values && !mean_std)) return BL_E_ARG;
+  const long hw = (long)H * W;
+  if (B <= 0 || B > (1 << 20) || H < 2 || W < 2 || hw > (1L << 28) || (pixel_values && (hw % 8))) return BL_E_SHAPE;
+  if ((((uintptr_t)workspace) & 7) || (((uintptr_t)params) & 3) || (pixel_values && !bl_aligned16(pixel_values))) return BL_E_ALIGN;
+  hipLaunchKernelGGL(augment_zero_sums_kernel, dim3((B * 3 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (long long*)workspace,
+                     B * 3);
+  BL_CHECK_LAUNCH();
+  const long per_image = (hw + 255) / 256, cap = B < 2048 ? 2048 / B : 1;     // ≈ 2048 workgroups in all, ≥ 1 per image
+  const int bpi = (int)(per_image < cap ? per_image : cap);
+  hipLaunchKernelGGL(augment_sums_kernel, dim3(B * bpi), dim3(256), 0, (hipStream_t)stream, src, H, W, bpi, params,
+                     (long long*)workspace);
+  BL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(augment_apply_kernel, dim3(grid_for((long)B * ((hw + 7) / 8), 256)), dim3(256), 0, (hipStream_t)stream, src,
+                     B, H, W, params, (const long long*)workspace, dst, pixel_values, mean_std);
   BL_CHECK_LAUNCH();
   return BL_OK;
 }

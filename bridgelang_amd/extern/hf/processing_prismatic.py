@@ -59,13 +59,17 @@ class PrismaticImageProcessor:
         if frames.shape[1:3] != (h, w):
             frames = ops.resize_bicubic_u8(frames, h, w)
         key = frames.device
-        if getattr(self, "_mean_std", None) is None or self._mean_std.device != key:
-            flat = [v for m in self.means for v in m] + [v for s_ in self.stds for v in s_]
-            self._mean_std = torch.tensor(flat, dtype=torch.float32, device=key)
         if out is None:
             out = torch.empty(frames.shape[0], 6, h, w, dtype=torch.bfloat16, device=key)
-        ops.preprocess_u8(frames, self._mean_std, out)
+        ops.preprocess_u8(frames, self.mean_std(key), out)
         return out
+
+    def mean_std(self, device) -> torch.Tensor:
+        """The 12 device floats mean[6] | std[6] that bl_preprocess_u8_bf16 / bl_augment_frames_u8 read (cached per device)."""
+        if getattr(self, "_mean_std", None) is None or self._mean_std.device != device:
+            flat = [v for m in self.means for v in m] + [v for s_ in self.stds for v in s_]
+            self._mean_std = torch.tensor(flat, dtype=torch.float32, device=device)
+        return self._mean_std
 
     # ---- preprocessor_config.json (the file AutoImageProcessor reads; reference ImageProcessingMixin fields :62-126) ----
     def to_dict(self) -> Dict[str, Any]:

@@ -21,7 +21,7 @@ from ._lib import (AttnDesc, GemmDesc, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_KE
                    EPI_RES, EPI_SWIGLU)
 
 __all__ = ["Op", "gemm", "gemm_fp8", "quantize_rows_fp8", "quantize_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "skinny_supported", "rope_kvcache", "embed_splice",
-           "argmax", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "write_prefix_tokens", "fill_synth", "run_all",
+           "argmax", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
            "EPI_NONE", "EPI_BIAS", "EPI_BIAS_GELU", "EPI_BIAS_RES", "EPI_RES", "EPI_SWIGLU", "EPI_F32", "EPI_F32_BF16R",
            "EPI_SWIGLU_KEEP", "EPI_BIAS_GELU_KEEP", "EPI_SWIGLU_BWD", "EPI_GELU_BWD"]
 
@@ -661,6 +661,47 @@ def crop_resize_bilinear_u8(frames: torch.Tensor, y_base: float, y_step: float, 
     if run:
         op.run()
         return out
+    return op
+
+
+def augment_frames_u8(frames: torch.Tensor, params: torch.Tensor, out: Optional[torch.Tensor] = None,
+                      pixel_values: Optional[torch.Tensor] = None, mean_std: Optional[torch.Tensor] = None,
+                      workspace: Optional[torch.Tensor] = None, run: bool = True) -> Op:
+    """OpenVLA's training-time image augmentation (vla/image_augment.py::augment_frame, bit-identical) on uint8 frames
+    [B, H, W, 3] in HBM with the host-drawn parameter table params [B, 8] fp32 on the device (bl_augment_frames_u8).
+    Writes `out` (uint8 [B, H, W, 3]) and / or, fused, `pixel_values` ([B, 6, H, W] bf16 with the 12-float `mean_std` of
+    preprocess_u8: equal to preprocess_u8 of `out`). `workspace`: int64 [B, 3], zeroed inside the call."""
+    lib = _lib.load()
+    if frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous() or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise TypeError("augment_frames_u8: frames must be a contiguous CUDA/HIP uint8 tensor [B, H, W, 3]")
+    B, H, W, _ = frames.shape
+    if H < 2 or W < 2:
+        raise ValueError("augment_frames_u8: H and W must be at least 2")
+    if (params.dtype != torch.float32 or params.device != frames.device or tuple(params.shape) != (B, 8)
+            or not params.is_contiguous()):
+        raise ValueError(f"augment_frames_u8: params must be a contiguous fp32 tensor [{B}, 8] on the frames' device")
+    if out is None and pixel_values is None:
+        raise ValueError("augment_frames_u8: give out, pixel_values or both")
+    if out is not None and (tuple(out.shape) != (B, H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous()
+                            or out.device != frames.device or out.data_ptr() == frames.data_ptr()):
+        raise ValueError(f"augment_frames_u8: out must be another contiguous uint8 tensor [{B}, {H}, {W}, 3] on the frames' device")
+    if pixel_values is not None:
+        if (tuple(pixel_values.shape) != (B, 6, H, W) or not pixel_values.is_contiguous() or pixel_values.device != frames.device
+                or mean_std is None or mean_std.dtype != torch.float32 or mean_std.numel() != 12 or mean_std.device != frames.device):
+            raise ValueError("augment_frames_u8: pixel_values must be contiguous [B, 6, H, W] bf16 with mean_std 12 floats")
+        _bf16(pixel_values, "pixel_values")
+    if workspace is None:
+        workspace = torch.empty(B, 3, dtype=torch.int64, device=frames.device)
+    elif (workspace.dtype != torch.int64 or workspace.numel() < B * 3 or not workspace.is_contiguous()
+          or workspace.device != frames.device):
+        raise ValueError(f"augment_frames_u8: workspace must be a contiguous int64 tensor of at least {B * 3} elements")
+    op = Op("bl_augment_frames_u8", lib.bl_augment_frames_u8,
+            (frames.data_ptr(), B, H, W, params.data_ptr(), workspace.data_ptr(), out.data_ptr() if out is not None else None,
+             pixel_values.data_ptr() if pixel_values is not None else None, mean_std.data_ptr() if pixel_values is not None else None),
+            (frames, params, workspace, out, pixel_values, mean_std),
+            nbytes=B * H * W * (3.0 + (3 if out is not None else 0) + (12 if pixel_values is not None else 0)))
+    if run:
+        op.run()
     return op
 
 

@@ -13,7 +13,7 @@ import torch.distributed as dist
 
 from .lora import LoraAdapters
 from .metrics import vla_action_metrics
-from .step import TrainStep
+from .step import TrainStep, set_loader_batch
 
 
 @dataclass
@@ -34,12 +34,16 @@ class FinetuneConfig:
     use_quantization: bool = False
     max_text_len: int = 48
     log_every: int = 10
+    image_aug: bool = False                # OpenVLA's image augmentations on the device (needs uint8 frames from the loader)
+    seed: int = 7                          # (seed, rank, micro-batch index) seeds each batch's augmentation parameters
 
 
 def finetune(vlm, dataloader: Iterable[Dict[str, Any]], action_tokenizer, cfg: FinetuneConfig,
              log_path: Optional[Path] = None) -> Dict[str, Any]:
     """`vlm`: OpenVLAForActionPrediction (HIP); `dataloader` yields PaddedCollatorForActionPrediction batches of
-    cfg.batch_size samples. Returns the last smoothed metrics and the paths written."""
+    cfg.batch_size samples — `pixel_values` either the normalised float tensor of the image processor or raw uint8 frames
+    [B, H, W, 3], which are preprocessed (and, with cfg.image_aug, augmented) on the device. Returns the last smoothed
+    metrics and the paths written."""
     if cfg.use_quantization:
         raise NotImplementedError("4-bit base weights (bitsandbytes) are outside the MI355X path: 288 GB HBM holds bf16")
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
@@ -59,7 +63,8 @@ def finetune(vlm, dataloader: Iterable[Dict[str, Any]], action_tokenizer, cfg: F
             engine = TrainStep(w, stage, cfg.batch_size, L, lora=lora, store=store, world=world, rank=rank,
                                max_grad_norm=float("inf"), weight_decay=0.01)      # AdamW(params, lr): torch defaults
             store = engine.store
-        engine.set_batch(ids, batch["attention_mask"], batch["pixel_values"], batch["labels"])
+        set_loader_batch(engine, ids, batch["attention_mask"], batch["pixel_values"], batch["labels"], image_aug=cfg.image_aug,
+                         seed=cfg.seed, rank=rank, step=batch_idx)
         loss = engine.forward(graph=True)
         engine.backward(graph=True)
         logits = engine.logits.view(engine.B, engine.S, -1)[:, :num_patches + ids.shape[1]]

@@ -24,6 +24,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import os
 
+import numpy as np
 import torch
 
 from .. import ops, train_ops as T
@@ -1291,6 +1292,46 @@ class TrainStep:
                   labels: torch.Tensor) -> None:
         """Right-padded batch (PaddedCollatorForActionPrediction, data_utils.py:101-142) → static device inputs. Batches
         shorter than the planned L are padded further (pad id 32000 / mask 0 / label -100: no effect on valid rows)."""
+        self._set_text_batch(input_ids, attention_mask, labels)
+        self.pixel_values.copy_(pixel_values.to(self.device).to(torch.bfloat16))
+
+    def set_batch_frames(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], frames_u8: torch.Tensor,
+                         labels: torch.Tensor, aug_params=None) -> None:
+        """`set_batch` for raw uint8 RGB frames [B, H, W, 3] (host or device): they are uploaded as uint8 and the static
+        `pixel_values` buffer is filled on the device. Without `aug_params` this is `preprocess_frames_gpu` alone (resize
+        included), bit-identical to `set_batch` with the host `apply_transform` of the same frames. With `aug_params`
+        ([B, 8] fp32, vla/image_augment.py::draw_params) the frames are resized first if needed, then augmented and
+        normalised in one fused op (bl_augment_frames_u8)."""
+        if (not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3
+                or frames_u8.shape[0] != self.B):
+            raise ValueError(f"set_batch_frames: expected uint8 frames [{self.B}, H, W, 3]")
+        self._set_text_batch(input_ids, attention_mask, labels)
+        frames = frames_u8.to(self.device).contiguous()
+        proc = self._frames_processor()
+        if aug_params is None:
+            proc.preprocess_frames_gpu(frames, out=self.pixel_values)
+            return
+        h, w = self.pixel_values.shape[-2:]
+        if tuple(frames.shape[1:3]) != (h, w):
+            frames = ops.resize_bicubic_u8(frames, h, w)
+        params = aug_params if torch.is_tensor(aug_params) else torch.from_numpy(np.ascontiguousarray(aug_params, dtype=np.float32))
+        params = params.to(frames.device, dtype=torch.float32).contiguous()
+        if self._aug_workspace is None:
+            self._aug_workspace = torch.empty(self.B, 3, dtype=torch.int64, device=frames.device)
+        ops.augment_frames_u8(frames, params, pixel_values=self.pixel_values, mean_std=proc.mean_std(frames.device),
+                              workspace=self._aug_workspace)
+
+    _aug_workspace: Optional[torch.Tensor] = None
+    _image_processor = None
+
+    def _frames_processor(self):
+        """The image processor whose normalisation constants the frames path uses (OpenVLA's fused-backbone defaults)."""
+        if self._image_processor is None:
+            from ..extern.hf.processing_prismatic import PrismaticImageProcessor
+            self._image_processor = PrismaticImageProcessor()
+        return self._image_processor
+
+    def _set_text_batch(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], labels: torch.Tensor) -> None:
         dev, B, L, P, S = self.device, self.B, self.L, self.dims.n_patches, self.S
         b, l = input_ids.shape
         if b != B or l > L:
@@ -1302,7 +1343,6 @@ class TrainStep:
         lab = torch.full((B, L), IGNORE_INDEX, dtype=torch.int64, device=dev)
         lab[:, :l] = labels.to(dev)
         self.input_ids.copy_(ids)
-        self.pixel_values.copy_(pixel_values.to(dev).to(torch.bfloat16))
         self.key_mask[:, :1] = m[:, :1]
         self.key_mask[:, 1:1 + P] = 1
         self.key_mask[:, 1 + P:] = m[:, 1:]
@@ -1470,3 +1510,28 @@ class TrainStep:
         norm = self.clip_grad_norm()
         self.optimizer_step(lr, graph)
         return loss, norm
+
+
+def is_uint8_frames(pixel_values) -> bool:
+    """A collated batch of raw RGB frames [B, H, W, 3] uint8 (an `image_transform` that returns the frame itself)."""
+    return (torch.is_tensor(pixel_values) and pixel_values.dtype == torch.uint8 and pixel_values.dim() == 4
+            and pixel_values.shape[-1] == 3)
+
+
+def set_loader_batch(engine, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], pixel_values, labels: torch.Tensor,
+                     image_aug: bool = False, seed: int = 7, rank: int = 0, step: int = 0) -> None:
+    """What both training loops do with a collated batch: uint8 frames take the device path (`set_batch_frames`), with one
+    augmentation parameter table per micro-batch drawn from (seed, rank, step) when `image_aug` is set; already-normalised
+    float pixel values go through `set_batch` as before, and cannot be augmented any more."""
+    if is_uint8_frames(pixel_values):
+        params = None
+        if image_aug:
+            from ..vla.image_augment import draw_params
+            params = draw_params(pixel_values.shape[0], seed, rank, step)
+        engine.set_batch_frames(input_ids, attention_mask, pixel_values, labels, aug_params=params)
+        return
+    if image_aug:
+        raise ValueError("image_aug needs uint8 frames [B, H, W, 3] under batch['pixel_values'] (the augmentation runs on raw "
+                         "frames, on the device): this loader yields already-normalised float pixel values — give the dataset "
+                         "an image_transform that returns the uint8 HWC frame")
+    engine.set_batch(input_ids, attention_mask, pixel_values, labels)

@@ -20,7 +20,7 @@ import torch.distributed as dist
 
 from .checkpoint import to_model_state_dicts
 from .metrics import vla_action_metrics
-from .step import STAGES, ParamStore, TrainStep
+from .step import STAGES, ParamStore, TrainStep, set_loader_batch
 
 
 def _rank_world() -> Tuple[int, int]:
@@ -248,7 +248,9 @@ class ShardedOptimizerStrategy:
 
     # -- the loop (base_strategy.py:245-389) --
     def run_vla_training(self, vla_dataset, collator, action_tokenizer, metrics: VLAMetrics, save_interval: int = 2500,
-                         save_full_model: bool = True) -> None:
+                         save_full_model: bool = True, image_aug: bool = False, seed: int = 7) -> None:
+        """`image_aug`: OpenVLA's image augmentations on the device, for loaders that yield raw uint8 frames [B, H, W, 3]
+        under `pixel_values`; each batch's parameters are drawn from (seed, rank, global step)."""
         from torch.utils.data import DataLoader, IterableDataset
         assert isinstance(vla_dataset, IterableDataset), "VLA training expects an IterableDataset!"
         assert self.grad_accumulation_steps == 1, "VLA training does not support gradient accumulation!"
@@ -263,7 +265,8 @@ class ShardedOptimizerStrategy:
             pv = batch["pixel_values"]
             if isinstance(pv, dict):          # the native fused backbone's transform yields {"dino", "siglip"} (dinosiglip_vit.py:33-40)
                 pv = torch.cat([pv["dino"], pv["siglip"]], dim=1)
-            eng.set_batch(ids, batch["attention_mask"], pv, batch["labels"])
+            set_loader_batch(eng, ids, batch["attention_mask"], pv, batch["labels"], image_aug=image_aug, seed=seed,
+                             rank=self.rank, step=metrics.global_step)
             loss = eng.forward(graph=True)                    # static plans replayed as HIP graphs
             metrics.commit(loss=loss)
             eng.backward(graph=True)                          # (sharded runs keep the backward eager: per-bucket collectives)

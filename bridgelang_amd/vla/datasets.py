@@ -37,6 +37,12 @@ def build_sample(action_tokenizer: ActionTokenizer, base_tokenizer: Any, image_t
     return dict(pixel_values=image_transform(image), input_ids=ids, labels=labels)
 
 
+def raw_frame_transform(image: Image.Image) -> torch.Tensor:
+    """An `image_transform` that keeps the frame raw: the PIL image as a uint8 [H, W, 3] tensor. The collator stacks these
+    unchanged and the training loops then resize / augment / normalise on the device (TrainStep.set_batch_frames)."""
+    return torch.from_numpy(np.array(image.convert("RGB"), dtype=np.uint8))
+
+
 @dataclass
 class RLDSBatchTransform:
     action_tokenizer: ActionTokenizer

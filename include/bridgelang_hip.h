@@ -384,6 +384,19 @@ int bl_resample_pass_u8(const uint8_t* src, uint8_t* dst, int32_t B, int32_t lin
  * restatement bridgelang_amd/vla/eval_preprocess.py (TensorFlow itself is absent: unpinned against TF). */
 int bl_crop_resize_bilinear_u8(const uint8_t* src, uint8_t* dst, int32_t B, int32_t H, int32_t W, int32_t out_h, int32_t out_w,
                                float y_base, float y_step, float x_base, float x_step, void* stream);
+/* OpenVLA's training-time image augmentation (`image_aug`, prismatic/vla/datasets/datasets.py:121-136 → dlimp
+ * augment_image) on uint8 frames src [B, H, W, 3] (H, W >= 2), output at the input size: u8/255 → random_resized_crop
+ * (tf.image.crop_and_resize, bilinear, box (y1, x1, y1 + side_y, x1 + side_x)) → + brightness δ → contrast
+ * (x − mean_c)·f + mean_c about the per-image channel means → saturation (RGB → HSV, S·f, → RGB) → hue (h + δ mod 1), each
+ * followed by clip [0, 1], then the saturating uint8 convert (× 255.5, truncate). params [B, 8] device fp32 rows =
+ * (y1, x1, side_y, side_x, brightness δ, contrast f, saturation f, hue δ): the host draws them, the op is a pure function
+ * of (src, params). Two passes: the first accumulates mean_c as Σ rint(x·2^24) into workspace [B, 3] int64 (zeroed on
+ * the stream inside the call: the op is replayable), the second recomputes the sample and writes dst [B, H, W, 3] uint8
+ * and / or, fused (H*W % 8 == 0), pixel_values [B, 6, H, W] bf16 = bl_preprocess_u8_bf16 of that uint8 output with
+ * mean_std as there (either output may be NULL, not both). Bit-identical to the host restatement
+ * bridgelang_amd/vla/image_augment.py::augment_frame (TensorFlow and dlimp are absent: unpinned against them). */
+int bl_augment_frames_u8(const uint8_t* src, int32_t B, int32_t H, int32_t W, const float* params, int64_t* workspace,
+                         uint8_t* dst, bl_bf16* pixel_values, const float* mean_std, void* stream);
 /* pixel_values [B, 6, 224, 224] bf16 (processing_prismatic.py:128-145 layout) → 14x14 patch rows for one tower:
  * out[b*256 + py*16 + px, c*196 + i*14 + j] = pixel_values[b, chan0 + c, py*14 + i, px*14 + j]; columns 588..ld-1
  * are zeroed (K padded to a multiple of 64 for the patch-embed GEMM; timm PatchEmbed conv flattening order). */

@@ -13,7 +13,9 @@ hand-written training step (bridgelang_amd/training/{lora,step}.py) and multi-GP
 Nothing is downloaded: `--vla_path` is a local HF export, or `synthetic:openvla-7b` / `synthetic:openvla-tiny` for the
 seeded synthetic checkpoint; `--dataset_name dummy` trains on DummyDataset (the RLDS reader is outside the hot path);
 W&B logging is replaced by a JSONL file in the run directory with the same three keys (train_loss, action_accuracy,
-l1_loss).
+l1_loss). `--image_aug True` (the reference's default) trains with OpenVLA's image augmentations: the reference applies them
+inside its TF/dlimp ingest, here the loader yields raw uint8 frames and bl_augment_frames_u8 applies them on the device
+(bridgelang_amd/vla/image_augment.py).
 """
 from __future__ import annotations
 
@@ -86,7 +88,7 @@ def finetune(cfg: FinetuneConfig) -> dict:
     from bridgelang_amd.util.data_utils import PaddedCollatorForActionPrediction
     from bridgelang_amd.util.synthetic_tokenizer import load_tokenizer
     from bridgelang_amd.vla.action_tokenizer import ActionTokenizer
-    from bridgelang_amd.vla.datasets import DummyDataset
+    from bridgelang_amd.vla.datasets import DummyDataset, raw_frame_transform
 
     print(f"Fine-tuning OpenVLA Model `{cfg.vla_path}` on `{cfg.dataset_name}`")
     assert torch.cuda.is_available(), "Fine-tuning assumes at least one GPU is available!"
@@ -114,7 +116,10 @@ def finetune(cfg: FinetuneConfig) -> dict:
     if cfg.dataset_name != "dummy":
         raise NotImplementedError(f"dataset `{cfg.dataset_name}` needs the RLDS/TFDS reader (outside the hot path, SURVEY §2 "
                                   f"row 16); `--dataset_name dummy` trains on DummyDataset")
-    ds = DummyDataset(at, tok, processor.image_processor.apply_transform, length=cfg.dummy_length, seed=cfg.seed + 1000 * rank)
+    # --image_aug: the dataset hands over the raw uint8 HWC frame; resize, OpenVLA's augmentations and the normalisation
+    # then run on the device (TrainStep.set_batch_frames), the parameters drawn per batch from (seed, rank, batch index)
+    image_transform = raw_frame_transform if cfg.image_aug else processor.image_processor.apply_transform
+    ds = DummyDataset(at, tok, image_transform, length=cfg.dummy_length, seed=cfg.seed + 1000 * rank)
     if rank == 0:
         (run_dir / "dataset_statistics.json").write_text(json.dumps(
             {k: {kk: {s: [float(x) for x in v] for s, v in vv.items()} for kk, vv in d.items()} for k, d in ds.dataset_statistics.items()},
@@ -125,7 +130,8 @@ def finetune(cfg: FinetuneConfig) -> dict:
     fc = F.FinetuneConfig(run_root_dir=run_dir, adapter_tmp_dir=adapter_dir, batch_size=cfg.batch_size, max_steps=cfg.max_steps,
                           save_steps=cfg.save_steps, learning_rate=cfg.learning_rate, grad_accumulation_steps=cfg.grad_accumulation_steps,
                           save_latest_checkpoint_only=cfg.save_latest_checkpoint_only, use_lora=cfg.use_lora, lora_rank=cfg.lora_rank,
-                          lora_dropout=cfg.lora_dropout, use_quantization=cfg.use_quantization)
+                          lora_dropout=cfg.lora_dropout, use_quantization=cfg.use_quantization, image_aug=cfg.image_aug,
+                          seed=cfg.seed)
     out = F.finetune(vla, loader, at, fc, log_path=run_dir / "train_log.jsonl")
     if rank == 0:
         (run_dir / "finetune_args.json").write_text(json.dumps(cli.encode(cfg), indent=2))

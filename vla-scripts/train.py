@@ -14,6 +14,8 @@ checkpoint (benchmark / smoke runs); (ii) the RLDS/TFDS reader is outside the ho
 dummy` trains on `DummyDataset` (vla/datasets.py), any other mixture needs an RLDS reader and raises; (iii) trackers: `jsonl`
 (W&B is a network service); (iv) `--tokenizer synthetic|<dir>` names the tokenizer (none ships offline); (v) `--fp8_gemms True`
 runs the decoder layers' forward / input-gradient GEMMs on the e4m3 MFMA path (an extension; BASELINE configs[4]).
+(vi) `--image_aug True`: the reference augments inside its TF/dlimp ingest; here the loader yields raw uint8 frames and
+bl_augment_frames_u8 applies OpenVLA's augmentations on the device (bridgelang_amd/vla/image_augment.py).
 `--vla.train_strategy fsdp-full-shard` shards the decoder layers' parameters, `fsdp-shard-grad-op` keeps them replicated.
 One process per GPU under torchrun (RANK / LOCAL_RANK / WORLD_SIZE); collectives are RCCL over xGMI.
 """
@@ -98,7 +100,7 @@ def train(cfg: TrainConfig) -> Path:
     from bridgelang_amd.util.data_utils import PaddedCollatorForActionPrediction
     from bridgelang_amd.util.synthetic_tokenizer import load_tokenizer
     from bridgelang_amd.vla.action_tokenizer import ActionTokenizer
-    from bridgelang_amd.vla.datasets import DummyDataset, EpochIterable
+    from bridgelang_amd.vla.datasets import DummyDataset, EpochIterable, raw_frame_transform
 
     rank, local_rank, world = replicas.env_rank()
     torch.cuda.set_device(local_rank)
@@ -141,7 +143,10 @@ def train(cfg: TrainConfig) -> Path:
     if cfg.vla.data_mix != "dummy":
         raise NotImplementedError(f"data mixture `{cfg.vla.data_mix}` needs the RLDS/TFDS reader (outside the hot path, "
                                   f"SURVEY §2 row 16); `--vla.data_mix dummy` trains on DummyDataset")
-    ds = DummyDataset(at, tok, vlm.vision_backbone.get_image_transform(), prompt_builder_fn=vlm.llm_backbone.prompt_builder_fn,
+    # --image_aug: the dataset hands over the raw uint8 HWC frame; resize, OpenVLA's augmentations and the normalisation
+    # then run on the device (TrainStep.set_batch_frames), the parameters drawn per batch from (seed, rank, global step)
+    image_transform = raw_frame_transform if cfg.image_aug else vlm.vision_backbone.get_image_transform()
+    ds = DummyDataset(at, tok, image_transform, prompt_builder_fn=vlm.llm_backbone.prompt_builder_fn,
                       length=cfg.dummy_length, seed=cfg.seed + 1000 * rank)
     vla_dataset = EpochIterable(ds)
     collator = PaddedCollatorForActionPrediction(tok.model_max_length, tok.pad_token_id, padding_side="right")
@@ -159,7 +164,8 @@ def train(cfg: TrainConfig) -> Path:
     strategy.run_setup(run_dir=run_dir, n_train_examples=len(vla_dataset))
     metrics = VLAMetrics(tuple(t for t in cfg.trackers if t != "wandb"), cfg.run_id, run_dir, cli.encode(cfg),
                          resume_step=cfg.resume_step, resume_epoch=cfg.resume_epoch)
-    strategy.run_vla_training(vla_dataset, collator, at, metrics, save_interval=cfg.save_interval)
+    strategy.run_vla_training(vla_dataset, collator, at, metrics, save_interval=cfg.save_interval, image_aug=cfg.image_aug,
+                              seed=cfg.seed)
     metrics.finalize()
     if dist.is_initialized():
         dist.barrier()
