@@ -16,6 +16,7 @@
 #include "bl_common.h"
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace bl_attention_impl {
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
@@ -491,11 +492,18 @@ __global__ __launch_bounds__(512) void attn_seq_kernel(AttnArgs p, int s_pad) {
 struct DecodeGroups {
   uint16_t* k[8]; uint16_t* v[8]; int pos[8];
 };
+// GPOS (groups of RIGHT-PADDED batches, StaggeredDecodePipeline(padded=True)): every sequence of a group sits at its own
+// position, read from the group's device array rope_pos[g][b] — cache row, rotation angle and key count - 1, as the
+// un-grouped p.rope_pos form. The position is known on the device only, so the kernel itself keeps it inside the cache.
+struct DecodeGroupsPos {
+  uint16_t* k[8]; uint16_t* v[8]; const int* rope_pos[8]; int cache_len;
+};
 
-template <bool ROPE, bool GROUPED = false>
+template <bool ROPE, bool GROUPED = false, bool GPOS = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs p, const uint16_t* kn, const uint16_t* vn,
                                                           const uint16_t* cos_tab, const uint16_t* sin_tab, int pos,
-                                                          DecodeGroups gr) {
+                                                          std::conditional_t<GPOS, DecodeGroupsPos, DecodeGroups> gr) {
+  static_assert(!GPOS || (ROPE && GROUPED), "per-sequence group positions are a form of the grouped RoPE kernel");
   constexpr int MAXKV = 2048;   // head_dim is fixed at 128 (16 lanes × 16 B per row)
   __shared__ float sc[MAXKV];
   __shared__ float part[4][128];
@@ -505,7 +513,12 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs p, const uint
     const int per = p.B * p.H, g = bh / per;
     bh -= g * per;
     p.k = gr.k[g]; p.v = gr.v[g];
-    pos = gr.pos[g];
+    if constexpr (GPOS) {   // one position per workgroup: uniform (SGPR), so `resident` below stays a scalar branch
+      pos = __builtin_amdgcn_readfirstlane(gr.rope_pos[g][bh / p.H]);
+      if (pos < 0 || pos >= gr.cache_len) return;   // a position outside the cache writes nothing (whole workgroup)
+    } else {
+      pos = gr.pos[g];
+    }
     p.Skv = pos + 1;
     const long roff = (long)g * p.B * p.q_bs;
     p.q += roff; kn += roff; vn += roff;
@@ -839,6 +852,36 @@ extern "C" int bl_attention_decode_rope_grouped_bf16(const bl_attn_desc* d, cons
   if ((((uintptr_t)d->o) & 15) || !bl_aligned16(cos_tab) || !bl_aligned16(sin_tab)) return BL_E_ALIGN;
   const long D = (long)d->H * d->head_dim;
   hipLaunchKernelGGL((attn_decode_kernel<true, true>), dim3(n_groups * d->B * d->H), dim3(256), 0, (hipStream_t)stream, a,
+                     d->q + D, d->q + 2 * D, cos_tab, sin_tab, 0, gr);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
+extern "C" int bl_attention_decode_rope_pos_grouped_bf16(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab,
+                                                         int32_t n_groups, bl_bf16* const* k_caches, bl_bf16* const* v_caches,
+                                                         const int32_t* const* rope_pos, int32_t cache_len, void* stream) {
+  if (!d || !d->q || !d->o || !cos_tab || !sin_tab || !k_caches || !v_caches || !rope_pos) return BL_E_ARG;
+  if (d->key_mask) return BL_E_ARG;           // every sequence attends to its own rows 0..pos: no key mask in this form
+  if (n_groups < 1 || n_groups > 8 || cache_len < 1 || cache_len > 2048) return BL_E_SHAPE;
+  bl_attn_desc d0 = *d;                       // validate strides / alignment with group 0's caches in place of k / v
+  d0.k = k_caches[0]; d0.v = v_caches[0]; d0.Skv = cache_len;
+  AttnArgs a;
+  const int rc = fill_args(&d0, a);
+  if (rc != BL_OK) return rc;
+  DecodeGroupsPos gr{};
+  for (int g = 0; g < n_groups; ++g) {
+    if (!k_caches[g] || !v_caches[g] || !rope_pos[g]) return BL_E_ARG;
+    if (!bl_aligned16(k_caches[g]) || !bl_aligned16(v_caches[g]) || (((uintptr_t)rope_pos[g]) & 3)) return BL_E_ALIGN;
+    gr.k[g] = k_caches[g]; gr.v[g] = v_caches[g]; gr.rope_pos[g] = rope_pos[g];
+  }
+  gr.cache_len = cache_len;
+  if (d->head_dim != 128 || d->Sq != 1) return BL_E_SHAPE;
+  // the guard keeps a position inside [0, cache_len): the cache row stride must hold that many rows per head
+  if (d->k_hs < (int64_t)cache_len * d->k_rs || d->v_hs < (int64_t)cache_len * d->v_rs || d->k_rs < 128 || d->v_rs < 128)
+    return BL_E_SHAPE;
+  if ((((uintptr_t)d->o) & 15) || !bl_aligned16(cos_tab) || !bl_aligned16(sin_tab)) return BL_E_ALIGN;
+  const long D = (long)d->H * d->head_dim;
+  hipLaunchKernelGGL((attn_decode_kernel<true, true, true>), dim3(n_groups * d->B * d->H), dim3(256), 0, (hipStream_t)stream, a,
                      d->q + D, d->q + 2 * D, cos_tab, sin_tab, 0, gr);
   BL_CHECK_LAUNCH();
   return BL_OK;

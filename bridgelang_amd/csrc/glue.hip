@@ -96,6 +96,19 @@ __global__ void embed_splice_kernel(const int64_t* ids, int B, int L, const uint
   }
 }
 
+// ---- dst[b] = row row_index[b] of batch b (the padded plan's last real position); an index outside the batch copies nothing ----
+__global__ void gather_rows_kernel(const uint16_t* src, const int64_t* row_index, long rows_per_batch, long row_stride, int width,
+                                   uint16_t* dst, int B) {
+  const int cpr = width >> 3;
+  const long total = (long)B * cpr;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % cpr), b = (int)(i / cpr);
+    const long r = row_index[b];
+    if (r < 0 || r >= rows_per_batch) continue;
+    *(u32x4_t*)(dst + (long)b * width + ch * 8) = *(const u32x4_t*)(src + ((long)b * rows_per_batch + r) * row_stride + ch * 8);
+  }
+}
+
 // ---- argmax over fp32 rows; ties → lowest index (torch.argmax) ----
 __global__ __launch_bounds__(256) void argmax_kernel(const float* logits, long ld, int n, int64_t* out) {
   __shared__ float sv[4];
@@ -637,6 +650,17 @@ extern "C" int bl_embed_splice_bf16(const int64_t* ids, int32_t B, int32_t L, co
   const long total = (long)B * L * (dim / 8);
   hipLaunchKernelGGL(embed_splice_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, ids, B, L,
                      table, dim, n_patches, dst);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
+extern "C" int bl_gather_rows_bf16(const bl_bf16* src, const int64_t* row_index, int64_t rows_per_batch, int64_t row_stride,
+                                   int32_t width, bl_bf16* dst, int32_t B, void* stream) {
+  if (!src || !row_index || !dst) return BL_E_ARG;
+  if (B <= 0 || rows_per_batch <= 0 || width <= 0 || (width % 8) || row_stride < width) return BL_E_SHAPE;
+  if ((row_stride % 8) || !bl_aligned16(src) || !bl_aligned16(dst) || (((uintptr_t)row_index) & 7)) return BL_E_ALIGN;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for((long)B * (width / 8), 256)), dim3(256), 0, (hipStream_t)stream, src,
+                     row_index, (long)rows_per_batch, (long)row_stride, width, dst, B);
   BL_CHECK_LAUNCH();
   return BL_OK;
 }

@@ -119,8 +119,7 @@ class OpenVLAEngine:
             self.key_mask = self.cache_mask[:, :S]
             self.last_row = torch.full((B,), S - 1, dtype=torch.int64, device=dev)      # index of the last real position
             self.rope_pos = torch.zeros(n_new, B, dtype=torch.int32, device=dev)        # rotation position of new token t
-            self.q_last, self.x_last = z(B, 3 * D), z(B, D)
-            self._rows = torch.arange(B, device=dev)
+            self.q_last, self.x_last = z(B, D), z(B, D)
         else:
             self.key_mask = torch.ones(B, S, dtype=torch.uint8, device=dev) if use_mask else None
         self.logits_all = z(B * S, d.vocab, dtype=torch.float32) if all_rows else None
@@ -244,16 +243,14 @@ class OpenVLAEngine:
                 continue
             plan.append(ops.rope_kvcache(qkv, self.cos, self.sin, kc, vc, B=B, S=S, H=H, head_dim=hd, pos0=0, run=False))
             if last and self.padded:
-                # each sequence's last REAL position: gather its (rotated) q row and residual row (index glue, no
-                # arithmetic), then the same single-query attention / weight-streaming GEMMs as the un-padded plan
-                def gather(qkv=qkv, x3=x3):
-                    self.q_last.copy_(qkv.view(B, S, 3 * D)[self._rows, self.last_row])
-                    self.x_last.copy_(x3[self._rows, self.last_row])
-                plan.append(ops.glue("gather_last_real_rows", gather, (qkv, x3)))
-                q_last, x_last = self.q_last, self.x_last
+                # each sequence's last REAL position: gather its (rotated) q row and residual row (bl_gather_rows_bf16: a
+                # copy, no arithmetic), then the same single-query attention / weight-streaming GEMMs as the un-padded plan
+                q_last, x_last, last_row = self.q_last[b0:b1], self.x_last[b0:b1], self.last_row[b0:b1]
+                plan.append(ops.gather_rows(qkv.view(B, S, 3 * D)[:, :, :D], last_row, q_last, run=False))   # the q third
+                plan.append(ops.gather_rows(x3, last_row, x_last, run=False))
                 plan.append(ops.attention_decode(q_last, kc, vc, aod, B=B, H=H, Skv=S, head_dim=hd,
-                                                 q_strides=(3 * D, hd, 3 * D), k_strides=cs, v_strides=cs,
-                                                 o_strides=(D, hd, D), key_mask=self.cache_mask, run=False))
+                                                 q_strides=(D, hd, D), k_strides=cs, v_strides=cs,
+                                                 o_strides=(D, hd, D), key_mask=self.cache_mask[b0:b1], run=False))
             elif last:
                 q_last = qkv.view(B, S, 3 * D)[:, S - 1]                       # roped in place; row stride S·3D
                 x_last = x3[:, S - 1, :]
@@ -394,16 +391,19 @@ class OpenVLAEngine:
         self.pixel_values.copy_(pixel_values.to(torch.bfloat16))
         self.epoch += 1
 
-    def set_padded_inputs(self, input_ids: torch.Tensor, pixel_values: torch.Tensor, attention_mask: torch.Tensor) -> None:
+    def set_padded_inputs(self, input_ids: torch.Tensor, pixel_values: torch.Tensor, attention_mask: torch.Tensor,
+                          check: bool = True) -> None:
         """Right-padded prompts [B, L] with attention_mask [B, L] (1 = real token; the collator's layout,
-        util/data_utils.py:101-142). Fills the cache mask, the per-sequence last position and rotation positions."""
+        util/data_utils.py:101-142). Fills the cache mask, the per-sequence last position and rotation positions.
+        check=False skips the test of the mask's layout (a host synchronisation) for a caller that has made it 1…1 0…0
+        with at least one token itself; positions come from the mask's row sums (at most L), so they stay inside the cache either way."""
         if not self.padded:
             raise ValueError("engine was not built with padded=True")
         m = attention_mask.to(self.device).bool()
         if tuple(m.shape) != (self.B, self.L):
             raise ValueError(f"attention_mask must be {(self.B, self.L)}")
         n_real = m.sum(dim=1)
-        if bool((n_real < 1).any()) or not bool((m == (torch.arange(self.L, device=self.device)[None, :] < n_real[:, None])).all()):
+        if check and (bool((n_real < 1).any()) or not bool((m == (torch.arange(self.L, device=self.device)[None, :] < n_real[:, None])).all())):
             raise ValueError("generate(): prompts must be right-padded (attention_mask = 1…1 0…0) with at least one token")
         self.set_inputs(input_ids, pixel_values)
         P = self.dims.n_patches

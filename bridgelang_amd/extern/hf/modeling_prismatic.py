@@ -29,7 +29,7 @@ from __future__ import annotations
 from collections import OrderedDict
 from dataclasses import dataclass
 from types import SimpleNamespace
-from typing import Any, Dict, Optional, Tuple, Union
+from typing import Any, Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -323,10 +323,17 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         # de-tokenisation vocabulary: the padded "multiple of 64" rows are not action tokens (reference :503-504)
         self.vocab_size = self.dims.vocab - config.pad_to_multiple_of
 
-    def predict_action(self, input_ids: Optional[torch.LongTensor] = None, unnorm_key: Optional[str] = None,
+    def predict_action(self, input_ids: Optional[torch.LongTensor] = None, unnorm_key: Union[str, Sequence[Optional[str]], None] = None,
                        **kwargs: Any) -> np.ndarray:
-        """ids → 7 greedy action tokens → bin centres → un-normalised 7-DoF action (reference :506-536)."""
+        """ids → 7 greedy action tokens → bin centres → un-normalised 7-DoF action (reference :506-536). `unnorm_key` may
+        be a list with one key per sequence (extension: a server batch that mixes datasets of one action dimension);
+        the result is then always [B, n]."""
         input_ids = input_ids.to(self.device)
+        keys = list(unnorm_key) if isinstance(unnorm_key, (list, tuple)) else None
+        if keys is not None:
+            if len(keys) != input_ids.shape[0] or len({self.get_action_dim(k) for k in keys}) != 1:
+                raise ValueError("predict_action: a list of unnorm_keys needs one key per sequence, all of one action dimension")
+            unnorm_key = keys[0]
         m = kwargs.get("attention_mask")
         if m is not None and not bool(m.bool().all()):
             # right-padded batch: the empty token goes behind each sequence's last REAL token (one more column)
@@ -346,7 +353,10 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
                 kwargs["attention_mask"] = torch.cat((m, torch.ones_like(m[:, :1])), dim=1)
         n = self.get_action_dim(unnorm_key)
         generated = self.generate(input_ids, max_new_tokens=n, **kwargs)
-        return self.actions_from_token_ids(generated[:, -n:].cpu().numpy(), unnorm_key)
+        tokens = generated[:, -n:].cpu().numpy()
+        if keys is not None:
+            return np.stack([np.asarray(self.actions_from_token_ids(tokens[i:i + 1], k)).reshape(-1) for i, k in enumerate(keys)])
+        return self.actions_from_token_ids(tokens, unnorm_key)
 
     def with_empty_token(self, input_ids: torch.LongTensor) -> torch.LongTensor:
         """Append the special empty token 29871 the Llama tokenizer would have put after "Out:" (reference :510-515)."""

@@ -20,7 +20,7 @@ from ._lib import (AttnDesc, GemmDesc, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_KE
                    EPI_NONE, EPI_SWIGLU_BWD, EPI_SWIGLU_KEEP,
                    EPI_RES, EPI_SWIGLU)
 
-__all__ = ["Op", "gemm", "gemm_fp8", "quantize_rows_fp8", "quantize_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "skinny_supported", "rope_kvcache", "embed_splice",
+__all__ = ["Op", "gemm", "gemm_fp8", "quantize_rows_fp8", "quantize_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
            "argmax", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
            "EPI_NONE", "EPI_BIAS", "EPI_BIAS_GELU", "EPI_BIAS_RES", "EPI_RES", "EPI_SWIGLU", "EPI_F32", "EPI_F32_BF16R",
            "EPI_SWIGLU_KEEP", "EPI_BIAS_GELU_KEEP", "EPI_SWIGLU_BWD", "EPI_GELU_BWD"]
@@ -505,11 +505,16 @@ def write_prefix_tokens(prefix: torch.Tensor, x: torch.Tensor, B: int, T: int, r
 
 def attention_decode_rope_grouped(qkv: torch.Tensor, k_caches: Sequence[torch.Tensor], v_caches: Sequence[torch.Tensor],
                                   o: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, *, B: int, H: int, head_dim: int,
-                                  pos: Sequence[int], run: bool = True) -> Op:
-    """len(pos) decode iterations of different batches in one launch: rows g*B.. of qkv [G*B, 3*H*hd] / o [G*B, H*hd] use
-    caches k_caches[g] / v_caches[g] and position pos[g] (bl_attention_decode_rope_grouped_bf16)."""
+                                  pos: Optional[Sequence[int]] = None, rope_pos: Optional[Sequence[torch.Tensor]] = None,
+                                  run: bool = True) -> Op:
+    """G decode iterations of different batches in one launch: rows g*B.. of qkv [G*B, 3*H*hd] / o [G*B, H*hd] use
+    caches k_caches[g] / v_caches[g]. Exactly one of `pos` / `rope_pos` gives the positions: `pos[g]`, one host int for
+    the whole group (bl_attention_decode_rope_grouped_bf16), or `rope_pos[g]`, a contiguous int32 device tensor [B] with
+    every sequence's own position (right-padded batches, bl_attention_decode_rope_pos_grouped_bf16)."""
     lib = _lib.load()
-    G, D = len(pos), H * head_dim
+    if (pos is None) == (rope_pos is None):
+        raise ValueError("attention_decode_rope_grouped: give exactly one of pos / rope_pos")
+    G, D = len(pos if rope_pos is None else rope_pos), H * head_dim
     if not (1 <= G <= 8) or len(k_caches) != G or len(v_caches) != G:
         raise ValueError("attention_decode_rope_grouped: 1..8 groups, one cache pair and position each")
     for t, n in [(qkv, "qkv"), (cos, "cos"), (sin, "sin")] + [(t, "cache") for t in list(k_caches) + list(v_caches)]:
@@ -519,16 +524,52 @@ def attention_decode_rope_grouped(qkv: torch.Tensor, k_caches: Sequence[torch.Te
     cache_len = k_caches[0].shape[2]
     if any(tuple(t.shape) != tuple(k_caches[0].shape) for t in list(k_caches) + list(v_caches)):
         raise ValueError("attention_decode_rope_grouped: all caches must share one shape")
-    if max(pos) >= cache_len or max(pos) >= cos.shape[0] or qkv.shape[0] != G * B or o.shape[0] != G * B:
-        raise ValueError("attention_decode_rope_grouped: position outside the cache / rope table, or row count != G*B")
+    if qkv.shape[0] != G * B or o.shape[0] != G * B:
+        raise ValueError("attention_decode_rope_grouped: row count != G*B")
     cs = (H * cache_len * head_dim, cache_len * head_dim, head_dim)
-    d = _attn_desc(qkv, k_caches[0], v_caches[0], o, B, H, 1, pos[0] + 1, head_dim, (3 * D, head_dim, 3 * D), cs, cs,
-                   (D, head_dim, D), False, head_dim ** -0.5, None)
     kp = (C.c_void_p * G)(*[t.data_ptr() for t in k_caches])
     vp = (C.c_void_p * G)(*[t.data_ptr() for t in v_caches])
+    if rope_pos is not None:
+        for t in rope_pos:
+            if t.dtype != torch.int32 or not t.is_cuda or t.numel() != B or not t.is_contiguous():
+                raise TypeError("attention_decode_rope_grouped: each rope_pos[g] must be a contiguous CUDA/HIP int32 tensor [B]")
+        if tuple(k_caches[0].shape[:2]) != (B, H) or cache_len > cos.shape[0]:
+            raise ValueError("attention_decode_rope_grouped: caches must be [B, H, cache_len, hd] with cache_len inside the rope table")
+        d = _attn_desc(qkv, k_caches[0], v_caches[0], o, B, H, 1, cache_len, head_dim, (3 * D, head_dim, 3 * D), cs, cs,
+                       (D, head_dim, D), False, head_dim ** -0.5, None)
+        rp = (C.c_void_p * G)(*[t.data_ptr() for t in rope_pos])
+        op = Op("bl_attention_decode_rope_pos_grouped_bf16", lib.bl_attention_decode_rope_pos_grouped_bf16,
+                (C.byref(d), cos.data_ptr(), sin.data_ptr(), G, kp, vp, rp, cache_len),
+                (d, qkv, o, cos, sin, kp, vp, rp, list(k_caches), list(v_caches), list(rope_pos)))
+        if run:
+            op.run()
+        return op
+    if max(pos) >= cache_len or max(pos) >= cos.shape[0]:
+        raise ValueError("attention_decode_rope_grouped: position outside the cache / rope table")
+    d = _attn_desc(qkv, k_caches[0], v_caches[0], o, B, H, 1, pos[0] + 1, head_dim, (3 * D, head_dim, 3 * D), cs, cs,
+                   (D, head_dim, D), False, head_dim ** -0.5, None)
     pp = (C.c_int32 * G)(*[int(x) for x in pos])
     op = Op("bl_attention_decode_rope_grouped_bf16", lib.bl_attention_decode_rope_grouped_bf16,
             (C.byref(d), cos.data_ptr(), sin.data_ptr(), G, kp, vp, pp), (d, qkv, o, cos, sin, kp, vp, pp, list(k_caches), list(v_caches)))
+    if run:
+        op.run()
+    return op
+
+
+def gather_rows(src: torch.Tensor, row_index: torch.Tensor, dst: torch.Tensor, run: bool = True) -> Op:
+    """dst[b] = src[b, row_index[b]] (bl_gather_rows_bf16): src [B, R, W] with contiguous rows (any row stride), row_index
+    int64 device [B], dst contiguous [B, W]. A pure 16-byte copy, no allocation: usable inside a captured graph."""
+    lib = _lib.load()
+    _bf16(src, "src"); _bf16(dst, "dst")
+    if src.dim() != 3 or src.stride(2) != 1 or src.stride(0) != src.shape[1] * src.stride(1):
+        raise ValueError(f"gather_rows: src must be [B, R, W] with contiguous rows and batch stride R * row stride, got stride {src.stride()}")
+    B, R, Wd = src.shape
+    if tuple(dst.shape) != (B, Wd) or not dst.is_contiguous():
+        raise ValueError(f"gather_rows: dst must be contiguous [{B}, {Wd}]")
+    if row_index.dtype != torch.int64 or not row_index.is_cuda or row_index.numel() != B or not row_index.is_contiguous():
+        raise TypeError("gather_rows: row_index must be a contiguous CUDA/HIP int64 tensor [B]")
+    op = Op("bl_gather_rows_bf16", lib.bl_gather_rows_bf16,
+            (src.data_ptr(), row_index.data_ptr(), R, src.stride(1), Wd, dst.data_ptr(), B), (src, row_index, dst))
     if run:
         op.run()
     return op

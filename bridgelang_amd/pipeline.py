@@ -88,19 +88,28 @@ class StaggeredDecodePipeline:
 
     Results per sequence equal the plain engine's bit for bit: the stacked rows go through kernels that reproduce the
     per-batch kernels' fp32 summation order (_plan_merged; tests/test_pipeline_gpu.py).
+
+    padded=True serves prompts of DIFFERENT lengths (up to prompt_len) from the one set of slots and graphs: every slot is
+    an `OpenVLAEngine(padded=True)`, a batch arrives right-padded with its attention mask (`step(..., attention_mask)`),
+    and in the merged iteration every sequence rotates, appends and attends at its own position — the slot engine's
+    device-side `rope_pos` rows, read by bl_attention_decode_rope_pos_grouped_bf16. Every sequence gets the ids and logits
+    of its own un-padded batch-1 run, bit for bit (tests/test_pipeline_padded_gpu.py).
     """
 
     def __init__(self, weights: VLAWeights, batch: int, prompt_len: int, n_new: int = 7, split_vision: bool = False,
-                 fp8: bool = False):
+                 fp8: bool = False, padded: bool = False):
         """split_vision=True adds a third stage: the vision towers + projector of the batch submitted NOW run beside the
         Llama prefill of the batch submitted one step earlier (n_new + 1 slots, latency n_new + 1 steps)."""
         if n_new < 2:
             raise ValueError("StaggeredDecodePipeline needs at least one decode iteration (n_new >= 2)")
+        if padded and fp8:
+            raise ValueError("padded generation is built for the bf16 generation plan")
+        self.padded = padded
         self.w, self.dims, self.B, self.n_new = weights, weights.dims, batch, n_new
         self.split_vision = split_vision
         self.lag = 1 if split_vision else 0         # steps between a batch's submission and its prefill
         self.slots = n_new + self.lag
-        self.engines = [OpenVLAEngine(weights, batch, prompt_len, n_new, fp8=fp8) for _ in range(self.slots)]
+        self.engines = [OpenVLAEngine(weights, batch, prompt_len, n_new, fp8=fp8, padded=padded) for _ in range(self.slots)]
         self.device = dev = weights.embed.device
         d = self.dims
         G = n_new - 1
@@ -153,16 +162,20 @@ class StaggeredDecodePipeline:
             plan += gm(self.hd, lw.qkv_w, self.qkvd, EPI_NONE)
             grouped = fused and len(groups) <= 8
             if grouped:     # all decode iterations' attention in one launch
+                # padded: group g's sequences sit at their own positions, row g of the slot engine's device-side rope_pos
+                at = (dict(rope_pos=[e.rope_pos[g] for g, e, _ in groups]) if self.padded else
+                      dict(pos=[e.S + g - 1 for g, e, _ in groups]))
                 plan.append(ops.attention_decode_rope_grouped(
                     self.qkvd, [e.k_cache[l] for _, e, _ in groups], [e.v_cache[l] for _, e, _ in groups], self.aod,
-                    e0.cos, e0.sin, B=B, H=H, head_dim=hd, pos=[e.S + g - 1 for g, e, _ in groups], run=False))
+                    e0.cos, e0.sin, B=B, H=H, head_dim=hd, run=False, **at))
             for g, e, r in groups:
                 pos = e.S + g - 1
                 if grouped:
                     continue
                 if fused:
+                    pad_kw = dict(rope_pos=e.rope_pos[g]) if self.padded else {}
                     plan.append(ops.attention_decode_rope(self.qkvd[r], e.k_cache[l], e.v_cache[l], self.aod[r], e0.cos, e0.sin,
-                                                          B=B, H=H, head_dim=hd, pos=pos, run=False))
+                                                          B=B, H=H, head_dim=hd, pos=pos, run=False, **pad_kw))
                 else:
                     cs = (H * e.cache_len * hd, e.cache_len * hd, hd)
                     plan.append(ops.rope_kvcache(self.qkvd[r], e0.cos, e0.sin, e.k_cache[l], e.v_cache[l], B=B, S=1, H=H,
@@ -214,12 +227,22 @@ class StaggeredDecodePipeline:
             self._graphs[k] = g
 
     @torch.no_grad()
-    def step(self, input_ids: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def step(self, input_ids: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
+             attention_mask: Optional[torch.Tensor] = None, mask_checked: bool = False) -> torch.Tensor:
         """Submit a batch (None: re-use the inputs resident in the slot's buffers) and return the [B, n_new] ids of the
         batch submitted n_new-1 steps earlier, which this step completed (garbage until the pipeline has filled). The
-        returned view is overwritten by the next step() — copy it first."""
+        returned view is overwritten by the next step() — copy it first. A padded pipeline takes right-padded prompts with
+        their `attention_mask` [B, prompt_len] (1…1 0…0; None: all ones); the slot keeps the masks and positions derived
+        from it until its batch completes (with split_vision its prefill reads them one step later). The mask's layout is
+        checked on the device, which costs a host synchronisation per step; `mask_checked=True` skips it for a caller
+        that built the masks itself (the server), so submission stays asynchronous like the un-padded one."""
         k = self._tick % self.slots
-        if input_ids is not None:
+        if attention_mask is not None and (not self.padded or input_ids is None):
+            raise ValueError("attention_mask goes with the input_ids of a pipeline built with padded=True")
+        if input_ids is not None and self.padded:
+            mask = attention_mask if attention_mask is not None else torch.ones_like(input_ids)
+            self.engines[k].set_padded_inputs(input_ids, pixel_values, mask, check=not (mask_checked or attention_mask is None))
+        elif input_ids is not None:
             self.engines[k].set_inputs(input_ids, pixel_values)
         if self._graphs[k] is not None:
             self._graphs[k].replay()

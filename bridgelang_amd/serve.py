@@ -21,6 +21,13 @@ single merged pass over the weights (pipeline.py; the mode `bench.py` measures, 
 request is answered 7 ticks after its batch was submitted; when the queue runs dry the pipeline is drained at once
 (`flush`), so a lone request still returns after one prefill + six plain decode steps. Partial batches are padded with
 copies of their last request.
+
+Mixed-length traffic (`pad_to=L`, opt-in): instructions differ in length, so batches keyed on the prompt length stay small
+and every change of length drains the pipeline. With `pad_to`, every prompt of at most L tokens (its empty token 29871
+included) is right-padded to L with an attention mask and shares batches with all the others, whatever its length and
+`unnorm_key` (equal action dimension); throughput mode then runs ONE `StaggeredDecodePipeline(padded=True)` for all of
+them. Each request still gets the action of its own batch-1 call, bit for bit (tests/test_serve_padded_gpu.py). Longer
+prompts take the per-length route above.
 """
 from __future__ import annotations
 
@@ -93,21 +100,29 @@ def decode_tree(obj: Any) -> Any:
 
 # ---- server ----------------------------------------------------------------------------------------------------------
 class _Request:
-    __slots__ = ("input_ids", "pixel_values", "unnorm_key", "future")
+    __slots__ = ("input_ids", "pixel_values", "unnorm_key", "future", "mask", "group")
 
     def __init__(self, input_ids, pixel_values, unnorm_key):
         self.input_ids, self.pixel_values, self.unnorm_key = input_ids, pixel_values, unnorm_key
         self.future: Future = Future()
+        self.mask: Optional[torch.Tensor] = None      # pad_to: attention mask [1, pad_to] of the right-padded input_ids
+        self.group: Optional[tuple] = None            # requests with equal group keys may share a GPU batch
 
 
 class OpenVLAServer:
     """`vla`: OpenVLAForActionPrediction (HIP) — anything with `predict_action(input_ids=, pixel_values=, unnorm_key=,
-    do_sample=False) -> ndarray [B, 7] (or [7] at B = 1)`; `processor(prompt, PIL image) -> {input_ids, pixel_values}`."""
+    do_sample=False) -> ndarray [B, 7] (or [7] at B = 1)`; `processor(prompt, PIL image) -> {input_ids, pixel_values}`.
+    `pad_to=L` additionally uses `vla.with_empty_token`, `vla.pad_token_id`, `vla.get_action_dim` and calls
+    `predict_action(..., attention_mask=, unnorm_key=[one key per sequence])`."""
 
     def __init__(self, vla: Any, processor: Any, openvla_path: Union[str, Path] = "openvla/openvla-7b",
                  max_batch: int = 16, max_wait_ms: float = 2.0, norm_stats_path: Optional[Union[str, Path]] = None,
-                 pipeline_batch: Optional[int] = None, max_pipelines: int = 2):
+                 pipeline_batch: Optional[int] = None, max_pipelines: int = 2, pad_to: Optional[int] = None):
         self.vla, self.processor, self.openvla_path = vla, processor, str(openvla_path)
+        self.pad_to = int(pad_to) if pad_to else None
+        self._pad_pipe: Optional[Tuple[Any, Dict[int, Any]]] = None     # pad_to: the one padded pipeline + its batches in flight
+        self.pipelines_built = 0                  # StaggeredDecodePipelines constructed so far (observability / tests)
+        self.batch_lengths: List[List[int]] = []  # per GPU batch: its requests' prompt lengths as the model sees them (empty token included)
         self.max_batch, self.max_wait = int(max_batch), float(max_wait_ms) * 1e-3
         self.pipeline_batch = pipeline_batch
         if pipeline_batch:
@@ -115,6 +130,7 @@ class OpenVLAServer:
         # prompt length → (StaggeredDecodePipeline, {tick: requests}); least recently used first. A pipeline is 7 engines
         # (KV caches + activations, ≈ 3 GB each at B = 16 on 7B) + 7 graphs, and instruction lengths vary per request, so
         # only `max_pipelines` are kept; the plain path's engines are bounded the same way on the model (engine LRU).
+        # With `pad_to` the ONE padded pipeline is held in addition to these and is never evicted (7 more engines).
         self._pipes: "OrderedDict[int, Any]" = OrderedDict()
         self.max_pipelines = max(1, int(max_pipelines))
         stats = Path(norm_stats_path) if norm_stats_path else Path(self.openvla_path) / "dataset_statistics.json"
@@ -127,13 +143,16 @@ class OpenVLAServer:
         self._worker.start()
 
     # -- request side (any thread) --
-    def _submit(self, payload: Dict[str, Any]) -> np.ndarray:
+    def _make_request(self, payload: Dict[str, Any]) -> _Request:
         from PIL import Image
         image, instruction = payload["image"], payload["instruction"]
         unnorm_key = payload.get("unnorm_key", None)
         prompt = get_openvla_prompt(instruction, self.openvla_path)
         inputs = self.processor(prompt, Image.fromarray(np.asarray(image, dtype=np.uint8)).convert("RGB"))
-        req = _Request(inputs["input_ids"], inputs["pixel_values"], unnorm_key)
+        return _Request(inputs["input_ids"], inputs["pixel_values"], unnorm_key)
+
+    def _submit(self, payload: Dict[str, Any]) -> np.ndarray:
+        req = self._make_request(payload)
         self._q.put(req)
         return req.future.result()
 
@@ -164,7 +183,7 @@ class OpenVLAServer:
         self._held = None
         if first is None:
             return None
-        batch, key = [first], (tuple(first.input_ids.shape), first.unnorm_key)
+        batch, key = [first], self._group(first)
         deadline = time.monotonic() + self.max_wait
         while len(batch) < self.max_batch:
             try:
@@ -174,13 +193,53 @@ class OpenVLAServer:
             if nxt is None:
                 self._q.put(None)
                 break
-            if (tuple(nxt.input_ids.shape), nxt.unnorm_key) != key:
+            if self._group(nxt) != key:
                 self._held = nxt               # different prompt length / statistics: heads the next batch
                 break
             batch.append(nxt)
         return batch
 
-    # -- throughput mode: one pipeline per prompt length --
+    def _group(self, r: _Request) -> tuple:
+        """The key requests must share to ride one GPU batch: prompt shape and `unnorm_key`; with `pad_to`, every prompt
+        that fits is first right-padded to it (`_pad`) and then shares a batch with all others of its action dimension."""
+        if r.group is None:
+            r.group = (tuple(r.input_ids.shape), r.unnorm_key)
+            if self.pad_to is not None:
+                try:
+                    self._pad(r)
+                except Exception:   # noqa: BLE001 — this runs on the batcher thread: the request keeps the un-padded route
+                    logging.warning("pad_to: request left un-padded:\n%s", traceback.format_exc())
+                    r.mask, r.group = None, (tuple(r.input_ids.shape), r.unnorm_key)
+        return r.group
+
+    def _pad(self, r: _Request) -> None:
+        """pad_to: the empty token goes behind the request's own last token, then pad ids up to `pad_to` columns, hidden
+        by the attention mask 1…1 0…0. A prompt that does not fit, or a key without statistics, keeps today's route."""
+        ids = self.vla.with_empty_token(r.input_ids)
+        n, L = ids.shape[1], self.pad_to
+        if ids.shape[0] != 1 or n > L:
+            return
+        try:
+            dim = self.vla.get_action_dim(r.unnorm_key)
+        except Exception:   # noqa: BLE001 — unknown unnorm_key: the request fails alone, on the route it takes today
+            return
+        r.input_ids = torch.cat([ids, torch.full((1, L - n), self.vla.pad_token_id, dtype=ids.dtype, device=ids.device)], dim=1)
+        r.mask = (torch.arange(L, device=ids.device)[None, :] < n).long()
+        r.group = ("padded", L, dim)
+
+    # -- throughput mode: one pipeline per prompt length (pad_to: ONE padded pipeline for every prompt that fits) --
+    def _live(self) -> List[Tuple[Any, Dict[int, Any]]]:
+        return ([self._pad_pipe] if self._pad_pipe is not None else []) + list(self._pipes.values())
+
+    def _padded_pipe(self):
+        from .pipeline import StaggeredDecodePipeline
+        if self._pad_pipe is None:
+            pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, self.pad_to, padded=True)
+            pipe.capture()
+            self.pipelines_built += 1
+            self._pad_pipe = (pipe, {})
+        return self._pad_pipe
+
     def _pipe_for(self, L: int):
         from .pipeline import StaggeredDecodePipeline
         if L in self._pipes:
@@ -194,6 +253,7 @@ class OpenVLAServer:
             torch.cuda.empty_cache()
         pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, L)
         pipe.capture()
+        self.pipelines_built += 1
         self._pipes[L] = (pipe, {})
         return self._pipes[L]
 
@@ -206,7 +266,7 @@ class OpenVLAServer:
                 r.future.set_exception(e)
 
     def _drain(self) -> None:
-        for pipe, inflight in self._pipes.values():
+        for pipe, inflight in self._live():
             if inflight:
                 outs = pipe.flush(ticks=set(inflight))    # oldest first; None for slots answered earlier
                 for t, out in zip(range(pipe._tick - len(outs), pipe._tick), outs):
@@ -217,7 +277,7 @@ class OpenVLAServer:
     def _serve_pipelined(self) -> None:
         dev = self.vla.device
         while True:
-            busy = any(inflight for _, inflight in self._pipes.values())
+            busy = any(inflight for _, inflight in self._live())
             if busy and self._held is None and self._q.empty():
                 self._drain()                             # nothing waiting: finish what is in flight right away
                 continue
@@ -230,20 +290,28 @@ class OpenVLAServer:
                     # the pipelines decode 7 tokens; other action dimensions go through the plain engine
                     self._run_plain(batch)
                     continue
-                ids = self.vla.with_empty_token(torch.cat([r.input_ids for r in batch], dim=0).to(dev))
+                padded = batch[0].mask is not None
+                ids = torch.cat([r.input_ids for r in batch], dim=0).to(dev)
+                if not padded:
+                    ids = self.vla.with_empty_token(ids)
                 pv = torch.cat([r.pixel_values for r in batch], dim=0).to(dev, torch.bfloat16)
+                mask = torch.cat([r.mask for r in batch], dim=0).to(dev) if padded else None
                 pad = self.pipeline_batch - len(batch)
                 if pad:
                     ids = torch.cat([ids, ids[-1:].expand(pad, -1)], dim=0)
                     pv = torch.cat([pv, pv[-1:].expand(pad, -1, -1, -1)], dim=0)
-                for L2, (other, infl) in self._pipes.items():      # one pipeline at a time keeps the tick bookkeeping simple
-                    if L2 != ids.shape[1] and infl:
-                        self._drain()
-                pipe, inflight = self._pipe_for(ids.shape[1])
+                    mask = torch.cat([mask, mask[-1:].expand(pad, -1)], dim=0) if padded else None
+                # one pipeline at a time keeps the tick bookkeeping simple: every OTHER pipeline is drained before this
+                # batch's pipeline is fetched (or built: _pipe_for may evict, and evicts drained pipelines only)
+                target = self._pad_pipe if padded else self._pipes.get(ids.shape[1])
+                if any(e[1] and e is not target for e in self._live()):
+                    self._drain()
+                pipe, inflight = self._padded_pipe() if padded else self._pipe_for(ids.shape[1])
                 tick = pipe._tick
-                out = pipe.step(ids, pv)
+                # the masks were built here, on the host (_pad): 1…1 0…0 by construction, nothing to check on the device
+                out = pipe.step(ids, pv, mask, mask_checked=True) if padded else pipe.step(ids, pv)
                 inflight[tick] = batch
-                self.batch_sizes.append(len(batch))
+                self._record(batch)
                 done = tick - (pipe.slots - 1)
                 if done in inflight:
                     self._resolve(inflight.pop(done), out.clone())
@@ -261,6 +329,11 @@ class OpenVLAServer:
                 return
             self._run_plain(batch)
 
+    def _record(self, batch: List[_Request]) -> None:
+        self.batch_sizes.append(len(batch))
+        self.batch_lengths.append([int(r.mask.sum()) if r.mask is not None else
+                                   int(r.input_ids.shape[1]) + int(r.input_ids[0, -1] != 29871) for r in batch])
+
     def _run_plain(self, batch: List[_Request]) -> None:
         """One predict_action call for the batch. Batch sizes are rounded up to 1 / 2 / 4 / 8 / 16 … with copies of the
         last request, so the model builds (and its engine LRU holds) few distinct engines."""
@@ -269,12 +342,18 @@ class OpenVLAServer:
             size = 1
             while size < n:
                 size *= 2
-            ids = torch.cat([r.input_ids for r in batch] + [batch[-1].input_ids] * (size - n), dim=0)
-            pv = torch.cat([r.pixel_values for r in batch] + [batch[-1].pixel_values] * (size - n), dim=0)
-            actions = np.asarray(self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=batch[0].unnorm_key,
-                                                         do_sample=False))
+            rows = batch + [batch[-1]] * (size - n)
+            ids = torch.cat([r.input_ids for r in rows], dim=0)
+            pv = torch.cat([r.pixel_values for r in rows], dim=0)
+            if batch[0].mask is not None:     # pad_to: lengths and keys are mixed — every sequence un-normalised with its own key
+                actions = np.asarray(self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=[r.unnorm_key for r in rows],
+                                                             attention_mask=torch.cat([r.mask for r in rows], dim=0),
+                                                             do_sample=False))
+            else:
+                actions = np.asarray(self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=batch[0].unnorm_key,
+                                                             do_sample=False))
             actions = actions.reshape(size, -1)[:n]
-            self.batch_sizes.append(n)
+            self._record(batch)
             for r, a in zip(batch, actions):
                 r.future.set_result(a)
         except Exception as e:   # noqa: BLE001 — delivered to every waiting request

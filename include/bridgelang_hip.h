@@ -228,6 +228,17 @@ int bl_attention_decode_rope_pos_bf16(const bl_attn_desc* d, const bl_bf16* cos_
  * bl_attention_decode_rope_bf16. */
 int bl_attention_decode_rope_grouped_bf16(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab, int32_t n_groups,
                                           bl_bf16* const* k_caches, bl_bf16* const* v_caches, const int32_t* pos, void* stream);
+/* The grouped form for RIGHT-PADDED batches (StaggeredDecodePipeline(padded=True)): group g carries a DEVICE array
+ * rope_pos[g] (int32 [B]) in place of the one host position; sequence b of group g rotates, appends and attends at
+ * rope_pos[g][b], as in bl_attention_decode_rope_pos_bf16 — per row bit-identical to that call on the group alone, and to
+ * bl_attention_decode_rope_bf16 where a group's positions coincide. The pointer arrays are HOST arrays read at call time;
+ * the positions are read by the kernel, so nothing on the host can check them: a sequence whose position lies outside
+ * [0, cache_len) is skipped (no cache write, no output). cache_len <= 2048 rows per head (d->k_hs / d->v_hs must hold
+ * them), and cos_tab / sin_tab must hold at least cache_len rows: the call cannot see their length. d->k / d->v / d->Skv
+ * are ignored and d->key_mask must be NULL. */
+int bl_attention_decode_rope_pos_grouped_bf16(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab,
+                                              int32_t n_groups, bl_bf16* const* k_caches, bl_bf16* const* v_caches,
+                                              const int32_t* const* rope_pos, int32_t cache_len, void* stream);
 
 /* ---- Llama glue -------------------------------------------------------------------------------------------- */
 /* Half-split RoPE (HF apply_rotary_pos_emb) on the q and k thirds of a fused qkv buffer [B*S, 3*H*hd], bf16 cos/sin
@@ -241,6 +252,11 @@ int bl_rope_kvcache_bf16(bl_bf16* qkv, int32_t B, int32_t S, int32_t H, int32_t 
  * projector epilogue. ids int64 [B, L]; dst [B, L+n_patches, dim]. With n_patches = 0 it is a plain gather. */
 int bl_embed_splice_bf16(const int64_t* ids, int32_t B, int32_t L, const bl_bf16* table, int32_t dim,
                          int32_t n_patches, bl_bf16* dst, void* stream);
+/* dst[b, :width] = src[b, row_index[b], :width] for b < B: src is [B, rows_per_batch] rows of row_stride elements, dst a
+ * dense [B, width]; row_index is a DEVICE int64 [B] (the last real position of each right-padded prompt). 16-byte copies:
+ * width and row_stride multiples of 8. An index outside [0, rows_per_batch) copies nothing for that row. */
+int bl_gather_rows_bf16(const bl_bf16* src, const int64_t* row_index, int64_t rows_per_batch, int64_t row_stride,
+                        int32_t width, bl_bf16* dst, int32_t B, void* stream);
 /* Row-wise argmax of fp32 logits [rows, n] (first maximal index, as torch.argmax); out int64 [rows]. */
 int bl_argmax_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, int64_t* out, void* stream);
 
