@@ -42,7 +42,7 @@ def _fp8_layers(weights: VLAWeights) -> list:
 class OpenVLAEngine:
     def __init__(self, weights: VLAWeights, batch: int, prompt_len: int, n_new: int = 7, all_rows: bool = False,
                  use_mask: bool = False, splitk: bool = False, fp8: bool = False, padded: bool = False,
-                 vision_only: bool = False, text_only: bool = False):
+                 vision_only: bool = False, text_only: bool = False, sample: bool = False):
         """all_rows=True builds the training/eval-style forward instead of generation: logits for every position
         (`logits_all` [B*S, vocab] fp32) and no decode steps. use_mask=True threads a [B, S] uint8 key-padding mask
         (`key_mask`, 1 = attend) through the Llama attention (modeling_prismatic.py:387-390). splitk=True lets
@@ -58,7 +58,12 @@ class OpenVLAEngine:
         sequence gets exactly the ids and logits it gets alone, un-padded (tests/test_hf_boundary_gpu.py).
         vision_only=True plans the towers alone (the training step's frozen front end): no Llama plans, so nothing here
         holds the decoder-layer weights (parameter-sharded training frees them). text_only=True plans the reference's
-        language-only forward (`pixel_values is None`, modeling_prismatic.py:343-359): no towers, no projector, S = L."""
+        language-only forward (`pixel_values is None`, modeling_prismatic.py:343-359): no towers, no projector, S = L.
+        sample=True ends every generation step in bl_sample_f32 instead of bl_argmax_f32 (sampling.py is its
+        specification): per-sequence temperature / top-k / top-p / seed live in device buffers filled by `set_sampling`
+        (so one captured graph serves any settings; a sequence at temperature 0 is greedy, bit for bit), and `gen_wt`
+        [n_new, B, 2] receives each drawn token's integer weight and the kept total (its probability = their quotient).
+        Step t of a sequence draws from Philox(key = its seed, counter = t): the draw does not depend on the batch slot."""
         self.w, self.dims = weights, weights.dims
         self.vision_only, self.text_only = vision_only, text_only
         if text_only and (vision_only or padded or fp8):
@@ -67,7 +72,9 @@ class OpenVLAEngine:
         if not vision_only and not weights.layers_resident:
             raise RuntimeError("the decoder-layer weights are sharded out of the model (parameter-sharded training in progress): "
                                "call the strategy's finish() / TrainStep.materialize_params() before building an inference engine")
-        self.padded = padded
+        self.padded, self.sample = padded, sample
+        if sample and (all_rows or vision_only):
+            raise ValueError("sample=True belongs to a generation plan")
         use_mask = use_mask or padded
         if padded and (all_rows or fp8):
             raise ValueError("padded generation is built for the bf16 generation plan")
@@ -90,6 +97,10 @@ class OpenVLAEngine:
         self.input_ids = z(B, prompt_len, dtype=torch.int64)
         self.gen_ids = z(n_new, B, dtype=torch.int64)
         self.logits = z(n_new, B, d.vocab, dtype=torch.float32)
+        if sample:      # settings of the sequences now in the buffers (zeros: temperature 0 = greedy) and the weight pairs
+            self.samp_temperature, self.samp_top_k = z(B, dtype=torch.float32), z(B, dtype=torch.int32)
+            self.samp_top_p, self.samp_seed = torch.ones(B, dtype=torch.float32, device=dev), z(B, dtype=torch.int64)
+            self.gen_wt = z(n_new, B, 2, dtype=torch.int64)
         # vision buffers (sized for the larger tower, shared by both: they run back to back on one stream)
         tmax = max(d.dino.tokens, d.siglip.tokens)
         dmax = max(d.dino.dim, d.siglip.dim)
@@ -283,7 +294,8 @@ class OpenVLAEngine:
         return plan
 
     def _head(self, x_rows: torch.Tensor, t: int, b0: int = 0, b1: Optional[int] = None) -> List[Op]:
-        """final RMSNorm → lm_head (bf16-rounded fp32 logits) → greedy argmax, for generation step t."""
+        """final RMSNorm → lm_head (bf16-rounded fp32 logits) → greedy argmax (sample=True: the seeded draw), for
+        generation step t."""
         d, w = self.dims, self.w
         b1 = self.B if b1 is None else b1
         logits, ids, hdd = self.logits[t][b0:b1], self.gen_ids[t][b0:b1], self.hd[b0:b1]
@@ -292,7 +304,11 @@ class OpenVLAEngine:
         else:
             plan = [ops.rmsnorm(x_rows, w.norm, hdd, d.rms_eps, run=False),
                     self._g(hdd, w.lm_head, logits, EPI_F32_BF16R, run=False)]
-        plan.append(ops.argmax(logits, ids, run=False))
+        if self.sample:
+            plan.append(ops.sample(logits, self.samp_temperature[b0:b1], self.samp_top_k[b0:b1], self.samp_top_p[b0:b1],
+                                   self.samp_seed[b0:b1], t, ids, self.gen_wt[t][b0:b1], run=False))
+        else:
+            plan.append(ops.argmax(logits, ids, run=False))
         return plan
 
     def _plan_decode(self, t: int) -> List[Op]:
@@ -412,9 +428,22 @@ class OpenVLAEngine:
         self.last_row.copy_(P + n_real - 1)
         self.rope_pos.copy_((P + n_real)[None, :].to(torch.int32) + torch.arange(self.n_new, device=self.device, dtype=torch.int32)[:, None] - 1)
 
+    def set_sampling(self, params) -> None:
+        """Fill the per-sequence settings buffers from a `sampling.SamplingParams` (scalars or one value per sequence;
+        seed=None draws the seeds from torch's default CPU generator). They stay until the next call."""
+        if not self.sample:
+            raise ValueError("engine was not built with sample=True")
+        T, k, p, seed = params.resolve(self.B)
+        for buf, a in ((self.samp_temperature, T), (self.samp_top_k, k), (self.samp_top_p, p), (self.samp_seed, seed)):
+            buf.copy_(torch.from_numpy(a))
+
     @torch.no_grad()
-    def generate(self, input_ids: torch.Tensor, pixel_values: torch.Tensor) -> torch.Tensor:
-        """Greedy n_new tokens for every sequence. Returns int64 [B, n_new] (device tensor; no host sync inside)."""
+    def generate(self, input_ids: torch.Tensor, pixel_values: torch.Tensor, sampling=None) -> torch.Tensor:
+        """n_new tokens for every sequence: greedy, or on a sample=True engine drawn under `sampling` (None: the settings
+        already in the buffers; the weight pairs are left in `gen_wt`). Returns int64 [B, n_new] (device tensor; no host
+        sync inside)."""
+        if sampling is not None:
+            self.set_sampling(sampling)
         self.set_inputs(input_ids, pixel_values)
         self.replay()
         return self.gen_ids.t()

@@ -21,7 +21,10 @@ Differences from the reference, all deliberate:
   * batched `predict_action` is supported (returns [B, 7]); batch 1 returns the reference's 1-D array.
   * batched generation takes RIGHT-padded prompts + attention_mask (the collator's layout); every sequence gets the ids
     it gets alone (the reference asserts batch 1 in its cached branch, :326, :460-463).
-  * the greedy loop runs on-device (no per-token host sync); `do_sample=True` is rejected.
+  * the greedy loop runs on-device (no per-token host sync). Sampling runs on the device too, through `sampling=
+    SamplingParams(...)` (seeded Philox draws with temperature / top-k / top-p, bridgelang_amd/sampling.py) and
+    `sample_actions`; `do_sample=True` alone is rejected: HF draws from torch's global device RNG stream, which this path
+    does not reproduce.
   * when 29871 is appended to the prompt the attention mask is extended with it (reference quirk C.1).
 """
 from __future__ import annotations
@@ -36,6 +39,7 @@ import torch
 from transformers import PreTrainedModel
 
 from ...engine import OpenVLAEngine
+from ...sampling import SamplingParams, derive_seed, logprob
 from ...weights import TowerDims, VLADims, VLAWeights, allocate
 from .configuration_prismatic import OpenVLAConfig, PrismaticConfig
 
@@ -202,13 +206,15 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             cache.move_to_end(key)
         return eng
 
-    def engine(self, batch: int, prompt_len: int, n_new: int = 7, padded: bool = False, cached: bool = False) -> OpenVLAEngine:
+    def engine(self, batch: int, prompt_len: int, n_new: int = 7, padded: bool = False, cached: bool = False,
+               sample: bool = False) -> OpenVLAEngine:
         """`cached=True`: the engine behind a `forward(..., use_cache=True)` KV-cache handle — keyed apart from the engines
         `predict_action` / `generate` use, so an interleaved action prediction of the same shape does not invalidate the
         caller's cache (each kind has its own LRU slot; a second cached prefill of the same shape still does)."""
         fp8 = bool(getattr(self, "fp8", False))       # `model.fp8 = True`: W8A8 e4m3 Llama prefill projections (extension)
-        return self._lru(self._engines, (batch, prompt_len, n_new, fp8, padded, cached),
-                         lambda: OpenVLAEngine(self.weights, batch, prompt_len, n_new=n_new, fp8=fp8 and not padded, padded=padded))
+        return self._lru(self._engines, (batch, prompt_len, n_new, fp8, padded, cached, sample),
+                         lambda: OpenVLAEngine(self.weights, batch, prompt_len, n_new=n_new, fp8=fp8 and not padded, padded=padded,
+                                               sample=sample))
 
     # ---- forward: the reference's three branches (modeling_prismatic.py:322-415) ----
     cache_new_tokens = 7       # tokens a `forward(..., use_cache=True)` KV cache is sized for (prefill token + 6 cached steps)
@@ -286,29 +292,41 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
 
     # nn.Module.__call__ dispatches to forward()
 
-    # ---- greedy generation ----
+    # ---- generation: greedy, or seeded sampling ----
     @torch.no_grad()
     def generate(self, input_ids: torch.LongTensor, max_new_tokens: int = 7, pixel_values: Optional[torch.Tensor] = None,
                  attention_mask: Optional[torch.Tensor] = None, do_sample: bool = False, use_cache: bool = True,
-                 **_: Any) -> torch.LongTensor:
+                 sampling: Optional[SamplingParams] = None, return_weights: bool = False, **_: Any):
         """Greedy decoding, returns [B, L + max_new_tokens] like GenerationMixin (prompt ‖ new tokens). `use_cache` is
         accepted and ignored: the KV cache is always used (use_cache=False in the fork's demo re-runs the vision towers
         7 times, run_openvla_demo.py:43 — same result, 7× the work). A batch whose attention_mask has zeros is taken as
-        RIGHT-padded prompts: pads are hidden from attention and every sequence continues from its own last token."""
-        if do_sample:
-            raise NotImplementedError("only greedy decoding (do_sample=False) is on the HIP path")
+        RIGHT-padded prompts: pads are hidden from attention and every sequence continues from its own last token.
+        `sampling=SamplingParams(temperature, top_k, top_p, seed)` draws the tokens instead (per-sequence settings and
+        seeds; bridgelang_amd/sampling.py is the exact specification, and a sequence's tokens depend on its own seed only,
+        not on the batch around it); `return_weights=True` then returns (ids, wt [B, max_new_tokens, 2] int64): the drawn
+        token's integer weight and the kept total of every step, whose quotient is its probability (`sampling.logprob`)."""
+        if do_sample and sampling is None:
+            raise NotImplementedError("do_sample=True draws from torch's global device RNG stream, which the HIP path does "
+                                      "not reproduce: pass sampling=SamplingParams(temperature=, top_k=, top_p=, seed=) instead")
+        if return_weights and sampling is None:
+            raise ValueError("return_weights goes with sampling=")
         if pixel_values is None:
             raise ValueError("generate() needs pixel_values")
         B, L = input_ids.shape
         ids, pv = input_ids.to(self.device), pixel_values.to(self.device)
+        sample = sampling is not None
         if attention_mask is not None and not bool(attention_mask.bool().all()):
-            eng = self.engine(B, L, max_new_tokens, padded=True)
+            eng = self.engine(B, L, max_new_tokens, padded=True, sample=sample)
+            if sample:
+                eng.set_sampling(sampling)
             eng.set_padded_inputs(ids, pv, attention_mask)
             eng.run_eager()
             new = eng.gen_ids.t()
         else:
-            new = self.engine(B, L, max_new_tokens).generate(ids, pv)
-        return torch.cat([ids, new], dim=1)
+            eng = self.engine(B, L, max_new_tokens, sample=sample)
+            new = eng.generate(ids, pv, sampling)
+        out = torch.cat([ids, new], dim=1)
+        return (out, eng.gen_wt.permute(1, 0, 2).clone()) if return_weights else out
 
 
 class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
@@ -353,10 +371,46 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
                 kwargs["attention_mask"] = torch.cat((m, torch.ones_like(m[:, :1])), dim=1)
         n = self.get_action_dim(unnorm_key)
         generated = self.generate(input_ids, max_new_tokens=n, **kwargs)
+        wt = None
+        if isinstance(generated, tuple):                 # sampling= with return_weights=True
+            generated, wt = generated
         tokens = generated[:, -n:].cpu().numpy()
         if keys is not None:
-            return np.stack([np.asarray(self.actions_from_token_ids(tokens[i:i + 1], k)).reshape(-1) for i, k in enumerate(keys)])
-        return self.actions_from_token_ids(tokens, unnorm_key)
+            actions = np.stack([np.asarray(self.actions_from_token_ids(tokens[i:i + 1], k)).reshape(-1) for i, k in enumerate(keys)])
+        else:
+            actions = self.actions_from_token_ids(tokens, unnorm_key)
+        return actions if wt is None else (actions, tokens, wt.cpu().numpy())
+
+    def sample_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor,
+                       unnorm_key: Union[str, Sequence[Optional[str]], None] = None, sampling: Optional[SamplingParams] = None,
+                       num_samples: int = 1, attention_mask: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`num_samples` sampled actions per sequence with their log-probabilities (RL rollouts, best-of-N, uncertainty):
+        → (actions [B, num_samples, n], token_ids int64 [B, num_samples, n], logprobs fp64 [B, num_samples, n]). The batch
+        is repeated `num_samples` times (several copies per engine run while the run stays within 16 sequences); copy j of a sequence with seed s draws with
+        seed s + 0x9E3779B97F4A7C15·j mod 2^64 (`sampling.derive_seed`), so copy j equals that one call. logprobs[b, j, t] =
+        log(w / total) of step t's weight pair: the token's log-probability under the warped (temperature / top-k /
+        top-p) distribution."""
+        if sampling is None:
+            sampling = SamplingParams()
+        if num_samples < 1:
+            raise ValueError("num_samples must be >= 1")
+        B = input_ids.shape[0]
+        T, k, p, seed = sampling.resolve(B)
+        keys = list(unnorm_key) if isinstance(unnorm_key, (list, tuple)) else None
+        per_call = max(1, 16 // B)          # copies per engine run: batches up to 16 keep "a sequence's result is its batch-1 result"
+        acts, toks, lps = [], [], []
+        for j0 in range(0, num_samples, per_call):
+            c = min(per_call, num_samples - j0)
+            sp = SamplingParams(temperature=np.tile(T, c), top_k=np.tile(k, c), top_p=np.tile(p, c),
+                                seed=np.concatenate([derive_seed(seed, j) for j in range(j0, j0 + c)]))
+            a, tok, wt = self.predict_action(input_ids.repeat(c, 1), keys * c if keys is not None else unnorm_key,
+                                             pixel_values=pixel_values.repeat(c, 1, 1, 1),
+                                             attention_mask=None if attention_mask is None else attention_mask.repeat(c, 1),
+                                             sampling=sp, return_weights=True)
+            acts.append(np.asarray(a).reshape(c, B, -1))
+            toks.append(tok.reshape(c, B, -1))
+            lps.append(logprob(wt).reshape(c, B, -1))
+        return tuple(np.concatenate(x, axis=0).transpose(1, 0, 2) for x in (acts, toks, lps))
 
     def with_empty_token(self, input_ids: torch.LongTensor) -> torch.LongTensor:
         """Append the special empty token 29871 the Llama tokenizer would have put after "Out:" (reference :510-515)."""

@@ -21,7 +21,7 @@ from ._lib import (AttnDesc, GemmDesc, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_KE
                    EPI_RES, EPI_SWIGLU)
 
 __all__ = ["Op", "gemm", "gemm_fp8", "quantize_rows_fp8", "quantize_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
-           "argmax", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
+           "argmax", "sample", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
            "EPI_NONE", "EPI_BIAS", "EPI_BIAS_GELU", "EPI_BIAS_RES", "EPI_RES", "EPI_SWIGLU", "EPI_F32", "EPI_F32_BF16R",
            "EPI_SWIGLU_KEEP", "EPI_BIAS_GELU_KEEP", "EPI_SWIGLU_BWD", "EPI_GELU_BWD"]
 
@@ -459,6 +459,29 @@ def argmax(logits: torch.Tensor, out: torch.Tensor, run: bool = True) -> Op:
     rows, n = logits.shape
     op = Op("bl_argmax_f32", lib.bl_argmax_f32, (logits.data_ptr(), _rows(logits, "logits"), rows, n, out.data_ptr()),
             (logits, out))
+    if run:
+        op.run()
+    return op
+
+
+def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
+           step: int, ids: torch.Tensor, wt: torch.Tensor, run: bool = True) -> Op:
+    """One seeded draw per row of fp32 logits [rows, n] (bl_sample_f32; specification: sampling.sample_rows). Per-row
+    DEVICE settings: temperature fp32 (0 = greedy), top_k int32 (0 = off), top_p fp32 (>= 1 = off), seed int64; `step` is
+    the Philox counter. Writes ids int64 [rows] and wt int64 [rows, 2] = (weight of the token, kept total)."""
+    lib = _lib.load()
+    rows, n = logits.shape
+    want = ((logits, torch.float32, (rows, n)), (temperature, torch.float32, (rows,)), (top_k, torch.int32, (rows,)),
+            (top_p, torch.float32, (rows,)), (seed, torch.int64, (rows,)), (ids, torch.int64, (rows,)), (wt, torch.int64, (rows, 2)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_cuda or (t.dim() == 1 and rows > 1 and t.stride(0) != 1):
+            raise TypeError("sample: logits fp32 [rows, n]; temperature fp32, top_k int32, top_p fp32, seed int64, ids int64 "
+                            "[rows] (contiguous); wt int64 [rows, 2]; all on the device")
+    if not wt.is_contiguous():
+        raise TypeError("sample: wt must be contiguous")
+    op = Op("bl_sample_f32", lib.bl_sample_f32,
+            (logits.data_ptr(), _rows(logits, "logits"), rows, n, temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
+             seed.data_ptr(), int(step), ids.data_ptr(), wt.data_ptr()), (logits, temperature, top_k, top_p, seed, ids, wt))
     if run:
         op.run()
     return op

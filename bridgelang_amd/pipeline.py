@@ -97,19 +97,20 @@ class StaggeredDecodePipeline:
     """
 
     def __init__(self, weights: VLAWeights, batch: int, prompt_len: int, n_new: int = 7, split_vision: bool = False,
-                 fp8: bool = False, padded: bool = False):
+                 fp8: bool = False, padded: bool = False, sample: bool = False):
         """split_vision=True adds a third stage: the vision towers + projector of the batch submitted NOW run beside the
         Llama prefill of the batch submitted one step earlier (n_new + 1 slots, latency n_new + 1 steps)."""
         if n_new < 2:
             raise ValueError("StaggeredDecodePipeline needs at least one decode iteration (n_new >= 2)")
         if padded and fp8:
             raise ValueError("padded generation is built for the bf16 generation plan")
-        self.padded = padded
+        self.padded, self.sample = padded, sample
         self.w, self.dims, self.B, self.n_new = weights, weights.dims, batch, n_new
         self.split_vision = split_vision
         self.lag = 1 if split_vision else 0         # steps between a batch's submission and its prefill
         self.slots = n_new + self.lag
-        self.engines = [OpenVLAEngine(weights, batch, prompt_len, n_new, fp8=fp8, padded=padded) for _ in range(self.slots)]
+        self.engines = [OpenVLAEngine(weights, batch, prompt_len, n_new, fp8=fp8, padded=padded, sample=sample)
+                        for _ in range(self.slots)]
         self.device = dev = weights.embed.device
         d = self.dims
         G = n_new - 1
@@ -189,7 +190,11 @@ class StaggeredDecodePipeline:
             plan += gm(self.actd, lw.down_w, self.xd, EPI_RES, res=self.xd)
         plan.append(norm(self.xd, w.norm, self.hd, ops.skinny_supported(B, D, EPI_F32_BF16R)))   # OpenVLAEngine._head
         plan += gm(self.hd, w.lm_head, self.logits, EPI_F32_BF16R)
-        plan += [ops.argmax(self.logits[r], e.gen_ids[g], run=False) for g, e, r in groups]
+        if self.sample:     # iteration g of a batch draws with ITS slot's settings at Philox counter g, as its engine would
+            plan += [ops.sample(self.logits[r], e.samp_temperature, e.samp_top_k, e.samp_top_p, e.samp_seed, g, e.gen_ids[g],
+                                e.gen_wt[g], run=False) for g, e, r in groups]
+        else:
+            plan += [ops.argmax(self.logits[r], e.gen_ids[g], run=False) for g, e, r in groups]
         return plan
 
     def _run_tick(self, k: int) -> None:
@@ -228,15 +233,23 @@ class StaggeredDecodePipeline:
 
     @torch.no_grad()
     def step(self, input_ids: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
-             attention_mask: Optional[torch.Tensor] = None, mask_checked: bool = False) -> torch.Tensor:
+             attention_mask: Optional[torch.Tensor] = None, mask_checked: bool = False, sampling=None):
         """Submit a batch (None: re-use the inputs resident in the slot's buffers) and return the [B, n_new] ids of the
         batch submitted n_new-1 steps earlier, which this step completed (garbage until the pipeline has filled). The
         returned view is overwritten by the next step() — copy it first. A padded pipeline takes right-padded prompts with
         their `attention_mask` [B, prompt_len] (1…1 0…0; None: all ones); the slot keeps the masks and positions derived
         from it until its batch completes (with split_vision its prefill reads them one step later). The mask's layout is
         checked on the device, which costs a host synchronisation per step; `mask_checked=True` skips it for a caller
-        that built the masks itself (the server), so submission stays asynchronous like the un-padded one."""
+        that built the masks itself (the server), so submission stays asynchronous like the un-padded one.
+        A sample=True pipeline takes the submitted batch's `sampling` (a SamplingParams; None: every sequence greedy) into
+        the slot's settings buffers, where they stay until the batch completes, and returns the pair (ids [B, n_new],
+        wt [B, n_new, 2]) — both views that the next step() overwrites."""
         k = self._tick % self.slots
+        if sampling is not None and (not self.sample or input_ids is None):
+            raise ValueError("sampling goes with the input_ids of a pipeline built with sample=True")
+        if input_ids is not None and self.sample:
+            from .sampling import SamplingParams
+            self.engines[k].set_sampling(sampling if sampling is not None else SamplingParams(temperature=0.0))
         if attention_mask is not None and (not self.padded or input_ids is None):
             raise ValueError("attention_mask goes with the input_ids of a pipeline built with padded=True")
         if input_ids is not None and self.padded:
@@ -249,12 +262,14 @@ class StaggeredDecodePipeline:
         else:
             self._run_tick(k)
         self._tick += 1
-        return self.engines[(k + 1) % self.slots].gen_ids.t()
+        done = self.engines[(k + 1) % self.slots]
+        return (done.gen_ids.t(), done.gen_wt.permute(1, 0, 2)) if self.sample else done.gen_ids.t()
 
     def flush(self, ticks: Optional[Sequence[int]] = None) -> List[Optional[torch.Tensor]]:
         """Drain: finish the batches still in flight with each slot's own per-batch plans; returns their ids oldest
         first (copies), one entry per step of the last `slots - 1` steps. `ticks`: finish only the batches submitted at
-        these step indices (None entries for the others) — a server that already answered the older slots skips them."""
+        these step indices (None entries for the others) — a server that already answered the older slots skips them.
+        A sample=True pipeline returns (ids, wt) pairs."""
         out: List[Optional[torch.Tensor]] = []
         for a in range(min(self.slots - 2, self._tick - 1), -1, -1):    # a = steps since the batch was submitted
             tick = self._tick - 1 - a
@@ -268,5 +283,5 @@ class StaggeredDecodePipeline:
                 j = 0
             for step in e.decode_ops[j:]:
                 ops.run_all(step)
-            out.append(e.gen_ids.t().clone())
+            out.append((e.gen_ids.t().clone(), e.gen_wt.permute(1, 0, 2).clone()) if self.sample else e.gen_ids.t().clone())
         return out

@@ -28,6 +28,13 @@ included) is right-padded to L with an attention mask and shares batches with al
 `unnorm_key` (equal action dimension); throughput mode then runs ONE `StaggeredDecodePipeline(padded=True)` for all of
 them. Each request still gets the action of its own batch-1 call, bit for bit (tests/test_serve_padded_gpu.py). Longer
 prompts take the per-length route above.
+
+Sampled actions (`sample=True`, opt-in): a payload may carry `temperature`, `top_k`, `top_p` and `seed` (the settings of
+bridgelang_amd/sampling.py; no seed: one is drawn from torch's default generator), and `return_logprob` to get
+{"action": ndarray[7], "logprob": ndarray[7]} back — the log-probability of every drawn token under its warped
+distribution. The settings are per-sequence device arrays, so requests with different settings (and requests with none:
+greedy rows, temperature 0, the greedy server's action bit for bit) share batches and pipelines. Any other payload key is
+answered with "error"; so is a sampling key sent to a server without `sample=True`.
 """
 from __future__ import annotations
 
@@ -100,25 +107,33 @@ def decode_tree(obj: Any) -> Any:
 
 # ---- server ----------------------------------------------------------------------------------------------------------
 class _Request:
-    __slots__ = ("input_ids", "pixel_values", "unnorm_key", "future", "mask", "group")
+    __slots__ = ("input_ids", "pixel_values", "unnorm_key", "future", "mask", "group", "sampling", "want_logprob")
 
     def __init__(self, input_ids, pixel_values, unnorm_key):
         self.input_ids, self.pixel_values, self.unnorm_key = input_ids, pixel_values, unnorm_key
         self.future: Future = Future()
         self.mask: Optional[torch.Tensor] = None      # pad_to: attention mask [1, pad_to] of the right-padded input_ids
         self.group: Optional[tuple] = None            # requests with equal group keys may share a GPU batch
+        self.sampling: Tuple[float, int, float, int] = (0.0, 0, 1.0, 0)    # sample=True: temperature (0 = greedy), top_k, top_p, seed
+        self.want_logprob = False
 
 
 class OpenVLAServer:
     """`vla`: OpenVLAForActionPrediction (HIP) — anything with `predict_action(input_ids=, pixel_values=, unnorm_key=,
     do_sample=False) -> ndarray [B, 7] (or [7] at B = 1)`; `processor(prompt, PIL image) -> {input_ids, pixel_values}`.
     `pad_to=L` additionally uses `vla.with_empty_token`, `vla.pad_token_id`, `vla.get_action_dim` and calls
-    `predict_action(..., attention_mask=, unnorm_key=[one key per sequence])`."""
+    `predict_action(..., attention_mask=, unnorm_key=[one key per sequence])`. `sample=True` calls
+    `predict_action(..., sampling=SamplingParams(per-row arrays), return_weights=True) -> (actions, token ids, wt [B, 7, 2])`."""
+
+    _BASE_KEYS = ("image", "instruction", "unnorm_key")
+    _SAMPLING_KEYS = ("temperature", "top_k", "top_p", "seed", "return_logprob")
 
     def __init__(self, vla: Any, processor: Any, openvla_path: Union[str, Path] = "openvla/openvla-7b",
                  max_batch: int = 16, max_wait_ms: float = 2.0, norm_stats_path: Optional[Union[str, Path]] = None,
-                 pipeline_batch: Optional[int] = None, max_pipelines: int = 2, pad_to: Optional[int] = None):
+                 pipeline_batch: Optional[int] = None, max_pipelines: int = 2, pad_to: Optional[int] = None,
+                 sample: bool = False):
         self.vla, self.processor, self.openvla_path = vla, processor, str(openvla_path)
+        self.sample = bool(sample)
         self.pad_to = int(pad_to) if pad_to else None
         self._pad_pipe: Optional[Tuple[Any, Dict[int, Any]]] = None     # pad_to: the one padded pipeline + its batches in flight
         self.pipelines_built = 0                  # StaggeredDecodePipelines constructed so far (observability / tests)
@@ -147,9 +162,27 @@ class OpenVLAServer:
         from PIL import Image
         image, instruction = payload["image"], payload["instruction"]
         unnorm_key = payload.get("unnorm_key", None)
+        sampling_keys = [k for k in self._SAMPLING_KEYS if k in payload]
+        if sampling_keys and not self.sample:
+            raise ValueError(f"{sampling_keys}: this server was started without sample=True")
+        unknown = [k for k in payload if k not in self._BASE_KEYS + self._SAMPLING_KEYS] if self.sample else []
+        if unknown:
+            raise ValueError(f"unknown payload keys {unknown}")
         prompt = get_openvla_prompt(instruction, self.openvla_path)
         inputs = self.processor(prompt, Image.fromarray(np.asarray(image, dtype=np.uint8)).convert("RGB"))
-        return _Request(inputs["input_ids"], inputs["pixel_values"], unnorm_key)
+        req = _Request(inputs["input_ids"], inputs["pixel_values"], unnorm_key)
+        if any(k in payload for k in ("temperature", "top_k", "top_p", "seed")):
+            from .sampling import SamplingParams
+            T, k, p, seed = SamplingParams(payload.get("temperature", 1.0), payload.get("top_k", 0), payload.get("top_p", 1.0),
+                                           payload.get("seed", None)).resolve(1)        # validates; draws a missing seed
+            req.sampling = (float(T[0]), int(k[0]), float(p[0]), int(seed[0]))
+        req.want_logprob = bool(payload.get("return_logprob", False))
+        return req
+
+    def _sampling_of(self, rows: List[_Request]):
+        from .sampling import SamplingParams
+        T, k, p, seed = zip(*(r.sampling for r in rows))
+        return SamplingParams(np.array(T, np.float32), np.array(k, np.int64), np.array(p, np.float32), np.array(seed, np.int64))
 
     def _submit(self, payload: Dict[str, Any]) -> np.ndarray:
         req = self._make_request(payload)
@@ -166,6 +199,8 @@ class OpenVLAServer:
             else:
                 payload = decode_tree(payload)
             action = self._submit(payload)
+            if isinstance(action, dict):      # return_logprob
+                return dumps(action) if double_encode else {k: encode_ndarray(v) for k, v in action.items()}
             return dumps(action) if double_encode else encode_ndarray(action)
         except Exception:   # noqa: BLE001 — the reference answers every failure with "error"
             logging.error(traceback.format_exc())
@@ -234,7 +269,7 @@ class OpenVLAServer:
     def _padded_pipe(self):
         from .pipeline import StaggeredDecodePipeline
         if self._pad_pipe is None:
-            pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, self.pad_to, padded=True)
+            pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, self.pad_to, padded=True, sample=self.sample)
             pipe.capture()
             self.pipelines_built += 1
             self._pad_pipe = (pipe, {})
@@ -251,17 +286,28 @@ class OpenVLAServer:
             del self._pipes[old_len]
             del old
             torch.cuda.empty_cache()
-        pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, L)
+        pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, L, sample=self.sample)
         pipe.capture()
         self.pipelines_built += 1
         self._pipes[L] = (pipe, {})
         return self._pipes[L]
 
-    def _resolve(self, reqs: List[_Request], token_ids: torch.Tensor) -> None:
+    @staticmethod
+    def _answer(r: _Request, action: np.ndarray, wt: Optional[np.ndarray]) -> Any:
+        if not r.want_logprob:
+            return action
+        from .sampling import logprob
+        return {"action": action, "logprob": logprob(wt)}
+
+    def _resolve(self, reqs: List[_Request], out) -> None:
+        """`out`: the pipeline's token ids [B, 7], or with sample=True the pair (ids, wt [B, 7, 2])."""
+        token_ids, wt = out if self.sample else (out, None)
         ids = token_ids.cpu().numpy()
+        wt = wt.cpu().numpy() if wt is not None else None
         for i, r in enumerate(reqs):
             try:
-                r.future.set_result(np.asarray(self.vla.actions_from_token_ids(ids[i:i + 1], r.unnorm_key)).reshape(-1))
+                action = np.asarray(self.vla.actions_from_token_ids(ids[i:i + 1], r.unnorm_key)).reshape(-1)
+                r.future.set_result(self._answer(r, action, None if wt is None else wt[i]))
             except Exception as e:   # noqa: BLE001 — e.g. an unknown unnorm_key: that request alone fails
                 r.future.set_exception(e)
 
@@ -309,12 +355,13 @@ class OpenVLAServer:
                 pipe, inflight = self._padded_pipe() if padded else self._pipe_for(ids.shape[1])
                 tick = pipe._tick
                 # the masks were built here, on the host (_pad): 1…1 0…0 by construction, nothing to check on the device
-                out = pipe.step(ids, pv, mask, mask_checked=True) if padded else pipe.step(ids, pv)
+                kw = dict(sampling=self._sampling_of(batch + [batch[-1]] * pad)) if self.sample else {}
+                out = pipe.step(ids, pv, mask, mask_checked=True, **kw) if padded else pipe.step(ids, pv, **kw)
                 inflight[tick] = batch
                 self._record(batch)
                 done = tick - (pipe.slots - 1)
                 if done in inflight:
-                    self._resolve(inflight.pop(done), out.clone())
+                    self._resolve(inflight.pop(done), tuple(o.clone() for o in out) if self.sample else out.clone())
             except Exception as e:   # noqa: BLE001
                 for r in batch:
                     if not r.future.done():
@@ -345,7 +392,14 @@ class OpenVLAServer:
             rows = batch + [batch[-1]] * (size - n)
             ids = torch.cat([r.input_ids for r in rows], dim=0)
             pv = torch.cat([r.pixel_values for r in rows], dim=0)
-            if batch[0].mask is not None:     # pad_to: lengths and keys are mixed — every sequence un-normalised with its own key
+            wt = None
+            if self.sample:                   # per-row settings: mixed requests (greedy ones included) ride one call
+                kw = dict(unnorm_key=[r.unnorm_key for r in rows], attention_mask=torch.cat([r.mask for r in rows], dim=0)) \
+                    if batch[0].mask is not None else dict(unnorm_key=batch[0].unnorm_key)
+                actions, _, wt = self.vla.predict_action(input_ids=ids, pixel_values=pv, sampling=self._sampling_of(rows),
+                                                         return_weights=True, **kw)
+                actions, wt = np.asarray(actions), np.asarray(wt)[:n]
+            elif batch[0].mask is not None:     # pad_to: lengths and keys are mixed — every sequence un-normalised with its own key
                 actions = np.asarray(self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=[r.unnorm_key for r in rows],
                                                              attention_mask=torch.cat([r.mask for r in rows], dim=0),
                                                              do_sample=False))
@@ -354,8 +408,8 @@ class OpenVLAServer:
                                                              do_sample=False))
             actions = actions.reshape(size, -1)[:n]
             self._record(batch)
-            for r, a in zip(batch, actions):
-                r.future.set_result(a)
+            for i, (r, a) in enumerate(zip(batch, actions)):
+                r.future.set_result(self._answer(r, a, None if wt is None else wt[i]))
         except Exception as e:   # noqa: BLE001 — delivered to every waiting request
             for r in batch:
                 if not r.future.done():

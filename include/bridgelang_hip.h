@@ -259,6 +259,16 @@ int bl_gather_rows_bf16(const bl_bf16* src, const int64_t* row_index, int64_t ro
                         int32_t width, bl_bf16* dst, int32_t B, void* stream);
 /* Row-wise argmax of fp32 logits [rows, n] (first maximal index, as torch.argmax); out int64 [rows]. */
 int bl_argmax_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, int64_t* out, void* stream);
+/* Seeded sampling of one token per row of fp32 logits [rows, n] (leading dimension ld; columns >= n are never read):
+ * temperature → top-k → top-p → one Philox4x32-10 draw, bit-identical to bridgelang_amd/sampling.py::sample_rows. The
+ * settings are DEVICE arrays with one entry per row — temperature fp32 (0 = greedy: the row's answer is bl_argmax_f32's),
+ * top_k int32 (0 = off), top_p fp32 (>= 1 = off), seed int64 (the Philox key; the counter is `step`) — so one captured
+ * graph serves any settings. ids int64 [rows]; wt int64 [rows, 2] = (weight of the drawn token, kept total): its
+ * probability under the warped distribution is their quotient. n % 4 == 0 and n <= 36480 (the row's weights live in LDS),
+ * else BL_E_SHAPE. */
+int bl_sample_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
+                  const int32_t* top_k, const float* top_p, const int64_t* seed, int32_t step, int64_t* ids,
+                  int64_t* wt, void* stream);
 
 /* Shifted causal-LM cross-entropy (HF LlamaForCausalLM loss; labels prepared by the caller as `targets[row]` =
  * label of the NEXT position, -100 = ignore; base_strategy.py:287-297 consumes `output.loss`). row_loss[rows] receives
