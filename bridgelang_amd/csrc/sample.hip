@@ -2,6 +2,9 @@
 // device twin of bridgelang_amd/sampling.py::sample_rows. Token id and both integers of the weight pair are bit-identical
 // to that specification: the exponential is a fixed sequence of individually rounded fp32 operations, and everything
 // behind it is integer arithmetic (weights <= 2^30, sums < 2^45).
+// bl_score_f32 (twin of sampling.py::score_rows) is the same kernel in its other mode: it READS a token per row where
+// the sampler writes one, and reports that token's kept weight — and, on request, the kept weights of an index range —
+// under the same warped distribution. Stages 1–4 and the first walk of stage 5 are one body of code for both.
 //
 // One 1024-thread workgroup per row. The row is read from HBM once (16-byte loads) into ONE uint32 image in LDS
 // (n·4 bytes: 128 256 B for the 32 064-token vocabulary, beside a 16.5 KB histogram inside the CU's 160 KB):
@@ -12,6 +15,8 @@
 //      whose strictly-heavier mass is below the bound; of the tokens AT w*, the first m in index order stay
 //   5. kept mass per wave (each wave owns a contiguous index range; ranks among the w* ties by ballot), the Philox
 //      draw → target, then the one wave that holds the target walks its range with a wave prefix sum
+//      (scoring: no draw and no second walk — during the first walk the lane that owns the given token keeps its kept
+//      weight and the lanes inside the requested range store theirs)
 // Histogram bins are 64-bit LDS atomics; one wave turns a histogram into the selected bin.
 #include "bl_common.h"
 
@@ -171,9 +176,13 @@ __device__ __forceinline__ uint32_t radix_select(const uint32_t* img, int n, u64
   return prefix;
 }
 
+// SCORE = false: the draw (seed, step → ids, wt). SCORE = true: the score of tokens[row] (→ wt, and range_wt[row][j] = the
+// kept weight of token range_first + j when range_wt is given); seed, step and ids are unused there, and the reverse.
+template <bool SCORE>
 __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, long ld, int n, const float* temperature,
                                                           const int* top_k, const float* top_p, const int64_t* seed,
-                                                          uint32_t step, int64_t* ids, int64_t* wt) {
+                                                          uint32_t step, int64_t* ids, const int64_t* tokens, int64_t* wt,
+                                                          int range_first, int range_count, int32_t* range_wt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   u64* hist = (u64*)smem;                                         // kHistSlots
   uint32_t* img = (uint32_t*)(smem + kFixedBytes);                // n: keys, then weights
@@ -214,8 +223,21 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, l
   for (int w = 1; w < kWaves; ++w)
     if (s_best[w] > best || (s_best[w] == best && s_arg[w] < bi)) { best = s_best[w]; bi = s_arg[w]; }
 
+  int64_t tok = -1;                                               // SCORE: the token to score; outside [0, n) it owns no lane
+  int32_t* rw = nullptr;                                          // SCORE: this row of range_wt
+  if constexpr (SCORE) {
+    tok = tokens[row];
+    if (range_wt) rw = range_wt + (long)row * range_count;
+  }
+
   if (!(T > 0.0f)) {                                              // greedy row (block-uniform)
-    if (tid == 0) { ids[row] = (int64_t)bi; wt[2 * row] = 1; wt[2 * row + 1] = 1; }
+    if constexpr (SCORE) {                                        // one-hot at the argmax
+      if (tid == 0) { wt[2 * row] = tok == (int64_t)bi; wt[2 * row + 1] = 1; }
+      if (rw)
+        for (int j = tid; j < range_count; j += kThreads) rw[j] = range_first + j == bi;
+    } else {
+      if (tid == 0) { ids[row] = (int64_t)bi; wt[2 * row] = 1; wt[2 * row + 1] = 1; }
+    }
     return;
   }
 
@@ -272,8 +294,16 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, l
     seen += (u64)__popcll(tb);
     return (w > wstar || (tie && rank < m)) ? (u64)w : 0ull;
   };
-  u64 seen = ties, acc = 0;
-  for (int i0 = lo; i0 < hi; i0 += 64) acc += kept(i0 + lane, seen);
+  u64 seen = ties, acc = 0, tokw = 0;
+  for (int i0 = lo; i0 < hi; i0 += 64) {
+    const int i = i0 + lane;
+    const u64 w = kept(i, seen);
+    acc += w;
+    if constexpr (SCORE) {
+      if ((int64_t)i == tok) tokw = w;                            // i >= hi: kept() gave 0
+      if (rw && i < hi && i >= range_first && i - range_first < range_count) rw[i - range_first] = (int32_t)w;
+    }
+  }
   acc = wave_sum_u64(acc);
   __syncthreads();
   if (lane == 0) red[wave] = acc;
@@ -283,6 +313,11 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, l
   for (int w = 0; w < kWaves; ++w) {
     if (w < wave) before += red[w];
     total_kept += red[w];
+  }
+  if constexpr (SCORE) {
+    tokw = block_sum_u64(tokw, red);                              // at most one lane of the block holds a non-zero
+    if (tid == 0) { wt[2 * row] = (int64_t)tokw; wt[2 * row + 1] = (int64_t)total_kept; }
+    return;
   }
   const u64 target = __umul64hi(philox_u64((u64)seed[row], step), total_kept);
   if (target < before || target >= before + acc) return;          // wave-uniform: one wave holds the target
@@ -312,6 +347,19 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, l
 
 }  // namespace
 
+// the 160 KB LDS layout needs the attribute once per kernel instantiation
+template <bool SCORE>
+static int allow_full_lds() {
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_kernel<SCORE>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes - 1024) != hipSuccess)
+      return BL_E_LAUNCH;
+    attr_set = true;
+  }
+  return BL_OK;
+}
+
 extern "C" int bl_sample_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
                              const int32_t* top_k, const float* top_p, const int64_t* seed, int32_t step, int64_t* ids,
                              int64_t* wt, void* stream) {
@@ -320,16 +368,29 @@ extern "C" int bl_sample_f32(const float* logits, int64_t ld, int32_t rows, int3
   if (!bl_aligned16(logits) || (((uintptr_t)seed | (uintptr_t)ids | (uintptr_t)wt) & 7) ||
       (((uintptr_t)temperature | (uintptr_t)top_k | (uintptr_t)top_p) & 3))
     return BL_E_ALIGN;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            kLdsBytes - 1024) != hipSuccess)
-      return BL_E_LAUNCH;
-    attr_set = true;
-  }
+  if (const int rc = allow_full_lds<false>()) return rc;
   const size_t lds = (size_t)kFixedBytes + (size_t)n * 4;
-  hipLaunchKernelGGL(sample_kernel, dim3(rows), dim3(kThreads), lds, (hipStream_t)stream, logits, (long)ld, n, temperature,
-                     top_k, top_p, seed, (uint32_t)step, ids, wt);
+  hipLaunchKernelGGL(sample_kernel<false>, dim3(rows), dim3(kThreads), lds, (hipStream_t)stream, logits, (long)ld, n,
+                     temperature, top_k, top_p, seed, (uint32_t)step, ids, (const int64_t*)nullptr, wt, 0, 0,
+                     (int32_t*)nullptr);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
+extern "C" int bl_score_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
+                            const int32_t* top_k, const float* top_p, const int64_t* tokens, int64_t* wt,
+                            int32_t range_first, int32_t range_count, int32_t* range_wt, void* stream) {
+  if (!logits || !temperature || !top_k || !top_p || !tokens || !wt || (range_count > 0 && !range_wt)) return BL_E_ARG;
+  if (rows <= 0 || n <= 0 || (n % 4) || (ld % 4) || ld < n || n > kMaxN) return BL_E_SHAPE;
+  if (range_count < 0 || (range_count > 0 && (range_first < 0 || (int64_t)range_first + range_count > n))) return BL_E_SHAPE;
+  if (!bl_aligned16(logits) || (((uintptr_t)tokens | (uintptr_t)wt) & 7) ||
+      (((uintptr_t)temperature | (uintptr_t)top_k | (uintptr_t)top_p) & 3) || (range_count > 0 && ((uintptr_t)range_wt & 3)))
+    return BL_E_ALIGN;
+  if (const int rc = allow_full_lds<true>()) return rc;
+  const size_t lds = (size_t)kFixedBytes + (size_t)n * 4;
+  hipLaunchKernelGGL(sample_kernel<true>, dim3(rows), dim3(kThreads), lds, (hipStream_t)stream, logits, (long)ld, n,
+                     temperature, top_k, top_p, (const int64_t*)nullptr, 0u, (int64_t*)nullptr, tokens, wt, range_first,
+                     range_count, range_count > 0 ? range_wt : (int32_t*)nullptr);
   BL_CHECK_LAUNCH();
   return BL_OK;
 }

@@ -10,7 +10,7 @@ only, modeling_prismatic.py:326,460-463); per-sample results equal independent b
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -42,7 +42,8 @@ def _fp8_layers(weights: VLAWeights) -> list:
 class OpenVLAEngine:
     def __init__(self, weights: VLAWeights, batch: int, prompt_len: int, n_new: int = 7, all_rows: bool = False,
                  use_mask: bool = False, splitk: bool = False, fp8: bool = False, padded: bool = False,
-                 vision_only: bool = False, text_only: bool = False, sample: bool = False):
+                 vision_only: bool = False, text_only: bool = False, sample: bool = False, score: bool = False,
+                 score_range: Optional[Tuple[int, int]] = None):
         """all_rows=True builds the training/eval-style forward instead of generation: logits for every position
         (`logits_all` [B*S, vocab] fp32) and no decode steps. use_mask=True threads a [B, S] uint8 key-padding mask
         (`key_mask`, 1 = attend) through the Llama attention (modeling_prismatic.py:387-390). splitk=True lets
@@ -63,7 +64,13 @@ class OpenVLAEngine:
         specification): per-sequence temperature / top-k / top-p / seed live in device buffers filled by `set_sampling`
         (so one captured graph serves any settings; a sequence at temperature 0 is greedy, bit for bit), and `gen_wt`
         [n_new, B, 2] receives each drawn token's integer weight and the kept total (its probability = their quotient).
-        Step t of a sequence draws from Philox(key = its seed, counter = t): the draw does not depend on the batch slot."""
+        Step t of a sequence draws from Philox(key = its seed, counter = t): the draw does not depend on the batch slot.
+        score=True is the opposite direction (sampling.score_rows is its specification): the plan is the greedy plan with
+        every bl_argmax_f32 replaced by bl_score_f32, which READS `gen_ids[t]` — the forced tokens of `set_forced_ids` —
+        and writes their weight pairs to `gen_wt[t]` under the settings of `set_sampling` (no seed); nothing writes
+        `gen_ids`, so decode step t consumes the forced token t-1 and every step's logits are the cached decode path's,
+        the ones a sample=True engine saw when it drew those tokens. score_range=(first, count) also keeps the kept
+        weights of tokens first … first + count - 1 of every step in `gen_range_wt` [n_new, B, count] int32."""
         self.w, self.dims = weights, weights.dims
         self.vision_only, self.text_only = vision_only, text_only
         if text_only and (vision_only or padded or fp8):
@@ -72,9 +79,13 @@ class OpenVLAEngine:
         if not vision_only and not weights.layers_resident:
             raise RuntimeError("the decoder-layer weights are sharded out of the model (parameter-sharded training in progress): "
                                "call the strategy's finish() / TrainStep.materialize_params() before building an inference engine")
-        self.padded, self.sample = padded, sample
-        if sample and (all_rows or vision_only):
-            raise ValueError("sample=True belongs to a generation plan")
+        self.padded, self.sample, self.score_mode = padded, sample, score
+        if sample and score:
+            raise ValueError("sample=True draws tokens, score=True scores given ones: build one engine for each")
+        if (sample or score) and (all_rows or vision_only):
+            raise ValueError("sample=True / score=True belong to a generation plan")
+        if score_range is not None and not score:
+            raise ValueError("score_range goes with score=True")
         use_mask = use_mask or padded
         if padded and (all_rows or fp8):
             raise ValueError("padded generation is built for the bf16 generation plan")
@@ -101,6 +112,17 @@ class OpenVLAEngine:
             self.samp_temperature, self.samp_top_k = z(B, dtype=torch.float32), z(B, dtype=torch.int32)
             self.samp_top_p, self.samp_seed = torch.ones(B, dtype=torch.float32, device=dev), z(B, dtype=torch.int64)
             self.gen_wt = z(n_new, B, 2, dtype=torch.int64)
+        self.score_range, self.gen_range_wt = None, None
+        if score:       # the same settings without a seed; gen_ids holds the forced tokens
+            self.samp_temperature, self.samp_top_k = z(B, dtype=torch.float32), z(B, dtype=torch.int32)
+            self.samp_top_p = torch.ones(B, dtype=torch.float32, device=dev)
+            self.gen_wt = z(n_new, B, 2, dtype=torch.int64)
+            if score_range is not None:
+                first, count = int(score_range[0]), int(score_range[1])
+                if first < 0 or count < 1 or first + count > d.vocab:
+                    raise ValueError(f"score_range {score_range} leaves the vocabulary [0, {d.vocab})")
+                self.score_range = (first, count)
+                self.gen_range_wt = z(n_new, B, count, dtype=torch.int32)
         # vision buffers (sized for the larger tower, shared by both: they run back to back on one stream)
         tmax = max(d.dino.tokens, d.siglip.tokens)
         dmax = max(d.dino.dim, d.siglip.dim)
@@ -294,8 +316,8 @@ class OpenVLAEngine:
         return plan
 
     def _head(self, x_rows: torch.Tensor, t: int, b0: int = 0, b1: Optional[int] = None) -> List[Op]:
-        """final RMSNorm → lm_head (bf16-rounded fp32 logits) → greedy argmax (sample=True: the seeded draw), for
-        generation step t."""
+        """final RMSNorm → lm_head (bf16-rounded fp32 logits) → greedy argmax (sample=True: the seeded draw; score=True:
+        the score of the forced token), for generation step t."""
         d, w = self.dims, self.w
         b1 = self.B if b1 is None else b1
         logits, ids, hdd = self.logits[t][b0:b1], self.gen_ids[t][b0:b1], self.hd[b0:b1]
@@ -307,9 +329,18 @@ class OpenVLAEngine:
         if self.sample:
             plan.append(ops.sample(logits, self.samp_temperature[b0:b1], self.samp_top_k[b0:b1], self.samp_top_p[b0:b1],
                                    self.samp_seed[b0:b1], t, ids, self.gen_wt[t][b0:b1], run=False))
+        elif self.score_mode:
+            plan.append(ops.score(logits, self.samp_temperature[b0:b1], self.samp_top_k[b0:b1], self.samp_top_p[b0:b1], ids,
+                                  self.gen_wt[t][b0:b1], *self._score_range_args(t, b0, b1), run=False))
         else:
             plan.append(ops.argmax(logits, ids, run=False))
         return plan
+
+    def _score_range_args(self, t: int, b0: int = 0, b1: Optional[int] = None) -> tuple:
+        """(range_first, range_wt) of ops.score for generation step t; no range: (0, None)."""
+        if self.score_range is None:
+            return 0, None
+        return self.score_range[0], self.gen_range_wt[t][b0:b1]
 
     def _plan_decode(self, t: int) -> List[Op]:
         """Cached-generation step t (modeling_prismatic.py:325-341): token gen_ids[t-1] at position S+t-1. Five
@@ -431,11 +462,30 @@ class OpenVLAEngine:
     def set_sampling(self, params) -> None:
         """Fill the per-sequence settings buffers from a `sampling.SamplingParams` (scalars or one value per sequence;
         seed=None draws the seeds from torch's default CPU generator). They stay until the next call."""
+        if self.score_mode:                      # a score has no seed: none is drawn from the generator, a given one is ignored
+            from dataclasses import replace
+            T, k, p, _ = replace(params, seed=0).resolve(self.B)
+            for buf, a in ((self.samp_temperature, T), (self.samp_top_k, k), (self.samp_top_p, p)):
+                buf.copy_(torch.from_numpy(a.copy()))
+            return
         if not self.sample:
-            raise ValueError("engine was not built with sample=True")
+            raise ValueError("engine was not built with sample=True or score=True")
         T, k, p, seed = params.resolve(self.B)
         for buf, a in ((self.samp_temperature, T), (self.samp_top_k, k), (self.samp_top_p, p), (self.samp_seed, seed)):
             buf.copy_(torch.from_numpy(a))
+
+    def set_forced_ids(self, forced_ids: torch.Tensor, check: bool = True) -> None:
+        """The tokens a score=True engine scores and conditions its decode steps on: int64 [B, n_new], copied into the
+        static `gen_ids` buffer (valid before eager and captured runs alike). The ids are checked against the vocabulary
+        (the next step's embedding lookup must not see one outside it), which for ids on the device costs a host
+        synchronisation; check=False skips it for a caller that has made sure itself."""
+        if not self.score_mode:
+            raise ValueError("engine was not built with score=True")
+        if tuple(forced_ids.shape) != (self.B, self.n_new) or forced_ids.dtype != torch.int64:
+            raise ValueError(f"forced_ids must be int64 {(self.B, self.n_new)}, got {forced_ids.dtype} {tuple(forced_ids.shape)}")
+        if check and (bool((forced_ids < 0).any()) or bool((forced_ids >= self.dims.vocab).any())):
+            raise ValueError(f"forced_ids must lie in [0, {self.dims.vocab})")
+        self.gen_ids.copy_(forced_ids.t())
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, pixel_values: torch.Tensor, sampling=None) -> torch.Tensor:
@@ -447,3 +497,17 @@ class OpenVLAEngine:
         self.set_inputs(input_ids, pixel_values)
         self.replay()
         return self.gen_ids.t()
+
+    @torch.no_grad()
+    def score(self, input_ids: torch.Tensor, pixel_values: torch.Tensor, forced_ids: torch.Tensor, sampling=None):
+        """The counterpart of `generate` on a score=True engine: run the plan conditioned on `forced_ids` [B, n_new] under
+        `sampling` (None: the settings already in the buffers). Returns wt int64 [B, n_new, 2] = every forced token's
+        (kept weight, kept total) — with score_range, the pair (wt, range_wt int32 [B, n_new, count]) — as views of the
+        static buffers (device tensors; no host sync inside)."""
+        if sampling is not None:
+            self.set_sampling(sampling)
+        self.set_forced_ids(forced_ids)
+        self.set_inputs(input_ids, pixel_values)
+        self.replay()
+        wt = self.gen_wt.permute(1, 0, 2)
+        return wt if self.gen_range_wt is None else (wt, self.gen_range_wt.permute(1, 0, 2))

@@ -24,13 +24,15 @@ Differences from the reference, all deliberate:
   * the greedy loop runs on-device (no per-token host sync). Sampling runs on the device too, through `sampling=
     SamplingParams(...)` (seeded Philox draws with temperature / top-k / top-p, bridgelang_amd/sampling.py) and
     `sample_actions`; `do_sample=True` alone is rejected: HF draws from torch's global device RNG stream, which this path
-    does not reproduce.
+    does not reproduce. The opposite direction runs there as well: `score_actions` / `generate(forced_ids=)` return the
+    log-probabilities of GIVEN action tokens under the same warped distribution, bit for bit what the sampler reports
+    when it draws them (`token_ids_from_actions` is the action tokenizer's encoding, for candidates given as actions).
   * when 29871 is appended to the prompt the attention mask is extended with it (reference quirk C.1).
 """
 from __future__ import annotations
 
 from collections import OrderedDict
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from types import SimpleNamespace
 from typing import Any, Dict, Optional, Sequence, Tuple, Union
 
@@ -207,14 +209,16 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         return eng
 
     def engine(self, batch: int, prompt_len: int, n_new: int = 7, padded: bool = False, cached: bool = False,
-               sample: bool = False) -> OpenVLAEngine:
+               sample: bool = False, score: bool = False, score_range: Optional[Tuple[int, int]] = None) -> OpenVLAEngine:
         """`cached=True`: the engine behind a `forward(..., use_cache=True)` KV-cache handle — keyed apart from the engines
         `predict_action` / `generate` use, so an interleaved action prediction of the same shape does not invalidate the
-        caller's cache (each kind has its own LRU slot; a second cached prefill of the same shape still does)."""
+        caller's cache (each kind has its own LRU slot; a second cached prefill of the same shape still does).
+        `score=True` (with `score_range`) is a kind of its own again: the engines that score given tokens."""
         fp8 = bool(getattr(self, "fp8", False))       # `model.fp8 = True`: W8A8 e4m3 Llama prefill projections (extension)
-        return self._lru(self._engines, (batch, prompt_len, n_new, fp8, padded, cached, sample),
+        key = (batch, prompt_len, n_new, fp8, padded, cached, sample) + (("score", score_range) if score else ())
+        return self._lru(self._engines, key,
                          lambda: OpenVLAEngine(self.weights, batch, prompt_len, n_new=n_new, fp8=fp8 and not padded, padded=padded,
-                                               sample=sample))
+                                               sample=sample, score=score, score_range=score_range))
 
     # ---- forward: the reference's three branches (modeling_prismatic.py:322-415) ----
     cache_new_tokens = 7       # tokens a `forward(..., use_cache=True)` KV cache is sized for (prefill token + 6 cached steps)
@@ -296,7 +300,8 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
     @torch.no_grad()
     def generate(self, input_ids: torch.LongTensor, max_new_tokens: int = 7, pixel_values: Optional[torch.Tensor] = None,
                  attention_mask: Optional[torch.Tensor] = None, do_sample: bool = False, use_cache: bool = True,
-                 sampling: Optional[SamplingParams] = None, return_weights: bool = False, **_: Any):
+                 sampling: Optional[SamplingParams] = None, return_weights: bool = False,
+                 forced_ids: Optional[torch.Tensor] = None, score_range: Optional[Tuple[int, int]] = None, **_: Any):
         """Greedy decoding, returns [B, L + max_new_tokens] like GenerationMixin (prompt ‖ new tokens). `use_cache` is
         accepted and ignored: the KV cache is always used (use_cache=False in the fork's demo re-runs the vision towers
         7 times, run_openvla_demo.py:43 — same result, 7× the work). A batch whose attention_mask has zeros is taken as
@@ -304,7 +309,12 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         `sampling=SamplingParams(temperature, top_k, top_p, seed)` draws the tokens instead (per-sequence settings and
         seeds; bridgelang_amd/sampling.py is the exact specification, and a sequence's tokens depend on its own seed only,
         not on the batch around it); `return_weights=True` then returns (ids, wt [B, max_new_tokens, 2] int64): the drawn
-        token's integer weight and the kept total of every step, whose quotient is its probability (`sampling.logprob`)."""
+        token's integer weight and the kept total of every step, whose quotient is its probability (`sampling.logprob`).
+        `forced_ids` [B, max_new_tokens] turns the call round: nothing is generated, the decode steps are conditioned on
+        these tokens and the result is (prompt ‖ forced_ids, wt [B, max_new_tokens, 2]) — every forced token's kept weight
+        and the kept total under `sampling` (None: the unwarped distribution, temperature 1), the pair the sampler reports
+        when it draws that token (`sampling.score_rows`; weight 0 = outside the support). `score_range=(first, count)`
+        appends range_wt int32 [B, max_new_tokens, count]: the kept weights of that token range at every step."""
         if do_sample and sampling is None:
             raise NotImplementedError("do_sample=True draws from torch's global device RNG stream, which the HIP path does "
                                       "not reproduce: pass sampling=SamplingParams(temperature=, top_k=, top_p=, seed=) instead")
@@ -314,6 +324,21 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             raise ValueError("generate() needs pixel_values")
         B, L = input_ids.shape
         ids, pv = input_ids.to(self.device), pixel_values.to(self.device)
+        if forced_ids is not None:
+            forced = torch.as_tensor(forced_ids).to(self.device, torch.int64)
+            padded = attention_mask is not None and not bool(attention_mask.bool().all())
+            eng = self.engine(B, L, max_new_tokens, padded=padded, score=True, score_range=score_range)
+            eng.set_sampling(sampling if sampling is not None else SamplingParams())
+            if padded:
+                eng.set_forced_ids(forced)
+                eng.set_padded_inputs(ids, pv, attention_mask)
+                eng.run_eager()
+            else:
+                eng.score(ids, pv, forced)
+            out = (torch.cat([ids, forced], dim=1), eng.gen_wt.permute(1, 0, 2).clone())
+            return out if score_range is None else out + (eng.gen_range_wt.permute(1, 0, 2).clone(),)
+        if score_range is not None:
+            raise ValueError("score_range goes with forced_ids=")
         sample = sampling is not None
         if attention_mask is not None and not bool(attention_mask.bool().all()):
             eng = self.engine(B, L, max_new_tokens, padded=True, sample=sample)
@@ -352,23 +377,9 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             if len(keys) != input_ids.shape[0] or len({self.get_action_dim(k) for k in keys}) != 1:
                 raise ValueError("predict_action: a list of unnorm_keys needs one key per sequence, all of one action dimension")
             unnorm_key = keys[0]
-        m = kwargs.get("attention_mask")
-        if m is not None and not bool(m.bool().all()):
-            # right-padded batch: the empty token goes behind each sequence's last REAL token (one more column)
-            m = m.to(self.device).long()
-            n = m.sum(dim=1)
-            rows = torch.arange(input_ids.shape[0], device=self.device)
-            need = input_ids[rows, n - 1] != 29871
-            ids = torch.cat((input_ids, torch.full_like(input_ids[:, :1], self.pad_token_id)), dim=1)
-            m = torch.cat((m, torch.zeros_like(m[:, :1])), dim=1)
-            ids[rows[need], n[need]] = 29871
-            m[rows[need], n[need]] = 1
-            input_ids, kwargs["attention_mask"] = ids, m
-        else:
-            input_ids = self.with_empty_token(input_ids)
-            if m is not None and m.shape[1] != input_ids.shape[1]:
-                m = m.to(self.device)
-                kwargs["attention_mask"] = torch.cat((m, torch.ones_like(m[:, :1])), dim=1)
+        input_ids, m = self._action_prompt(input_ids, kwargs.get("attention_mask"))
+        if m is not None:
+            kwargs["attention_mask"] = m
         n = self.get_action_dim(unnorm_key)
         generated = self.generate(input_ids, max_new_tokens=n, **kwargs)
         wt = None
@@ -380,6 +391,25 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         else:
             actions = self.actions_from_token_ids(tokens, unnorm_key)
         return actions if wt is None else (actions, tokens, wt.cpu().numpy())
+
+    def _action_prompt(self, input_ids: torch.LongTensor, m: Optional[torch.Tensor]):
+        """The prompt with the empty token 29871 behind each sequence's last token → (input_ids, attention_mask)."""
+        if m is not None and not bool(m.bool().all()):
+            # right-padded batch: the empty token goes behind each sequence's last REAL token (one more column)
+            m = m.to(self.device).long()
+            n = m.sum(dim=1)
+            rows = torch.arange(input_ids.shape[0], device=self.device)
+            need = input_ids[rows, n - 1] != 29871
+            ids = torch.cat((input_ids, torch.full_like(input_ids[:, :1], self.pad_token_id)), dim=1)
+            m = torch.cat((m, torch.zeros_like(m[:, :1])), dim=1)
+            ids[rows[need], n[need]] = 29871
+            m[rows[need], n[need]] = 1
+            return ids, m
+        input_ids = self.with_empty_token(input_ids)
+        if m is not None and m.shape[1] != input_ids.shape[1]:
+            m = m.to(self.device)
+            m = torch.cat((m, torch.ones_like(m[:, :1])), dim=1)
+        return input_ids, m
 
     def sample_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor,
                        unnorm_key: Union[str, Sequence[Optional[str]], None] = None, sampling: Optional[SamplingParams] = None,
@@ -411,6 +441,72 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             toks.append(tok.reshape(c, B, -1))
             lps.append(logprob(wt).reshape(c, B, -1))
         return tuple(np.concatenate(x, axis=0).transpose(1, 0, 2) for x in (acts, toks, lps))
+
+    def score_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor, token_ids=None, actions=None,
+                      unnorm_key: Optional[str] = None, sampling: Optional[SamplingParams] = None,
+                      attention_mask: Optional[torch.Tensor] = None, return_bins: bool = False):
+        """Log-probabilities of GIVEN actions under the policy `sample_actions` draws from (a PPO / GRPO learner's
+        log π(a | s), a reranker's score of a planner's proposal): exactly one of `token_ids` (int64) and `actions`
+        (tokenised by `token_ids_from_actions` with `unnorm_key`), shaped [B, n] or [B, K, n] with K candidates per
+        sequence → logprobs fp64 [B, K, n] (K = 1 for [B, n]), -inf where a token lies outside the support that
+        `sampling` (temperature / top-k / top-p per sequence; no seed) leaves. For tokens `sample_actions` drew under the
+        same settings the values equal its logprobs bit for bit: the decode steps run the cached plan conditioned on the
+        given tokens, so every step sees the logits the sampler saw. Candidates are batched like `sample_actions`' copies
+        (16 // B per engine run). `return_bins=True` → (logprobs, wt int64 [B, K, n, 2], bin_wt int32 [B, K, n,
+        n_action_bins]): the integer weight pairs and the kept weight of every action token, bin_wt[..., j] for token
+        vocab_size - n_action_bins + j, so bin_wt / wt[..., 1:] are exact per-bin probabilities (`sampling.range_entropy`)."""
+        if (token_ids is None) == (actions is None):
+            raise ValueError("score_actions: give exactly one of token_ids= and actions=")
+        if token_ids is None:
+            token_ids = self.token_ids_from_actions(actions, unnorm_key)
+        tok = np.asarray(token_ids.detach().cpu().numpy() if hasattr(token_ids, "detach") else token_ids)
+        B = input_ids.shape[0]
+        if tok.ndim == 2:
+            tok = tok[:, None, :]
+        if tok.ndim != 3 or tok.shape[0] != B or tok.shape[1] < 1 or not np.issubdtype(tok.dtype, np.integer):
+            raise ValueError(f"score_actions: integer token ids [B, n] or [B, K, n] with B = {B}, got {tok.dtype} {tok.shape}")
+        tok = tok.astype(np.int64)
+        K, n = tok.shape[1:]
+        if tok.min() < 0 or tok.max() >= self.dims.vocab:
+            raise ValueError(f"score_actions: token ids must lie in [0, {self.dims.vocab})")
+        if sampling is None:
+            sampling = SamplingParams()
+        T, k, p, _ = replace(sampling, seed=0).resolve(B)
+        n_bins = self.config.n_action_bins
+        rng = (self.vocab_size - n_bins, n_bins) if return_bins else None
+        ids, m = self._action_prompt(input_ids.to(self.device), attention_mask)      # the prompt as predict_action prepares it
+        per_call = max(1, 16 // B)          # candidates per engine run, as sample_actions batches its copies
+        wts, bins = [], []
+        for j0 in range(0, K, per_call):
+            c = min(per_call, K - j0)
+            sp = SamplingParams(temperature=np.tile(T, c), top_k=np.tile(k, c), top_p=np.tile(p, c), seed=0)
+            forced = torch.from_numpy(np.ascontiguousarray(tok[:, j0:j0 + c].transpose(1, 0, 2)).reshape(c * B, n))
+            out = self.generate(ids.repeat(c, 1), n, pixel_values=pixel_values.repeat(c, 1, 1, 1),
+                                attention_mask=None if m is None else m.repeat(c, 1), sampling=sp, forced_ids=forced,
+                                score_range=rng)
+            wts.append(out[1].cpu().numpy().reshape(c, B, n, 2))
+            if return_bins:
+                bins.append(out[2].cpu().numpy().reshape(c, B, n, n_bins))
+        wt = np.concatenate(wts, axis=0).transpose(1, 0, 2, 3)
+        lp = logprob(wt)
+        return (lp, wt, np.concatenate(bins, axis=0).transpose(1, 0, 2, 3)) if return_bins else lp
+
+    def token_ids_from_actions(self, actions: np.ndarray, unnorm_key: Optional[str] = None) -> np.ndarray:
+        """Un-normalised actions [..., n] → action token ids int64 [..., n]: the inverse of `actions_from_token_ids`, i.e.
+        what the training pipeline makes of a demonstrated action. The dataset's BOUNDS_Q99 normalisation first
+        (rlds/utils/data_utils.py:76-93): dimensions the statistics' `mask` selects go linearly from [q01, q99] to [-1, 1]
+        — 2·(a - q01) / (q99 - q01 + 1e-8) - 1 — and are clipped to it, the others (the gripper) pass through. Then the
+        action tokenizer (action_tokenizer.py:38-47): clip to [-1, 1], `np.digitize` against the bin edges, and
+        token = vocab_size - bin. An action beyond q01 / q99 therefore lands in an end bin."""
+        stats = self.get_action_stats(unnorm_key)
+        a = np.asarray(actions, dtype=np.float64)
+        lo, hi = np.asarray(stats["q01"], dtype=np.float64), np.asarray(stats["q99"], dtype=np.float64)
+        mask = np.asarray(stats.get("mask", np.ones_like(lo, dtype=bool)), dtype=bool)
+        if a.shape[-1] != lo.shape[0]:
+            raise ValueError(f"token_ids_from_actions: actions of dimension {lo.shape[0]} expected, got shape {a.shape}")
+        normalized = np.where(mask, np.clip(2.0 * (a - lo) / (hi - lo + 1e-8) - 1.0, -1.0, 1.0), a)
+        bins = np.digitize(np.clip(normalized, float(self.bins[0]), float(self.bins[-1])), self.bins)
+        return (self.vocab_size - bins).astype(np.int64)
 
     def with_empty_token(self, input_ids: torch.LongTensor) -> torch.LongTensor:
         """Append the special empty token 29871 the Llama tokenizer would have put after "Out:" (reference :510-515)."""

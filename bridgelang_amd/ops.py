@@ -21,7 +21,7 @@ from ._lib import (AttnDesc, GemmDesc, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_KE
                    EPI_RES, EPI_SWIGLU)
 
 __all__ = ["Op", "gemm", "gemm_fp8", "quantize_rows_fp8", "quantize_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
-           "argmax", "sample", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
+           "argmax", "sample", "score", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
            "EPI_NONE", "EPI_BIAS", "EPI_BIAS_GELU", "EPI_BIAS_RES", "EPI_RES", "EPI_SWIGLU", "EPI_F32", "EPI_F32_BF16R",
            "EPI_SWIGLU_KEEP", "EPI_BIAS_GELU_KEEP", "EPI_SWIGLU_BWD", "EPI_GELU_BWD"]
 
@@ -482,6 +482,38 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
     op = Op("bl_sample_f32", lib.bl_sample_f32,
             (logits.data_ptr(), _rows(logits, "logits"), rows, n, temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
              seed.data_ptr(), int(step), ids.data_ptr(), wt.data_ptr()), (logits, temperature, top_k, top_p, seed, ids, wt))
+    if run:
+        op.run()
+    return op
+
+
+def score(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, tokens: torch.Tensor,
+          wt: torch.Tensor, range_first: int = 0, range_wt: Optional[torch.Tensor] = None, run: bool = True) -> Op:
+    """The score of a given token per row of fp32 logits [rows, n] under `sample`'s warped distribution (bl_score_f32;
+    specification: sampling.score_rows). Settings as `sample`, without a seed; tokens int64 [rows] on the DEVICE (each in
+    [0, n): the caller's to guarantee — a token outside scores weight 0). Writes wt int64 [rows, 2] = (kept weight of the
+    token, kept total) and, given range_wt int32 [rows, count], the kept weights of tokens range_first … range_first +
+    count - 1."""
+    lib = _lib.load()
+    rows, n = logits.shape
+    want = ((logits, torch.float32, (rows, n)), (temperature, torch.float32, (rows,)), (top_k, torch.int32, (rows,)),
+            (top_p, torch.float32, (rows,)), (tokens, torch.int64, (rows,)), (wt, torch.int64, (rows, 2)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_cuda or (t.dim() == 1 and rows > 1 and t.stride(0) != 1):
+            raise TypeError("score: logits fp32 [rows, n]; temperature fp32, top_k int32, top_p fp32, tokens int64 [rows] "
+                            "(contiguous); wt int64 [rows, 2]; all on the device")
+    if not wt.is_contiguous():
+        raise TypeError("score: wt must be contiguous")
+    count = 0
+    if range_wt is not None:
+        if range_wt.dtype != torch.int32 or range_wt.dim() != 2 or range_wt.shape[0] != rows or not range_wt.is_cuda or \
+                not range_wt.is_contiguous():
+            raise TypeError("score: range_wt int32 [rows, count], contiguous, on the device")
+        count = range_wt.shape[1]
+    keep = (logits, temperature, top_k, top_p, tokens, wt) + ((range_wt,) if count else ())
+    op = Op("bl_score_f32", lib.bl_score_f32,
+            (logits.data_ptr(), _rows(logits, "logits"), rows, n, temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
+             tokens.data_ptr(), wt.data_ptr(), int(range_first), count, range_wt.data_ptr() if count else None), keep)
     if run:
         op.run()
     return op

@@ -12,7 +12,7 @@ Each of the two stage pairings is captured once as a HIP graph with fork/join st
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -97,20 +97,24 @@ class StaggeredDecodePipeline:
     """
 
     def __init__(self, weights: VLAWeights, batch: int, prompt_len: int, n_new: int = 7, split_vision: bool = False,
-                 fp8: bool = False, padded: bool = False, sample: bool = False):
+                 fp8: bool = False, padded: bool = False, sample: bool = False, score: bool = False,
+                 score_range: Optional[Tuple[int, int]] = None):
         """split_vision=True adds a third stage: the vision towers + projector of the batch submitted NOW run beside the
-        Llama prefill of the batch submitted one step earlier (n_new + 1 slots, latency n_new + 1 steps)."""
+        Llama prefill of the batch submitted one step earlier (n_new + 1 slots, latency n_new + 1 steps).
+        score=True (with score_range, as OpenVLAEngine's) scores given tokens instead of producing them: every slot is an
+        `OpenVLAEngine(score=True)`, `step(..., forced_ids=, sampling=)` fills the slot's forced ids and settings, and the
+        merged iteration ends in bl_score_f32 per group where a sampling pipeline draws."""
         if n_new < 2:
             raise ValueError("StaggeredDecodePipeline needs at least one decode iteration (n_new >= 2)")
         if padded and fp8:
             raise ValueError("padded generation is built for the bf16 generation plan")
-        self.padded, self.sample = padded, sample
+        self.padded, self.sample, self.score = padded, sample, score
         self.w, self.dims, self.B, self.n_new = weights, weights.dims, batch, n_new
         self.split_vision = split_vision
         self.lag = 1 if split_vision else 0         # steps between a batch's submission and its prefill
         self.slots = n_new + self.lag
-        self.engines = [OpenVLAEngine(weights, batch, prompt_len, n_new, fp8=fp8, padded=padded, sample=sample)
-                        for _ in range(self.slots)]
+        self.engines = [OpenVLAEngine(weights, batch, prompt_len, n_new, fp8=fp8, padded=padded, sample=sample, score=score,
+                                      score_range=score_range) for _ in range(self.slots)]
         self.device = dev = weights.embed.device
         d = self.dims
         G = n_new - 1
@@ -193,6 +197,9 @@ class StaggeredDecodePipeline:
         if self.sample:     # iteration g of a batch draws with ITS slot's settings at Philox counter g, as its engine would
             plan += [ops.sample(self.logits[r], e.samp_temperature, e.samp_top_k, e.samp_top_p, e.samp_seed, g, e.gen_ids[g],
                                 e.gen_wt[g], run=False) for g, e, r in groups]
+        elif self.score:    # … or scores ITS slot's forced token g, which the next iteration's embedding consumes unchanged
+            plan += [ops.score(self.logits[r], e.samp_temperature, e.samp_top_k, e.samp_top_p, e.gen_ids[g], e.gen_wt[g],
+                               *e._score_range_args(g), run=False) for g, e, r in groups]
         else:
             plan += [ops.argmax(self.logits[r], e.gen_ids[g], run=False) for g, e, r in groups]
         return plan
@@ -233,7 +240,8 @@ class StaggeredDecodePipeline:
 
     @torch.no_grad()
     def step(self, input_ids: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
-             attention_mask: Optional[torch.Tensor] = None, mask_checked: bool = False, sampling=None):
+             attention_mask: Optional[torch.Tensor] = None, mask_checked: bool = False, sampling=None,
+             forced_ids: Optional[torch.Tensor] = None, ids_checked: bool = False):
         """Submit a batch (None: re-use the inputs resident in the slot's buffers) and return the [B, n_new] ids of the
         batch submitted n_new-1 steps earlier, which this step completed (garbage until the pipeline has filled). The
         returned view is overwritten by the next step() — copy it first. A padded pipeline takes right-padded prompts with
@@ -243,13 +251,22 @@ class StaggeredDecodePipeline:
         that built the masks itself (the server), so submission stays asynchronous like the un-padded one.
         A sample=True pipeline takes the submitted batch's `sampling` (a SamplingParams; None: every sequence greedy) into
         the slot's settings buffers, where they stay until the batch completes, and returns the pair (ids [B, n_new],
-        wt [B, n_new, 2]) — both views that the next step() overwrites."""
+        wt [B, n_new, 2]) — both views that the next step() overwrites.
+        A score=True pipeline takes the submitted batch's `forced_ids` [B, n_new] (required with input_ids; checked
+        against the vocabulary unless `ids_checked=True`, a host synchronisation for ids on the device) and `sampling`
+        into the slot, and returns the completed batch's wt [B, n_new, 2] — with score_range the pair (wt, range_wt
+        [B, n_new, count]) — again views."""
         k = self._tick % self.slots
-        if sampling is not None and (not self.sample or input_ids is None):
-            raise ValueError("sampling goes with the input_ids of a pipeline built with sample=True")
-        if input_ids is not None and self.sample:
+        if sampling is not None and (not (self.sample or self.score) or input_ids is None):
+            raise ValueError("sampling goes with the input_ids of a pipeline built with sample=True or score=True")
+        if (forced_ids is not None) != (self.score and input_ids is not None):
+            raise ValueError("forced_ids goes with the input_ids of a pipeline built with score=True, and every batch "
+                             "submitted to such a pipeline needs them")
+        if input_ids is not None and (self.sample or self.score):
             from .sampling import SamplingParams
             self.engines[k].set_sampling(sampling if sampling is not None else SamplingParams(temperature=0.0))
+        if forced_ids is not None:
+            self.engines[k].set_forced_ids(forced_ids, check=not ids_checked)
         if attention_mask is not None and (not self.padded or input_ids is None):
             raise ValueError("attention_mask goes with the input_ids of a pipeline built with padded=True")
         if input_ids is not None and self.padded:
@@ -262,14 +279,20 @@ class StaggeredDecodePipeline:
         else:
             self._run_tick(k)
         self._tick += 1
-        done = self.engines[(k + 1) % self.slots]
-        return (done.gen_ids.t(), done.gen_wt.permute(1, 0, 2)) if self.sample else done.gen_ids.t()
+        return self._result(self.engines[(k + 1) % self.slots], lambda x: x)
+
+    def _result(self, e: OpenVLAEngine, own):
+        """What step() / flush() hand out for a slot's finished batch (`own`: identity for views, clone for copies)."""
+        if self.score:
+            wt = own(e.gen_wt.permute(1, 0, 2))
+            return wt if e.gen_range_wt is None else (wt, own(e.gen_range_wt.permute(1, 0, 2)))
+        return (own(e.gen_ids.t()), own(e.gen_wt.permute(1, 0, 2))) if self.sample else own(e.gen_ids.t())
 
     def flush(self, ticks: Optional[Sequence[int]] = None) -> List[Optional[torch.Tensor]]:
         """Drain: finish the batches still in flight with each slot's own per-batch plans; returns their ids oldest
         first (copies), one entry per step of the last `slots - 1` steps. `ticks`: finish only the batches submitted at
         these step indices (None entries for the others) — a server that already answered the older slots skips them.
-        A sample=True pipeline returns (ids, wt) pairs."""
+        A sample=True pipeline returns (ids, wt) pairs, a score=True pipeline what its step() returns."""
         out: List[Optional[torch.Tensor]] = []
         for a in range(min(self.slots - 2, self._tick - 1), -1, -1):    # a = steps since the batch was submitted
             tick = self._tick - 1 - a
@@ -283,5 +306,5 @@ class StaggeredDecodePipeline:
                 j = 0
             for step in e.decode_ops[j:]:
                 ops.run_all(step)
-            out.append((e.gen_ids.t().clone(), e.gen_wt.permute(1, 0, 2).clone()) if self.sample else e.gen_ids.t().clone())
+            out.append(self._result(e, torch.clone))
         return out

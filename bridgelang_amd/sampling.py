@@ -27,6 +27,13 @@ Per row the outputs are the token id and the integer pair (w_token, total_kept);
 under the warped distribution is log(w_token / total_kept), taken on the host in fp64 (`logprob`) — the device never
 computes a logarithm. The logits here are bf16-rounded fp32, so exact ties are common, also at the top-k and top-p
 boundaries: every rule above is defined on ties. Logits must be free of NaN.
+
+Scoring is the opposite direction: `score_row` / `score_rows` (device twin: `bl_score_f32`) take a GIVEN token and return
+its pair (kept weight, total_kept) under the same warped distribution — no seed and no step, the score does not depend on
+them. The defining property: for every token `sample_row` can draw from a row, `score_row` of that token returns
+`sample_row`'s pair; a token that top-k or top-p removed, or whose weight rounds to 0, scores (0, total_kept), i.e.
+log-probability -inf. `score_rows` also returns the kept weights of an index range (the 256 action bins, say): exact
+per-token probabilities, and with `range_entropy` the entropy over that range.
 """
 from __future__ import annotations
 
@@ -146,10 +153,55 @@ def sample_rows(logits, temperature, top_k, top_p, seed, t: int) -> Tuple[np.nda
     return ids, wt
 
 
+def score_row(logits, temperature: float, top_k: int, top_p: float, token: int) -> Tuple[int, int]:
+    """One row, one given token → (w_token, total_kept): `sample_row`'s pair whenever it draws `token`."""
+    l = np.asarray(logits, dtype=_f32)
+    if not _f32(temperature) > 0:
+        return int(int(token) == int(np.argmax(l))), 1
+    kept = kept_weights(l, temperature, int(top_k), float(top_p))
+    return int(kept[int(token)]), int(kept.sum())
+
+
+def score_rows(logits, temperature, top_k, top_p, tokens, first: int = 0, count: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """logits [rows, n] with one setting and one token per row → wt int64 [rows, 2] and range_wt int32 [rows, count] =
+    the kept weights of tokens first … first + count - 1 (a greedy row: the one-hot of its argmax) — what bl_score_f32
+    writes."""
+    l = np.asarray(logits, dtype=_f32)
+    rows, n = l.shape
+    if count < 0 or (count and (first < 0 or first + count > n)):
+        raise ValueError(f"score_rows: the range [{first}, {first + count}) leaves [0, {n})")
+    wt, range_wt = np.zeros((rows, 2), np.int64), np.zeros((rows, count), np.int32)
+    for r in range(rows):
+        tok = int(tokens[r])
+        if not 0 <= tok < n:
+            raise ValueError(f"score_rows: token {tok} of row {r} is outside [0, {n})")
+        if not _f32(temperature[r]) > 0:
+            kept = np.zeros(n, np.int64)
+            kept[int(np.argmax(l[r]))] = 1
+        else:
+            kept = kept_weights(l[r], temperature[r], int(top_k[r]), float(top_p[r]))
+        wt[r] = kept[tok], kept.sum()
+        range_wt[r] = kept[first:first + count]
+    return wt, range_wt
+
+
 def logprob(wt) -> np.ndarray:
-    """fp64 log-probability of the drawn tokens under the warped distribution, from weight pairs [..., 2]."""
+    """fp64 log-probability of the drawn (or scored) tokens under the warped distribution, from weight pairs [..., 2];
+    -inf where the weight is 0 (a scored token outside the support)."""
     wt = np.asarray(wt, dtype=np.float64)
-    return np.log(wt[..., 0] / wt[..., 1])
+    w, total = wt[..., 0], wt[..., 1]
+    inside = w > 0
+    return np.where(inside, np.log(np.where(inside, w, total) / total), -np.inf)
+
+
+def range_entropy(range_wt, total_kept) -> Tuple[np.ndarray, np.ndarray]:
+    """fp64 (-Σ p log p, Σ p) over a range of kept weights [..., count] with p = w / total_kept [...]: the entropy
+    contribution of the range's tokens (0 · log 0 = 0) and the probability mass the range holds. The mass is 1 when the
+    range covers the support, and the first value is then the entropy of the warped distribution."""
+    w = np.asarray(range_wt, dtype=np.float64)
+    p = w / np.asarray(total_kept, dtype=np.float64)[..., None]
+    inside = w > 0
+    return -(p * np.log(np.where(inside, p, 1.0))).sum(axis=-1), p.sum(axis=-1)
 
 
 def derive_seed(seed, j: int) -> np.ndarray:

@@ -269,6 +269,17 @@ int bl_argmax_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, int6
 int bl_sample_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
                   const int32_t* top_k, const float* top_p, const int64_t* seed, int32_t step, int64_t* ids,
                   int64_t* wt, void* stream);
+/* The score of a GIVEN token per row under the same warped distribution: bl_sample_f32 with the draw replaced by a read,
+ * bit-identical to bridgelang_amd/sampling.py::score_rows. tokens int64 [rows]; wt int64 [rows, 2] = (kept weight of
+ * tokens[row], kept total) — weight 0 for a token that top-k or top-p removed or whose weight rounds to 0; a greedy row
+ * (temperature 0) scores (token == argmax, 1). A token outside [0, n) is a caller error; the kernel reads nothing for it
+ * and writes (0, kept total). range_count > 0 also writes range_wt int32 [rows, range_count]: the kept weights of tokens
+ * range_first … range_first + range_count - 1 (a greedy row: the one-hot of its argmax); it needs 0 <= range_first and
+ * range_first + range_count <= n (else BL_E_SHAPE); range_count == 0 ignores range_wt (may be NULL). Shapes and alignment
+ * as bl_sample_f32. */
+int bl_score_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
+                 const int32_t* top_k, const float* top_p, const int64_t* tokens, int64_t* wt,
+                 int32_t range_first, int32_t range_count, int32_t* range_wt, void* stream);
 
 /* Shifted causal-LM cross-entropy (HF LlamaForCausalLM loss; labels prepared by the caller as `targets[row]` =
  * label of the NEXT position, -100 = ignore; base_strategy.py:287-297 consumes `output.loss`). row_loss[rows] receives
