@@ -1,0 +1,212 @@
+// policy.hip — the clipped-surrogate policy-gradient loss (PPO / GRPO form) over fp32 logits rows, with an entropy bonus
+// and a k3 KL penalty against a reference policy: the second loss the training step can plan, beside the shifted
+// cross-entropy (glue.hip / train.hip). bridgelang_amd/training/policy_loss.py is the fp64 definition; these kernels are
+// its fp32 twin to a tolerance (expf / logf, as the cross-entropy kernels).
+//
+// Same conventions as cross-entropy: one workgroup per row, targets[row] = token of the NEXT position, ignore_index rows
+// contribute nothing (and their logits are never read), 16-byte accesses, deterministic reductions, no float atomics.
+// HBM-bound: the forward reads a valid row twice, the backward once (m, log S, H and g are saved per row), and the bf16
+// zero fill of the ignored rows' dlogits is most of the traffic at training shapes.
+#include "bl_common.h"
+#include <math.h>
+
+namespace bl_policy_impl {
+
+// per-row statistics, fp32 [rows, 8]
+enum { RS_LOGP = 0, RS_H, RS_RATIO, RS_LOSS, RS_CLIPPED, RS_M, RS_LOGS, RS_G };
+
+struct PolicyParams {
+  float inv_t, clip_low, clip_high, entropy_coef, kl_coef;
+};
+
+// Everything of a row that follows from log π(a) alone. ONE definition for the row kernel and the step reduction.
+struct RowTerms {
+  float ratio, log_ratio, pg, kl, g;
+  bool active;
+};
+__device__ __forceinline__ RowTerms row_terms(float logp, float A, float q, const float* ref, int row, const PolicyParams& P) {
+  RowTerms t;
+  t.log_ratio = logp - q;
+  t.ratio = expf(t.log_ratio);
+  const float lo = 1.0f - P.clip_low, hi = 1.0f + P.clip_high;
+  const float clipped = fminf(fmaxf(t.ratio, lo), hi);
+  t.pg = -fminf(t.ratio * A, clipped * A);
+  t.active = (A >= 0.f && t.ratio <= hi) || (A < 0.f && t.ratio >= lo);   // clamp passes its gradient at the boundary
+  t.kl = 0.f;
+  t.g = t.active ? -A * t.ratio : 0.f;
+  if (ref) {
+    const float d = ref[row] - logp;
+    const float em1 = expm1f(d);
+    t.kl = em1 - d;                        // exp(d) − d − 1 (k3)
+    t.g -= P.kl_coef * em1;                // kl_coef·(1 − exp(d))
+  }
+  return t;
+}
+
+__global__ __launch_bounds__(256) void policy_rows_kernel(const float* logits, long ld, int n, const int64_t* targets,
+                                                          long ignore_index, const float* adv, const float* old_lp,
+                                                          const float* ref_lp, PolicyParams P, float* row_stats) {
+  __shared__ float red_m[4], red_s[4], red_w[4];
+  const int row = blockIdx.x;
+  const long tgt = targets[row];
+  float* rs = row_stats + (long)row * 8;
+  if (tgt == ignore_index) {          // uniform per workgroup
+    if (threadIdx.x < 8) rs[threadIdx.x] = 0.f;
+    return;
+  }
+  const float* lr = logits + (long)row * ld;
+  float mx = -INFINITY;
+  for (int i = threadIdx.x * 4; i < n; i += 1024) {
+    const f32x4_t q = *(const f32x4_t*)(lr + i);
+    mx = fmaxf(fmaxf(mx, fmaxf(q[0], q[1])), fmaxf(q[2], q[3]));
+  }
+  mx = wave_max(mx);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) red_m[wave] = mx;
+  __syncthreads();
+  // max of z = l / T is max(l) / T (T > 0); the row is scaled as it is read
+  const float m = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3])) * P.inv_t;
+  float s = 0.f, w = 0.f;             // S = Σ exp(z − m), W = Σ exp(z − m)·(z − m)
+  for (int i = threadIdx.x * 4; i < n; i += 1024) {
+    const f32x4_t q = *(const f32x4_t*)(lr + i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = q[e] * P.inv_t - m;
+      const float ex = expf(d);
+      s += ex;
+      w += ex * d;                    // exp underflows to 0 long before d overflows: 0·d = 0
+    }
+  }
+  s = wave_sum(s);
+  w = wave_sum(w);
+  if ((threadIdx.x & 63) == 0) { red_s[wave] = s; red_w[wave] = w; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float S = red_s[0] + red_s[1] + red_s[2] + red_s[3];
+    const float W = red_w[0] + red_w[1] + red_w[2] + red_w[3];
+    const float logS = logf(S);
+    const float H = logS - W / S;                                       // −Σ p·logp, logp = (z − m) − log S
+    const float za = (tgt >= 0 && tgt < n) ? lr[tgt] * P.inv_t : NAN;    // a token outside the row: NaN, never a stray read
+    const float logp = za - m - logS;
+    const RowTerms t = row_terms(logp, adv[row], old_lp[row], ref_lp, row, P);
+    rs[RS_LOGP] = logp;
+    rs[RS_H] = H;
+    rs[RS_RATIO] = t.ratio;
+    rs[RS_LOSS] = t.pg - P.entropy_coef * H + P.kl_coef * t.kl;
+    rs[RS_CLIPPED] = t.active ? 0.f : 1.f;
+    rs[RS_M] = m;
+    rs[RS_LOGS] = logS;
+    rs[RS_G] = t.g;
+  }
+}
+
+// the 8 step statistics: means over valid rows (single workgroup, fixed summation order → deterministic)
+__global__ __launch_bounds__(256) void policy_stats_kernel(const float* row_stats, const int64_t* targets, long ignore_index,
+                                                           const float* adv, const float* old_lp, const float* ref_lp,
+                                                           PolicyParams P, int rows, float* out) {
+  __shared__ float rsum[4][7];
+  __shared__ int rc[4];
+  float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // row_loss, pg, H, kl, clipped, approx KL, ratio
+  int c = 0;
+  for (int i = threadIdx.x; i < rows; i += 256) {
+    if (targets[i] == ignore_index) continue;
+    const float* rs = row_stats + (long)i * 8;
+    const RowTerms t = row_terms(rs[RS_LOGP], adv[i], old_lp[i], ref_lp, i, P);
+    a[0] += rs[RS_LOSS];
+    a[1] += t.pg;
+    a[2] += rs[RS_H];
+    a[3] += t.kl;
+    a[4] += rs[RS_CLIPPED];
+    a[5] += expm1f(t.log_ratio) - t.log_ratio;         // (ratio − 1) − log ratio
+    a[6] += t.ratio;
+    ++c;
+  }
+#pragma unroll
+  for (int k = 0; k < 7; ++k) a[k] = wave_sum(a[k]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k) rsum[threadIdx.x >> 6][k] = a[k];
+    rc[threadIdx.x >> 6] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x < 7) {
+    const int k = threadIdx.x;
+    const int cnt = rc[0] + rc[1] + rc[2] + rc[3];
+    const float mean = cnt > 0 ? (rsum[0][k] + rsum[1][k] + rsum[2][k] + rsum[3][k]) / (float)cnt : 0.f;
+    out[k == 0 ? 0 : k + 1] = mean;
+    if (k == 0) out[1] = (float)cnt;
+  }
+}
+
+__device__ __forceinline__ u32x4_t pack8(const float* v) {
+  u32x4_t q;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) q[i] = pack2bf(v[2 * i], v[2 * i + 1]);
+  return q;
+}
+
+// dlogits_i = [ g·(δ_ia − p_i) + entropy_coef·p_i·(logp_i + H) ] / (T · n_valid): one read of the row; logp_i by arithmetic
+// (z_i − m − log S), so an underflowed p_i gives 0·finite = 0, never 0·(−inf)
+__global__ __launch_bounds__(256) void policy_backward_kernel(const float* logits, long ld, int n, const int64_t* targets,
+                                                              long ignore_index, const float* row_stats, const float* stats,
+                                                              float inv_t, float entropy_coef, uint16_t* dlogits, long ldd) {
+  const int row = blockIdx.x;
+  const long tgt = targets[row];
+  uint16_t* dr = dlogits + (long)row * ldd;
+  if (tgt == ignore_index) {
+    for (int i = threadIdx.x * 8; i < n; i += 2048) *(u32x4_t*)(dr + i) = (u32x4_t){0u, 0u, 0u, 0u};
+    return;
+  }
+  const float* lr = logits + (long)row * ld;
+  const float* rs = row_stats + (long)row * 8;
+  const float H = rs[RS_H], g = rs[RS_G];
+  const float off = rs[RS_M] + rs[RS_LOGS];
+  const float scale = inv_t / stats[1];                 // 1 / (T · n_valid)
+  for (int i = threadIdx.x * 8; i < n; i += 2048) {
+    const f32x4_t a = *(const f32x4_t*)(lr + i), b = *(const f32x4_t*)(lr + i + 4);
+    float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float lp = v[e] * inv_t - off;
+      const float p = expf(lp);
+      v[e] = (g * (((long)(i + e) == tgt ? 1.f : 0.f) - p) + entropy_coef * p * (lp + H)) * scale;
+    }
+    *(u32x4_t*)(dr + i) = pack8(v);
+  }
+}
+
+}  // namespace bl_policy_impl
+using namespace bl_policy_impl;
+
+extern "C" int bl_policy_loss_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                  int64_t ignore_index, const float* advantages, const float* old_logprob,
+                                  const float* ref_logprob, float temperature, float clip_low, float clip_high,
+                                  float entropy_coef, float kl_coef, float* row_stats, float* stats, void* stream) {
+  if (!logits || !targets || !advantages || !old_logprob || !row_stats || !stats) return BL_E_ARG;
+  if (!(temperature > 0.f) || !(clip_low >= 0.f) || !(clip_high >= 0.f)) return BL_E_ARG;
+  if (rows <= 0 || n <= 0 || (n % 8) || (ld % 4) || ld < n) return BL_E_SHAPE;
+  if (!bl_aligned16(logits)) return BL_E_ALIGN;
+  const PolicyParams P = {1.0f / temperature, clip_low, clip_high, entropy_coef, ref_logprob ? kl_coef : 0.f};
+  hipLaunchKernelGGL(policy_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, n, targets,
+                     (long)ignore_index, advantages, old_logprob, ref_logprob, P, row_stats);
+  hipLaunchKernelGGL(policy_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, row_stats, targets, (long)ignore_index,
+                     advantages, old_logprob, ref_logprob, P, rows, stats);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
+extern "C" int bl_policy_loss_backward_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                           int64_t ignore_index, const float* row_stats, const float* stats,
+                                           float temperature, float entropy_coef, bl_bf16* dlogits, int64_t ldd,
+                                           void* stream) {
+  if (!logits || !targets || !row_stats || !stats || !dlogits) return BL_E_ARG;
+  if (!(temperature > 0.f)) return BL_E_ARG;
+  if (rows <= 0 || n <= 0 || (n % 8) || (ld % 4) || (ldd % 8) || ld < n || ldd < n) return BL_E_SHAPE;
+  if (!bl_aligned16(logits) || !bl_aligned16(dlogits)) return BL_E_ALIGN;
+  hipLaunchKernelGGL(policy_backward_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, n, targets,
+                     (long)ignore_index, row_stats, stats, 1.0f / temperature, entropy_coef, dlogits, (long)ldd);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}

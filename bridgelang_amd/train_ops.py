@@ -32,6 +32,42 @@ def cross_entropy_backward(logits, targets, mean_and_count, dlogits, ignore_inde
                (logits, targets, mean_and_count, dlogits), run, nbytes=6.0 * rows * n)
 
 
+def _policy_rows(logits, targets, row_stats, stats, what: str):
+    rows, n = logits.shape
+    if targets.dtype != torch.int64 or targets.numel() != rows:
+        raise TypeError(f"{what}: targets int64 [{rows}]")
+    if tuple(_f32(row_stats, "row_stats").shape) != (rows, 8) or not row_stats.is_contiguous() or _f32(stats, "stats").numel() != 8:
+        raise ValueError(f"{what}: row_stats fp32 [{rows}, 8] contiguous and stats fp32 [8]")
+    return rows, n
+
+
+def policy_loss(logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats, cfg, ignore_index: int = -100,
+                run: bool = True) -> Op:
+    """Clipped-surrogate policy-gradient loss over fp32 logits [rows, n] (training/policy_loss.py is the definition; `cfg` a
+    PolicyLossConfig). advantages / old_logprob / ref_logprob (None: no KL term) fp32 [rows]; row_stats fp32 [rows, 8] and
+    stats fp32 [8] receive policy_loss.ROW_STAT_NAMES / STAT_NAMES."""
+    rows, n = _policy_rows(logits, targets, row_stats, stats, "policy_loss")
+    for t, what in ((advantages, "advantages"), (old_logprob, "old_logprob"), (ref_logprob, "ref_logprob")):
+        if t is not None and (_f32(t, what).numel() != rows or not t.is_contiguous()):
+            raise ValueError(f"policy_loss: {what} fp32 [{rows}] contiguous")
+    return _op("bl_policy_loss_f32",
+               (_f32(logits, "logits").data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
+                advantages.data_ptr(), old_logprob.data_ptr(), ref_logprob.data_ptr() if ref_logprob is not None else None,
+                float(cfg.temperature), float(cfg.clip_low), float(cfg.clip_high), float(cfg.entropy_coef), float(cfg.kl_coef),
+                row_stats.data_ptr(), stats.data_ptr()),
+               (logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats), run, nbytes=8.0 * rows * n)
+
+
+def policy_loss_backward(logits, targets, row_stats, stats, dlogits, cfg, ignore_index: int = -100, run: bool = True) -> Op:
+    """bf16 dlogits of `policy_loss` from the logits and the row statistics it saved (stats[1] = n_valid)."""
+    rows, n = _policy_rows(logits, targets, row_stats, stats, "policy_loss_backward")
+    return _op("bl_policy_loss_backward_f32",
+               (_f32(logits, "logits").data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
+                row_stats.data_ptr(), stats.data_ptr(), float(cfg.temperature), float(cfg.entropy_coef),
+                _bf16(dlogits, "dlogits").data_ptr(), _rows(dlogits, "dlogits")),
+               (logits, targets, row_stats, stats, dlogits), run, nbytes=6.0 * rows * n)
+
+
 def rmsnorm_backward(x, w, dy, dx, dw, ws, eps: float, dres: Optional[torch.Tensor] = None, run: bool = True) -> Op:
     rows, dim = x.shape
     return _op("bl_rmsnorm_backward_bf16",

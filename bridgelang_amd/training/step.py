@@ -32,6 +32,7 @@ from ..engine import rope_tables
 from ..ops import (EPI_BIAS, EPI_BIAS_GELU_KEEP, EPI_F32, EPI_F32_BF16R, EPI_GELU_BWD, EPI_NONE, EPI_RES, EPI_SWIGLU_BWD,
                    EPI_SWIGLU_KEEP, Op)
 from ..weights import PackedGroup, VLAWeights, _block_view, _unpack
+from .policy_loss import STAT_NAMES, PolicyLossConfig
 from .sharding import ShardComm, ShardLayout, bucket_key, comm_order
 
 IGNORE_INDEX = -100
@@ -366,7 +367,7 @@ class TrainStep:
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, store: Optional[ParamStore] = None,
                  world: int = 1, rank: int = 0, group=None, reduce_dtype: torch.dtype = torch.float32, lora=None,
                  force_comm: bool = False, recompute: bool = False, shard_params: bool = False, fp8: bool = False,
-                 fp8_wgrad: bool = False):
+                 fp8_wgrad: bool = False, loss: str = "ce", policy: Optional[PolicyLossConfig] = None):
         """`lora`: a training.lora.LoraAdapters → stage "lora": the base model is frozen and only the adapters train.
         `recompute`: keep only each decoder layer's input and replay its forward inside the backward pass.
         `shard_params`: FSDP FULL_SHARD for every FSDP unit — decoder layers, ViT blocks and stems, projector, token
@@ -383,7 +384,17 @@ class TrainStep:
         families of those layers are fp8: dW[n, k] = Σ_t dy[t, n]·x[t, k] contracts over tokens, so dy and x are transposed
         to token-contiguous rows and quantised per ROW of the transposed matrix — one scale per output channel n of dy and
         per input channel k of x, i.e. along the non-contracted dimensions, where the scales factor out of the sum exactly —
-        and dW = s_dy[n]·s_x[k]·(dyT8 · xT8ᵀ) accumulates in fp32 straight into the flat gradient buffer."""
+        and dW = s_dy[n]·s_x[k]·(dyT8 · xT8ᵀ) accumulates in fp32 straight into the flat gradient buffer.
+        `loss`: "ce" (the shifted cross-entropy of the labelled tokens) or "policy": the clipped-surrogate policy gradient
+        of training/policy_loss.py over the same rows, configured by `policy` (a PolicyLossConfig; its defaults if None) and
+        fed by `set_policy_batch` after `set_batch`. Only the two ops at the loss boundary differ; everything below the
+        logits, and every other option, is shared."""
+        if loss not in ("ce", "policy"):
+            raise ValueError(f"loss must be 'ce' or 'policy', got {loss!r}")
+        if policy is not None and loss != "policy":
+            raise ValueError("`policy` configures loss='policy'")
+        self.loss_kind = loss
+        self.policy = (policy or PolicyLossConfig()) if loss == "policy" else None
         if (lora is not None) != (stage == "lora"):
             raise ValueError("stage 'lora' and the `lora` adapters go together")
         if (recompute or shard_params or fp8) and lora is not None:
@@ -480,7 +491,13 @@ class TrainStep:
         self.delta = z(B * d.llm_heads * pad, dtype=torch.float32)
         self.hn = z(Tn, D)
         self.logits = z(Tn, V, dtype=torch.float32)
-        self.row_loss, self.mean_cnt = z(Tn, dtype=torch.float32), z(2, dtype=torch.float32)
+        if self.policy is None:
+            self.row_loss, self.mean_cnt = z(Tn, dtype=torch.float32), z(2, dtype=torch.float32)
+        else:                                   # per-row inputs and statistics of the policy loss; mean_cnt = (loss, n_valid)
+            self.advantages, self.old_logprob, self.ref_logprob = (z(Tn, dtype=torch.float32) for _ in range(3))
+            self.row_stats, self.stats = z(Tn, 8, dtype=torch.float32), z(8, dtype=torch.float32)
+            self.row_loss, self.mean_cnt = self.row_stats[:, 3], self.stats[:2]
+            self._batch_len = prompt_len
         self.cos, self.sin = rope_tables(d.head_dim, d.max_pos, d.rope_theta, dev)
         # ---- backward scratch ----
         self.dlogits = z(Tn, V)
@@ -1006,8 +1023,13 @@ class TrainStep:
         if head:
             plan.append(self._u_await("llm.lm_head"))
         plan += [ops.rmsnorm(self.x[-1], w.norm, self.hn, d.rms_eps, run=False),
-                 g(self.hn, w.lm_head, self.logits, EPI_F32_BF16R),
-                 ops.cross_entropy(self.logits, self.targets, self.row_loss, self.mean_cnt, IGNORE_INDEX, run=False)]
+                 g(self.hn, w.lm_head, self.logits, EPI_F32_BF16R)]
+        if self.policy is None:
+            plan.append(ops.cross_entropy(self.logits, self.targets, self.row_loss, self.mean_cnt, IGNORE_INDEX, run=False))
+        else:
+            plan.append(T.policy_loss(self.logits, self.targets, self.advantages, self.old_logprob,
+                                      self.ref_logprob if self.policy.kl_coef != 0.0 else None, self.row_stats, self.stats,
+                                      self.policy, IGNORE_INDEX, run=False))
         return plan
 
     def _layer_forward(self, l: int, with_down: bool = True) -> List[Op]:
@@ -1035,7 +1057,10 @@ class TrainStep:
         d, w, B, S, st = self.dims, self.w, self.B, self.S, self.store
         D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
         lm = "language_model.model"
-        plan: List[Op] = [T.cross_entropy_backward(self.logits, self.targets, self.mean_cnt, self.dlogits, IGNORE_INDEX, run=False)]
+        plan: List[Op] = [T.cross_entropy_backward(self.logits, self.targets, self.mean_cnt, self.dlogits, IGNORE_INDEX, run=False)
+                          if self.policy is None else
+                          T.policy_loss_backward(self.logits, self.targets, self.row_stats, self.stats, self.dlogits, self.policy,
+                                                 IGNORE_INDEX, run=False)]
         head = "projector" in self._units
         if head:
             plan.append(self._u_await_grad("llm.lm_head"))
@@ -1346,12 +1371,51 @@ class TrainStep:
         self.key_mask[:, :1] = m[:, :1]
         self.key_mask[:, 1:1 + P] = 1
         self.key_mask[:, 1 + P:] = m[:, 1:]
-        full = torch.full((B, S), IGNORE_INDEX, dtype=torch.int64, device=dev)       # labels with 256 ignored patch columns
-        full[:, :1] = lab[:, :1]
-        full[:, 1 + P:] = lab[:, 1:]
-        tg = torch.full((B, S), IGNORE_INDEX, dtype=torch.int64, device=dev)
-        tg[:, :-1] = full[:, 1:]                                                       # position t predicts token t+1
-        self.targets.copy_(tg.view(-1))
+        self.targets.copy_(shift_to_rows(lab, P, IGNORE_INDEX).view(-1))
+        if self.policy is not None:
+            self._batch_len = l
+
+    def set_policy_batch(self, advantages: torch.Tensor, old_logprobs: torch.Tensor, ref_logprobs: Optional[torch.Tensor] = None) -> None:
+        """Per-token inputs of loss="policy", [B, l] aligned with the `labels` of the preceding `set_batch`: the advantage
+        and the behaviour policy's log-probability of each labelled token, and a reference policy's (needed iff kl_coef is
+        set). They get the padding, patch-column insertion and one-position shift the labels got; values on unlabelled
+        positions are not read. Non-finite values on labelled positions raise ValueError (a -inf from `score_actions`
+        under top-k / top-p: rollouts for training are drawn with temperature only)."""
+        if self.policy is None:
+            raise RuntimeError("set_policy_batch needs TrainStep(loss='policy')")
+        if (ref_logprobs is None) != (self.policy.kl_coef == 0.0):
+            raise ValueError("ref_logprobs goes together with a non-zero kl_coef")
+        dev, B, L, P, l = self.device, self.B, self.L, self.dims.n_patches, self._batch_len
+        valid = (self.targets != IGNORE_INDEX).view(B, self.S)
+        for name, src, dst in (("advantages", advantages, self.advantages), ("old_logprobs", old_logprobs, self.old_logprob),
+                               ("ref_logprobs", ref_logprobs, self.ref_logprob)):
+            if src is None:
+                continue
+            src = torch.as_tensor(src)
+            if tuple(src.shape) != (B, l):
+                raise ValueError(f"{name}: shape {tuple(src.shape)}, expected {(B, l)} (aligned with the labels of set_batch)")
+            pad = torch.zeros(B, L, dtype=torch.float32, device=dev)
+            pad[:, :l] = src.to(dev, dtype=torch.float32)
+            rows = shift_to_rows(pad, P, 0.0)
+            bad = valid & ~torch.isfinite(rows)
+            if bool(bad.any()):
+                raise ValueError(f"{name}: {int(bad.sum())} non-finite value(s) on labelled positions — a token outside the "
+                                 "rollout's top-k / top-p support scores -inf; draw training rollouts with temperature only")
+            dst.copy_(torch.where(valid, rows, torch.zeros_like(rows)).view(-1))
+
+    def policy_stats(self) -> Dict[str, torch.Tensor]:
+        """The 8 step statistics of the last forward (policy_loss.STAT_NAMES) as device scalars."""
+        if self.policy is None:
+            raise RuntimeError("policy_stats needs TrainStep(loss='policy')")
+        return {name: self.stats[i] for i, name in enumerate(STAT_NAMES)}
+
+    def token_logprobs(self) -> torch.Tensor:
+        """log π(token) of the last forward at the labelled positions, [B, l] aligned with `labels` (0 elsewhere): the row
+        statistics shifted back. This is how a learner gets on-policy `old_logprobs`, or a frozen model's `ref_logprobs`,
+        from the training forward itself."""
+        if self.policy is None:
+            raise RuntimeError("token_logprobs needs TrainStep(loss='policy')")
+        return shift_from_rows(self.row_stats[:, 0].view(self.B, self.S), self.dims.n_patches)[:, :self._batch_len]
 
     @contextlib.contextmanager
     def _side_scratch(self, on: bool):
@@ -1510,6 +1574,29 @@ class TrainStep:
         norm = self.clip_grad_norm()
         self.optimizer_step(lr, graph)
         return loss, norm
+
+
+def shift_to_rows(values: torch.Tensor, n_patches: int, fill) -> torch.Tensor:
+    """Per-token values [B, L] aligned with the text tokens → per-row values [B, L + n_patches] aligned with the logits rows:
+    the patch columns are inserted behind the first token (filled with `fill`), and everything moves one position to the
+    left, because position t predicts token t + 1 (the last row gets `fill`). The labels and the policy loss's per-token
+    inputs all take this one path."""
+    B, L = values.shape
+    full = torch.full((B, L + n_patches), fill, dtype=values.dtype, device=values.device)
+    full[:, :1] = values[:, :1]
+    full[:, 1 + n_patches:] = values[:, 1:]
+    out = torch.full_like(full, fill)
+    out[:, :-1] = full[:, 1:]
+    return out
+
+
+def shift_from_rows(rows: torch.Tensor, n_patches: int) -> torch.Tensor:
+    """Inverse of `shift_to_rows` on the text positions: per-row values [B, S] → per-token values [B, S - n_patches]; the
+    first token, which no row predicts, gets 0."""
+    B, S = rows.shape
+    out = torch.zeros(B, S - n_patches, dtype=rows.dtype, device=rows.device)
+    out[:, 1:] = rows[:, n_patches:S - 1]
+    return out
 
 
 def is_uint8_frames(pixel_values) -> bool:

@@ -294,6 +294,24 @@ int bl_cross_entropy_f32(const float* logits, int64_t ld, int32_t rows, int32_t 
 int bl_cross_entropy_backward_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
                                   int64_t ignore_index, const float* mean_and_count, bl_bf16* dlogits, int64_t ldd,
                                   void* stream);
+/* Clipped-surrogate policy-gradient loss (PPO / GRPO form) over the same logits rows and `targets` convention as
+ * bl_cross_entropy_f32; bridgelang_amd/training/policy_loss.py is the fp64 definition. With z = logits / temperature,
+ * logp = log_softmax(z)[target], ratio = exp(logp - old_logprob[row]):
+ *   row_loss = -min(ratio*A, clip(ratio, 1 - clip_low, 1 + clip_high)*A) - entropy_coef*H(softmax(z))
+ *              + kl_coef*(exp(d) - d - 1),  d = ref_logprob[row] - logp   (ref_logprob NULL: no KL term).
+ * advantages / old_logprob / ref_logprob fp32 [rows], read on valid rows only. row_stats fp32 [rows, 8] receives
+ * (logp, H, ratio, row_loss, clipped 0/1, max z, log sum exp(z - max), d row_loss / d logp), zeros on ignored rows.
+ * stats fp32 [8] = (loss, n_valid, mean pg, mean H, mean kl, clipped fraction, mean (ratio - 1) - log ratio, mean ratio)
+ * over valid rows in a fixed summation order. n % 8 == 0, ld % 4 == 0, logits 16-byte aligned. */
+int bl_policy_loss_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                       int64_t ignore_index, const float* advantages, const float* old_logprob, const float* ref_logprob,
+                       float temperature, float clip_low, float clip_high, float entropy_coef, float kl_coef,
+                       float* row_stats, float* stats, void* stream);
+/* dlogits (bf16) = d loss / d logits from the logits and what bl_policy_loss_f32 saved (same temperature and
+ * entropy_coef); stats[1] = n_valid. 0 on ignored rows. ldd % 8 == 0, dlogits 16-byte aligned. */
+int bl_policy_loss_backward_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                int64_t ignore_index, const float* row_stats, const float* stats, float temperature,
+                                float entropy_coef, bl_bf16* dlogits, int64_t ldd, void* stream);
 /* LlamaRMSNorm backward: dx = rstd*(w*dy - xhat*mean(w*dy*xhat)) [+ dres: the residual stream's own gradient];
  * dw[j] = sum_rows dy*bf16(xhat). partial_ws >= ceil(rows/64)*dim floats. */
 int bl_rmsnorm_backward_bf16(const bl_bf16* x, int64_t ldx, const bl_bf16* w, const bl_bf16* dy, int64_t lddy,

@@ -1,0 +1,184 @@
+"""CPU: the fp64 specification of the clipped-surrogate policy loss (training/policy_loss.py) against an independent torch
+restatement differentiated by autograd, its defining properties, and the host glue around it (training/rl.py, the
+label / per-token shift of the training step)."""
+import numpy as np
+import pytest
+import torch
+
+from bridgelang_amd.training.policy_loss import IGNORE_INDEX, PolicyLossConfig, policy_loss
+from bridgelang_amd.training.rl import group_advantages, policy_batch
+from bridgelang_amd.training.step import shift_from_rows, shift_to_rows
+
+
+def torch_restatement(logits, targets, A, q, ref, cfg):
+    """Independent fp64 restatement: log_softmax, torch.minimum, clamp; gradients by autograd.
+    → (loss, row_loss [rows] with 0 on ignored rows, dlogits)."""
+    lg = torch.tensor(np.asarray(logits), dtype=torch.float64, requires_grad=True)
+    tg = torch.tensor(np.asarray(targets), dtype=torch.int64)
+    valid = tg != IGNORE_INDEX
+    A, q = torch.tensor(np.asarray(A), dtype=torch.float64), torch.tensor(np.asarray(q), dtype=torch.float64)
+    lsm = torch.log_softmax(lg / cfg.temperature, dim=-1)
+    logp = lsm.gather(1, tg.clamp(min=0)[:, None])[:, 0]
+    ratio = torch.exp(logp - q)
+    pg = -torch.minimum(ratio * A, ratio.clamp(1 - cfg.clip_low, 1 + cfg.clip_high) * A)
+    H = -(lsm.exp() * lsm).sum(-1)
+    row = pg - cfg.entropy_coef * H
+    if ref is not None:
+        d = torch.tensor(np.asarray(ref), dtype=torch.float64) - logp
+        row = row + cfg.kl_coef * (torch.exp(d) - d - 1)
+    row = torch.where(valid, row, torch.zeros_like(row))
+    loss = row.sum() / valid.sum()
+    loss.backward()
+    return loss.item(), row.detach().numpy(), lg.grad.numpy()
+
+
+def make_case(rows, n, seed, T):
+    """Rows with A of both signs and 0 and q placed so that both clip sides and the unclipped case occur, every ratio at
+    least 1e-3 away from both boundaries (asserted by `margin_ok`); every third row ignored."""
+    g = np.random.default_rng(seed)
+    logits = (g.standard_normal((rows, n)) * 2).astype(np.float32).astype(np.float64)
+    tg = g.integers(0, n, rows)
+    tg[1], tg[2] = 0, n - 1
+    tg[::3] = IGNORE_INDEX
+    A = g.standard_normal(rows)
+    A[4 % rows] = 0.0
+    on = policy_loss(logits, tg, np.zeros(rows), np.zeros(rows), cfg=PolicyLossConfig(temperature=T)).logp
+    want = np.resize(np.array([0.5, 0.9, 1.0, 1.1, 1.6, 0.75, 1.3]), rows)          # target ratios: clipped low / inside / clipped high
+    q = on - np.log(want)
+    ref = on + g.standard_normal(rows) * 0.3
+    return logits, tg, A, q, ref
+
+
+def margin_ok(res, cfg):
+    r = res.ratio[res.valid]
+    return bool((np.abs(r - (1 - cfg.clip_low)) >= 1e-3).all() and (np.abs(r - (1 + cfg.clip_high)) >= 1e-3).all())
+
+
+@pytest.mark.parametrize("T", [1.0, 0.7])
+@pytest.mark.parametrize("ent,klc", [(0.0, 0.0), (0.01, 0.0), (0.0, 0.1), (0.02, 0.05)])
+def test_spec_equals_autograd_of_torch_restatement(T, ent, klc):
+    cfg = PolicyLossConfig(temperature=T, clip_low=0.2, clip_high=0.25, entropy_coef=ent, kl_coef=klc)
+    logits, tg, A, q, ref = make_case(21, 40, seed=int(T * 10) + 1, T=T)
+    ref = ref if klc else None
+    res = policy_loss(logits, tg, A, q, ref, cfg)
+    assert margin_ok(res, cfg)
+    v = res.valid
+    assert (A[v] > 0).any() and (A[v] < 0).any() and (A[v] == 0).any()
+    assert (res.ratio[v] > 1 + cfg.clip_high).any() and (res.ratio[v] < 1 - cfg.clip_low).any()
+    assert res.clipped.any() and (v & ~res.clipped).any() and not res.clipped[~v].any()
+    loss, row, dl = torch_restatement(logits, tg, A, q, ref, cfg)
+    assert abs(res.loss - loss) <= 1e-9
+    assert np.abs(res.row_loss - row).max() <= 1e-9
+    assert np.abs(res.dlogits - dl).max() <= 1e-9
+    assert (res.dlogits[~v] == 0).all() and (res.row_loss[~v] == 0).all()
+    assert res.stats[1] == v.sum() and abs(res.stats[5] - res.clipped.sum() / v.sum()) <= 1e-15
+
+
+def test_on_policy_ratio_one_and_cross_entropy_gradient():
+    rows, n = 9, 24
+    logits, tg, _, _, _ = make_case(rows, n, seed=5, T=1.0)
+    on = policy_loss(logits, tg, np.zeros(rows), np.zeros(rows)).logp
+    res = policy_loss(logits, tg, np.ones(rows), on)
+    v = res.valid
+    assert (res.ratio[v] == 1.0).all() and res.stats[5] == 0 and res.stats[6] == 0 and res.stats[7] == 1.0
+    lg = torch.tensor(logits, requires_grad=True)
+    torch.nn.functional.cross_entropy(lg, torch.tensor(tg), ignore_index=IGNORE_INDEX).backward()
+    assert np.abs(res.dlogits - lg.grad.numpy()).max() <= 1e-12       # (p − onehot) / n_valid
+
+
+def test_entropy_bonus_has_no_gradient_on_a_uniform_row():
+    logits = np.full((2, 16), 0.375)
+    res = policy_loss(logits, np.array([3, 5]), np.zeros(2), np.zeros(2), cfg=PolicyLossConfig(entropy_coef=0.3))
+    assert np.abs(res.dlogits).max() <= 1e-15 and np.allclose(res.entropy, np.log(16))
+
+
+def test_peaked_row_stays_finite():
+    logits = np.zeros((2, 32))
+    logits[0, 7] = 60.0
+    logits[1, 9] = 60.0
+    cfg = PolicyLossConfig(temperature=0.7, entropy_coef=0.01, kl_coef=0.1)
+    res = policy_loss(logits, np.array([7, 3]), np.array([1.0, -1.0]), np.array([-0.1, -85.0]), np.array([-0.2, -86.0]), cfg)
+    for v in (res.logp, res.entropy, res.ratio, res.row_loss, res.dlogits, res.stats):
+        assert np.isfinite(v).all()
+
+
+def test_spec_rejects_non_finite_inputs_on_valid_rows_only():
+    logits = np.zeros((3, 8))
+    tg = np.array([1, IGNORE_INDEX, 2])
+    policy_loss(logits, tg, np.ones(3), np.array([0.0, -np.inf, 0.0]))                       # ignored row: not read
+    with pytest.raises(ValueError):
+        policy_loss(logits, tg, np.ones(3), np.array([-np.inf, 0.0, 0.0]))
+    with pytest.raises(ValueError):
+        policy_loss(logits, tg, np.ones(3), np.zeros(3), np.array([0.0, 0.0, np.nan]), PolicyLossConfig(kl_coef=0.1))
+    with pytest.raises(ValueError):
+        PolicyLossConfig(temperature=0.0)
+
+
+def test_group_advantages():
+    r = torch.tensor([[1.0, 2.0, 4.0, 9.0], [3.0, 3.0, 3.0, 3.0], [0.0, 1.0, 0.0, 1.0]])
+    a = group_advantages(r)
+    assert a.dtype == torch.float32 and tuple(a.shape) == (3, 4)
+    assert a.sum(dim=1).abs().max().item() <= 1e-6
+    assert (a[1] == 0).all()
+    assert torch.allclose(a[2], torch.tensor([-1.0, 1.0, -1.0, 1.0]), atol=1e-5)
+    assert torch.equal(group_advantages(r.numpy()), a)
+    for bad in (torch.zeros(4), torch.zeros(2, 3, 4), torch.zeros(2, 0)):
+        with pytest.raises(ValueError):
+            group_advantages(bad)
+
+
+def test_policy_batch_layout():
+    prompts = torch.tensor([[1, 11, 12, 13, 32000, 32000],
+                            [1, 21, 22, 23, 24, 29871]])
+    mask = torch.tensor([[1, 1, 1, 1, 0, 0], [1, 1, 1, 1, 1, 1]])
+    tok = np.array([[31900, 31901, 31902], [31910, 31911, 31912]])
+    lp = np.array([[-1.0, -2.0, -3.0], [-0.5, -0.25, -0.125]])
+    b = policy_batch(prompts, mask, tok, lp, [2.0, -1.5])
+    assert b["input_ids"].tolist() == [[1, 11, 12, 13, 29871, 31900, 31901, 31902, 2, 32000],
+                                       [1, 21, 22, 23, 24, 29871, 31910, 31911, 31912, 2]]     # present empty token not duplicated
+    assert b["attention_mask"].tolist() == [[True] * 9 + [False], [True] * 10]
+    lab = b["labels"]
+    assert lab[0].tolist() == [-100] * 5 + [31900, 31901, 31902] + [-100] * 2
+    assert lab[1].tolist() == [-100] * 6 + [31910, 31911, 31912] + [-100]
+    on = lab != -100
+    assert int(on.sum()) == 6                                                               # exactly the n action tokens
+    assert b["advantages"][on].tolist() == [2.0] * 3 + [-1.5] * 3 and (b["advantages"][~on] == 0).all()
+    assert b["old_logprobs"][on].tolist() == [-1.0, -2.0, -3.0, -0.5, -0.25, -0.125] and (b["old_logprobs"][~on] == 0).all()
+    assert b["advantages"].dtype == torch.float32 and b["old_logprobs"].dtype == torch.float32
+    wide = policy_batch(prompts, mask, tok, lp, [2.0, -1.5], pad_to=14)
+    assert tuple(wide["input_ids"].shape) == (2, 14) and torch.equal(wide["input_ids"][:, :10], b["input_ids"])
+    assert (wide["input_ids"][:, 10:] == 32000).all() and not wide["attention_mask"][:, 10:].any() and (wide["labels"][:, 10:] == -100).all()
+    full = policy_batch(prompts[1:], None, tok[1:], lp[1:], [1.0])                           # no mask: no padding
+    assert torch.equal(full["input_ids"], b["input_ids"][1:])
+    with pytest.raises(ValueError):
+        policy_batch(prompts, mask, tok, lp, [2.0, -1.5], pad_to=9)
+    bad = lp.copy()
+    bad[1, 2] = -np.inf
+    with pytest.raises(ValueError):
+        policy_batch(prompts, mask, tok, bad, [2.0, -1.5])
+    with pytest.raises(ValueError):
+        policy_batch(prompts, mask, tok, lp[:, :2], [2.0, -1.5])
+
+
+def test_shift_helper_places_values_where_the_labels_go():
+    """The per-token inputs of the policy loss take the path of the labels: on a ragged batch, a value tagged with its
+    label lands on the row whose target is that label, and `shift_from_rows` brings it back."""
+    B, L, P = 3, 12, 5
+    g = torch.Generator().manual_seed(0)
+    labels = torch.full((B, L), IGNORE_INDEX, dtype=torch.int64)
+    for b, n in enumerate((12, 9, 6)):
+        labels[b, n - 4:n] = torch.randint(100, 200, (4,), generator=g)
+    labels[0, 0] = 150                                             # a label on the first token: no row predicts it
+    # the label placement of TrainStep._set_text_batch, written out
+    full = torch.cat([labels[:, :1], torch.full((B, P), IGNORE_INDEX), labels[:, 1:]], 1)
+    want = torch.full((B, L + P), IGNORE_INDEX, dtype=torch.int64)
+    want[:, :-1] = full[:, 1:]
+    targets = shift_to_rows(labels, P, IGNORE_INDEX)
+    assert torch.equal(targets, want)
+    values = torch.where(labels != IGNORE_INDEX, labels.float() + 0.5, torch.zeros(B, L))
+    rows = shift_to_rows(values, P, 0.0)
+    on = targets != IGNORE_INDEX
+    assert int(on.sum()) == 12 and torch.equal(rows[on], targets[on].float() + 0.5) and (rows[~on] == 0).all()
+    back = shift_from_rows(rows, P)
+    values[:, 0] = 0
+    assert torch.equal(back, values)
