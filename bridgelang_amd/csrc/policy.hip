@@ -7,6 +7,13 @@
 // contribute nothing (and their logits are never read), 16-byte accesses, deterministic reductions, no float atomics.
 // HBM-bound: the forward reads a valid row twice, the backward once (m, log S, H and g are saved per row), and the bf16
 // zero fill of the ignored rows' dlogits is most of the traffic at training shapes.
+//
+// bl_policy_loss_range_f32 / bl_policy_loss_backward_range_f32 take the policy over the columns [first, first + count) of
+// every row (the 256 action bins of the 32 064-row vocabulary): m, S, H, logp and p_i are over the range, no logit
+// outside it is read, and dlogits is 0 there. The forward is row_forward over the range, by a whole workgroup for a long
+// range and by ONE WAVE for a range of at most 256 columns (a float4 per lane: four rows per workgroup, no barrier and
+// no idle wave); both call the same finish_row → row_terms. The backward is the one kernel with a column window. The
+// unranged entry points are the (0, n) case of the workgroup kernels.
 #include "bl_common.h"
 #include <math.h>
 
@@ -43,7 +50,26 @@ __device__ __forceinline__ RowTerms row_terms(float logp, float A, float q, cons
   return t;
 }
 
-__global__ __launch_bounds__(256) void policy_rows_kernel(const float* logits, long ld, int n, const int64_t* targets,
+// what thread 0 / lane 0 does once S and W of a row are known. lr points at column `first`; tgt is relative to it.
+__device__ __forceinline__ void finish_row(const float* lr, int n, long tgt, float m, float S, float W, const float* adv,
+                                           const float* old_lp, const float* ref_lp, int row, const PolicyParams& P, float* rs) {
+  const float logS = logf(S);
+  const float H = logS - W / S;                                       // −Σ p·logp, logp = (z − m) − log S
+  const float za = (tgt >= 0 && tgt < n) ? lr[tgt] * P.inv_t : NAN;    // a token outside the row: NaN, never a stray read
+  const float logp = za - m - logS;
+  const RowTerms t = row_terms(logp, adv[row], old_lp[row], ref_lp, row, P);
+  rs[RS_LOGP] = logp;
+  rs[RS_H] = H;
+  rs[RS_RATIO] = t.ratio;
+  rs[RS_LOSS] = t.pg - P.entropy_coef * H + P.kl_coef * t.kl;
+  rs[RS_CLIPPED] = t.active ? 0.f : 1.f;
+  rs[RS_M] = m;
+  rs[RS_LOGS] = logS;
+  rs[RS_G] = t.g;
+}
+
+// one workgroup per row; the row is the n columns from column `first` on
+__global__ __launch_bounds__(256) void policy_rows_kernel(const float* logits, long ld, int first, int n, const int64_t* targets,
                                                           long ignore_index, const float* adv, const float* old_lp,
                                                           const float* ref_lp, PolicyParams P, float* row_stats) {
   __shared__ float red_m[4], red_s[4], red_w[4];
@@ -54,7 +80,7 @@ __global__ __launch_bounds__(256) void policy_rows_kernel(const float* logits, l
     if (threadIdx.x < 8) rs[threadIdx.x] = 0.f;
     return;
   }
-  const float* lr = logits + (long)row * ld;
+  const float* lr = logits + (long)row * ld + first;
   float mx = -INFINITY;
   for (int i = threadIdx.x * 4; i < n; i += 1024) {
     const f32x4_t q = *(const f32x4_t*)(lr + i);
@@ -81,23 +107,43 @@ __global__ __launch_bounds__(256) void policy_rows_kernel(const float* logits, l
   w = wave_sum(w);
   if ((threadIdx.x & 63) == 0) { red_s[wave] = s; red_w[wave] = w; }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const float S = red_s[0] + red_s[1] + red_s[2] + red_s[3];
-    const float W = red_w[0] + red_w[1] + red_w[2] + red_w[3];
-    const float logS = logf(S);
-    const float H = logS - W / S;                                       // −Σ p·logp, logp = (z − m) − log S
-    const float za = (tgt >= 0 && tgt < n) ? lr[tgt] * P.inv_t : NAN;    // a token outside the row: NaN, never a stray read
-    const float logp = za - m - logS;
-    const RowTerms t = row_terms(logp, adv[row], old_lp[row], ref_lp, row, P);
-    rs[RS_LOGP] = logp;
-    rs[RS_H] = H;
-    rs[RS_RATIO] = t.ratio;
-    rs[RS_LOSS] = t.pg - P.entropy_coef * H + P.kl_coef * t.kl;
-    rs[RS_CLIPPED] = t.active ? 0.f : 1.f;
-    rs[RS_M] = m;
-    rs[RS_LOGS] = logS;
-    rs[RS_G] = t.g;
+  if (threadIdx.x == 0)
+    finish_row(lr, n, tgt - first, m, red_s[0] + red_s[1] + red_s[2] + red_s[3], red_w[0] + red_w[1] + red_w[2] + red_w[3],
+               adv, old_lp, ref_lp, row, P, rs);
+}
+
+// n <= 256: one wave per row, four rows per workgroup, the lane's float4 stays in registers between the two passes. The
+// order of every sum is the workgroup kernel's on such a row (there waves 1–3 hold no column and add zeros).
+__global__ __launch_bounds__(256) void policy_rows_wave_kernel(const float* logits, long ld, int first, int n, int rows,
+                                                               const int64_t* targets, long ignore_index, const float* adv,
+                                                               const float* old_lp, const float* ref_lp, PolicyParams P,
+                                                               float* row_stats) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;            // uniform per wave, and the kernel has no barrier
+  const long tgt = targets[row];
+  float* rs = row_stats + (long)row * 8;
+  if (tgt == ignore_index) {
+    if (lane < 8) rs[lane] = 0.f;
+    return;
   }
+  const float* lr = logits + (long)row * ld + first;
+  const bool on = lane * 4 < n;       // n % 4 == 0: a lane's four columns are inside together
+  f32x4_t q = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  if (on) q = *(const f32x4_t*)(lr + lane * 4);
+  const float m = wave_max(fmaxf(fmaxf(-INFINITY, fmaxf(q[0], q[1])), fmaxf(q[2], q[3]))) * P.inv_t;
+  float s = 0.f, w = 0.f;
+  if (on) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = q[e] * P.inv_t - m;
+      const float ex = expf(d);
+      s += ex;
+      w += ex * d;
+    }
+  }
+  s = wave_sum(s);
+  w = wave_sum(w);
+  if (lane == 0) finish_row(lr, n, tgt - first, m, s + 0.f + 0.f + 0.f, w + 0.f + 0.f + 0.f, adv, old_lp, ref_lp, row, P, rs);
 }
 
 // the 8 step statistics: means over valid rows (single workgroup, fixed summation order → deterministic)
@@ -148,10 +194,12 @@ __device__ __forceinline__ u32x4_t pack8(const float* v) {
 }
 
 // dlogits_i = [ g·(δ_ia − p_i) + entropy_coef·p_i·(logp_i + H) ] / (T · n_valid): one read of the row; logp_i by arithmetic
-// (z_i − m − log S), so an underflowed p_i gives 0·finite = 0, never 0·(−inf)
+// (z_i − m − log S), so an underflowed p_i gives 0·finite = 0, never 0·(−inf). The policy is over columns [first, first +
+// count): the 8-column groups outside it (first and count are multiples of 8) are written as zeros and never read.
 __global__ __launch_bounds__(256) void policy_backward_kernel(const float* logits, long ld, int n, const int64_t* targets,
                                                               long ignore_index, const float* row_stats, const float* stats,
-                                                              float inv_t, float entropy_coef, uint16_t* dlogits, long ldd) {
+                                                              float inv_t, float entropy_coef, uint16_t* dlogits, long ldd,
+                                                              int first, int count) {
   const int row = blockIdx.x;
   const long tgt = targets[row];
   uint16_t* dr = dlogits + (long)row * ldd;
@@ -165,6 +213,10 @@ __global__ __launch_bounds__(256) void policy_backward_kernel(const float* logit
   const float off = rs[RS_M] + rs[RS_LOGS];
   const float scale = inv_t / stats[1];                 // 1 / (T · n_valid)
   for (int i = threadIdx.x * 8; i < n; i += 2048) {
+    if (i < first || i - first >= count) {
+      *(u32x4_t*)(dr + i) = (u32x4_t){0u, 0u, 0u, 0u};
+      continue;
+    }
     const f32x4_t a = *(const f32x4_t*)(lr + i), b = *(const f32x4_t*)(lr + i + 4);
     float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 #pragma unroll
@@ -180,33 +232,69 @@ __global__ __launch_bounds__(256) void policy_backward_kernel(const float* logit
 }  // namespace bl_policy_impl
 using namespace bl_policy_impl;
 
-extern "C" int bl_policy_loss_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
-                                  int64_t ignore_index, const float* advantages, const float* old_logprob,
-                                  const float* ref_logprob, float temperature, float clip_low, float clip_high,
-                                  float entropy_coef, float kl_coef, float* row_stats, float* stats, void* stream) {
+static bool bad_range(int32_t n, int32_t first, int32_t count) {
+  return n <= 0 || (n % 8) || first < 0 || count <= 0 || (first % 8) || (count % 8) || (int64_t)first + count > n;
+}
+
+// by_wave: a range of at most 256 columns goes to the wave-per-row kernel. The unranged entry point never asks for it.
+static int policy_forward(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                          int64_t ignore_index, const float* advantages, const float* old_logprob, const float* ref_logprob,
+                          float temperature, float clip_low, float clip_high, float entropy_coef, float kl_coef,
+                          float* row_stats, float* stats, int32_t vocab_first, int32_t vocab_count, bool by_wave, void* stream) {
   if (!logits || !targets || !advantages || !old_logprob || !row_stats || !stats) return BL_E_ARG;
   if (!(temperature > 0.f) || !(clip_low >= 0.f) || !(clip_high >= 0.f)) return BL_E_ARG;
-  if (rows <= 0 || n <= 0 || (n % 8) || (ld % 4) || ld < n) return BL_E_SHAPE;
+  if (rows <= 0 || bad_range(n, vocab_first, vocab_count) || (ld % 4) || ld < n) return BL_E_SHAPE;
   if (!bl_aligned16(logits)) return BL_E_ALIGN;
   const PolicyParams P = {1.0f / temperature, clip_low, clip_high, entropy_coef, ref_logprob ? kl_coef : 0.f};
-  hipLaunchKernelGGL(policy_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, n, targets,
-                     (long)ignore_index, advantages, old_logprob, ref_logprob, P, row_stats);
+  if (by_wave && vocab_count <= 256)
+    hipLaunchKernelGGL(policy_rows_wave_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, (long)ld,
+                       vocab_first, vocab_count, rows, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P,
+                       row_stats);
+  else
+    hipLaunchKernelGGL(policy_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, vocab_first,
+                       vocab_count, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P, row_stats);
   hipLaunchKernelGGL(policy_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, row_stats, targets, (long)ignore_index,
                      advantages, old_logprob, ref_logprob, P, rows, stats);
   BL_CHECK_LAUNCH();
   return BL_OK;
 }
 
+extern "C" int bl_policy_loss_range_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                        int64_t ignore_index, const float* advantages, const float* old_logprob,
+                                        const float* ref_logprob, float temperature, float clip_low, float clip_high,
+                                        float entropy_coef, float kl_coef, float* row_stats, float* stats,
+                                        int32_t vocab_first, int32_t vocab_count, void* stream) {
+  return policy_forward(logits, ld, rows, n, targets, ignore_index, advantages, old_logprob, ref_logprob, temperature, clip_low,
+                        clip_high, entropy_coef, kl_coef, row_stats, stats, vocab_first, vocab_count, true, stream);
+}
+
+extern "C" int bl_policy_loss_backward_range_f32(const float* logits, int64_t ld, int32_t rows, int32_t n,
+                                                 const int64_t* targets, int64_t ignore_index, const float* row_stats,
+                                                 const float* stats, float temperature, float entropy_coef, bl_bf16* dlogits,
+                                                 int64_t ldd, int32_t vocab_first, int32_t vocab_count, void* stream) {
+  if (!logits || !targets || !row_stats || !stats || !dlogits) return BL_E_ARG;
+  if (!(temperature > 0.f)) return BL_E_ARG;
+  if (rows <= 0 || bad_range(n, vocab_first, vocab_count) || (ld % 4) || (ldd % 8) || ld < n || ldd < n) return BL_E_SHAPE;
+  if (!bl_aligned16(logits) || !bl_aligned16(dlogits)) return BL_E_ALIGN;
+  hipLaunchKernelGGL(policy_backward_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, n, targets,
+                     (long)ignore_index, row_stats, stats, 1.0f / temperature, entropy_coef, dlogits, (long)ldd, vocab_first,
+                     vocab_count);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
+extern "C" int bl_policy_loss_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                  int64_t ignore_index, const float* advantages, const float* old_logprob,
+                                  const float* ref_logprob, float temperature, float clip_low, float clip_high,
+                                  float entropy_coef, float kl_coef, float* row_stats, float* stats, void* stream) {
+  return policy_forward(logits, ld, rows, n, targets, ignore_index, advantages, old_logprob, ref_logprob, temperature, clip_low,
+                        clip_high, entropy_coef, kl_coef, row_stats, stats, 0, n, false, stream);
+}
+
 extern "C" int bl_policy_loss_backward_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
                                            int64_t ignore_index, const float* row_stats, const float* stats,
                                            float temperature, float entropy_coef, bl_bf16* dlogits, int64_t ldd,
                                            void* stream) {
-  if (!logits || !targets || !row_stats || !stats || !dlogits) return BL_E_ARG;
-  if (!(temperature > 0.f)) return BL_E_ARG;
-  if (rows <= 0 || n <= 0 || (n % 8) || (ld % 4) || (ldd % 8) || ld < n || ldd < n) return BL_E_SHAPE;
-  if (!bl_aligned16(logits) || !bl_aligned16(dlogits)) return BL_E_ALIGN;
-  hipLaunchKernelGGL(policy_backward_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, n, targets,
-                     (long)ignore_index, row_stats, stats, 1.0f / temperature, entropy_coef, dlogits, (long)ldd);
-  BL_CHECK_LAUNCH();
-  return BL_OK;
+  return bl_policy_loss_backward_range_f32(logits, ld, rows, n, targets, ignore_index, row_stats, stats, temperature,
+                                           entropy_coef, dlogits, ldd, 0, n, stream);
 }

@@ -18,6 +18,11 @@
 //      (scoring: no draw and no second walk — during the first walk the lane that owns the given token keeps its kept
 //      weight and the lanes inside the requested range store theirs)
 // Histogram bins are 64-bit LDS atomics; one wave turns a histogram into the selected bin.
+//
+// bl_sample_range_f32 / bl_score_range_f32 restrict the policy to the columns [vocab_first, vocab_first + vocab_count) of
+// every row: the same kernel with a column base. The LDS image holds vocab_count entries read from logits + row·ld +
+// vocab_first, ids are reported as vocab_first + i, the scored token and the report range are taken relative to the
+// base, and no column outside the range is loaded. The unranged entry points are the base-0, count-n case.
 #include "bl_common.h"
 
 namespace {
@@ -178,11 +183,12 @@ __device__ __forceinline__ uint32_t radix_select(const uint32_t* img, int n, u64
 
 // SCORE = false: the draw (seed, step → ids, wt). SCORE = true: the score of tokens[row] (→ wt, and range_wt[row][j] = the
 // kept weight of token range_first + j when range_wt is given); seed, step and ids are unused there, and the reverse.
+// The row is the n columns from column `base` on; range_first is relative to base, tokens and ids are not.
 template <bool SCORE>
 __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, long ld, int n, const float* temperature,
                                                           const int* top_k, const float* top_p, const int64_t* seed,
                                                           uint32_t step, int64_t* ids, const int64_t* tokens, int64_t* wt,
-                                                          int range_first, int range_count, int32_t* range_wt) {
+                                                          int range_first, int range_count, int32_t* range_wt, int base) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   u64* hist = (u64*)smem;                                         // kHistSlots
   uint32_t* img = (uint32_t*)(smem + kFixedBytes);                // n: keys, then weights
@@ -192,7 +198,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, l
   __shared__ int s_arg[kWaves];
 
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* src = logits + (long)row * ld;
+  const float* src = logits + (long)row * ld + base;
   const float T = temperature[row];
   const float P = top_p[row];
   const int K = top_k[row];
@@ -223,10 +229,10 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, l
   for (int w = 1; w < kWaves; ++w)
     if (s_best[w] > best || (s_best[w] == best && s_arg[w] < bi)) { best = s_best[w]; bi = s_arg[w]; }
 
-  int64_t tok = -1;                                               // SCORE: the token to score; outside [0, n) it owns no lane
+  int64_t tok = -1;                                               // SCORE: the token to score, relative to base; outside [0, n) it owns no lane
   int32_t* rw = nullptr;                                          // SCORE: this row of range_wt
   if constexpr (SCORE) {
-    tok = tokens[row];
+    tok = tokens[row] - base;                                     // a token below the base is negative: no lane either
     if (range_wt) rw = range_wt + (long)row * range_count;
   }
 
@@ -236,7 +242,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, l
       if (rw)
         for (int j = tid; j < range_count; j += kThreads) rw[j] = range_first + j == bi;
     } else {
-      if (tid == 0) { ids[row] = (int64_t)bi; wt[2 * row] = 1; wt[2 * row + 1] = 1; }
+      if (tid == 0) { ids[row] = (int64_t)base + bi; wt[2 * row] = 1; wt[2 * row + 1] = 1; }
     }
     return;
   }
@@ -335,7 +341,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, l
     const u64 past = __ballot(run + incl > target);
     if (past) {
       if (lane == __ffsll((long long)past) - 1) {
-        ids[row] = (int64_t)(i0 + lane);
+        ids[row] = (int64_t)base + (i0 + lane);
         wt[2 * row] = (int64_t)w;
         wt[2 * row + 1] = (int64_t)total_kept;
       }
@@ -360,37 +366,60 @@ static int allow_full_lds() {
   return BL_OK;
 }
 
-extern "C" int bl_sample_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
-                             const int32_t* top_k, const float* top_p, const int64_t* seed, int32_t step, int64_t* ids,
-                             int64_t* wt, void* stream) {
+// n here is the number of columns a row has in memory; the policy is columns [vfirst, vfirst + vcount) of it
+static bool bad_vocab(int32_t n, int64_t ld, int32_t vfirst, int32_t vcount) {
+  return n <= 0 || (ld % 4) || ld < n || vfirst < 0 || vcount <= 0 || (vfirst % 4) || (vcount % 4) ||
+         (int64_t)vfirst + vcount > n || vcount > kMaxN;
+}
+
+extern "C" int bl_sample_range_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
+                                   const int32_t* top_k, const float* top_p, const int64_t* seed, int32_t step,
+                                   int64_t* ids, int64_t* wt, int32_t vocab_first, int32_t vocab_count, void* stream) {
   if (!logits || !temperature || !top_k || !top_p || !seed || !ids || !wt) return BL_E_ARG;
-  if (rows <= 0 || n <= 0 || (n % 4) || (ld % 4) || ld < n || n > kMaxN || step < 0) return BL_E_SHAPE;
+  if (rows <= 0 || bad_vocab(n, ld, vocab_first, vocab_count) || step < 0) return BL_E_SHAPE;
   if (!bl_aligned16(logits) || (((uintptr_t)seed | (uintptr_t)ids | (uintptr_t)wt) & 7) ||
       (((uintptr_t)temperature | (uintptr_t)top_k | (uintptr_t)top_p) & 3))
     return BL_E_ALIGN;
   if (const int rc = allow_full_lds<false>()) return rc;
-  const size_t lds = (size_t)kFixedBytes + (size_t)n * 4;
-  hipLaunchKernelGGL(sample_kernel<false>, dim3(rows), dim3(kThreads), lds, (hipStream_t)stream, logits, (long)ld, n,
-                     temperature, top_k, top_p, seed, (uint32_t)step, ids, (const int64_t*)nullptr, wt, 0, 0,
-                     (int32_t*)nullptr);
+  const size_t lds = (size_t)kFixedBytes + (size_t)vocab_count * 4;
+  hipLaunchKernelGGL(sample_kernel<false>, dim3(rows), dim3(kThreads), lds, (hipStream_t)stream, logits, (long)ld,
+                     vocab_count, temperature, top_k, top_p, seed, (uint32_t)step, ids, (const int64_t*)nullptr, wt, 0, 0,
+                     (int32_t*)nullptr, vocab_first);
   BL_CHECK_LAUNCH();
   return BL_OK;
+}
+
+extern "C" int bl_score_range_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
+                                  const int32_t* top_k, const float* top_p, const int64_t* tokens, int64_t* wt,
+                                  int32_t range_first, int32_t range_count, int32_t* range_wt, int32_t vocab_first,
+                                  int32_t vocab_count, void* stream) {
+  if (!logits || !temperature || !top_k || !top_p || !tokens || !wt || (range_count > 0 && !range_wt)) return BL_E_ARG;
+  if (rows <= 0 || bad_vocab(n, ld, vocab_first, vocab_count)) return BL_E_SHAPE;
+  if (range_count < 0 || (range_count > 0 && (range_first < vocab_first ||
+                                              (int64_t)range_first + range_count > (int64_t)vocab_first + vocab_count)))
+    return BL_E_SHAPE;
+  if (!bl_aligned16(logits) || (((uintptr_t)tokens | (uintptr_t)wt) & 7) ||
+      (((uintptr_t)temperature | (uintptr_t)top_k | (uintptr_t)top_p) & 3) || (range_count > 0 && ((uintptr_t)range_wt & 3)))
+    return BL_E_ALIGN;
+  if (const int rc = allow_full_lds<true>()) return rc;
+  const size_t lds = (size_t)kFixedBytes + (size_t)vocab_count * 4;
+  hipLaunchKernelGGL(sample_kernel<true>, dim3(rows), dim3(kThreads), lds, (hipStream_t)stream, logits, (long)ld,
+                     vocab_count, temperature, top_k, top_p, (const int64_t*)nullptr, 0u, (int64_t*)nullptr, tokens, wt,
+                     range_count > 0 ? range_first - vocab_first : 0, range_count,
+                     range_count > 0 ? range_wt : (int32_t*)nullptr, vocab_first);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
+extern "C" int bl_sample_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
+                             const int32_t* top_k, const float* top_p, const int64_t* seed, int32_t step, int64_t* ids,
+                             int64_t* wt, void* stream) {
+  return bl_sample_range_f32(logits, ld, rows, n, temperature, top_k, top_p, seed, step, ids, wt, 0, n, stream);
 }
 
 extern "C" int bl_score_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
                             const int32_t* top_k, const float* top_p, const int64_t* tokens, int64_t* wt,
                             int32_t range_first, int32_t range_count, int32_t* range_wt, void* stream) {
-  if (!logits || !temperature || !top_k || !top_p || !tokens || !wt || (range_count > 0 && !range_wt)) return BL_E_ARG;
-  if (rows <= 0 || n <= 0 || (n % 4) || (ld % 4) || ld < n || n > kMaxN) return BL_E_SHAPE;
-  if (range_count < 0 || (range_count > 0 && (range_first < 0 || (int64_t)range_first + range_count > n))) return BL_E_SHAPE;
-  if (!bl_aligned16(logits) || (((uintptr_t)tokens | (uintptr_t)wt) & 7) ||
-      (((uintptr_t)temperature | (uintptr_t)top_k | (uintptr_t)top_p) & 3) || (range_count > 0 && ((uintptr_t)range_wt & 3)))
-    return BL_E_ALIGN;
-  if (const int rc = allow_full_lds<true>()) return rc;
-  const size_t lds = (size_t)kFixedBytes + (size_t)n * 4;
-  hipLaunchKernelGGL(sample_kernel<true>, dim3(rows), dim3(kThreads), lds, (hipStream_t)stream, logits, (long)ld, n,
-                     temperature, top_k, top_p, (const int64_t*)nullptr, 0u, (int64_t*)nullptr, tokens, wt, range_first,
-                     range_count, range_count > 0 ? range_wt : (int32_t*)nullptr);
-  BL_CHECK_LAUNCH();
-  return BL_OK;
+  return bl_score_range_f32(logits, ld, rows, n, temperature, top_k, top_p, tokens, wt, range_first, range_count, range_wt,
+                            0, n, stream);
 }

@@ -43,7 +43,7 @@ class OpenVLAEngine:
     def __init__(self, weights: VLAWeights, batch: int, prompt_len: int, n_new: int = 7, all_rows: bool = False,
                  use_mask: bool = False, splitk: bool = False, fp8: bool = False, padded: bool = False,
                  vision_only: bool = False, text_only: bool = False, sample: bool = False, score: bool = False,
-                 score_range: Optional[Tuple[int, int]] = None):
+                 score_range: Optional[Tuple[int, int]] = None, vocab_range: Optional[Tuple[int, int]] = None):
         """all_rows=True builds the training/eval-style forward instead of generation: logits for every position
         (`logits_all` [B*S, vocab] fp32) and no decode steps. use_mask=True threads a [B, S] uint8 key-padding mask
         (`key_mask`, 1 = attend) through the Llama attention (modeling_prismatic.py:387-390). splitk=True lets
@@ -70,7 +70,11 @@ class OpenVLAEngine:
         and writes their weight pairs to `gen_wt[t]` under the settings of `set_sampling` (no seed); nothing writes
         `gen_ids`, so decode step t consumes the forced token t-1 and every step's logits are the cached decode path's,
         the ones a sample=True engine saw when it drew those tokens. score_range=(first, count) also keeps the kept
-        weights of tokens first … first + count - 1 of every step in `gen_range_wt` [n_new, B, count] int32."""
+        weights of tokens first … first + count - 1 of every step in `gen_range_wt` [n_new, B, count] int32.
+        vocab_range=(first, count), with sample=True or score=True, restricts the policy to that token range (the 256
+        action bins): the plan ends in bl_sample_range_f32 / bl_score_range_f32, the softmax, top-k, top-p, the draw and a
+        greedy sequence's argmax are taken over the range alone, and a score_range must lie inside it. Fixed per engine,
+        like score_range."""
         self.w, self.dims = weights, weights.dims
         self.vision_only, self.text_only = vision_only, text_only
         if text_only and (vision_only or padded or fp8):
@@ -86,6 +90,14 @@ class OpenVLAEngine:
             raise ValueError("sample=True / score=True belong to a generation plan")
         if score_range is not None and not score:
             raise ValueError("score_range goes with score=True")
+        self.vocab_range = None
+        if vocab_range is not None:
+            if not (sample or score):
+                raise ValueError("vocab_range goes with sample=True or score=True")
+            first, count = int(vocab_range[0]), int(vocab_range[1])
+            if first < 0 or count < 1 or first + count > self.dims.vocab or first % 4 or count % 4:
+                raise ValueError(f"vocab_range {vocab_range}: multiples of 4 inside the vocabulary [0, {self.dims.vocab})")
+            self.vocab_range = (first, count)
         use_mask = use_mask or padded
         if padded and (all_rows or fp8):
             raise ValueError("padded generation is built for the bf16 generation plan")
@@ -121,6 +133,8 @@ class OpenVLAEngine:
                 first, count = int(score_range[0]), int(score_range[1])
                 if first < 0 or count < 1 or first + count > d.vocab:
                     raise ValueError(f"score_range {score_range} leaves the vocabulary [0, {d.vocab})")
+                if self.vocab_range is not None and (first < self.vocab_range[0] or first + count > sum(self.vocab_range)):
+                    raise ValueError(f"score_range {score_range} leaves vocab_range {self.vocab_range}")
                 self.score_range = (first, count)
                 self.gen_range_wt = z(n_new, B, count, dtype=torch.int32)
         # vision buffers (sized for the larger tower, shared by both: they run back to back on one stream)
@@ -328,10 +342,11 @@ class OpenVLAEngine:
                     self._g(hdd, w.lm_head, logits, EPI_F32_BF16R, run=False)]
         if self.sample:
             plan.append(ops.sample(logits, self.samp_temperature[b0:b1], self.samp_top_k[b0:b1], self.samp_top_p[b0:b1],
-                                   self.samp_seed[b0:b1], t, ids, self.gen_wt[t][b0:b1], run=False))
+                                   self.samp_seed[b0:b1], t, ids, self.gen_wt[t][b0:b1], run=False, vocab=self.vocab_range))
         elif self.score_mode:
             plan.append(ops.score(logits, self.samp_temperature[b0:b1], self.samp_top_k[b0:b1], self.samp_top_p[b0:b1], ids,
-                                  self.gen_wt[t][b0:b1], *self._score_range_args(t, b0, b1), run=False))
+                                  self.gen_wt[t][b0:b1], *self._score_range_args(t, b0, b1), run=False,
+                                  vocab=self.vocab_range))
         else:
             plan.append(ops.argmax(logits, ids, run=False))
         return plan

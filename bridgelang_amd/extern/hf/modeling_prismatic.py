@@ -209,16 +209,21 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         return eng
 
     def engine(self, batch: int, prompt_len: int, n_new: int = 7, padded: bool = False, cached: bool = False,
-               sample: bool = False, score: bool = False, score_range: Optional[Tuple[int, int]] = None) -> OpenVLAEngine:
+               sample: bool = False, score: bool = False, score_range: Optional[Tuple[int, int]] = None,
+               vocab_range: Optional[Tuple[int, int]] = None) -> OpenVLAEngine:
         """`cached=True`: the engine behind a `forward(..., use_cache=True)` KV-cache handle — keyed apart from the engines
         `predict_action` / `generate` use, so an interleaved action prediction of the same shape does not invalidate the
         caller's cache (each kind has its own LRU slot; a second cached prefill of the same shape still does).
-        `score=True` (with `score_range`) is a kind of its own again: the engines that score given tokens."""
+        `score=True` (with `score_range`) is a kind of its own again: the engines that score given tokens. `vocab_range`
+        (sample=True / score=True: the restricted policy) is fixed per engine, so it is part of the key as well."""
         fp8 = bool(getattr(self, "fp8", False))       # `model.fp8 = True`: W8A8 e4m3 Llama prefill projections (extension)
-        key = (batch, prompt_len, n_new, fp8, padded, cached, sample) + (("score", score_range) if score else ())
+        if vocab_range is not None:
+            vocab_range = (int(vocab_range[0]), int(vocab_range[1]))
+        key = (batch, prompt_len, n_new, fp8, padded, cached, sample) + (("score", score_range) if score else ()) + \
+            (("vocab", vocab_range) if vocab_range is not None else ())
         return self._lru(self._engines, key,
                          lambda: OpenVLAEngine(self.weights, batch, prompt_len, n_new=n_new, fp8=fp8 and not padded, padded=padded,
-                                               sample=sample, score=score, score_range=score_range))
+                                               sample=sample, score=score, score_range=score_range, vocab_range=vocab_range))
 
     # ---- forward: the reference's three branches (modeling_prismatic.py:322-415) ----
     cache_new_tokens = 7       # tokens a `forward(..., use_cache=True)` KV cache is sized for (prefill token + 6 cached steps)
@@ -301,7 +306,8 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
     def generate(self, input_ids: torch.LongTensor, max_new_tokens: int = 7, pixel_values: Optional[torch.Tensor] = None,
                  attention_mask: Optional[torch.Tensor] = None, do_sample: bool = False, use_cache: bool = True,
                  sampling: Optional[SamplingParams] = None, return_weights: bool = False,
-                 forced_ids: Optional[torch.Tensor] = None, score_range: Optional[Tuple[int, int]] = None, **_: Any):
+                 forced_ids: Optional[torch.Tensor] = None, score_range: Optional[Tuple[int, int]] = None,
+                 vocab_range: Optional[Tuple[int, int]] = None, **_: Any):
         """Greedy decoding, returns [B, L + max_new_tokens] like GenerationMixin (prompt ‖ new tokens). `use_cache` is
         accepted and ignored: the KV cache is always used (use_cache=False in the fork's demo re-runs the vision towers
         7 times, run_openvla_demo.py:43 — same result, 7× the work). A batch whose attention_mask has zeros is taken as
@@ -314,7 +320,10 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         these tokens and the result is (prompt ‖ forced_ids, wt [B, max_new_tokens, 2]) — every forced token's kept weight
         and the kept total under `sampling` (None: the unwarped distribution, temperature 1), the pair the sampler reports
         when it draws that token (`sampling.score_rows`; weight 0 = outside the support). `score_range=(first, count)`
-        appends range_wt int32 [B, max_new_tokens, count]: the kept weights of that token range at every step."""
+        appends range_wt int32 [B, max_new_tokens, count]: the kept weights of that token range at every step.
+        `vocab_range=(first, count)` restricts the policy to that token range (`sampling.py`, `vocab=`): draws, scores and
+        weights are under the softmax of those logits alone, a forced token outside it scores weight 0, and without
+        `sampling=` the call is constrained greedy decoding (temperature 0 through the sampling engine)."""
         if do_sample and sampling is None:
             raise NotImplementedError("do_sample=True draws from torch's global device RNG stream, which the HIP path does "
                                       "not reproduce: pass sampling=SamplingParams(temperature=, top_k=, top_p=, seed=) instead")
@@ -327,7 +336,7 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         if forced_ids is not None:
             forced = torch.as_tensor(forced_ids).to(self.device, torch.int64)
             padded = attention_mask is not None and not bool(attention_mask.bool().all())
-            eng = self.engine(B, L, max_new_tokens, padded=padded, score=True, score_range=score_range)
+            eng = self.engine(B, L, max_new_tokens, padded=padded, score=True, score_range=score_range, vocab_range=vocab_range)
             eng.set_sampling(sampling if sampling is not None else SamplingParams())
             if padded:
                 eng.set_forced_ids(forced)
@@ -339,16 +348,18 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             return out if score_range is None else out + (eng.gen_range_wt.permute(1, 0, 2).clone(),)
         if score_range is not None:
             raise ValueError("score_range goes with forced_ids=")
+        if vocab_range is not None and sampling is None:
+            sampling = SamplingParams(temperature=0.0, seed=0)
         sample = sampling is not None
         if attention_mask is not None and not bool(attention_mask.bool().all()):
-            eng = self.engine(B, L, max_new_tokens, padded=True, sample=sample)
+            eng = self.engine(B, L, max_new_tokens, padded=True, sample=sample, vocab_range=vocab_range)
             if sample:
                 eng.set_sampling(sampling)
             eng.set_padded_inputs(ids, pv, attention_mask)
             eng.run_eager()
             new = eng.gen_ids.t()
         else:
-            eng = self.engine(B, L, max_new_tokens, sample=sample)
+            eng = self.engine(B, L, max_new_tokens, sample=sample, vocab_range=vocab_range)
             new = eng.generate(ids, pv, sampling)
         out = torch.cat([ids, new], dim=1)
         return (out, eng.gen_wt.permute(1, 0, 2).clone()) if return_weights else out
@@ -366,12 +377,22 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         # de-tokenisation vocabulary: the padded "multiple of 64" rows are not action tokens (reference :503-504)
         self.vocab_size = self.dims.vocab - config.pad_to_multiple_of
 
+    def action_token_range(self) -> Tuple[int, int]:
+        """(first, count) of the token ids that carry an action bin: vocab_size - n_action_bins … vocab_size - 1. The range
+        of the restricted policy (`action_tokens_only=True`; `PolicyLossConfig.token_range`, `rl.policy_batch`)."""
+        n_bins = int(self.config.n_action_bins)
+        return int(self.vocab_size) - n_bins, n_bins
+
     def predict_action(self, input_ids: Optional[torch.LongTensor] = None, unnorm_key: Union[str, Sequence[Optional[str]], None] = None,
-                       **kwargs: Any) -> np.ndarray:
+                       action_tokens_only: bool = False, **kwargs: Any) -> np.ndarray:
         """ids → 7 greedy action tokens → bin centres → un-normalised 7-DoF action (reference :506-536). `unnorm_key` may
         be a list with one key per sequence (extension: a server batch that mixes datasets of one action dimension);
-        the result is then always [B, n]."""
+        the result is then always [B, n]. `action_tokens_only=True` decodes under the policy restricted to
+        `action_token_range()`: with `sampling=` every draw is an action token, without it the call is constrained greedy
+        decoding (the argmax over the action tokens)."""
         input_ids = input_ids.to(self.device)
+        if action_tokens_only:
+            kwargs["vocab_range"] = self.action_token_range()
         keys = list(unnorm_key) if isinstance(unnorm_key, (list, tuple)) else None
         if keys is not None:
             if len(keys) != input_ids.shape[0] or len({self.get_action_dim(k) for k in keys}) != 1:
@@ -413,13 +434,16 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
 
     def sample_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor,
                        unnorm_key: Union[str, Sequence[Optional[str]], None] = None, sampling: Optional[SamplingParams] = None,
-                       num_samples: int = 1, attention_mask: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                       num_samples: int = 1, attention_mask: Optional[torch.Tensor] = None,
+                       action_tokens_only: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """`num_samples` sampled actions per sequence with their log-probabilities (RL rollouts, best-of-N, uncertainty):
         → (actions [B, num_samples, n], token_ids int64 [B, num_samples, n], logprobs fp64 [B, num_samples, n]). The batch
         is repeated `num_samples` times (several copies per engine run while the run stays within 16 sequences); copy j of a sequence with seed s draws with
         seed s + 0x9E3779B97F4A7C15·j mod 2^64 (`sampling.derive_seed`), so copy j equals that one call. logprobs[b, j, t] =
         log(w / total) of step t's weight pair: the token's log-probability under the warped (temperature / top-k /
-        top-p) distribution."""
+        top-p) distribution. `action_tokens_only=True` draws from the policy restricted to `action_token_range()`: every
+        token is an action token and its log-probability is the one under that restricted policy — what a learner with
+        `PolicyLossConfig(token_range=model.action_token_range())` trains against."""
         if sampling is None:
             sampling = SamplingParams()
         if num_samples < 1:
@@ -436,7 +460,7 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             a, tok, wt = self.predict_action(input_ids.repeat(c, 1), keys * c if keys is not None else unnorm_key,
                                              pixel_values=pixel_values.repeat(c, 1, 1, 1),
                                              attention_mask=None if attention_mask is None else attention_mask.repeat(c, 1),
-                                             sampling=sp, return_weights=True)
+                                             sampling=sp, return_weights=True, action_tokens_only=action_tokens_only)
             acts.append(np.asarray(a).reshape(c, B, -1))
             toks.append(tok.reshape(c, B, -1))
             lps.append(logprob(wt).reshape(c, B, -1))
@@ -444,7 +468,8 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
 
     def score_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor, token_ids=None, actions=None,
                       unnorm_key: Optional[str] = None, sampling: Optional[SamplingParams] = None,
-                      attention_mask: Optional[torch.Tensor] = None, return_bins: bool = False):
+                      attention_mask: Optional[torch.Tensor] = None, return_bins: bool = False,
+                      action_tokens_only: bool = False):
         """Log-probabilities of GIVEN actions under the policy `sample_actions` draws from (a PPO / GRPO learner's
         log π(a | s), a reranker's score of a planner's proposal): exactly one of `token_ids` (int64) and `actions`
         (tokenised by `token_ids_from_actions` with `unnorm_key`), shaped [B, n] or [B, K, n] with K candidates per
@@ -454,7 +479,9 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         given tokens, so every step sees the logits the sampler saw. Candidates are batched like `sample_actions`' copies
         (16 // B per engine run). `return_bins=True` → (logprobs, wt int64 [B, K, n, 2], bin_wt int32 [B, K, n,
         n_action_bins]): the integer weight pairs and the kept weight of every action token, bin_wt[..., j] for token
-        vocab_size - n_action_bins + j, so bin_wt / wt[..., 1:] are exact per-bin probabilities (`sampling.range_entropy`)."""
+        vocab_size - n_action_bins + j, so bin_wt / wt[..., 1:] are exact per-bin probabilities (`sampling.range_entropy`).
+        `action_tokens_only=True` scores under the policy restricted to `action_token_range()`, as `sample_actions` draws
+        with the same flag: a token outside the range scores -inf, and the bin weights then sum to the kept total exactly."""
         if (token_ids is None) == (actions is None):
             raise ValueError("score_actions: give exactly one of token_ids= and actions=")
         if token_ids is None:
@@ -483,7 +510,7 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             forced = torch.from_numpy(np.ascontiguousarray(tok[:, j0:j0 + c].transpose(1, 0, 2)).reshape(c * B, n))
             out = self.generate(ids.repeat(c, 1), n, pixel_values=pixel_values.repeat(c, 1, 1, 1),
                                 attention_mask=None if m is None else m.repeat(c, 1), sampling=sp, forced_ids=forced,
-                                score_range=rng)
+                                score_range=rng, vocab_range=self.action_token_range() if action_tokens_only else None)
             wts.append(out[1].cpu().numpy().reshape(c, B, n, 2))
             if return_bins:
                 bins.append(out[2].cpu().numpy().reshape(c, B, n, n_bins))

@@ -465,10 +465,11 @@ def argmax(logits: torch.Tensor, out: torch.Tensor, run: bool = True) -> Op:
 
 
 def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
-           step: int, ids: torch.Tensor, wt: torch.Tensor, run: bool = True) -> Op:
+           step: int, ids: torch.Tensor, wt: torch.Tensor, run: bool = True, vocab: Optional[Tuple[int, int]] = None) -> Op:
     """One seeded draw per row of fp32 logits [rows, n] (bl_sample_f32; specification: sampling.sample_rows). Per-row
     DEVICE settings: temperature fp32 (0 = greedy), top_k int32 (0 = off), top_p fp32 (>= 1 = off), seed int64; `step` is
-    the Philox counter. Writes ids int64 [rows] and wt int64 [rows, 2] = (weight of the token, kept total)."""
+    the Philox counter. Writes ids int64 [rows] and wt int64 [rows, 2] = (weight of the token, kept total).
+    vocab=(first, count) restricts the policy to that token range (bl_sample_range_f32)."""
     lib = _lib.load()
     rows, n = logits.shape
     want = ((logits, torch.float32, (rows, n)), (temperature, torch.float32, (rows,)), (top_k, torch.int32, (rows,)),
@@ -479,21 +480,27 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
                             "[rows] (contiguous); wt int64 [rows, 2]; all on the device")
     if not wt.is_contiguous():
         raise TypeError("sample: wt must be contiguous")
-    op = Op("bl_sample_f32", lib.bl_sample_f32,
-            (logits.data_ptr(), _rows(logits, "logits"), rows, n, temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
-             seed.data_ptr(), int(step), ids.data_ptr(), wt.data_ptr()), (logits, temperature, top_k, top_p, seed, ids, wt))
+    args = (logits.data_ptr(), _rows(logits, "logits"), rows, n, temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
+            seed.data_ptr(), int(step), ids.data_ptr(), wt.data_ptr())
+    keep = (logits, temperature, top_k, top_p, seed, ids, wt)
+    if vocab is None:
+        op = Op("bl_sample_f32", lib.bl_sample_f32, args, keep)
+    else:
+        op = Op("bl_sample_range_f32", lib.bl_sample_range_f32, args + (int(vocab[0]), int(vocab[1])), keep)
     if run:
         op.run()
     return op
 
 
 def score(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, tokens: torch.Tensor,
-          wt: torch.Tensor, range_first: int = 0, range_wt: Optional[torch.Tensor] = None, run: bool = True) -> Op:
+          wt: torch.Tensor, range_first: int = 0, range_wt: Optional[torch.Tensor] = None, run: bool = True,
+          vocab: Optional[Tuple[int, int]] = None) -> Op:
     """The score of a given token per row of fp32 logits [rows, n] under `sample`'s warped distribution (bl_score_f32;
     specification: sampling.score_rows). Settings as `sample`, without a seed; tokens int64 [rows] on the DEVICE (each in
     [0, n): the caller's to guarantee — a token outside scores weight 0). Writes wt int64 [rows, 2] = (kept weight of the
     token, kept total) and, given range_wt int32 [rows, count], the kept weights of tokens range_first … range_first +
-    count - 1."""
+    count - 1. vocab=(first, count) restricts the policy to that token range (bl_score_range_f32); range_first keeps its
+    full-vocabulary numbering and the report range must lie inside `vocab`."""
     lib = _lib.load()
     rows, n = logits.shape
     want = ((logits, torch.float32, (rows, n)), (temperature, torch.float32, (rows,)), (top_k, torch.int32, (rows,)),
@@ -511,9 +518,12 @@ def score(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, 
             raise TypeError("score: range_wt int32 [rows, count], contiguous, on the device")
         count = range_wt.shape[1]
     keep = (logits, temperature, top_k, top_p, tokens, wt) + ((range_wt,) if count else ())
-    op = Op("bl_score_f32", lib.bl_score_f32,
-            (logits.data_ptr(), _rows(logits, "logits"), rows, n, temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
-             tokens.data_ptr(), wt.data_ptr(), int(range_first), count, range_wt.data_ptr() if count else None), keep)
+    args = (logits.data_ptr(), _rows(logits, "logits"), rows, n, temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
+            tokens.data_ptr(), wt.data_ptr(), int(range_first), count, range_wt.data_ptr() if count else None)
+    if vocab is None:
+        op = Op("bl_score_f32", lib.bl_score_f32, args, keep)
+    else:
+        op = Op("bl_score_range_f32", lib.bl_score_range_f32, args + (int(vocab[0]), int(vocab[1])), keep)
     if run:
         op.run()
     return op

@@ -98,12 +98,13 @@ class StaggeredDecodePipeline:
 
     def __init__(self, weights: VLAWeights, batch: int, prompt_len: int, n_new: int = 7, split_vision: bool = False,
                  fp8: bool = False, padded: bool = False, sample: bool = False, score: bool = False,
-                 score_range: Optional[Tuple[int, int]] = None):
+                 score_range: Optional[Tuple[int, int]] = None, vocab_range: Optional[Tuple[int, int]] = None):
         """split_vision=True adds a third stage: the vision towers + projector of the batch submitted NOW run beside the
         Llama prefill of the batch submitted one step earlier (n_new + 1 slots, latency n_new + 1 steps).
         score=True (with score_range, as OpenVLAEngine's) scores given tokens instead of producing them: every slot is an
         `OpenVLAEngine(score=True)`, `step(..., forced_ids=, sampling=)` fills the slot's forced ids and settings, and the
-        merged iteration ends in bl_score_f32 per group where a sampling pipeline draws."""
+        merged iteration ends in bl_score_f32 per group where a sampling pipeline draws. vocab_range=(first, count), with
+        sample=True or score=True, is OpenVLAEngine's: every draw and score is under the policy restricted to that range."""
         if n_new < 2:
             raise ValueError("StaggeredDecodePipeline needs at least one decode iteration (n_new >= 2)")
         if padded and fp8:
@@ -114,7 +115,8 @@ class StaggeredDecodePipeline:
         self.lag = 1 if split_vision else 0         # steps between a batch's submission and its prefill
         self.slots = n_new + self.lag
         self.engines = [OpenVLAEngine(weights, batch, prompt_len, n_new, fp8=fp8, padded=padded, sample=sample, score=score,
-                                      score_range=score_range) for _ in range(self.slots)]
+                                      score_range=score_range, vocab_range=vocab_range) for _ in range(self.slots)]
+        self.vocab_range = self.engines[0].vocab_range
         self.device = dev = weights.embed.device
         d = self.dims
         G = n_new - 1
@@ -196,10 +198,10 @@ class StaggeredDecodePipeline:
         plan += gm(self.hd, w.lm_head, self.logits, EPI_F32_BF16R)
         if self.sample:     # iteration g of a batch draws with ITS slot's settings at Philox counter g, as its engine would
             plan += [ops.sample(self.logits[r], e.samp_temperature, e.samp_top_k, e.samp_top_p, e.samp_seed, g, e.gen_ids[g],
-                                e.gen_wt[g], run=False) for g, e, r in groups]
+                                e.gen_wt[g], run=False, vocab=self.vocab_range) for g, e, r in groups]
         elif self.score:    # … or scores ITS slot's forced token g, which the next iteration's embedding consumes unchanged
             plan += [ops.score(self.logits[r], e.samp_temperature, e.samp_top_k, e.samp_top_p, e.gen_ids[g], e.gen_wt[g],
-                               *e._score_range_args(g), run=False) for g, e, r in groups]
+                               *e._score_range_args(g), run=False, vocab=self.vocab_range) for g, e, r in groups]
         else:
             plan += [ops.argmax(self.logits[r], e.gen_ids[g], run=False) for g, e, r in groups]
         return plan

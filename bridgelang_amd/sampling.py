@@ -34,6 +34,13 @@ them. The defining property: for every token `sample_row` can draw from a row, `
 `sample_row`'s pair; a token that top-k or top-p removed, or whose weight rounds to 0, scores (0, total_kept), i.e.
 log-probability -inf. `score_rows` also returns the kept weights of an index range (the 256 action bins, say): exact
 per-token probabilities, and with `range_entropy` the entropy over that range.
+
+A restricted policy: `vocab=(first, count)` on the four row functions makes the policy the softmax of
+`l[first : first + count]` alone (device twins: `bl_sample_range_f32` / `bl_score_range_f32`). The definition is one line:
+the result is what the function returns on that slice — maximum, top-k, top-p, the draw and the greedy argmax are all
+taken over the slice — with token ids reported in full-vocabulary numbering. Every token outside the range has
+probability 0 and is never read: it scores (0, total_kept), like a token that top-k removed. An OpenVLA action is one of
+256 bins carried by token ids vocab_size - 256 … vocab_size - 1, so the action policy is `vocab=(31744, 256)`.
 """
 from __future__ import annotations
 
@@ -135,39 +142,77 @@ def pick(kept: np.ndarray, u64) -> Tuple[np.ndarray, np.ndarray, int]:
     return ids, kept[ids], total
 
 
-def sample_row(logits, temperature: float, top_k: int, top_p: float, seed: int, t: int) -> Tuple[int, int, int]:
-    """One row, one step → (token id, w_token, total_kept)."""
+def check_vocab(vocab, n: int, what: str = "vocab") -> Optional[Tuple[int, int]]:
+    """None or (first, count) with the range inside [0, n) → the pair as Python integers; ValueError otherwise."""
+    if vocab is None:
+        return None
+    first, count = int(vocab[0]), int(vocab[1])
+    if first < 0 or count < 1 or first + count > n:
+        raise ValueError(f"{what}: the token range [{first}, {first + count}) is empty or leaves [0, {n})")
+    return first, count
+
+
+def sample_row(logits, temperature: float, top_k: int, top_p: float, seed: int, t: int, vocab=None) -> Tuple[int, int, int]:
+    """One row, one step → (token id, w_token, total_kept). vocab=(first, count): the same on l[first : first + count],
+    the id in full-vocabulary numbering."""
     l = np.asarray(logits, dtype=_f32)
+    vocab = check_vocab(vocab, l.shape[0], "sample_row")
+    if vocab is not None:
+        i, w, total = sample_row(l[vocab[0]:vocab[0] + vocab[1]], temperature, top_k, top_p, seed, t)
+        return i + vocab[0], w, total
     if not _f32(temperature) > 0:
         return int(np.argmax(l)), 1, 1
     i, w, total = pick(kept_weights(l, temperature, int(top_k), float(top_p)), draw_u64(int(seed), t))
     return int(i), int(w), total
 
 
-def sample_rows(logits, temperature, top_k, top_p, seed, t: int) -> Tuple[np.ndarray, np.ndarray]:
-    """logits [rows, n] with one setting per row → ids int64 [rows], wt int64 [rows, 2] — what bl_sample_f32 writes."""
+def sample_rows(logits, temperature, top_k, top_p, seed, t: int, vocab=None) -> Tuple[np.ndarray, np.ndarray]:
+    """logits [rows, n] with one setting per row → ids int64 [rows], wt int64 [rows, 2] — what bl_sample_f32 writes
+    (with vocab=(first, count): bl_sample_range_f32)."""
     l = np.asarray(logits, dtype=_f32)
+    vocab = check_vocab(vocab, l.shape[1], "sample_rows")
     ids, wt = np.zeros(l.shape[0], np.int64), np.zeros((l.shape[0], 2), np.int64)
     for r in range(l.shape[0]):
-        ids[r], wt[r, 0], wt[r, 1] = sample_row(l[r], temperature[r], top_k[r], top_p[r], int(seed[r]), t)
+        ids[r], wt[r, 0], wt[r, 1] = sample_row(l[r], temperature[r], top_k[r], top_p[r], int(seed[r]), t, vocab)
     return ids, wt
 
 
-def score_row(logits, temperature: float, top_k: int, top_p: float, token: int) -> Tuple[int, int]:
-    """One row, one given token → (w_token, total_kept): `sample_row`'s pair whenever it draws `token`."""
+def score_row(logits, temperature: float, top_k: int, top_p: float, token: int, vocab=None) -> Tuple[int, int]:
+    """One row, one given token → (w_token, total_kept): `sample_row`'s pair whenever it draws `token`. vocab=(first,
+    count): the same on l[first : first + count]; a token outside the range scores (0, total_kept)."""
     l = np.asarray(logits, dtype=_f32)
+    vocab = check_vocab(vocab, l.shape[0], "score_row")
+    if vocab is not None:
+        first, count = vocab
+        inside = first <= int(token) < first + count
+        w, total = score_row(l[first:first + count], temperature, top_k, top_p, int(token) - first if inside else 0)
+        return (w if inside else 0), total
     if not _f32(temperature) > 0:
         return int(int(token) == int(np.argmax(l))), 1
     kept = kept_weights(l, temperature, int(top_k), float(top_p))
     return int(kept[int(token)]), int(kept.sum())
 
 
-def score_rows(logits, temperature, top_k, top_p, tokens, first: int = 0, count: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+def score_rows(logits, temperature, top_k, top_p, tokens, first: int = 0, count: int = 0, vocab=None) -> Tuple[np.ndarray, np.ndarray]:
     """logits [rows, n] with one setting and one token per row → wt int64 [rows, 2] and range_wt int32 [rows, count] =
     the kept weights of tokens first … first + count - 1 (a greedy row: the one-hot of its argmax) — what bl_score_f32
-    writes."""
+    writes. vocab=(vfirst, vcount): the policy is over that token range (bl_score_range_f32); `first`, `count` and the
+    tokens keep their full-vocabulary numbering, and the report range must lie inside `vocab`."""
     l = np.asarray(logits, dtype=_f32)
     rows, n = l.shape
+    vocab = check_vocab(vocab, n, "score_rows")
+    if vocab is not None:
+        vf, vc = vocab
+        if count < 0 or (count and (first < vf or first + count > vf + vc)):
+            raise ValueError(f"score_rows: the range [{first}, {first + count}) leaves the token range [{vf}, {vf + vc})")
+        tok = np.asarray(tokens, dtype=np.int64)
+        if ((tok < 0) | (tok >= n)).any():
+            raise ValueError(f"score_rows: a token is outside [0, {n})")
+        inside = (tok >= vf) & (tok < vf + vc)
+        wt, range_wt = score_rows(l[:, vf:vf + vc], temperature, top_k, top_p, np.where(inside, tok - vf, 0),
+                                  first - vf if count else 0, count)
+        wt[~inside, 0] = 0
+        return wt, range_wt
     if count < 0 or (count and (first < 0 or first + count > n)):
         raise ValueError(f"score_rows: the range [{first}, {first + count}) leaves [0, {n})")
     wt, range_wt = np.zeros((rows, 2), np.int64), np.zeros((rows, count), np.int32)

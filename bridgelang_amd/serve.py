@@ -123,7 +123,10 @@ class OpenVLAServer:
     do_sample=False) -> ndarray [B, 7] (or [7] at B = 1)`; `processor(prompt, PIL image) -> {input_ids, pixel_values}`.
     `pad_to=L` additionally uses `vla.with_empty_token`, `vla.pad_token_id`, `vla.get_action_dim` and calls
     `predict_action(..., attention_mask=, unnorm_key=[one key per sequence])`. `sample=True` calls
-    `predict_action(..., sampling=SamplingParams(per-row arrays), return_weights=True) -> (actions, token ids, wt [B, 7, 2])`."""
+    `predict_action(..., sampling=SamplingParams(per-row arrays), return_weights=True) -> (actions, token ids, wt [B, 7, 2])`.
+    `sample=True, action_tokens_only=True` draws (and, for a greedy request, takes the argmax) under the policy restricted
+    to `vla.action_token_range()`: every answered action was decoded from action tokens, and a reported log-probability
+    is the one under that restricted policy."""
 
     _BASE_KEYS = ("image", "instruction", "unnorm_key")
     _SAMPLING_KEYS = ("temperature", "top_k", "top_p", "seed", "return_logprob")
@@ -131,9 +134,12 @@ class OpenVLAServer:
     def __init__(self, vla: Any, processor: Any, openvla_path: Union[str, Path] = "openvla/openvla-7b",
                  max_batch: int = 16, max_wait_ms: float = 2.0, norm_stats_path: Optional[Union[str, Path]] = None,
                  pipeline_batch: Optional[int] = None, max_pipelines: int = 2, pad_to: Optional[int] = None,
-                 sample: bool = False):
+                 sample: bool = False, action_tokens_only: bool = False):
         self.vla, self.processor, self.openvla_path = vla, processor, str(openvla_path)
         self.sample = bool(sample)
+        if action_tokens_only and not sample:
+            raise ValueError("action_tokens_only goes with sample=True")
+        self.vocab_range: Optional[Tuple[int, int]] = tuple(vla.action_token_range()) if action_tokens_only else None
         self.pad_to = int(pad_to) if pad_to else None
         self._pad_pipe: Optional[Tuple[Any, Dict[int, Any]]] = None     # pad_to: the one padded pipeline + its batches in flight
         self.pipelines_built = 0                  # StaggeredDecodePipelines constructed so far (observability / tests)
@@ -269,7 +275,8 @@ class OpenVLAServer:
     def _padded_pipe(self):
         from .pipeline import StaggeredDecodePipeline
         if self._pad_pipe is None:
-            pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, self.pad_to, padded=True, sample=self.sample)
+            pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, self.pad_to, padded=True, sample=self.sample,
+                                           vocab_range=self.vocab_range)
             pipe.capture()
             self.pipelines_built += 1
             self._pad_pipe = (pipe, {})
@@ -286,7 +293,7 @@ class OpenVLAServer:
             del self._pipes[old_len]
             del old
             torch.cuda.empty_cache()
-        pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, L, sample=self.sample)
+        pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, L, sample=self.sample, vocab_range=self.vocab_range)
         pipe.capture()
         self.pipelines_built += 1
         self._pipes[L] = (pipe, {})
@@ -397,7 +404,8 @@ class OpenVLAServer:
                 kw = dict(unnorm_key=[r.unnorm_key for r in rows], attention_mask=torch.cat([r.mask for r in rows], dim=0)) \
                     if batch[0].mask is not None else dict(unnorm_key=batch[0].unnorm_key)
                 actions, _, wt = self.vla.predict_action(input_ids=ids, pixel_values=pv, sampling=self._sampling_of(rows),
-                                                         return_weights=True, **kw)
+                                                         return_weights=True, **kw,
+                                                         **(dict(action_tokens_only=True) if self.vocab_range is not None else {}))
                 actions, wt = np.asarray(actions), np.asarray(wt)[:n]
             elif batch[0].mask is not None:     # pad_to: lengths and keys are mixed — every sequence un-normalised with its own key
                 actions = np.asarray(self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=[r.unnorm_key for r in rows],

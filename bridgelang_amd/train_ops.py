@@ -45,27 +45,32 @@ def policy_loss(logits, targets, advantages, old_logprob, ref_logprob, row_stats
                 run: bool = True) -> Op:
     """Clipped-surrogate policy-gradient loss over fp32 logits [rows, n] (training/policy_loss.py is the definition; `cfg` a
     PolicyLossConfig). advantages / old_logprob / ref_logprob (None: no KL term) fp32 [rows]; row_stats fp32 [rows, 8] and
-    stats fp32 [8] receive policy_loss.ROW_STAT_NAMES / STAT_NAMES."""
+    stats fp32 [8] receive policy_loss.ROW_STAT_NAMES / STAT_NAMES. With cfg.token_range the policy is over that token
+    range alone (bl_policy_loss_range_f32)."""
     rows, n = _policy_rows(logits, targets, row_stats, stats, "policy_loss")
     for t, what in ((advantages, "advantages"), (old_logprob, "old_logprob"), (ref_logprob, "ref_logprob")):
         if t is not None and (_f32(t, what).numel() != rows or not t.is_contiguous()):
             raise ValueError(f"policy_loss: {what} fp32 [{rows}] contiguous")
-    return _op("bl_policy_loss_f32",
+    rng = getattr(cfg, "token_range", None)
+    return _op("bl_policy_loss_f32" if rng is None else "bl_policy_loss_range_f32",
                (_f32(logits, "logits").data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
                 advantages.data_ptr(), old_logprob.data_ptr(), ref_logprob.data_ptr() if ref_logprob is not None else None,
                 float(cfg.temperature), float(cfg.clip_low), float(cfg.clip_high), float(cfg.entropy_coef), float(cfg.kl_coef),
-                row_stats.data_ptr(), stats.data_ptr()),
-               (logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats), run, nbytes=8.0 * rows * n)
+                row_stats.data_ptr(), stats.data_ptr()) + (() if rng is None else (int(rng[0]), int(rng[1]))),
+               (logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats), run,
+               nbytes=8.0 * rows * (n if rng is None else rng[1]))
 
 
 def policy_loss_backward(logits, targets, row_stats, stats, dlogits, cfg, ignore_index: int = -100, run: bool = True) -> Op:
-    """bf16 dlogits of `policy_loss` from the logits and the row statistics it saved (stats[1] = n_valid)."""
+    """bf16 dlogits of `policy_loss` from the logits and the row statistics it saved (stats[1] = n_valid); with
+    cfg.token_range, zeros outside the range (bl_policy_loss_backward_range_f32)."""
     rows, n = _policy_rows(logits, targets, row_stats, stats, "policy_loss_backward")
-    return _op("bl_policy_loss_backward_f32",
+    rng = getattr(cfg, "token_range", None)
+    return _op("bl_policy_loss_backward_f32" if rng is None else "bl_policy_loss_backward_range_f32",
                (_f32(logits, "logits").data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
                 row_stats.data_ptr(), stats.data_ptr(), float(cfg.temperature), float(cfg.entropy_coef),
-                _bf16(dlogits, "dlogits").data_ptr(), _rows(dlogits, "dlogits")),
-               (logits, targets, row_stats, stats, dlogits), run, nbytes=6.0 * rows * n)
+                _bf16(dlogits, "dlogits").data_ptr(), _rows(dlogits, "dlogits")) + (() if rng is None else (int(rng[0]), int(rng[1]))),
+               (logits, targets, row_stats, stats, dlogits), run, nbytes=(2.0 * n + 4.0 * (n if rng is None else rng[1])) * rows)
 
 
 def rmsnorm_backward(x, w, dy, dx, dw, ws, eps: float, dres: Optional[torch.Tensor] = None, run: bool = True) -> Op:

@@ -26,12 +26,20 @@ behaviour log-probability q and (optionally) a reference policy's log-probabilit
 Preconditions: finite logits; on valid rows finite A, q and ref — the host entry points raise ValueError otherwise. The
 case that matters in practice is the -inf `score_actions` reports for a token outside a top-k / top-p support. Top-k and
 top-p warping are NOT part of this loss: log π here is the temperature-only softmax, so rollouts meant for training are
-drawn with temperature only (top_k = 0, top_p = 1), and `temperature` here is the rollout's.
+drawn with temperature only (top_k = 0, top_p = 1).
+
+A token range IS part of it. With `PolicyLossConfig.token_range = (first, count)` the policy is the softmax of
+`l[first : first + count]` alone — the restricted policy of `sampling.py` (`vocab=`): the definition above on the sliced
+rows with the targets shifted by `first`, so m, S, H, logp and p_i are all over the range, `dlogits` is exactly 0 in every
+column outside it, and no logit outside it is read. A valid row whose target lies outside the range is an error: that
+action has probability 0 and the loss is undefined. Sampler, scorer and loss must describe ONE distribution or the ratio
+of an on-policy step is not 1: `temperature` and `token_range` here must be the rollout's (`action_tokens_only=True` on
+`sample_actions` / `score_actions` ↔ `token_range = model.action_token_range()`).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -50,8 +58,18 @@ class PolicyLossConfig:
     clip_high: float = 0.2
     entropy_coef: float = 0.0
     kl_coef: float = 0.0
+    token_range: Optional[Tuple[int, int]] = None    # (first, count): the policy is over these tokens alone
 
     def __post_init__(self):
+        if self.token_range is not None:
+            try:
+                first, count = (int(v) for v in self.token_range)
+                exact = (first, count) == tuple(self.token_range)
+            except (TypeError, ValueError):
+                exact = False
+            if not exact or first < 0 or count < 1:
+                raise ValueError("PolicyLossConfig: token_range is None or (first, count) with first >= 0 and count >= 1")
+            object.__setattr__(self, "token_range", (first, count))
         if not (np.isfinite(self.temperature) and self.temperature > 0):
             raise ValueError("PolicyLossConfig: temperature must be > 0 (a greedy rollout has no policy gradient)")
         if not (0 <= self.clip_low < 1 and 0 <= self.clip_high and np.isfinite(self.clip_high)):
@@ -94,6 +112,8 @@ class PolicyLossResult:
 def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cfg: Optional[PolicyLossConfig] = None,
                 ignore_index: int = IGNORE_INDEX) -> PolicyLossResult:
     cfg = cfg or PolicyLossConfig()
+    if cfg.token_range is not None:
+        return _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, cfg, ignore_index)
     l = np.asarray(logits, dtype=np.float64)
     tg = np.asarray(targets, dtype=np.int64)
     rows, n = l.shape
@@ -140,3 +160,25 @@ def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cf
                       mean(np.expm1(lr) - lr), mean(ratio)], dtype=np.float64)
     return PolicyLossResult(logp=zero(logp), entropy=zero(H), ratio=zero(ratio), pg=zero(pg), kl=zero(kl), row_loss=zero(row_loss),
                             clipped=valid & ~active, valid=valid, g=zero(g), loss=stats[0], stats=stats, dlogits=dl)
+
+
+def _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, cfg: PolicyLossConfig, ignore_index: int) -> PolicyLossResult:
+    """`policy_loss` on logits[:, first : first + count] with the targets shifted by `first`; dlogits widened with zeros."""
+    import dataclasses
+    first, count = cfg.token_range
+    n = np.shape(logits)[1]
+    if first + count > n:
+        raise ValueError(f"policy_loss: token_range [{first}, {first + count}) leaves [0, {n})")
+    tg = np.asarray(targets, dtype=np.int64)
+    valid = tg != ignore_index
+    outside = valid & ((tg < first) | (tg >= first + count))
+    if outside.any():
+        raise ValueError(f"policy_loss: {int(outside.sum())} target(s) outside token_range [{first}, {first + count}) "
+                         f"(first at row {int(np.argmax(outside))}): that action has probability 0 under the restricted policy")
+    sliced = np.asarray(logits)[:, first:first + count]           # only the range is looked at, also by the finiteness check
+    res = policy_loss(sliced, np.where(valid, tg - first, ignore_index), advantages, old_logprobs, ref_logprobs,
+                      dataclasses.replace(cfg, token_range=None), ignore_index)
+    dl = np.zeros((sliced.shape[0], n), dtype=np.float64)
+    dl[:, first:first + count] = res.dlogits
+    res.dlogits = dl
+    return res

@@ -3,7 +3,7 @@
 Host-side tensor layout only; the loop that uses it is the caller's."""
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -30,7 +30,8 @@ def group_advantages(rewards, eps: float = 1e-6) -> torch.Tensor:
     return ((r - mean) / (std + eps)).to(torch.float32)
 
 
-def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pad_to: Optional[int] = None) -> Dict[str, torch.Tensor]:
+def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pad_to: Optional[int] = None,
+                 token_range: Optional[Tuple[int, int]] = None) -> Dict[str, torch.Tensor]:
     """The training batch of one sampled action per sequence. prompt_ids int64 [B, lp] right-padded with attention_mask
     [B, lp] (None: no padding); token_ids int64 [B, n] and logprobs [B, n] as `sample_actions` reports them (K samples per
     prompt: repeat the prompt rows and flatten to [B·K, n] first); advantages [B], one per sequence, broadcast over its n
@@ -42,7 +43,9 @@ def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pa
     EOS position was never sampled and stays ignored. → dict of CPU tensors `input_ids`, `attention_mask`, `labels` (for
     `set_batch`) and `advantages`, `old_logprobs` fp32 [B, l] aligned with the labels (for `set_policy_batch`).
     A non-finite log-probability raises ValueError: a token outside a top-k / top-p support scores -inf, and the policy
-    loss is defined for temperature-only rollouts."""
+    loss is defined for temperature-only rollouts. `token_range=(first, count)` is the learner's
+    `PolicyLossConfig.token_range` (`model.action_token_range()`): an action token outside it raises ValueError — it has
+    probability 0 under the restricted policy, so the rollouts were not drawn from it."""
     ids, tok = _cpu(prompt_ids, torch.int64), _cpu(token_ids, torch.int64)
     lp, adv = _cpu(logprobs, torch.float64), _cpu(advantages, torch.float64)
     if ids.dim() != 2 or tok.dim() != 2 or tok.shape[0] != ids.shape[0] or tok.shape[1] < 1:
@@ -55,6 +58,12 @@ def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pa
                          "-inf; draw training rollouts with temperature only")
     if not bool(torch.isfinite(adv).all()):
         raise ValueError("policy_batch: advantages must be finite")
+    if token_range is not None:
+        first, count = int(token_range[0]), int(token_range[1])
+        outside = (tok < first) | (tok >= first + count)
+        if bool(outside.any()):
+            raise ValueError(f"policy_batch: {int(outside.sum())} action token(s) outside token_range [{first}, {first + count}) "
+                             f"(first: {int(tok[outside][0])}) — draw rollouts with action_tokens_only=True")
     if attention_mask is None:
         lens = [ids.shape[1]] * B
     else:

@@ -388,13 +388,20 @@ class TrainStep:
         `loss`: "ce" (the shifted cross-entropy of the labelled tokens) or "policy": the clipped-surrogate policy gradient
         of training/policy_loss.py over the same rows, configured by `policy` (a PolicyLossConfig; its defaults if None) and
         fed by `set_policy_batch` after `set_batch`. Only the two ops at the loss boundary differ; everything below the
-        logits, and every other option, is shared."""
+        logits, and every other option, is shared. With `policy.token_range=(first, count)` the two ops are the ranged
+        entry points: the policy — and with it `token_logprobs()` and `policy_stats()` — is the softmax over that token range
+        alone, as rollouts drawn with `action_tokens_only=True` need, and dlogits is 0 outside it."""
         if loss not in ("ce", "policy"):
             raise ValueError(f"loss must be 'ce' or 'policy', got {loss!r}")
         if policy is not None and loss != "policy":
             raise ValueError("`policy` configures loss='policy'")
         self.loss_kind = loss
         self.policy = (policy or PolicyLossConfig()) if loss == "policy" else None
+        if self.policy is not None and self.policy.token_range is not None:
+            first, count = self.policy.token_range
+            if first % 8 or count % 8 or first + count > weights.dims.vocab:
+                raise ValueError(f"policy.token_range {self.policy.token_range}: multiples of 8 inside the vocabulary "
+                                 f"[0, {weights.dims.vocab})")
         if (lora is not None) != (stage == "lora"):
             raise ValueError("stage 'lora' and the `lora` adapters go together")
         if (recompute or shard_params or fp8) and lora is not None:
@@ -1371,6 +1378,13 @@ class TrainStep:
         self.key_mask[:, :1] = m[:, :1]
         self.key_mask[:, 1:1 + P] = 1
         self.key_mask[:, 1 + P:] = m[:, 1:]
+        if self.policy is not None and self.policy.token_range is not None:
+            first, count = self.policy.token_range
+            outside = (lab != IGNORE_INDEX) & ((lab < first) | (lab >= first + count))
+            if bool(outside.any()):
+                raise ValueError(f"labels: {int(outside.sum())} labelled token(s) outside policy.token_range [{first}, {first + count}): "
+                                 "that action has probability 0 under the restricted policy — draw rollouts with "
+                                 "action_tokens_only=True")
         self.targets.copy_(shift_to_rows(lab, P, IGNORE_INDEX).view(-1))
         if self.policy is not None:
             self._batch_len = l

@@ -280,6 +280,21 @@ int bl_sample_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, cons
 int bl_score_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
                  const int32_t* top_k, const float* top_p, const int64_t* tokens, int64_t* wt,
                  int32_t range_first, int32_t range_count, int32_t* range_wt, void* stream);
+/* bl_sample_f32 with the policy restricted to the token range [vocab_first, vocab_first + vocab_count) of every row: the
+ * draw is from the softmax of logits[vocab_first : vocab_first + vocab_count] alone (maximum, top-k, top-p and the greedy
+ * argmax are all taken over the range; bit-identical to sampling.py::sample_rows(vocab=(first, count))), ids are in
+ * full-row numbering, and no column outside the range is read. vocab_first % 4 == 0, vocab_count % 4 == 0,
+ * 0 < vocab_count <= 36480 and the range inside [0, n), else BL_E_SHAPE. (0, n) is bl_sample_f32 bit for bit. */
+int bl_sample_range_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
+                        const int32_t* top_k, const float* top_p, const int64_t* seed, int32_t step, int64_t* ids,
+                        int64_t* wt, int32_t vocab_first, int32_t vocab_count, void* stream);
+/* bl_score_f32 under the same restricted policy (sampling.py::score_rows(vocab=(first, count))): a token outside the
+ * vocabulary range scores (0, kept total), like a token that top-k removed. range_first keeps full-row numbering; the
+ * report range must lie inside the vocabulary range (else BL_E_SHAPE). Other constraints as bl_sample_range_f32. */
+int bl_score_range_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const float* temperature,
+                       const int32_t* top_k, const float* top_p, const int64_t* tokens, int64_t* wt,
+                       int32_t range_first, int32_t range_count, int32_t* range_wt, int32_t vocab_first,
+                       int32_t vocab_count, void* stream);
 
 /* Shifted causal-LM cross-entropy (HF LlamaForCausalLM loss; labels prepared by the caller as `targets[row]` =
  * label of the NEXT position, -100 = ignore; base_strategy.py:287-297 consumes `output.loss`). row_loss[rows] receives
@@ -312,6 +327,22 @@ int bl_policy_loss_f32(const float* logits, int64_t ld, int32_t rows, int32_t n,
 int bl_policy_loss_backward_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
                                 int64_t ignore_index, const float* row_stats, const float* stats, float temperature,
                                 float entropy_coef, bl_bf16* dlogits, int64_t ldd, void* stream);
+/* bl_policy_loss_f32 with the policy taken over the token range [vocab_first, vocab_first + vocab_count) of every row
+ * (training/policy_loss.py with PolicyLossConfig.token_range): max, sum, entropy and logp are over the range and only the
+ * range of a valid row is read. targets stay in full-row numbering; a valid target outside the range gives NaN in that
+ * row's statistics, never a stray read. vocab_first % 8 == 0, vocab_count % 8 == 0, the range inside [0, n), else
+ * BL_E_SHAPE. (0, n) gives bl_policy_loss_f32's results. */
+int bl_policy_loss_range_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                             int64_t ignore_index, const float* advantages, const float* old_logprob,
+                             const float* ref_logprob, float temperature, float clip_low, float clip_high,
+                             float entropy_coef, float kl_coef, float* row_stats, float* stats, int32_t vocab_first,
+                             int32_t vocab_count, void* stream);
+/* bl_policy_loss_backward_f32 for the same range: writes the whole [rows, n] dlogits — exact zeros outside the range and on
+ * ignored rows, the gradient inside — and reads logits only inside the range of valid rows. */
+int bl_policy_loss_backward_range_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                      int64_t ignore_index, const float* row_stats, const float* stats, float temperature,
+                                      float entropy_coef, bl_bf16* dlogits, int64_t ldd, int32_t vocab_first,
+                                      int32_t vocab_count, void* stream);
 /* LlamaRMSNorm backward: dx = rstd*(w*dy - xhat*mean(w*dy*xhat)) [+ dres: the residual stream's own gradient];
  * dw[j] = sum_rows dy*bf16(xhat). partial_ws >= ceil(rows/64)*dim floats. */
 int bl_rmsnorm_backward_bf16(const bl_bf16* x, int64_t ldx, const bl_bf16* w, const bl_bf16* dy, int64_t lddy,
