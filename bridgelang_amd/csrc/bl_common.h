@@ -40,9 +40,12 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // ---- activation functions, written so the CPU oracle can restate them op for op --------------------------------
-// erf by Abramowitz & Stegun 7.1.26 (|abs error| <= 1.5e-7, below fp32 resolution of values near 1): one reciprocal, one
-// exp and five FMAs instead of ocml's branchy erff — the exact-GELU epilogue of the ViT fc1 GEMMs was costing as much as
-// their whole K = 1024 MFMA loop. Same evaluation structure as torch's `0.5 * x * (1 + erf(x / sqrt(2)))`.
+// erf by Abramowitz & Stegun 7.1.26: one reciprocal, one exp and five FMAs instead of ocml's branchy erff — the exact-GELU
+// epilogue of the ViT fc1 GEMMs was costing as much as their whole K = 1024 MFMA loop. Same evaluation structure as torch's
+// `0.5 * x * (1 + erf(x / sqrt(2)))`. Absolute error: the formula's own is <= 1.5e-7; evaluated in fp32 (coefficients and
+// Horner steps of size ~1.5 rounded to 2^-24 each) it is <= 1.5e-7 + 11·2^-24 = 8.1e-7 (derived in tests/train_ref64.py;
+// the fp32 restatement in tests/test_train_ref_cpu.py measures 4.8e-7). GELU inherits 0.5·|x| times that, which only
+// shows in the far negative tail, where 0.5·x·(1 + erf) itself vanishes.
 __device__ __forceinline__ float erf_as(float x) {
   const float ax = fabsf(x);
   const float t = __frcp_rn(fmaf(0.3275911f, ax, 1.0f));
@@ -51,7 +54,9 @@ __device__ __forceinline__ float erf_as(float x) {
   return copysignf(y, x);
 }
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erf_as(x * 0.70710678118654752440f)); }
-// x·sigmoid(x) with the hardware exp2 / reciprocal (≈ 3 fp32 ulp): the SwiGLU epilogue evaluates it 1.6e9 times per step
+// x·sigmoid(x) with the hardware exp2 / reciprocal: the SwiGLU epilogue evaluates it 1.6e9 times per step. Relative error
+// <= (|x| + 6)·2^-24 (≈ 3 fp32 ulp for |x| <= 6; the |x| term is the rounding of x·log2e inside __expf). Below x = −87.3 the
+// result is 0 (1 + e^-x exceeds 2^126 and v_rcp_f32 flushes; e^-x overflows below −88.7) where the value is <= 88·2^-126.
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 // Backward of act = bf16(silu(g)) * u for one (gate, up) pair given d = dL/d act — ONE definition for
 // bl_swiglu_backward_bf16 and the BL_EPI_SWIGLU_BWD GEMM epilogue (bit-identical paths).
