@@ -1417,12 +1417,15 @@ int launch_rows_sk(const GemmArgs& a, hipStream_t s) {
     int rc;
     if ((n_tiles + 7) / 8 >= 200) {                       // one round of 8-wave workgroups fills the chip (lm_head)
       p.splitk = 1;
+      record_form(GF_ROWS_STREAM, 8, 8);
       rc = launch_rs<EPI, 8, 8>(p, s, n_tiles);
     } else if ((n_tiles + 5) / 6 >= 200 || !can_split) {  // 6-wave workgroups do (gate/up: 230)
       p.splitk = 1;
+      record_form(GF_ROWS_STREAM, 6, 8);
       rc = launch_rs<EPI, 6, 8>(p, s, n_tiles);
     } else {                                              // two K-halves of 4 slices each + the last tree level
       p.splitk = 2;
+      record_form(GF_ROWS_STREAM, 8, 4);
       rc = launch_rs<BL_EPI_NONE, 8, 4>(p, s, n_tiles);
       const long work = (long)p.M * (p.N / 4);
       if (rc == BL_OK)
@@ -1438,6 +1441,7 @@ int launch_rows_sk(const GemmArgs& a, hipStream_t s) {
   // the tree is finished by the reduce kernel — the split is exact (see gemm_mid_kernel) and the same for every row.
   const bool split = slabs64 * 2 <= 256 && p.slab && p.slab_bytes >= 4L * p.M * p.N * 4;
   p.splitk = split ? 4 : 1;
+  record_form(GF_ROWS_MID, 0, split ? 2 : 8);
   if (split) {
     hipLaunchKernelGGL((gemm_mid_kernel<EPI, 2, 4, 2>), dim3(slabs64, 4), dim3(256), (mid_lds_bytes<2, 4>()), s, p);
     const long work = (long)p.M * (p.N / 4);
@@ -1516,6 +1520,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
       // 64 columns on a 2-stage ring so that two workgroups share a CU and one's LDS-DMA issue runs under the other's
       // MFMAs (qkv 59 -> 44 us, gate/up 112 -> 83 us at M = 288); the widest (lm_head) 128 columns.
       const int mb = (p.M + 159) / 160;
+      record_form(GF_MID2, !wide ? 1 : slabs64 >= 400 ? 4 : 2, !wide || slabs64 >= 400 ? 0 : 2);
       if (!wide)
         hipLaunchKernelGGL((gemm_mid2_kernel<EPI, 1>), dim3(p.N / 32, mb), dim3(256), 3 * (160 * ROW_BYTES + 4096), s, p);
       else if (slabs64 >= 400)
@@ -1532,6 +1537,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
     }
     p.splitk = S;
     const dim3 grid(slabs, S);
+    record_form(GF_MID, p.M <= 128 ? 2 : p.M <= 256 ? 4 : 5, wide ? 4 : 1, S);
     if (p.M <= 128) launch_mid<EPI, 2>(p, s, wide, grid);
     else if (p.M <= 256) launch_mid<EPI, 4>(p, s, wide, grid);
     else launch_mid<EPI, 5>(p, s, wide, grid);
@@ -1546,6 +1552,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
       p.tiles_m = (p.M + 159) / 160;
       p.tiles_n = (p.N + 127) / 128;
       p.tail_base = -1;
+      record_form(GF_RING160);
       hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 160, 128, 4>), dim3(t160), dim3(512), ring8_lds_bytes(160, 128), s, p);
       BL_CHECK_LAUNCH();
       return BL_OK;
@@ -1564,9 +1571,11 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
     }
     if (S128 > 1) {
       p.splitk = S128;
+      record_form(GF_RING128_KSLICED, 0, 0, S128);
       hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 128, 128, 4>), dim3(tiles, S128), dim3(512), ring8_lds_bytes(128, 128), s, p);
       launch_slab_reduce<EPI>(p, s);
     } else {
+      record_form(GF_GEMM128);
       hipLaunchKernelGGL((gemm128_kernel<EPI>), dim3(tiles), dim3(256), LDS128, s, p);
     }
     BL_CHECK_LAUNCH();
@@ -1583,6 +1592,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
     if (cost288 < 0.97f * cost256) {
       p.tiles_m = bm288;
       p.tiles_n = bn;
+      record_form(GF_GEMM288S);
       hipLaunchKernelGGL((gemm288s_kernel<EPI>), dim3(t288), dim3(512), LDS288, s, p);
       BL_CHECK_LAUNCH();
       return BL_OK;
@@ -1604,19 +1614,20 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
   // more than one round of tiles: the persistent form (one workgroup per CU walks its tiles, the next tile's first K-tiles
   // land behind this tile's epilogue); needs an even number of K-tiles (stage parity carries over) and 32-bit extents
   const bool persist_ok = (nk % 2) == 0 && (long)p.M * p.lda * 2 < (1L << 32) && (long)p.N * p.K * 2 < (1L << 32);
-  auto launch256 = [&](int grid) {
+  auto launch256 = [&](int grid) {   // returns the form it took (for record_form)
     if (persist_ok && p.splitk <= 1 && grid > CUS) {
       GemmArgs pp = p;
       pp.ptiles = grid;
       hipLaunchKernelGGL((gemm256s_kernel<EPI>), dim3(CUS), dim3(512), LDS256, s, pp);
-    } else {
-      hipLaunchKernelGGL((gemm256s_kernel<EPI>), dim3(grid), dim3(512), LDS256, s, p);
+      return GF_GEMM256S_PERSISTENT;
     }
+    hipLaunchKernelGGL((gemm256s_kernel<EPI>), dim3(grid), dim3(512), LDS256, s, p);
+    return GF_GEMM256S;
   };
   const bool can_split = tail && S >= 2 && p.K >= 8192 && p.slab && p.slab_bytes >= (long)tail * S * 256 * 256 * 4;
   if (can_split) {
     main_tiles = big_tiles - tail;
-    if (main_tiles) launch256(main_tiles);
+    record_form(main_tiles ? launch256(main_tiles) : GF_GEMM256S, 0, 0, 0, GT_SPLITK, S);
     p.tail_base = main_tiles;
     p.splitk = S;
     launch256(tail * S);
@@ -1625,7 +1636,8 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
     // (65 … 128 leftover tiles — Llama qkv at B = 16: 96 — as 256 × 128 half tiles instead of a quarter-filled fourth round
     // was measured at −0.6 % end to end: the half tiles stage 3/4 of a full tile's bytes for half its FLOPs)
     if (tail != 0 && tail <= 64 && main_tiles > tail) main_tiles = big_tiles - tail; else tail = 0;
-    launch256(main_tiles);
+    record_form(launch256(main_tiles), 0, 0, 0,
+                tail == 0 ? GT_NONE : tail <= 16 ? GT_SUB64X64 : tail <= 32 ? GT_SUB128X64 : GT_SUB128X128);
     if (tail) {
       // leftover 256x256 tiles on gemm_ring8_kernel's tail mode, cut so that the sub-tiles cover (up to) every CU once
       p.tail_base = main_tiles;
@@ -1661,23 +1673,24 @@ int launch_gemm_tn(const GemmArgs& a, hipStream_t s) {
                          p.slab_bytes >= (long)tail * S * 256 * 256 * 4;
   const bool persist_ok = (nk % 2) == 0 && ((long)(p.K - 1) * p.lda + p.M) * 2 < (1L << 32) &&
                           ((long)(p.K - 1) * p.ldw + p.N) * 2 < (1L << 32);
-  auto launch_main = [&](int grid) {
+  auto launch_main = [&](int grid) {   // returns the form it took (for record_form)
     if (persist_ok && grid > CUS) {
       GemmArgs pp = p;
       pp.ptiles = grid;
       hipLaunchKernelGGL((gemm256s_kernel<BL_EPI_F32, true>), dim3(CUS), dim3(512), LDS256, s, pp);
-    } else {
-      hipLaunchKernelGGL((gemm256s_kernel<BL_EPI_F32, true>), dim3(grid), dim3(512), LDS256, s, p);
+      return GF_TN_PERSISTENT;
     }
+    hipLaunchKernelGGL((gemm256s_kernel<BL_EPI_F32, true>), dim3(grid), dim3(512), LDS256, s, p);
+    return GF_TN;
   };
   if (can_split) {
-    if (tiles > tail) launch_main(tiles - tail);
+    record_form(tiles > tail ? launch_main(tiles - tail) : GF_TN_ALL_SPLIT, 0, 0, 0, GT_SPLITK, S);
     p.tail_base = tiles - tail;
     p.splitk = S;
     hipLaunchKernelGGL((gemm256s_kernel<BL_EPI_F32, true>), dim3(tail * S), dim3(512), LDS256, s, p);
     hipLaunchKernelGGL((gemm_splitk_reduce_kernel<BL_EPI_F32, true>), dim3(tail * 32), dim3(512), 0, s, p);
   } else {
-    launch_main(tiles);
+    record_form(launch_main(tiles));
   }
   BL_CHECK_LAUNCH();
   return BL_OK;
@@ -1686,7 +1699,10 @@ int launch_gemm_tn(const GemmArgs& a, hipStream_t s) {
 }  // namespace bl_gemm_bf16_impl
 using namespace bl_gemm_bf16_impl;
 
+extern "C" int bl_gemm_last_form(void) { return gemm_last_form(); }
+
 extern "C" int bl_gemm_bf16(const bl_gemm_desc* d, void* stream) {
+  gemm_last_form() = 0;
   GemmArgs a;
   const int rc = fill_gemm_args(d, a);
   if (rc != BL_OK) return rc;
@@ -1710,6 +1726,7 @@ extern "C" int bl_gemm_bf16(const bl_gemm_desc* d, void* stream) {
 }
 
 extern "C" int bl_gemm_skinny_rows_bf16(const bl_gemm_desc* d, void* stream) {
+  gemm_last_form() = 0;
   GemmArgs a;
   const int rc = fill_gemm_args(d, a);
   if (rc != BL_OK) return rc;
@@ -1727,6 +1744,7 @@ extern "C" int bl_gemm_skinny_rows_bf16(const bl_gemm_desc* d, void* stream) {
 }
 
 extern "C" int bl_gemm_tn_bf16(const bl_gemm_desc* d, void* stream) {
+  gemm_last_form() = 0;
   if (!d || !d->A || !d->W || !d->C) return BL_E_ARG;
   if (d->epilogue != BL_EPI_F32 || d->out_group || d->a_norm_weight) return BL_E_ARG;
   if (d->M <= 0 || d->N <= 0 || d->K <= 0 || (d->M % 8) || (d->N % 8)) return BL_E_SHAPE;

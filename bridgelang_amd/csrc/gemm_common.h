@@ -272,6 +272,24 @@ __device__ __forceinline__ void epilogue_tile(const GemmArgs& p, int mrow, const
     for (int j = 0; j < NJ; ++j) epilogue_store4<EPI>(p, mrow + j * 16, ncol[i], acc[i][j]);
 }
 
+// host side: the kernel form the calling thread's last bf16 GEMM entry point took (bl_gemm_last_form; 0 = none launched).
+// Written once per call by the launchers, read only by tests: it takes no part in any dispatch decision.
+//   bits 0-7 main kernel (GF_*), 8-11 / 12-15 its two template parameters, 16-21 its K slices (or the skinny KS),
+//   22-24 tail treatment (GT_*), 25-29 the split-K tail's slice count
+enum {
+  GF_GEMM128 = 1, GF_RING160 = 2, GF_RING128_KSLICED = 3, GF_MID = 4, GF_MID2 = 5, GF_GEMM288S = 6, GF_GEMM256S = 7,
+  GF_GEMM256S_PERSISTENT = 8, GF_ROWS_STREAM = 10, GF_ROWS_MID = 11, GF_SKINNY = 12, GF_TN = 13, GF_TN_PERSISTENT = 14,
+  GF_TN_ALL_SPLIT = 15
+};
+enum { GT_NONE = 0, GT_SUB64X64 = 1, GT_SUB128X64 = 2, GT_SUB128X128 = 3, GT_SPLITK = 4 };
+inline int& gemm_last_form() {
+  static thread_local int form = 0;
+  return form;
+}
+inline void record_form(int kind, int a = 0, int b = 0, int s = 0, int tail = GT_NONE, int tail_s = 0) {
+  gemm_last_form() = kind | (a << 8) | (b << 12) | (s << 16) | (tail << 22) | (tail_s << 25);
+}
+
 // host side: validate a descriptor and copy it into the device argument block
 inline int fill_gemm_args(const bl_gemm_desc* d, GemmArgs& a) {
   if (!d || !d->A || !d->W || !d->C) return BL_E_ARG;

@@ -156,6 +156,7 @@ int launch_ks(const GemmArgs& a, hipStream_t s) {
   // Balanced tiles per workgroup on 256 slots: 768 tiles → 256 × 3; 1376 → 230 × 6 (not 256 × 5 + 96 stragglers).
   const int tpw = (n_tiles + 255) / 256;
   const int grid = (n_tiles + tpw - 1) / tpw;
+  record_form(GF_SKINNY, a.norm_w ? 1 : 0, 0, KS);
   if (a.norm_w) hipLaunchKernelGGL((gemm_skinny_kernel<KS, GS, EPI, true>), dim3(grid), dim3(NW * 64), 0, s, a, n_tiles);
   else hipLaunchKernelGGL((gemm_skinny_kernel<KS, GS, EPI, false>), dim3(grid), dim3(NW * 64), 0, s, a, n_tiles);
   BL_CHECK_LAUNCH();
@@ -209,6 +210,7 @@ int launch_norm_skinny(const uint16_t* x, long ldx, const uint16_t* w, uint16_t*
 using namespace bl_gemm_skinny_impl;
 
 extern "C" int bl_gemm_skinny_bf16(const bl_gemm_desc* d, void* stream) {
+  gemm_last_form() = 0;
   GemmArgs a;
   const int rc = fill_gemm_args(d, a);
   if (rc != BL_OK) return rc;

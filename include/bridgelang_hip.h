@@ -128,6 +128,13 @@ int bl_gemm_skinny_rows_bf16(const bl_gemm_desc* d, void* stream);
  * rows past the end read as zeros); M, N multiples of 8. workspace (optional): fp32 scratch for a K-split last round. */
 int bl_gemm_tn_bf16(const bl_gemm_desc* d, void* stream);
 
+/* Which kernel form the calling thread's last bl_gemm_bf16 / bl_gemm_skinny_bf16 / bl_gemm_skinny_rows_bf16 /
+ * bl_gemm_tn_bf16 call launched (0: none — the call returned an error before launching). A host-side, thread-local
+ * record for tests; it takes no part in dispatch. Bits 0-7 main kernel, 8-11 and 12-15 its template parameters,
+ * 16-21 K slices (skinny kernel: k-steps per wave), 22-24 tail treatment, 25-29 split-K tail slices; the codes are in
+ * csrc/gemm_common.h and decoded by ops.gemm_last_form(). */
+int bl_gemm_last_form(void);
+
 /* HF LlamaRMSNorm (transformers modeling_llama.py LlamaRMSNorm.forward; called per decoder layer from the cached-decode
  * branch, modeling_prismatic.py:325-341) in exactly the arithmetic of bl_gemm_skinny_bf16's fused a_norm (same
  * sum-of-squares order, same two roundings): y = bf16(w * bf16(x * rsqrt(mean(x^2) + eps))). dim in {512, 1024, 1536,

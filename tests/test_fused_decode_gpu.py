@@ -69,6 +69,16 @@ def test_attention_decode_rope(dev, pos):
     close_bf16(o, o2.cpu().float(), "fused vs unfused decode attention", rtol=2 ** -6, min_exact=0.9)
 
 
+# (M, N, K) → the rows form without / with a workspace of 4·M·N·4 bytes (ops.gemm_last_form)
+_MID8, _MID2 = "rows_mid<SK=8>", "rows_mid<SK=2>+tree"
+ROWS_FORMS = {(96, 4096, 4096): (_MID8, _MID2), (96, 1024, 11008): (_MID8, _MID2), (17, 512, 512): (_MID8, _MID2),
+              (128, 3072, 1536): (_MID8, _MID2), (40, 2048, 1024): (_MID8, _MID2), (112, 640, 5120): (_MID8, _MID2),
+              (96, 256, 13824): (_MID8, _MID2), (33, 22016, 512): (_MID8, _MID8),
+              (96, 22016, 4096): ("rows_stream<6,8>", "rows_stream<6,8>"), (70, 12288, 4096): ("rows_stream<6,8>", "rows_stream<8,4>+tree"),
+              (96, 32064, 1024): ("rows_stream<8,8>", "rows_stream<8,8>"), (16, 6176, 5120): ("rows_stream<6,8>", "rows_stream<8,4>+tree"),
+              (1, 8192, 1024): ("rows_stream<6,8>", "rows_stream<8,4>+tree")}
+
+
 @pytest.mark.parametrize("M,N,K", [(96, 4096, 4096), (96, 1024, 11008), (17, 512, 512), (128, 3072, 1536), (40, 2048, 1024),
                                    (112, 640, 5120), (96, 256, 13824), (33, 22016, 512),
                                    # the wide layers' weight-streaming form (gemm_rows_stream_kernel): 6-wave workgroups walking
@@ -91,8 +101,10 @@ def test_skinny_rows_bit_identical_to_skinny(dev, M, N, K):
     for name, epi, Wp, dt, n_out, res in cases:
         got = torch.full((M, n_out), 7.0, dtype=dt, device=dev)
         ops.gemm(A, Wp, got, epi, res=res, skinny_rows=True)              # one workgroup walks all 8 K-slices
+        assert ops.gemm_last_form() == ROWS_FORMS[(M, N, K)][0]
         got4 = torch.full((M, n_out), 7.0, dtype=dt, device=dev)
         ops.gemm(A, Wp, got4, epi, res=res, skinny_rows=True, workspace=ws)   # narrow N: K split over 4 workgroups + tree reduce
+        assert ops.gemm_last_form() == ROWS_FORMS[(M, N, K)][1]
         assert torch.equal(got, got4), f"{name}: the K split across workgroups changed {(got != got4).sum().item()} elements"
         want = torch.empty_like(got)
         for r0 in range(0, M, 16):      # the per-batch kernel, 16 rows (one batch) at a time; odd group sizes too
@@ -100,10 +112,15 @@ def test_skinny_rows_bit_identical_to_skinny(dev, M, N, K):
             for q0, q1 in ((r0, r1), (r1, min(M, r0 + 16))):
                 if q1 > q0:
                     ops.gemm(A[q0:q1], Wp, want[q0:q1], epi, res=None if res is None else res[q0:q1], skinny=True)
+                    assert ops.gemm_last_form() == f"skinny<KS={K // 256}>"
         assert torch.equal(got, want), f"{name}: {(got != want).sum().item()} of {got.numel()} elements differ"
     out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     ops.gemm(A, W, out, ops.EPI_NONE, skinny_rows=True)
     close_bf16(out, R.linear(P, a, w), "skinny rows vs oracle")
+
+
+ROWS_STREAM_FORMS = {(96, 12288, 4096): ("rows_stream<6,8>", "rows_stream<8,4>+tree"), (48, 22016, 1024): ("rows_stream<6,8>",) * 2,
+                     (96, 32064, 1024): ("rows_stream<8,8>",) * 2}
 
 
 @pytest.mark.parametrize("M,N,K", [(96, 12288, 4096), (48, 22016, 1024), (96, 32064, 1024)])
@@ -121,6 +138,8 @@ def test_rows_stream_equals_mid_kernel(dev, M, N, K, monkeypatch):
         for wsp in (None, ws):
             out = torch.full((M, N), 7.0, dtype=torch.bfloat16, device=dev)
             ops.gemm(A, W, out, ops.EPI_NONE, skinny_rows=True, workspace=wsp)
+            # BL_ROWS_STREAM=0 keeps the wide layers on gemm_mid_kernel<SK> (never split: more than 128 column slabs)
+            assert ops.gemm_last_form() == ("rows_mid<SK=8>" if on == "0" else ROWS_STREAM_FORMS[(M, N, K)][wsp is not None])
             got[on, wsp is None] = out.cpu()
     assert torch.equal(got["0", True], got["1", True]) and torch.equal(got["0", False], got["1", False])
     assert torch.equal(got["1", True], got["1", False])

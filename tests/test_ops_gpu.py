@@ -108,6 +108,13 @@ def test_gemm_none_bias_gelu(dev, M, N, K):
     close_bf16(outf, R.linear(P, a, w), "EPI_F32_BF16R")
 
 
+# (M, N, K) → the form with a 64-MiB workspace, the form without (ops.gemm_last_form)
+WORKSPACE_FORMS = {(4608, 4096, 512): ("gemm288s", "gemm288s"), (4608, 1024, 1024): ("ring160x128", "ring160x128"),
+                   (4400, 3584, 768): ("gemm256s", "gemm256s"), (4608, 12288, 256): ("gemm128", "gemm128"),
+                   (4608, 64, 4096): ("ring128x128/S7", "gemm128"), (4176, 192, 3072): ("ring128x128/S3", "gemm128"),
+                   (300, 128, 2048): ("mid<5,4>/S4", "mid2<1>"), (1000, 256, 1536): ("ring128x128/S3", "gemm128")}
+
+
 @pytest.mark.parametrize("M,N,K,epi", [(4608, 4096, 512, "res"), (4608, 1024, 1024, "gelu"), (4400, 3584, 768, "swiglu"),
                                        (4608, 12288, 256, "none"),
                                        # few-tile (tall-skinny) problems: with a workspace the ring or mid kernels slice K
@@ -115,10 +122,12 @@ def test_gemm_none_bias_gelu(dev, M, N, K):
                                        (1000, 256, 1536, "swiglu")])
 def test_gemm_workspace_dispatch(dev, M, N, K, epi):
     """The dispatch with a workspace must equal the oracle, and equal the no-workspace dispatch bit for bit except for
-    fp32 summation order. The shapes take 288-row tiles, one round of 160 × 128 ring tiles, one partial round of 256 × 256
-    tiles and, with the workspace, the K-sliced ring and mid kernels (the few-tile shapes). None reaches the split-K tail
-    of the 256 × 256 kernel, which needs K >= 8192."""
+    fp32 summation order. The forms each shape takes with / without the workspace are in WORKSPACE_FORMS and asserted:
+    288-row tiles, one round of 160 × 128 ring tiles, one partial round of 256 × 256 tiles, the 128 × 128 kernel (K = 256:
+    every K < 512 runs there, workspace or not) and, with the workspace, the K-sliced ring and mid kernels (the few-tile
+    shapes). None reaches the split-K tail of the 256 × 256 kernel, which needs K >= 8192 (tests/test_gemm_ref_gpu.py does)."""
     from bridgelang_amd import ops
+    form_ws, form_plain = WORKSPACE_FORMS[(M, N, K)]
     a, w, b, r = rand_bf16((M, K), 1), rand_bf16((N, K), 2, 0.05), rand_bf16((N,), 3, 0.1), rand_bf16((M, N), 4)
     A, Bv, Rr = dv(a, dev), dv(b, dev), dv(r, dev)
     ws = torch.empty(64 << 20, dtype=torch.uint8, device=dev)
@@ -127,7 +136,9 @@ def test_gemm_workspace_dispatch(dev, M, N, K, epi):
         W = pk(torch.stack([w[:I], w[I:]], 1).reshape(N, K), dev)
         out, out2 = (torch.zeros(M, I, dtype=torch.bfloat16, device=dev) for _ in range(2))
         ops.gemm(A, W, out, ops.EPI_SWIGLU, workspace=ws)
+        assert ops.gemm_last_form() == form_ws
         ops.gemm(A, W, out2, ops.EPI_SWIGLU)
+        assert ops.gemm_last_form() == form_plain
         g, u = R.linear(P, a, w[:I]), R.linear(P, a, w[I:])
         ref = P.rb(P.rb(torch.nn.functional.silu(g)) * u)
     else:
@@ -136,7 +147,9 @@ def test_gemm_workspace_dispatch(dev, M, N, K, epi):
         code = {"res": ops.EPI_RES, "gelu": ops.EPI_BIAS_GELU, "none": ops.EPI_NONE}[epi]
         kw = {"res": dict(res=Rr), "gelu": dict(bias=Bv), "none": {}}[epi]
         ops.gemm(A, W, out, code, workspace=ws, **kw)
+        assert ops.gemm_last_form() == form_ws
         ops.gemm(A, W, out2, code, **kw)
+        assert ops.gemm_last_form() == form_plain
         lin = R.linear(P, a, w, b if epi == "gelu" else None)
         ref = {"res": lambda: P.rb(r + lin), "gelu": lambda: R.gelu(P, lin), "none": lambda: lin}[epi]()
     close_bf16(out, ref, f"workspace dispatch {epi}")
@@ -160,8 +173,8 @@ def test_gemm_rows_independent_of_batch(dev, N, K):
         assert torch.equal(one, big[b * S:(b + 1) * S]), f"sequence {b}"
 
 
-@pytest.mark.parametrize("M,N,K,epi", [(4608, 4096, 1024, "res"), (4591, 4000, 512, "none"), (4608, 12288, 256, "bias"),
-                                       (4608, 2048, 384, "swiglu")])
+@pytest.mark.parametrize("M,N,K,epi", [(4608, 4096, 1024, "res"), (4591, 4000, 512, "none"), (4608, 12288, 512, "bias"),
+                                       (4608, 4096, 512, "swiglu")])
 def test_gemm288_sequence_tiles(dev, M, N, K, epi):
     """288-row tiles (one 288-token sequence per row tile: gemm288s_kernel) where they remove the leftover round of 256-row
     tiling — Llama o_proj / down_proj / qkv at 16 × 288 rows — incl. ragged M and N and every epilogue family, against the
@@ -184,11 +197,13 @@ def test_gemm288_sequence_tiles(dev, M, N, K, epi):
         ref = {"res": lambda: P.rb(r[sel] + R.linear(P, a[sel], w)), "bias": lambda: R.linear(P, a[sel], w, b),
                "none": lambda: R.linear(P, a[sel], w)}[epi]()
     ops.gemm(A, W, out, e, **kw)
+    assert ops.gemm_last_form() == "gemm288s"
     close_bf16(out[sel], ref, f"gemm288 {epi}")
     for s0 in (0, 288 * 7, M - 288 - (M % 288 and 5)):              # one 288-row sequence at a time: the mid kernels
         one = torch.empty(288, out.shape[1], dtype=torch.bfloat16, device=dev)
         kw1 = {k: (v[s0:s0 + 288] if k == "res" else v) for k, v in kw.items()}
         ops.gemm(A[s0:s0 + 288], W, one, e, **kw1)
+        assert ops.gemm_last_form().startswith("mid2<")
         assert torch.equal(one, out[s0:s0 + 288]), f"rows {s0}..: result depends on the tiling"
 
 
@@ -196,6 +211,8 @@ def test_gemm288_sequence_tiles(dev, M, N, K, epi):
 RING8_TAILS = {(4608, 22016, 640): "64x64",     # 1548 tiles, 12 left over, 10 K-tiles
                (4608, 4096, 576): "128x64",     # 288 tiles, 32 left over, 9 K-tiles (K % 128 != 0: no 288-row tiling)
                (4608, 4352, 1024): "128x128"}   # 306 tiles, 50 left over, 16 K-tiles
+# the whole rounds before the tail: 1536 tiles with an even K-tile count walk persistently, 256 tiles are one plain round
+RING8_MAIN = {(4608, 22016, 640): "gemm256s_persistent", (4608, 4096, 576): "gemm256s", (4608, 4352, 1024): "gemm256s"}
 
 
 @pytest.mark.parametrize("M,N,K,epi", [(4608, 22016, 640, "none"), (4608, 22016, 640, "f32"),
@@ -230,6 +247,7 @@ def test_gemm_ring8_tail_modes(dev, M, N, K, epi):
         ref = P.rb(r[sel] + R.linear(P, a[sel], w)) if epi == "res" else R.linear(P, a[sel], w)
     out.fill_(float("nan"))
     ops.gemm(A, W, out, e, **kw)
+    assert ops.gemm_last_form() == f"{RING8_MAIN[(M, N, K)]}+tail{RING8_TAILS[(M, N, K)]}"
     assert not torch.isnan(out.float()).any(), "an output tile was never written"
     what = f"ring8 tail {RING8_TAILS[(M, N, K)]} {epi}"
     if epi == "f32":
@@ -244,13 +262,14 @@ def test_gemm_ring8_tail_modes(dev, M, N, K, epi):
         assert torch.equal(one, out[s0:s0 + 288]), f"{what}: rows {s0}..: result depends on the tiling"
 
 
-@pytest.mark.parametrize("M,N,K,epi", [(2333, 15360, 256, "bias"), (2560, 15344, 384, "none"), (2333, 15360, 256, "swiglu"),
-                                       (2500, 15360, 128, "res")])
+@pytest.mark.parametrize("M,N,K,epi", [(2333, 15360, 512, "bias"), (2560, 15344, 768, "none"), (2333, 15360, 1024, "swiglu"),
+                                       (2500, 15360, 512, "res")])
 def test_gemm256_persistent_multi_round(dev, M, N, K, epi):
     """More than one round of 256 x 256 tiles with a partial last round of > 64 tiles (600 tiles: 88 workgroups walk three
     tiles, 168 walk two) goes to the PERSISTENT form of gemm256s_kernel — one workgroup per CU, the next tile's first
     K-tiles staged behind this tile's epilogue. Ragged M and N (edge tiles take the per-store epilogue, interior tiles
-    the straight-line one), even K-tile counts 2 … 6, four epilogue families: against the oracle on sampled rows, and —
+    the straight-line one), K >= 512 (below that every problem runs on gemm128_kernel) with even K-tile counts 8 … 16, four
+    epilogue families, the form asserted through ops.gemm_last_form(): against the oracle on sampled rows, and —
     since a row's K order is the same in every tile kernel — bit-identical to 288-row slices run on their own (mid
     kernels)."""
     from bridgelang_amd import ops
@@ -272,6 +291,7 @@ def test_gemm256_persistent_multi_round(dev, M, N, K, epi):
                "none": lambda: R.linear(P, a[sel], w)}[epi]()
     out.fill_(float("nan"))
     ops.gemm(A, W, out, e, **kw)
+    assert ops.gemm_last_form() == "gemm256s_persistent"
     assert not torch.isnan(out.float()).any(), "a tile of the persistent walk was never written"
     close_bf16(out[sel], ref, f"gemm256 persistent {epi}")
     for s0 in (0, 288 * 3, M - 288):
@@ -294,11 +314,13 @@ def test_gemm_ring160_vit_shapes_and_batch_invariance(dev, T, N, K):
     A, Bv, Rr, Ls, W = dv(a, dev), dv(b, dev), dv(r, dev), dv(ls, dev), pk(w, dev)
     out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     ops.gemm(A, W, out, ops.EPI_BIAS_RES, bias=Bv, scale=Ls, res=Rr)
+    assert ops.gemm_last_form() == "ring160x128"
     sel = torch.cat([torch.arange(0, 300), torch.arange(M - 300, M)])          # first / last rows (incl. the ragged last tile)
     close_bf16(out[sel], P.rb(r[sel] + P.rb(R.linear(P, a[sel], w, b) * ls)), "ring160 BIAS_RES+LayerScale")
     for img in (0, 9, 15):
         one = torch.empty(T, N, dtype=torch.bfloat16, device=dev)
         ops.gemm(A[img * T:(img + 1) * T], W, one, ops.EPI_BIAS_RES, bias=Bv, scale=Ls, res=Rr[img * T:(img + 1) * T])
+        assert ops.gemm_last_form() == "mid2<1>"
         assert torch.equal(one, out[img * T:(img + 1) * T]), f"image {img}: result depends on the batch it ran in"
 
 
@@ -670,6 +692,13 @@ def test_lanczos_resize_device_twin_bit_exact(dev, H, W, size):
                           np.stack([EP.resize_image(f, size) for f in frames]))
 
 
+# (M, N, K) → the mid form the M-row call takes (ops.gemm_last_form); the 700-row call takes a tile kernel
+MID_ROWS_FORMS = {(288, 12288, 4096): "mid2<2,2>", (288, 4096, 1024): "mid2<1>", (261, 1024, 4096): "mid2<1>", (256, 4352, 1152): "mid2<1>",
+                  (100, 192, 512): "mid<2,1>", (33, 64, 1536): "mid<2,1>", (320, 3072, 1536): "mid2<1>", (288, 256, 1088): "mid2<1>",
+                  (576, 4096, 1024): "mid2<1>", (640, 12288, 512): "mid2<2,2>", (522, 1024, 1024): "mid2<1>", (161, 32064, 512): "mid2<4>",
+                  (600, 22016, 512): "mid2<2,2>"}
+
+
 @pytest.mark.parametrize("M,N,K,epi", [(288, 12288, 4096, "none"), (288, 4096, 1024, "res"), (261, 1024, 4096, "res"), (256, 4352, 1152, "gelu"),
                                        (100, 192, 512, "gelu"), (33, 64, 1536, "none"), (320, 3072, 1536, "swiglu"), (288, 256, 1088, "res"),
                                        (576, 4096, 1024, "res"), (640, 12288, 512, "none"), (522, 1024, 1024, "gelu"), (161, 32064, 512, "none"),
@@ -698,7 +727,9 @@ def test_gemm_mid_rows(dev, M, N, K, epi):
     out, big, out_ws = (torch.zeros(Mbig, ncols, dtype=torch.bfloat16, device=dev) for _ in range(3))
     kws = {k: (v[:M] if k == "res" else v) for k, v in kw.items()}
     ops.gemm(A[:M], W, out[:M], code, **kws)                                   # mid kernel
+    assert ops.gemm_last_form() == MID_ROWS_FORMS[(M, N, K)]
     ops.gemm(A, W, big, code, **kw)                                            # tile kernels on 700 rows
+    assert not ops.gemm_last_form().startswith("mid")
     close_bf16(out[:M], ref, f"mid {epi}")
     assert torch.equal(out[:M], big[:M]), "a row's result must not depend on the number of rows in the call"
     ops.gemm(A[:M], W, out_ws[:M], code, workspace=torch.empty(64 << 20, dtype=torch.uint8, device=dev), **kws)

@@ -339,8 +339,14 @@ def test_pack_into_windows(dev):
     assert torch.equal(WTe, ops.pack_weight(dv(torch.cat([w.t(), a.t()], 1).contiguous(), dev)))
 
 
-# the last shape runs on the 256 x 256 tile kernel (576 tiles, persistent walk, ragged last row tile): whole-tile epilogue path
-@pytest.mark.parametrize("M,N,K", [(300, 256, 128), (9472 // 8, 1024, 512), (70, 64, 192), (4500, 8192, 256)])
+# the last two shapes reach the straight-line whole-tile epilogue of the 256-row tile kernels (ragged last row tile):
+# 288-row tiles (16 x 32 tiles in two rounds) and the persistent walk of gemm256s_kernel (9 x 37 tiles); the first three
+# run on gemm128_kernel. Asserted through ops.gemm_last_form().
+TRAIN_EPI_FORMS = {(300, 256, 128): "gemm128", (9472 // 8, 1024, 512): "gemm128", (70, 64, 192): "gemm128",
+                   (4500, 8192, 512): "gemm288s", (2100, 9280, 512): "gemm256s_persistent"}
+
+
+@pytest.mark.parametrize("M,N,K", [(300, 256, 128), (9472 // 8, 1024, 512), (70, 64, 192), (4500, 8192, 512), (2100, 9280, 512)])
 def test_training_epilogues_equal_the_two_kernel_forms(dev, M, N, K):
     """The training-step GEMM epilogues (BL_EPI_SWIGLU_KEEP / BIAS_GELU_KEEP / SWIGLU_BWD / GELU_BWD) must reproduce, bit for
     bit, the plain epilogue followed by the elementwise kernel they replace (bl_swiglu_bf16, bl_gelu_bf16,
@@ -354,6 +360,7 @@ def test_training_epilogues_equal_the_two_kernel_forms(dev, M, N, K):
     pre_a, act_a, pre_b, act_b = z(M, N), z(M, N // 2), z(M, N), z(M, N // 2)
     ops.gemm(x, wp, pre_a, ops.EPI_NONE); T.swiglu(pre_a, act_a)
     ops.gemm(x, wp, pre_b, ops.EPI_SWIGLU_KEEP, out2=act_b)
+    assert ops.gemm_last_form() == TRAIN_EPI_FORMS[(M, N, K)]
     assert torch.equal(bits(pre_a), bits(pre_b)) and torch.equal(bits(act_a), bits(act_b))
     only = z(M, N // 2)
     ops.gemm(x, wp, only, ops.EPI_SWIGLU)                           # the inference epilogue: same activation
@@ -362,16 +369,19 @@ def test_training_epilogues_equal_the_two_kernel_forms(dev, M, N, K):
     g_a, g_b, t_b = z(M, N), z(M, N), z(M, N)
     ops.gemm(x, wp, pre_a, ops.EPI_BIAS, bias=bias); T.gelu(pre_a, g_a)
     ops.gemm(x, wp, t_b, ops.EPI_BIAS_GELU_KEEP, bias=bias, out2=g_b)
+    assert ops.gemm_last_form() == TRAIN_EPI_FORMS[(M, N, K)]
     assert torch.equal(bits(pre_a), bits(t_b)) and torch.equal(bits(g_a), bits(g_b))
     # backward: dy [M, K'] · Wt → d act [M, N'] with the saved pre-activation
     saved_gu, saved_t = dv(rand_bf16((M, 2 * N), 5, 2.0), dev), dv(rand_bf16((M, N), 6, 2.0), dev)
     d_act, dgu_a, dgu_b = z(M, N), z(M, 2 * N), z(M, 2 * N)
     ops.gemm(x, wp, d_act, ops.EPI_NONE); T.swiglu_backward(saved_gu, d_act, dgu_a)
     ops.gemm(x, wp, dgu_b, ops.EPI_SWIGLU_BWD, res=saved_gu)
+    assert ops.gemm_last_form() == TRAIN_EPI_FORMS[(M, N, K)]
     assert torch.equal(bits(dgu_a), bits(dgu_b)) and dgu_b.float().abs().max() > 0
     dt_a, dt_b = z(M, N), z(M, N)
     T.gelu_backward(saved_t, d_act, dt_a)
     ops.gemm(x, wp, dt_b, ops.EPI_GELU_BWD, res=saved_t)
+    assert ops.gemm_last_form() == TRAIN_EPI_FORMS[(M, N, K)]
     assert torch.equal(bits(dt_a), bits(dt_b)) and dt_b.float().abs().max() > 0
 
 

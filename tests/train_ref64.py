@@ -130,8 +130,22 @@ RATIOS: Dict[str, float] = {}      # label → largest err / bound seen (printed
 _SLICE_ELEMS = 1 << 21
 
 
+_ON_DEVICE = [False]
+
+
 def f64(t: torch.Tensor) -> torch.Tensor:
-    return t.detach().cpu().double()
+    return t.detach().double() if _ON_DEVICE[0] else t.detach().cpu().double()
+
+
+class on_device:
+    """Context: the element-wise references and the comparators stay on the device their arguments live on (same fp64
+    arithmetic; used by tests/gemm_ref64.py, whose largest outputs hold 4·10^7 elements). Default: everything on the CPU."""
+
+    def __enter__(self):
+        self.was, _ON_DEVICE[0] = _ON_DEVICE[0], True
+
+    def __exit__(self, *exc):
+        _ON_DEVICE[0] = self.was
 
 
 def _slices(rows: int, cols: int):
@@ -143,8 +157,10 @@ def _slices(rows: int, cols: int):
 # ---- bf16 rounding of fp64 values -------------------------------------------------------------------------------------
 def ulp_bf16(v: torch.Tensor) -> torch.Tensor:
     """Spacing of bf16 around the fp64 value v (8-bit significand; denormal spacing 2^-133 below 2^-126)."""
-    _, ex = torch.frexp(v)                       # |v| = m·2^ex, m in [0.5, 1)
-    return torch.ldexp(torch.ones_like(v), torch.clamp(ex - 8, min=-133))
+    # |v| = m·2^ex, m in [0.5, 1): ex and 2^(ex − 8) straight from / to the fp64 exponent field — integer work, exact on every
+    # device (a device ldexp / frexp may go through exp2 and miss the power of two by an ulp)
+    ex = ((v.contiguous().view(torch.int64) >> 52) & 0x7FF) - 1022
+    return ((torch.clamp(ex - 8, min=-133) + 1023) << 52).view(torch.float64)
 
 
 def rb64(v: torch.Tensor) -> torch.Tensor:
