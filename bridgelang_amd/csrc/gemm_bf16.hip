@@ -14,7 +14,7 @@
 //   * 1-D grid remapped so that each XCD (private L2) receives a contiguous run of tiles, walked in groups of
 //     GROUP_M row-tiles so concurrently resident tiles share weight panels.
 //
-// Kernels (launch_gemm picks one per shape):
+// Kernels (plan_gemm in gemm_plan.h picks per shape):
 //   gemm256s_kernel   — 256×256×64 tile, 8 waves in two staggered groups, 1 workgroup/CU; whole rounds of big problems.
 //   gemm288s_kernel   — the same on 288-row tiles (one 288-token sequence per row tile) where they remove a leftover round.
 //   gemm_ring8_kernel — 4-stage LDS-DMA ring, 8 waves: the sub-tiles of a leftover round, one round of 160×128 tiles for
@@ -27,8 +27,6 @@
 namespace bl_gemm_bf16_impl {
 using namespace blgemm;
 
-constexpr int BK = 64;          // bf16 elements per K-step = 128 B per activation-tile row
-constexpr int ROW_BYTES = 128;
 constexpr int GROUP_M = 4;   // round 3 same-box A/B: 4 beats 8 by 0.75 % end to end (gate||up -1.7 %), 2 / 3 tie, 9 … 18 lose
 
 // linear tile index → (row tile, column tile): groups of GROUP_M row-tiles walked column by column
@@ -1372,326 +1370,52 @@ __global__ __launch_bounds__(512) void gemm_splitk_reduce_kernel(GemmArgs p) {
                        TN ? tn * 256 + (i >> 1) * 128 + wn * 32 + (i & 1) * 16 + lg * 4 : tn * 256 + wn * 64 + i * 16 + lg * 4, sum);
 }
 
-constexpr int CUS = 256;   // MI355X compute units: the 256-row tile kernels run one workgroup per CU, a round is CUS tiles
-constexpr int LDS128 = 2 * 256 * ROW_BYTES, LDS256 = 2 * 65536, LDS288 = 2 * 73728;
-// gemm_ring8_kernel<EPI, BM, BN, 4>: four ring slots of BM activation + BN weight rows, and the 1-KiB dump
-constexpr int ring8_lds_bytes(int bm, int bn) { return 4 * (bm + bn) * ROW_BYTES + 1024; }
+// kernel id (gemm_plan.h) → instantiation, per entry point. The LDS attributes and the launcher's switch both walk these
+// lists, and both take the LDS bytes from lds_bytes(id). The template parameters are written once, for the id and the kernel.
+#define BL_RING8(X, EPI, BM, BN) X(kid(KN_RING8, BM, BN), (gemm_ring8_kernel<EPI, BM, BN, 4>))
+#define BL_MID(X, EPI, MB, NB, SK) X(kid(KN_MID, MB, NB, SK), (gemm_mid_kernel<EPI, MB, NB, SK>))
+#define BL_MID2(X, EPI, NT, NST) X(kid(KN_MID2, NT, NST), (gemm_mid2_kernel<EPI, NT, NST>))
+#define BL_ROWS_STREAM(X, ID, EPI, NWV, SK) X(kid(ID, NWV, SK), (gemm_rows_stream_kernel<EPI, NWV, SK>))
+#define BL_TILE_KERNELS(X, EPI)                                                                                       \
+  X(kid(KN_GEMM128), (gemm128_kernel<EPI>)) X(kid(KN_GEMM288S), (gemm288s_kernel<EPI>))                               \
+  X(kid(KN_GEMM256S), (gemm256s_kernel<EPI>)) X(kid(KN_TILE_REDUCE), (gemm_splitk_reduce_kernel<EPI>))                \
+  X(kid(KN_SLAB_REDUCE), (gemm128_splitk_reduce_kernel<EPI>))                                                         \
+  BL_RING8(X, EPI, 160, 128) BL_RING8(X, EPI, 128, 128) BL_RING8(X, EPI, 128, 64) BL_RING8(X, EPI, 64, 64)            \
+  BL_MID(X, EPI, 2, 4, 0) BL_MID(X, EPI, 4, 4, 0) BL_MID(X, EPI, 5, 4, 0) BL_MID(X, EPI, 2, 1, 0) BL_MID(X, EPI, 4, 1, 0) \
+  BL_MID(X, EPI, 5, 1, 0) BL_MID2(X, EPI, 1, 3) BL_MID2(X, EPI, 4, 3) BL_MID2(X, EPI, 2, 2)
+#define BL_ROWS_KERNELS(X, EPI)                                                                                       \
+  BL_ROWS_STREAM(X, KN_ROWS_STREAM, EPI, 8, 8) BL_ROWS_STREAM(X, KN_ROWS_STREAM, EPI, 6, 8)                           \
+  BL_ROWS_STREAM(X, KN_ROWS_STREAM_HALVES, BL_EPI_NONE, 8, 4) BL_MID(X, EPI, 2, 4, 8) BL_MID(X, EPI, 2, 4, 2)         \
+  X(kid(KN_TREE_REDUCE), (gemm_rows_tree_reduce_kernel<EPI>))
+#define BL_TN_KERNELS(X, EPI) \
+  X(kid(KN_GEMM256S, 1), (gemm256s_kernel<BL_EPI_F32, true>)) X(kid(KN_TILE_REDUCE, 1), (gemm_splitk_reduce_kernel<BL_EPI_F32, true>))
 
-template <typename Kernel>
-bool lds_attr(Kernel* kernel, int bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) ==
-         hipSuccess;
-}
+enum { FAM_TILE, FAM_ROWS, FAM_TN };   // bl_gemm_bf16, bl_gemm_skinny_rows_bf16, bl_gemm_tn_bf16
 
-template <int MB, int NB>
-constexpr int mid_lds_bytes() { return 3 * (64 * MB * ROW_BYTES + NB * 2048); }
-template <int EPI, int MB, int NB, int SK = 0>
-bool mid_attr() { return lds_attr(&gemm_mid_kernel<EPI, MB, NB, SK>, mid_lds_bytes<MB, NB>()); }
-
-constexpr int RS_LDS_BYTES = 4 * 2 * 6 * 16 * ROW_BYTES;   // gemm_rows_stream_kernel: NWB chunks of 96 rows × 2 K-tiles
-template <int EPI, int NWV, int SK>
-int launch_rs(const GemmArgs& p, hipStream_t s, int n_tiles) {
-  static const int attr_rc = lds_attr(&gemm_rows_stream_kernel<EPI, NWV, SK>, RS_LDS_BYTES) ? BL_OK : BL_E_LAUNCH;
-  if (attr_rc != BL_OK) return attr_rc;
-  hipLaunchKernelGGL((gemm_rows_stream_kernel<EPI, NWV, SK>), dim3((n_tiles + NWV - 1) / NWV, 8 / SK), dim3(NWV * 64),
-                     RS_LDS_BYTES, s, p, n_tiles);
-  return BL_OK;
-}
-
-// bl_gemm_skinny_rows_bf16: M <= 128 rows in the skinny kernel's summation order — gemm_rows_stream_kernel for the wide
-// layers at M <= 96 (qkv, gate/up, lm_head), gemm_mid_kernel<SK> otherwise
-template <int EPI>
-int launch_rows_sk(const GemmArgs& a, hipStream_t s) {
-  static const int attr_rc = mid_attr<EPI, 2, 4, 8>() && mid_attr<EPI, 2, 4, 2>() ? BL_OK : BL_E_LAUNCH;
-  if (attr_rc != BL_OK) return attr_rc;
-  GemmArgs p = a;
-  p.fold_ks = p.K / 256;                       // 8 slices of K/8 columns = K/256 MFMA k-steps each
-  // Rows-stream form: slices that end on its 4-k-step chunks (K a multiple of 1024), more than 256 weight tiles (the narrow
-  // layers' two launches — K split + reduce — are launch-bound and the mid kernel's are shorter: o 16.7 vs 19.5 µs, down
-  // 28.3 vs 33.5). 7B at 96 rows, same box: gate/up 53.5 → 40.2 µs (6 waves × 230 workgroups), qkv 38.1 → 32.7 (8 waves ×
-  // 96 column groups × 2 K-halves + the tree's last level in the reduce kernel). BL_ROWS_STREAM=0 switches it off (A/B).
-  const int n_tiles = p.N / 16;
-  const char* e_on = getenv("BL_ROWS_STREAM");
-  if (p.M <= 96 && p.fold_ks % 4 == 0 && n_tiles > 256 && (e_on ? atoi(e_on) : 1)) {
-    const bool can_split = p.slab && p.slab_bytes >= 2L * p.M * p.N * 4;
-    int rc;
-    if ((n_tiles + 7) / 8 >= 200) {                       // one round of 8-wave workgroups fills the chip (lm_head)
-      p.splitk = 1;
-      record_form(GF_ROWS_STREAM, 8, 8);
-      rc = launch_rs<EPI, 8, 8>(p, s, n_tiles);
-    } else if ((n_tiles + 5) / 6 >= 200 || !can_split) {  // 6-wave workgroups do (gate/up: 230)
-      p.splitk = 1;
-      record_form(GF_ROWS_STREAM, 6, 8);
-      rc = launch_rs<EPI, 6, 8>(p, s, n_tiles);
-    } else {                                              // two K-halves of 4 slices each + the last tree level
-      p.splitk = 2;
-      record_form(GF_ROWS_STREAM, 8, 4);
-      rc = launch_rs<BL_EPI_NONE, 8, 4>(p, s, n_tiles);
-      const long work = (long)p.M * (p.N / 4);
-      if (rc == BL_OK)
-        hipLaunchKernelGGL((gemm_rows_tree_reduce_kernel<EPI>), dim3((int)min((work + 255) / 256, 2048L)), dim3(256), 0, s, p);
-    }
-    if (rc != BL_OK) return rc;
-    BL_CHECK_LAUNCH();
-    return BL_OK;
-  }
-  const int slabs64 = (p.N + 63) / 64;
-  // 64-column slabs, every weight byte once, all rows of A staged once per workgroup. Where that leaves most CUs without
-  // a workgroup (N = 4096: 64 slabs) and the caller gave a workspace, grid.y = 4 workgroups take two K-slices each and
-  // the tree is finished by the reduce kernel — the split is exact (see gemm_mid_kernel) and the same for every row.
-  const bool split = slabs64 * 2 <= 256 && p.slab && p.slab_bytes >= 4L * p.M * p.N * 4;
-  p.splitk = split ? 4 : 1;
-  record_form(GF_ROWS_MID, 0, split ? 2 : 8);
-  if (split) {
-    hipLaunchKernelGGL((gemm_mid_kernel<EPI, 2, 4, 2>), dim3(slabs64, 4), dim3(256), (mid_lds_bytes<2, 4>()), s, p);
-    const long work = (long)p.M * (p.N / 4);
-    hipLaunchKernelGGL((gemm_rows_tree_reduce_kernel<EPI>), dim3((int)min((work + 255) / 256, 2048L)), dim3(256), 0, s, p);
-  } else {
-    hipLaunchKernelGGL((gemm_mid_kernel<EPI, 2, 4, 8>), dim3(slabs64), dim3(256), (mid_lds_bytes<2, 4>()), s, p);
-  }
-  BL_CHECK_LAUNCH();
-  return BL_OK;
-}
-
-template <int EPI>
-int set_lds_attr() {
-  static const int rc = [] {
-    const bool ok =
-        lds_attr(&gemm256s_kernel<EPI>, LDS256) && lds_attr(&gemm288s_kernel<EPI>, LDS288) &&
-        lds_attr(&gemm128_kernel<EPI>, LDS128) &&
-        lds_attr(&gemm_ring8_kernel<EPI, 160, 128, 4>, ring8_lds_bytes(160, 128)) &&
-        lds_attr(&gemm_ring8_kernel<EPI, 128, 128, 4>, ring8_lds_bytes(128, 128)) &&
-        lds_attr(&gemm_ring8_kernel<EPI, 128, 64, 4>, ring8_lds_bytes(128, 64)) &&
-        lds_attr(&gemm_ring8_kernel<EPI, 64, 64, 4>, ring8_lds_bytes(64, 64)) &&
-        lds_attr(&gemm_mid2_kernel<EPI, 1>, 3 * (160 * ROW_BYTES + 4096)) &&
-        lds_attr(&gemm_mid2_kernel<EPI, 4>, 3 * (160 * ROW_BYTES + 4 * 4096)) &&
-        lds_attr(&gemm_mid2_kernel<EPI, 2, 2>, 2 * (160 * ROW_BYTES + 2 * 4096)) &&
-        mid_attr<EPI, 2, 4>() && mid_attr<EPI, 4, 4>() && mid_attr<EPI, 5, 4>() && mid_attr<EPI, 2, 1>() &&
-        mid_attr<EPI, 4, 1>() && mid_attr<EPI, 5, 1>();
+// Carries a plan out: per launch the caller's arguments with the launch's overrides, on the kernel its id names. Decides
+// nothing. The LDS attributes of the family's kernels are set once per EPI.
+template <int EPI, int FAM>
+int launch_plan(const GemmPlan& plan, const GemmArgs& a, hipStream_t s) {
+#define BL_ATTR(ID, KERNEL) ok = ok && lds_attr(KERNEL, lds_bytes(ID));
+#define BL_CASE(ID, KERNEL) case ID: launch_kernel(KERNEL, l, p, s); break;
+  static const int attr_rc = [] {
+    bool ok = true;
+    if constexpr (FAM == FAM_TILE) { BL_TILE_KERNELS(BL_ATTR, EPI) }
+    else if constexpr (FAM == FAM_ROWS) { BL_ROWS_KERNELS(BL_ATTR, EPI) }
+    else { BL_TN_KERNELS(BL_ATTR, EPI) }
     return ok ? BL_OK : BL_E_LAUNCH;
   }();
-  return rc;
-}
-
-// K-sliced forms: slices write fp32 partials [M, N] to the slab, gemm128_splitk_reduce_kernel sums them in slice order and
-// applies the epilogue
-template <int EPI>
-void launch_slab_reduce(const GemmArgs& p, hipStream_t s) {
-  const long work = (long)p.M * (p.N / 4);
-  hipLaunchKernelGGL((gemm128_splitk_reduce_kernel<EPI>), dim3((int)min((work + 255) / 256, 2048L)), dim3(256), 0, s, p);
-}
-
-// gemm_mid_kernel for M ≤ 64·MB rows: 64-column slabs (wide) or 16-column slabs
-template <int EPI, int MB>
-void launch_mid(const GemmArgs& p, hipStream_t s, bool wide, dim3 grid) {
-  if (wide) hipLaunchKernelGGL((gemm_mid_kernel<EPI, MB, 4>), grid, dim3(256), (mid_lds_bytes<MB, 4>()), s, p);
-  else hipLaunchKernelGGL((gemm_mid_kernel<EPI, MB, 1>), grid, dim3(256), (mid_lds_bytes<MB, 1>()), s, p);
-}
-
-template <int EPI>
-int launch_gemm(const GemmArgs& a, hipStream_t s) {
-  if (set_lds_attr<EPI>() != BL_OK) return BL_E_LAUNCH;
-  GemmArgs p = a;
-  const int bm = (p.M + 255) / 256, bn = (p.N + 255) / 256, big_tiles = bm * bn;
-  // one (partial) round of big tiles beats 1.5+ rounds of the 128 kernel once about half of the CUs get a tile (ViT qkv at
-  // B = 16: 204 / 224 tiles, 45 → 39 µs; round 3, the narrow ViT layers at the training batch of 32 images — 132 / 160 tiles
-  // for M = 8352 / 8192, N = 1024 / 1152 — where the 128 kernel needs 528 / 576 > 512 workgroup slots: 104 → 82 µs at
-  // K = 4096, 35 → 30 µs at K = 1024)
-  const bool big = big_tiles >= 128 && p.K >= 512;
-  // M <= 320: the weight-streaming mid kernels; up to 640 rows (B = 2 prefill) the 160-row mid2 kernel still beats the
-  // tile kernels (38.2 -> 36.4 ms per batch), beyond that it loses (B = 4: 42.7 vs 48.2 ms)
-  const bool mid2_only = p.M > 320;
-  if (p.M <= 640 && p.M > 32 && p.K >= 512 && !(mid2_only && (p.slab || (p.N % 32)))) {
-    // every weight byte once: one workgroup per column slab, all rows; 64-column slabs when that already gives ≥ 160
-    // workgroups, else 16-column slabs. grid.y slices K only with a workspace (opt-in).
-    const int slabs64 = (p.N + 63) / 64, nkm = p.K / BK;
-    bool wide = slabs64 >= 160;   // measured: 64-column slabs for N = 4096 without K slicing (64 workgroups) cost +2.2 ms at B = 1
-    int S = 1;
-    if (!wide && p.slab && slabs64 * 2 <= CUS) {
-      // Every workgroup re-reads ALL M rows of A from L2, so the L2 traffic is (N / slab width) · M · K · 2 B: with a
-      // workspace, narrow layers (N = 4096: 64 slabs of 64 columns) keep the 64-column slabs — a quarter of the activation
-      // traffic of 16-column slabs — and fill the chip by slicing K instead (same slicing for every row: slot-invariant)
-      int S2 = min(8, CUS / slabs64);
-      while (S2 > 1 && (nkm / S2 < 8 || p.slab_bytes < (long)S2 * p.M * p.N * 4)) --S2;
-      if (S2 > 1) { wide = true; S = S2; }
-    }
-    if (S == 1 && p.M > 128 && (p.N % 32) == 0) {
-      // 160-row workgroups (gemm_mid2_kernel): narrow layers 32 columns (3-stage ring, 2 workgroups per CU); wide layers
-      // 64 columns on a 2-stage ring so that two workgroups share a CU and one's LDS-DMA issue runs under the other's
-      // MFMAs (qkv 59 -> 44 us, gate/up 112 -> 83 us at M = 288); the widest (lm_head) 128 columns.
-      const int mb = (p.M + 159) / 160;
-      record_form(GF_MID2, !wide ? 1 : slabs64 >= 400 ? 4 : 2, !wide || slabs64 >= 400 ? 0 : 2);
-      if (!wide)
-        hipLaunchKernelGGL((gemm_mid2_kernel<EPI, 1>), dim3(p.N / 32, mb), dim3(256), 3 * (160 * ROW_BYTES + 4096), s, p);
-      else if (slabs64 >= 400)
-        hipLaunchKernelGGL((gemm_mid2_kernel<EPI, 4>), dim3((p.N + 127) / 128, mb), dim3(256), 3 * (160 * ROW_BYTES + 4 * 4096), s, p);
-      else
-        hipLaunchKernelGGL((gemm_mid2_kernel<EPI, 2, 2>), dim3((p.N + 63) / 64, mb), dim3(256), 2 * (160 * ROW_BYTES + 2 * 4096), s, p);
-      BL_CHECK_LAUNCH();
-      return BL_OK;
-    }
-    const int slabs = wide ? slabs64 : (p.N + 15) / 16;
-    if (S == 1 && !wide && p.slab && slabs < CUS) {
-      S = min(8, (CUS + CUS / 2 + slabs - 1) / slabs);
-      while (S > 1 && (nkm / S < 8 || p.slab_bytes < (long)S * p.M * p.N * 4)) --S;
-    }
-    p.splitk = S;
-    const dim3 grid(slabs, S);
-    record_form(GF_MID, p.M <= 128 ? 2 : p.M <= 256 ? 4 : 5, wide ? 4 : 1, S);
-    if (p.M <= 128) launch_mid<EPI, 2>(p, s, wide, grid);
-    else if (p.M <= 256) launch_mid<EPI, 4>(p, s, wide, grid);
-    else launch_mid<EPI, 5>(p, s, wide, grid);
-    if (S > 1) launch_slab_reduce<EPI>(p, s);
-    BL_CHECK_LAUNCH();
-    return BL_OK;
-  }
-  if (!big && p.K >= 512) {
-    // one round of 160 × 128 tiles on the ring-buffered kernel when that covers the problem with ≥ 3/4 of the CUs busy
-    const int t160 = ((p.M + 159) / 160) * ((p.N + 127) / 128);
-    if (t160 <= CUS && t160 >= (3 * CUS) / 4) {
-      p.tiles_m = (p.M + 159) / 160;
-      p.tiles_n = (p.N + 127) / 128;
-      p.tail_base = -1;
-      record_form(GF_RING160);
-      hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 160, 128, 4>), dim3(t160), dim3(512), ring8_lds_bytes(160, 128), s, p);
-      BL_CHECK_LAUNCH();
-      return BL_OK;
-    }
-  }
-  if (!big) {
-    p.tiles_m = (p.M + 127) / 128;
-    p.tiles_n = (p.N + 127) / 128;
-    const int tiles = p.tiles_m * p.tiles_n, nk128 = p.K / BK;
-    // few tiles, long K (tall-skinny): slice K over grid.y on the ring kernel (one workgroup per CU: 129 KiB of LDS) when
-    // the caller gave a workspace (opt-in, as for the 256 kernel: sliced sums are not batch-slot invariant)
-    int S128 = 1;
-    if (p.slab && tiles <= CUS / 2) {
-      S128 = min(8, CUS / tiles);
-      while (S128 > 1 && (nk128 / S128 < 8 || p.slab_bytes < (long)S128 * p.M * p.N * 4)) --S128;
-    }
-    if (S128 > 1) {
-      p.splitk = S128;
-      record_form(GF_RING128_KSLICED, 0, 0, S128);
-      hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 128, 128, 4>), dim3(tiles, S128), dim3(512), ring8_lds_bytes(128, 128), s, p);
-      launch_slab_reduce<EPI>(p, s);
-    } else {
-      record_form(GF_GEMM128);
-      hipLaunchKernelGGL((gemm128_kernel<EPI>), dim3(tiles), dim3(256), LDS128, s, p);
-    }
-    BL_CHECK_LAUNCH();
-    return BL_OK;
-  }
-  // 288-row tiles (one 288-token sequence per row tile) where they remove the leftover round: estimated cost in units of
-  // one round of 256 × 256 tiles — 256-row tiling: full rounds + 0.45 for a ≤ 64-tile tail on sub-tiles, 1 for a larger
-  // partial round; 288-row tiling: rounds × 1.12 (12.5 % more MFMA work and 6 % more staging per tile).
-  if ((p.K % 128) == 0) {
-    const int t256 = big_tiles, r256 = t256 % CUS;
-    const float cost256 = (float)(t256 / CUS) + (r256 == 0 ? 0.f : (r256 <= 64 && t256 > CUS) ? 0.45f : 1.0f);
-    const int bm288 = (p.M + 287) / 288, t288 = bm288 * bn;
-    const float cost288 = 1.12f * (float)((t288 + CUS - 1) / CUS);
-    if (cost288 < 0.97f * cost256) {
-      p.tiles_m = bm288;
-      p.tiles_n = bn;
-      record_form(GF_GEMM288S);
-      hipLaunchKernelGGL((gemm288s_kernel<EPI>), dim3(t288), dim3(512), LDS288, s, p);
-      BL_CHECK_LAUNCH();
-      return BL_OK;
-    }
-  }
-  // Whole rounds of 256 tiles on the pipelined kernel; a partial last round would leave most CUs idle for a full tile
-  // time, so its tiles are cut into sub-tiles and run by the ring kernel instead.
-  p.tiles_m = bm;
-  p.tiles_n = bn;
-  // The last round of 256-tile launches is usually partial (e.g. 288 tiles = 1.125 rounds). Measured cost of the
-  // leftover `tail` tiles in units of one full round T(K) (tools/bench_gemm.py, profiles/): plain partial round 1.0;
-  // 128x128 quarters on the small kernel ≈ 0.65 when they fit one small round (tail ≤ 64 … 128), > 1 beyond; split-K
-  // over S = 256/tail slices ≈ 1/S + 45 µs of fp32 slab traffic, i.e. ≈ 0.28 at K = 11008 but ≈ 0.7 at K = 4096.
-  int main_tiles = big_tiles, tail = big_tiles % CUS;
-  const int nk = p.K / BK;
-  int S = tail ? CUS / tail : 1;
-  if (S > 16) S = 16;
-  while (S > 1 && nk / S < 4) --S;
-  // more than one round of tiles: the persistent form (one workgroup per CU walks its tiles, the next tile's first K-tiles
-  // land behind this tile's epilogue); needs an even number of K-tiles (stage parity carries over) and 32-bit extents
-  const bool persist_ok = (nk % 2) == 0 && (long)p.M * p.lda * 2 < (1L << 32) && (long)p.N * p.K * 2 < (1L << 32);
-  auto launch256 = [&](int grid) {   // returns the form it took (for record_form)
-    if (persist_ok && p.splitk <= 1 && grid > CUS) {
-      GemmArgs pp = p;
-      pp.ptiles = grid;
-      hipLaunchKernelGGL((gemm256s_kernel<EPI>), dim3(CUS), dim3(512), LDS256, s, pp);
-      return GF_GEMM256S_PERSISTENT;
-    }
-    hipLaunchKernelGGL((gemm256s_kernel<EPI>), dim3(grid), dim3(512), LDS256, s, p);
-    return GF_GEMM256S;
-  };
-  const bool can_split = tail && S >= 2 && p.K >= 8192 && p.slab && p.slab_bytes >= (long)tail * S * 256 * 256 * 4;
-  if (can_split) {
-    main_tiles = big_tiles - tail;
-    record_form(main_tiles ? launch256(main_tiles) : GF_GEMM256S, 0, 0, 0, GT_SPLITK, S);
-    p.tail_base = main_tiles;
-    p.splitk = S;
-    launch256(tail * S);
-    hipLaunchKernelGGL((gemm_splitk_reduce_kernel<EPI>), dim3(tail * 32), dim3(512), 0, s, p);
-  } else {
-    // (65 … 128 leftover tiles — Llama qkv at B = 16: 96 — as 256 × 128 half tiles instead of a quarter-filled fourth round
-    // was measured at −0.6 % end to end: the half tiles stage 3/4 of a full tile's bytes for half its FLOPs)
-    if (tail != 0 && tail <= 64 && main_tiles > tail) main_tiles = big_tiles - tail; else tail = 0;
-    record_form(launch256(main_tiles), 0, 0, 0,
-                tail == 0 ? GT_NONE : tail <= 16 ? GT_SUB64X64 : tail <= 32 ? GT_SUB128X64 : GT_SUB128X128);
-    if (tail) {
-      // leftover 256x256 tiles on gemm_ring8_kernel's tail mode, cut so that the sub-tiles cover (up to) every CU once
-      p.tail_base = main_tiles;
-      if (tail <= 16)
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 64, 64, 4>), dim3(tail * 16), dim3(512), ring8_lds_bytes(64, 64), s, p);
-      else if (tail <= 32)
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 128, 64, 4>), dim3(tail * 8), dim3(512), ring8_lds_bytes(128, 64), s, p);
-      else
-        hipLaunchKernelGGL((gemm_ring8_kernel<EPI, 128, 128, 4>), dim3(tail * 4), dim3(512), ring8_lds_bytes(128, 128), s, p);
-    }
-  }
-  BL_CHECK_LAUNCH();
-  return BL_OK;
-}
-
-// bl_gemm_tn_bf16: C[M, N] (fp32) = Aᵀ·B over K token rows, A = [K, M] and B = [K, N] row-major — the weight gradient
-// dW = dyᵀ·x straight from the row-major gradient and activation buffers (no transposed copies). Whole rounds of 256 × 256
-// tiles on the staggered kernel's TN form; a partial last round is split along K when the caller gave a workspace.
-int launch_gemm_tn(const GemmArgs& a, hipStream_t s) {
-  static const int attr_rc = lds_attr(&gemm256s_kernel<BL_EPI_F32, true>, LDS256) ? BL_OK : BL_E_LAUNCH;
   if (attr_rc != BL_OK) return attr_rc;
-  GemmArgs p = a;
-  p.tiles_m = (p.M + 255) / 256;
-  p.tiles_n = (p.N + 255) / 256;
-  const int tiles = p.tiles_m * p.tiles_n, nk = (p.K + BK - 1) / BK;
-  // fewer tiles than half the CUs (ViT blocks: 16 … 85 tiles): every tile is K-split so the launch fills the chip
-  int tail = tiles > CUS ? tiles % CUS : (2 * tiles <= CUS ? tiles : 0);
-  int S = tail ? CUS / tail : 1;
-  if (tiles <= CUS && S > 8) S = 8;
-  if (S > 16) S = 16;
-  while (S > 1 && nk / S < 4) --S;
-  const bool can_split = tail && S >= 2 && (nk >= 128 || tiles <= CUS) && p.slab &&
-                         p.slab_bytes >= (long)tail * S * 256 * 256 * 4;
-  const bool persist_ok = (nk % 2) == 0 && ((long)(p.K - 1) * p.lda + p.M) * 2 < (1L << 32) &&
-                          ((long)(p.K - 1) * p.ldw + p.N) * 2 < (1L << 32);
-  auto launch_main = [&](int grid) {   // returns the form it took (for record_form)
-    if (persist_ok && grid > CUS) {
-      GemmArgs pp = p;
-      pp.ptiles = grid;
-      hipLaunchKernelGGL((gemm256s_kernel<BL_EPI_F32, true>), dim3(CUS), dim3(512), LDS256, s, pp);
-      return GF_TN_PERSISTENT;
-    }
-    hipLaunchKernelGGL((gemm256s_kernel<BL_EPI_F32, true>), dim3(grid), dim3(512), LDS256, s, p);
-    return GF_TN;
-  };
-  if (can_split) {
-    record_form(tiles > tail ? launch_main(tiles - tail) : GF_TN_ALL_SPLIT, 0, 0, 0, GT_SPLITK, S);
-    p.tail_base = tiles - tail;
-    p.splitk = S;
-    hipLaunchKernelGGL((gemm256s_kernel<BL_EPI_F32, true>), dim3(tail * S), dim3(512), LDS256, s, p);
-    hipLaunchKernelGGL((gemm_splitk_reduce_kernel<BL_EPI_F32, true>), dim3(tail * 32), dim3(512), 0, s, p);
-  } else {
-    record_form(launch_main(tiles));
+  for (int i = 0; i < plan.n; ++i) {
+    const Launch& l = plan.l[i];
+    const GemmArgs p = with_overrides(a, l);
+    if constexpr (FAM == FAM_TILE) switch (l.kernel) { BL_TILE_KERNELS(BL_CASE, EPI) default: return BL_E_LAUNCH; }
+    else if constexpr (FAM == FAM_ROWS) switch (l.kernel) { BL_ROWS_KERNELS(BL_CASE, EPI) default: return BL_E_LAUNCH; }
+    else switch (l.kernel) { BL_TN_KERNELS(BL_CASE, EPI) default: return BL_E_LAUNCH; }
   }
+#undef BL_ATTR
+#undef BL_CASE
+  if (plan.n) gemm_last_form() = plan.form;
   BL_CHECK_LAUNCH();
   return BL_OK;
 }
@@ -1707,22 +1431,10 @@ extern "C" int bl_gemm_bf16(const bl_gemm_desc* d, void* stream) {
   const int rc = fill_gemm_args(d, a);
   if (rc != BL_OK) return rc;
   if (d->a_norm_weight) return BL_E_ARG;   // the fused A-operand RMSNorm exists only in the skinny kernel
-  hipStream_t s = (hipStream_t)stream;
-  switch (d->epilogue) {
-    case BL_EPI_NONE: return launch_gemm<BL_EPI_NONE>(a, s);
-    case BL_EPI_BIAS: return launch_gemm<BL_EPI_BIAS>(a, s);
-    case BL_EPI_BIAS_GELU: return launch_gemm<BL_EPI_BIAS_GELU>(a, s);
-    case BL_EPI_BIAS_RES: return launch_gemm<BL_EPI_BIAS_RES>(a, s);
-    case BL_EPI_RES: return launch_gemm<BL_EPI_RES>(a, s);
-    case BL_EPI_SWIGLU: return launch_gemm<BL_EPI_SWIGLU>(a, s);
-    case BL_EPI_F32: return launch_gemm<BL_EPI_F32>(a, s);
-    case BL_EPI_F32_BF16R: return launch_gemm<BL_EPI_F32_BF16R>(a, s);
-    case BL_EPI_SWIGLU_KEEP: return launch_gemm<BL_EPI_SWIGLU_KEEP>(a, s);
-    case BL_EPI_BIAS_GELU_KEEP: return launch_gemm<BL_EPI_BIAS_GELU_KEEP>(a, s);
-    case BL_EPI_SWIGLU_BWD: return launch_gemm<BL_EPI_SWIGLU_BWD>(a, s);
-    case BL_EPI_GELU_BWD: return launch_gemm<BL_EPI_GELU_BWD>(a, s);
-    default: return BL_E_ARG;
-  }
+  const GemmPlan plan = plan_gemm(gemm_shape(a));
+  return with_epilogue<ALL_EPIS>(d->epilogue, [&](auto epi) {
+    return launch_plan<decltype(epi)::value, FAM_TILE>(plan, a, (hipStream_t)stream);
+  });
 }
 
 extern "C" int bl_gemm_skinny_rows_bf16(const bl_gemm_desc* d, void* stream) {
@@ -1732,15 +1444,11 @@ extern "C" int bl_gemm_skinny_rows_bf16(const bl_gemm_desc* d, void* stream) {
   if (rc != BL_OK) return rc;
   if (d->M > 128 || (d->K % 256) || d->a_norm_weight) return BL_E_SHAPE;   // the norm is its own launch: bl_rmsnorm_skinny_bf16
   if (d->out_group) return BL_E_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  switch (d->epilogue) {
-    case BL_EPI_NONE: return launch_rows_sk<BL_EPI_NONE>(a, s);
-    case BL_EPI_RES: return launch_rows_sk<BL_EPI_RES>(a, s);
-    case BL_EPI_SWIGLU: return launch_rows_sk<BL_EPI_SWIGLU>(a, s);
-    case BL_EPI_F32: return launch_rows_sk<BL_EPI_F32>(a, s);
-    case BL_EPI_F32_BF16R: return launch_rows_sk<BL_EPI_F32_BF16R>(a, s);
-    default: return BL_E_ARG;
-  }
+  const char* e_on = getenv("BL_ROWS_STREAM");   // read per call: BL_ROWS_STREAM=0 switches the rows-stream form off (A/B)
+  const GemmPlan plan = plan_rows(gemm_shape(a, e_on ? atoi(e_on) != 0 : true));
+  return with_epilogue<SKINNY_EPIS>(d->epilogue, [&](auto epi) {
+    return launch_plan<decltype(epi)::value, FAM_ROWS>(plan, a, (hipStream_t)stream);
+  });
 }
 
 extern "C" int bl_gemm_tn_bf16(const bl_gemm_desc* d, void* stream) {
@@ -1758,5 +1466,5 @@ extern "C" int bl_gemm_tn_bf16(const bl_gemm_desc* d, void* stream) {
   a.M = d->M; a.N = d->N; a.K = d->K;
   a.tail_base = -1;
   a.slab = (float*)d->workspace; a.slab_bytes = d->workspace_bytes; a.splitk = 1;
-  return launch_gemm_tn(a, (hipStream_t)stream);
+  return launch_plan<BL_EPI_F32, FAM_TN>(plan_gemm_tn(gemm_shape(a)), a, (hipStream_t)stream);
 }

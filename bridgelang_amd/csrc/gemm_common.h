@@ -3,8 +3,11 @@
 // output columns n..n+3 of one row m; the epilogue below is written for that layout.
 #pragma once
 #include "bl_common.h"
+#include "gemm_plan.h"
+#include <type_traits>
 
 namespace blgemm {
+using namespace blplan;
 
 struct GemmArgs {
   const uint16_t* A; const uint16_t* W; void* C;
@@ -272,22 +275,49 @@ __device__ __forceinline__ void epilogue_tile(const GemmArgs& p, int mrow, const
     for (int j = 0; j < NJ; ++j) epilogue_store4<EPI>(p, mrow + j * 16, ncol[i], acc[i][j]);
 }
 
-// host side: the kernel form the calling thread's last bf16 GEMM entry point took (bl_gemm_last_form; 0 = none launched).
-// Written once per call by the launchers, read only by tests: it takes no part in any dispatch decision.
-//   bits 0-7 main kernel (GF_*), 8-11 / 12-15 its two template parameters, 16-21 its K slices (or the skinny KS),
-//   22-24 tail treatment (GT_*), 25-29 the split-K tail's slice count
-enum {
-  GF_GEMM128 = 1, GF_RING160 = 2, GF_RING128_KSLICED = 3, GF_MID = 4, GF_MID2 = 5, GF_GEMM288S = 6, GF_GEMM256S = 7,
-  GF_GEMM256S_PERSISTENT = 8, GF_ROWS_STREAM = 10, GF_ROWS_MID = 11, GF_SKINNY = 12, GF_TN = 13, GF_TN_PERSISTENT = 14,
-  GF_TN_ALL_SPLIT = 15
-};
-enum { GT_NONE = 0, GT_SUB64X64 = 1, GT_SUB128X64 = 2, GT_SUB128X128 = 3, GT_SPLITK = 4 };
+// host side: the kernel form the calling thread's last bf16 GEMM entry point took (bl_gemm_last_form; 0 = none launched):
+// the form code of the plan the launcher carried out (gemm_plan.h), read only by tests.
 inline int& gemm_last_form() {
   static thread_local int form = 0;
   return form;
 }
-inline void record_form(int kind, int a = 0, int b = 0, int s = 0, int tail = GT_NONE, int tail_s = 0) {
-  gemm_last_form() = kind | (a << 8) | (b << 12) | (s << 16) | (tail << 22) | (tail_s << 25);
+
+// host side: calls f(std::integral_constant<int, EPI>) for d->epilogue if bit EPI of ALLOWED is set — only those epilogues
+// are instantiated — and returns BL_E_ARG otherwise
+template <typename... T>
+constexpr unsigned epi_set(T... e) { return ((1u << e) | ... | 0u); }
+constexpr unsigned SKINNY_EPIS = epi_set(BL_EPI_NONE, BL_EPI_RES, BL_EPI_SWIGLU, BL_EPI_F32, BL_EPI_F32_BF16R);
+constexpr unsigned INFER_EPIS = SKINNY_EPIS | epi_set(BL_EPI_BIAS, BL_EPI_BIAS_GELU, BL_EPI_BIAS_RES);   // bl_gemm_fp8
+constexpr unsigned ALL_EPIS = INFER_EPIS | epi_set(BL_EPI_SWIGLU_KEEP, BL_EPI_BIAS_GELU_KEEP, BL_EPI_SWIGLU_BWD, BL_EPI_GELU_BWD);
+template <unsigned ALLOWED, int E = 0, typename F>
+int with_epilogue(int epi, F&& f) {
+  if constexpr ((ALLOWED >> E) == 0) return BL_E_ARG;
+  else {
+    if constexpr (ALLOWED >> E & 1u) if (epi == E) return f(std::integral_constant<int, E>{});
+    return with_epilogue<ALLOWED, E + 1>(epi, f);
+  }
+}
+
+// host side: carrying out a plan (gemm_plan.h)
+template <typename Kernel>
+bool lds_attr(Kernel* kernel, int bytes) {
+  return bytes == 0 || hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           bytes) == hipSuccess;
+}
+inline GemmArgs with_overrides(GemmArgs p, const GemmOverrides& o) {
+  p.tiles_m = o.tiles_m; p.tiles_n = o.tiles_n; p.tail_base = o.tail_base; p.splitk = o.splitk; p.ptiles = o.ptiles; p.fold_ks = o.fold_ks;
+  return p;
+}
+inline void launch_kernel(void (*kernel)(GemmArgs), const Launch& l, const GemmArgs& p, hipStream_t s) {
+  hipLaunchKernelGGL(kernel, dim3(l.grid_x, l.grid_y), dim3(l.block), l.lds, s, p);
+}
+// the weight-streaming kernels also take the count of 16-row weight tiles
+inline void launch_kernel(void (*kernel)(GemmArgs, int), const Launch& l, const GemmArgs& p, hipStream_t s) {
+  hipLaunchKernelGGL(kernel, dim3(l.grid_x, l.grid_y), dim3(l.block), l.lds, s, p, p.N / 16);
+}
+// a workspace pointer with no bytes behind it still counts as a workspace (it bars the M > 320 mid2 form)
+inline GemmShape gemm_shape(const GemmArgs& a, bool rows_stream = true) {
+  return {a.M, a.N, a.K, a.lda, a.ldw, a.slab ? (a.slab_bytes > 0 ? a.slab_bytes : 1) : 0, rows_stream};
 }
 
 // host side: validate a descriptor and copy it into the device argument block

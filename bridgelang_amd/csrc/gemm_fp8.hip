@@ -417,17 +417,13 @@ __global__ __launch_bounds__(256) void transpose_quantize_fp8_kernel(const uint1
 
 template <int EPI>
 int launch_fp8(const GemmArgs& a, hipStream_t s) {
-  static bool done = false;
-  if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_fp8_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * 65536) != hipSuccess)
-      return BL_E_LAUNCH;
-    done = true;
-  }
+  constexpr int lds = lds_bytes(kid(KN_GEMM256S_FP8));
+  static const int attr_rc = lds_attr(gemm256s_fp8_kernel<EPI>, lds) ? BL_OK : BL_E_LAUNCH;
+  if (attr_rc != BL_OK) return attr_rc;
   GemmArgs p = a;
   p.tiles_m = (p.M + 255) / 256;
   p.tiles_n = (p.N + 255) / 256;
-  hipLaunchKernelGGL((gemm256s_fp8_kernel<EPI>), dim3(p.tiles_m * p.tiles_n), dim3(512), 2 * 65536, s, p);
+  hipLaunchKernelGGL((gemm256s_fp8_kernel<EPI>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds, s, p);
   BL_CHECK_LAUNCH();
   return BL_OK;
 }
@@ -445,18 +441,7 @@ extern "C" int bl_gemm_fp8(const bl_gemm_desc* d, const float* scale_a, const fl
   const int rc = fill_gemm_args(&h, a);
   if (rc != BL_OK) return rc;
   a.qa = scale_a; a.qw = scale_w;
-  hipStream_t s = (hipStream_t)stream;
-  switch (d->epilogue) {
-    case BL_EPI_NONE: return launch_fp8<BL_EPI_NONE>(a, s);
-    case BL_EPI_BIAS: return launch_fp8<BL_EPI_BIAS>(a, s);
-    case BL_EPI_BIAS_GELU: return launch_fp8<BL_EPI_BIAS_GELU>(a, s);
-    case BL_EPI_BIAS_RES: return launch_fp8<BL_EPI_BIAS_RES>(a, s);
-    case BL_EPI_RES: return launch_fp8<BL_EPI_RES>(a, s);
-    case BL_EPI_SWIGLU: return launch_fp8<BL_EPI_SWIGLU>(a, s);
-    case BL_EPI_F32: return launch_fp8<BL_EPI_F32>(a, s);
-    case BL_EPI_F32_BF16R: return launch_fp8<BL_EPI_F32_BF16R>(a, s);
-    default: return BL_E_ARG;
-  }
+  return with_epilogue<INFER_EPIS>(d->epilogue, [&](auto epi) { return launch_fp8<decltype(epi)::value>(a, (hipStream_t)stream); });
 }
 
 extern "C" int bl_quantize_rows_fp8(const bl_bf16* x, int64_t ldx, int32_t rows, int32_t cols, uint8_t* q, int64_t ldq,

@@ -148,35 +148,22 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs p, int n_
 #undef BL_LOAD_GROUP
 }
 
-template <int KS, int GS, int EPI>
-int launch_ks(const GemmArgs& a, hipStream_t s) {
-  const int n_tiles = a.N / 16;
-  // One 8-wave workgroup per CU: every variant needs > 128 VGPRs (x fragments 4·KS, two weight buffers, the fused-norm
-  // weights: 148–254), so two workgroups never co-reside; a grid of 384 (768 tiles ÷ 2) ran as 1.5 rounds of 256.
-  // Balanced tiles per workgroup on 256 slots: 768 tiles → 256 × 3; 1376 → 230 × 6 (not 256 × 5 + 96 stragglers).
-  const int tpw = (n_tiles + 255) / 256;
-  const int grid = (n_tiles + tpw - 1) / tpw;
-  record_form(GF_SKINNY, a.norm_w ? 1 : 0, 0, KS);
-  if (a.norm_w) hipLaunchKernelGGL((gemm_skinny_kernel<KS, GS, EPI, true>), dim3(grid), dim3(NW * 64), 0, s, a, n_tiles);
-  else hipLaunchKernelGGL((gemm_skinny_kernel<KS, GS, EPI, false>), dim3(grid), dim3(NW * 64), 0, s, a, n_tiles);
+// Carries a skinny plan (gemm_plan.h::plan_skinny) out: one launch, whose kernel id names <KS, GS, NORM>; it sets no GemmArgs scalar
+template <int EPI>
+int launch_plan(const GemmPlan& plan, const GemmArgs& a, hipStream_t s) {
+  if (plan.n == 0) return BL_E_SHAPE;   // no instantiation for this K: the caller falls back to bl_gemm_bf16
+  switch (plan.l[0].kernel) {
+#define BL_CASE(K, KS, GS)                                                                                         \
+  case kid(KN_SKINNY, KS, GS, 0): launch_kernel((gemm_skinny_kernel<KS, GS, EPI, false>), plan.l[0], a, s); break; \
+  case kid(KN_SKINNY, KS, GS, 1): launch_kernel((gemm_skinny_kernel<KS, GS, EPI, true>), plan.l[0], a, s); break;
+    BL_SKINNY_TABLE(BL_CASE)
+#undef BL_CASE
+    default: return BL_E_LAUNCH;
+  }
+  gemm_last_form() = plan.form;
   BL_CHECK_LAUNCH();
   return BL_OK;
 }
-
-template <int EPI>
-int launch_skinny(const GemmArgs& a, hipStream_t s) {
-  switch (a.K) {
-    case 4096: return launch_ks<16, 8, EPI>(a, s);    // Llama-2-7B hidden
-    case 11008: return launch_ks<43, 8, EPI>(a, s);   // Llama-2-7B MLP
-    case 5120: return launch_ks<20, 5, EPI>(a, s);    // Llama-2-13B hidden
-    case 13824: return launch_ks<54, 9, EPI>(a, s);   // Llama-2-13B MLP
-    case 512: return launch_ks<2, 1, EPI>(a, s);      // reduced-width test / oracle configs
-    case 1024: return launch_ks<4, 2, EPI>(a, s);
-    case 1536: return launch_ks<6, 3, EPI>(a, s);
-    default: return BL_E_SHAPE;                    // caller falls back to bl_gemm_bf16
-  }
-}
-
 
 // RMSNorm of rows in the fused-norm arithmetic of gemm_skinny_kernel: one workgroup per 16 rows, fragments in, fragments
 // out (y may alias x).
@@ -215,15 +202,10 @@ extern "C" int bl_gemm_skinny_bf16(const bl_gemm_desc* d, void* stream) {
   const int rc = fill_gemm_args(d, a);
   if (rc != BL_OK) return rc;
   if (d->M > 16) return BL_E_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  switch (d->epilogue) {
-    case BL_EPI_NONE: return launch_skinny<BL_EPI_NONE>(a, s);
-    case BL_EPI_RES: return launch_skinny<BL_EPI_RES>(a, s);
-    case BL_EPI_SWIGLU: return launch_skinny<BL_EPI_SWIGLU>(a, s);
-    case BL_EPI_F32: return launch_skinny<BL_EPI_F32>(a, s);
-    case BL_EPI_F32_BF16R: return launch_skinny<BL_EPI_F32_BF16R>(a, s);
-    default: return BL_E_ARG;
-  }
+  const GemmPlan plan = plan_skinny(gemm_shape(a), a.norm_w != nullptr);
+  return with_epilogue<SKINNY_EPIS>(d->epilogue, [&](auto epi) {
+    return launch_plan<decltype(epi)::value>(plan, a, (hipStream_t)stream);
+  });
 }
 
 extern "C" int bl_rmsnorm_skinny_bf16(const bl_bf16* x, int64_t ldx, const bl_bf16* w, bl_bf16* y, int64_t ldy,
@@ -234,13 +216,9 @@ extern "C" int bl_rmsnorm_skinny_bf16(const bl_bf16* x, int64_t ldx, const bl_bf
     return BL_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   switch (dim) {   // the K values gemm_skinny_kernel is instantiated for
-    case 4096: return launch_norm_skinny<16>(x, ldx, w, y, ldy, rows, dim, eps, s);
-    case 11008: return launch_norm_skinny<43>(x, ldx, w, y, ldy, rows, dim, eps, s);
-    case 5120: return launch_norm_skinny<20>(x, ldx, w, y, ldy, rows, dim, eps, s);
-    case 13824: return launch_norm_skinny<54>(x, ldx, w, y, ldy, rows, dim, eps, s);
-    case 512: return launch_norm_skinny<2>(x, ldx, w, y, ldy, rows, dim, eps, s);
-    case 1024: return launch_norm_skinny<4>(x, ldx, w, y, ldy, rows, dim, eps, s);
-    case 1536: return launch_norm_skinny<6>(x, ldx, w, y, ldy, rows, dim, eps, s);
+#define BL_CASE(K, KS, GS) case K: return launch_norm_skinny<KS>(x, ldx, w, y, ldy, rows, dim, eps, s);
+    BL_SKINNY_TABLE(BL_CASE)
+#undef BL_CASE
     default: return BL_E_SHAPE;
   }
 }

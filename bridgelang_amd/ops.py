@@ -100,7 +100,7 @@ _SKINNY_EPI = (EPI_NONE, EPI_RES, EPI_SWIGLU, EPI_F32, EPI_F32_BF16R)
 
 
 def skinny_supported(M: int, K: int, epilogue: int) -> bool:
-    """Shapes the weight-streaming kernel is instantiated for (gemm_skinny.hip::launch_skinny)."""
+    """Shapes the weight-streaming kernel is instantiated for (gemm_plan.h::BL_SKINNY_TABLE)."""
     return M <= 16 and K in SKINNY_K and epilogue in _SKINNY_EPI
 
 
@@ -206,7 +206,7 @@ _GF_TAIL = {0: "", 1: "+tail64x64", 2: "+tail128x64", 3: "+tail128x128"}
 
 
 def gemm_form_name(code: int) -> str:
-    """Name of a bl_gemm_last_form code (csrc/gemm_common.h): the main kernel with its template form and K slices, then
+    """Name of a bl_gemm_last_form code (csrc/gemm_plan.h): the main kernel with its template form and K slices, then
     the tail treatment — e.g. "gemm128", "mid<4,4>/S8", "mid2<2,2>", "gemm256s_persistent+tail64x64",
     "gemm256s+splitk4", "rows_stream<8,4>+tree", "rows_mid<SK=2>+tree", "skinny<KS=43>", "tn+splitk2"."""
     kind, a, b, S = code & 0xFF, (code >> 8) & 0xF, (code >> 12) & 0xF, (code >> 16) & 0x3F

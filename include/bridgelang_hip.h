@@ -132,7 +132,7 @@ int bl_gemm_tn_bf16(const bl_gemm_desc* d, void* stream);
  * bl_gemm_tn_bf16 call launched (0: none — the call returned an error before launching). A host-side, thread-local
  * record for tests; it takes no part in dispatch. Bits 0-7 main kernel, 8-11 and 12-15 its template parameters,
  * 16-21 K slices (skinny kernel: k-steps per wave), 22-24 tail treatment, 25-29 split-K tail slices; the codes are in
- * csrc/gemm_common.h and decoded by ops.gemm_last_form(). */
+ * csrc/gemm_plan.h and decoded by ops.gemm_last_form(). */
 int bl_gemm_last_form(void);
 
 /* HF LlamaRMSNorm (transformers modeling_llama.py LlamaRMSNorm.forward; called per decoder layer from the cached-decode

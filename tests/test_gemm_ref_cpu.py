@@ -21,7 +21,8 @@ from gemm_ref64 import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_KEEP, EPI_BIAS_RE
 f32 = torch.float32
 
 # ---- the GPU module's cases: form → (M, N, K, workspace) --------------------------------------------------------------------
-# Read off launch_gemm (csrc/gemm_bf16.hip); every case asserts the form it names through ops.gemm_last_form().
+# What the planner (csrc/gemm_plan.h) gives these shapes: tests/test_gemm_plan_cpu.py checks every entry against it without a
+# GPU, and every case asserts the form it names through ops.gemm_last_form().
 TILE_CASES = [
     ("gemm128", 700, 272, 448, False),
     ("gemm128", 1, 16, 64, False),
@@ -47,6 +48,11 @@ TILE_CASES = [
     ("gemm256s+tail128x64", 3900, 4368, 576, False),
     ("gemm256s+tail128x128", 4353, 4112, 576, False),
     ("gemm256s+splitk2", 2000, 4000, 8256, True),
+    # whole rounds on the persistent walk (more than 512 tiles, an even K-tile count), then the leftover tiles
+    ("gemm256s_persistent+tail64x64", 1159, 26256, 640, False),       # 5 x 103 tiles: 3 left over
+    ("gemm256s_persistent+tail128x64", 1159, 26928, 640, False),      # 5 x 106: 18
+    ("gemm256s_persistent+tail128x128", 1159, 27824, 640, False),     # 5 x 109: 33
+    ("gemm256s_persistent+splitk16", 321, 65744, 8320, True),         # 2 x 257: 2; K >= 8192 and 513 tiles: no smaller shape gets here
 ]
 SKINNY_K = (512, 1024, 1536, 4096, 5120, 11008, 13824)
 SKINNY_KS = {512: 2, 1024: 4, 1536: 6, 4096: 16, 5120: 20, 11008: 43, 13824: 54}

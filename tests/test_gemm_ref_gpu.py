@@ -11,17 +11,18 @@ the logical output must still be NaN and every element inside finite. A sits in 
 residual in [rows + 3, N + 12]; the workspace is NaN-filled before every form. References and comparisons run on the
 device (test_reference_same_on_cpu_and_device checks them against the CPU once).
 
-Form → case
-  launch_gemm: TILE_CASES — gemm128 (700 x 272 x 448, 1 x 16 x 64, M = 32); mid<2|4|5, 1|4> unsliced and K-sliced S = 8 / 2 / 4;
+Form → case (the planners of csrc/gemm_plan.h; tests/test_gemm_plan_cpu.py checks the tables against them on the CPU)
+  plan_gemm: TILE_CASES — gemm128 (700 x 272 x 448, 1 x 16 x 64, M = 32); mid<2|4|5, 1|4> unsliced and K-sliced S = 8 / 2 / 4;
       mid2<1>, <2,2>, <4>; ring 160 x 128; ring 128 x 128 K-sliced; gemm288s; gemm256s one partial round, persistent, and
-      multi-round with an odd K-tile count; the 64 x 64 / 128 x 64 / 128 x 128 sub-tile tails; the split-K tail
+      multi-round with an odd K-tile count; the 64 x 64 / 128 x 64 / 128 x 128 sub-tile tails; the split-K tail; each tail
+      behind a persistent walk of the whole rounds
       test_tile_form_dyadic: twelve epilogues, LayerScale, res_row_mod + out_map, in-place residual; bit-exact or bounded
       test_tile_form_gauss: EPI_F32 and EPI_BIAS_RES on full-mantissa operands (K <= 1536)
       (unsliced mid<4|5, ·> exists only for N % 32 != 0, which the SwiGLU epilogues reject: SWIGLU_UNREACHABLE)
-  launch_skinny: seven K x five epilogues x M 1, 5, 16 x N 4112 (257 tiles: two per workgroup, one in the last) and 16
+  plan_skinny: seven K x five epilogues x M 1, 5, 16 x N 4112 (257 tiles: two per workgroup, one in the last) and 16
       test_skinny_dyadic; fused a_norm through a 0/1 weight and a Gaussian weight      test_skinny_fused_norm
-  launch_rows_sk: rows_stream<8,8>, <6,8>, <8,4> + tree, mid<SK=8>, mid<SK=2> + tree x M 1, 17, 96, 128   test_rows_dyadic
-  launch_gemm_tn: plain (odd / even K-tiles), persistent, all tiles split, split-K tail                  test_tn_dyadic
+  plan_rows: rows_stream<8,8>, <6,8>, <8,4> + tree, mid<SK=8>, mid<SK=2> + tree x M 1, 17, 96, 128   test_rows_dyadic
+  plan_gemm_tn: plain (odd / even K-tiles), persistent, all tiles split, split-K tail                  test_tn_dyadic
   norm_rows_kernel<NCH 1..10, RMS | LN>, rmsnorm_skinny_kernel<KS>                  test_norm_forward, test_rmsnorm_skinny
 """
 import pytest
@@ -41,15 +42,16 @@ OUT_MAP, RES_MOD = (50, 52, 4), 37          # rows 48, 49 of every 50-row group 
 SWIGLU_UNREACHABLE = {"mid<4,1>", "mid<5,1>", "mid<4,4>", "mid<5,4>"}
 
 ALL_FORMS = {
-    # launch_gemm
+    # plan_gemm
     "gemm128", "mid<2,1>", "mid<2,4>", "mid<4,1>", "mid<5,1>", "mid<4,4>", "mid<5,4>", "mid<2,4>/S8", "mid<4,4>/S2", "mid<5,4>/S4",
     "mid2<1>", "mid2<2,2>", "mid2<4>", "ring160x128", "ring128x128/S8", "gemm288s", "gemm256s", "gemm256s_persistent",
     "gemm256s+tail64x64", "gemm256s+tail128x64", "gemm256s+tail128x128", "gemm256s+splitk2",
-    # launch_skinny
+    "gemm256s_persistent+tail64x64", "gemm256s_persistent+tail128x64", "gemm256s_persistent+tail128x128", "gemm256s_persistent+splitk16",
+    # plan_skinny
     *(f"skinny<KS={ks}>" for ks in SKINNY_KS.values()), *(f"skinny<KS={ks}>+norm" for ks in SKINNY_KS.values()),
-    # launch_rows_sk
+    # plan_rows
     "rows_stream<8,8>", "rows_stream<6,8>", "rows_stream<8,4>+tree", "rows_mid<SK=8>", "rows_mid<SK=2>+tree",
-    # launch_gemm_tn
+    # plan_gemm_tn
     "tn", "tn_persistent", "tn_all_split+splitk4", "tn+splitk16",
 }
 REACHED = set()
