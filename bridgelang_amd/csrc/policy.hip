@@ -14,6 +14,12 @@
 // range and by ONE WAVE for a range of at most 256 columns (a float4 per lane: four rows per workgroup, no barrier and
 // no idle wave); both call the same finish_row → row_terms. The backward is the one kernel with a column window. The
 // unranged entry points are the (0, n) case of the workgroup kernels.
+//
+// bl_policy_loss_grouped_f32 takes the importance ratio per ACTION, not per token: the valid rows of each run of group_rows
+// consecutive rows (one sequence) share ratio_G = exp(c·Σ (logp − q)), c = 1 or 1 / n_G. It is the row pass above, then
+// policy_group_kernel (one wave per sequence; it overwrites ratio, row_loss, clipped and g of the valid rows with the
+// group-level values and writes group_stats), then the statistics with the log-ratio read from group_stats. m, log S, H
+// and g stay where the backward kernel reads them, so the backward entry points serve both levels.
 #include "bl_common.h"
 #include <math.h>
 
@@ -26,14 +32,15 @@ struct PolicyParams {
   float inv_t, clip_low, clip_high, entropy_coef, kl_coef;
 };
 
-// Everything of a row that follows from log π(a) alone. ONE definition for the row kernel and the step reduction.
+// Everything of a row that follows from log π(a) alone. ONE definition for the row kernels, the group kernel and both step
+// reductions: the clipped surrogate from a given log-ratio (a token's or a group's), then the KL term of the row.
 struct RowTerms {
   float ratio, log_ratio, pg, kl, g;
   bool active;
 };
-__device__ __forceinline__ RowTerms row_terms(float logp, float A, float q, const float* ref, int row, const PolicyParams& P) {
+__device__ __forceinline__ RowTerms surrogate_terms(float log_ratio, float A, const PolicyParams& P) {
   RowTerms t;
-  t.log_ratio = logp - q;
+  t.log_ratio = log_ratio;
   t.ratio = expf(t.log_ratio);
   const float lo = 1.0f - P.clip_low, hi = 1.0f + P.clip_high;
   const float clipped = fminf(fmaxf(t.ratio, lo), hi);
@@ -41,13 +48,24 @@ __device__ __forceinline__ RowTerms row_terms(float logp, float A, float q, cons
   t.active = (A >= 0.f && t.ratio <= hi) || (A < 0.f && t.ratio >= lo);   // clamp passes its gradient at the boundary
   t.kl = 0.f;
   t.g = t.active ? -A * t.ratio : 0.f;
+  return t;
+}
+// kl = k3 of the row, and its share of ∂row_loss/∂logp taken off g
+__device__ __forceinline__ void kl_terms(float logp, const float* ref, int row, const PolicyParams& P, float& kl, float& g) {
   if (ref) {
     const float d = ref[row] - logp;
     const float em1 = expm1f(d);
-    t.kl = em1 - d;                        // exp(d) − d − 1 (k3)
-    t.g -= P.kl_coef * em1;                // kl_coef·(1 − exp(d))
+    kl = em1 - d;                          // exp(d) − d − 1 (k3)
+    g -= P.kl_coef * em1;                  // kl_coef·(1 − exp(d))
   }
+}
+__device__ __forceinline__ RowTerms row_terms(float logp, float A, float q, const float* ref, int row, const PolicyParams& P) {
+  RowTerms t = surrogate_terms(logp - q, A, P);
+  kl_terms(logp, ref, row, P, t.kl, t.g);
   return t;
+}
+__device__ __forceinline__ float row_loss_of(const RowTerms& t, float H, const PolicyParams& P) {
+  return t.pg - P.entropy_coef * H + P.kl_coef * t.kl;
 }
 
 // what thread 0 / lane 0 does once S and W of a row are known. lr points at column `first`; tgt is relative to it.
@@ -61,7 +79,7 @@ __device__ __forceinline__ void finish_row(const float* lr, int n, long tgt, flo
   rs[RS_LOGP] = logp;
   rs[RS_H] = H;
   rs[RS_RATIO] = t.ratio;
-  rs[RS_LOSS] = t.pg - P.entropy_coef * H + P.kl_coef * t.kl;
+  rs[RS_LOSS] = row_loss_of(t, H, P);
   rs[RS_CLIPPED] = t.active ? 0.f : 1.f;
   rs[RS_M] = m;
   rs[RS_LOGS] = logS;
@@ -146,10 +164,72 @@ __global__ __launch_bounds__(256) void policy_rows_wave_kernel(const float* logi
   if (lane == 0) finish_row(lr, n, tgt - first, m, s + 0.f + 0.f + 0.f, w + 0.f + 0.f + 0.f, adv, old_lp, ref_lp, row, P, rs);
 }
 
-// the 8 step statistics: means over valid rows (single workgroup, fixed summation order → deterministic)
-__global__ __launch_bounds__(256) void policy_stats_kernel(const float* row_stats, const int64_t* targets, long ignore_index,
-                                                           const float* adv, const float* old_lp, const float* ref_lp,
-                                                           PolicyParams P, int rows, float* out) {
+// The action-level ratio. One wave per sequence (its group_rows consecutive rows), four sequences per workgroup, no barrier.
+// The group is the sequence's valid rows; lane l takes rows l, l + 64, ... in ascending order and every sum is a wave_sum
+// of those lane partials (deterministic, no float atomics). Reads what the row pass left (logp, H) and overwrites ratio,
+// row_loss, clipped and g of the valid rows: ratio_G = exp(s_G), s_G = c·Σ (logp − q), and
+// g_r = c·Σ_j (−A_j·ratio_G·[active_j]) − kl_coef·expm1(ref_r − logp_r). group_stats[seq] = (s_G, ratio_G, n_G, Σ logp);
+// an empty group writes zeros there and touches no row.
+__global__ __launch_bounds__(256) void policy_group_kernel(float* row_stats, int group_rows, int groups, int by_mean,
+                                                           const int64_t* targets, long ignore_index, const float* adv,
+                                                           const float* old_lp, const float* ref_lp, PolicyParams P,
+                                                           float* group_stats) {
+  const int seq = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (seq >= groups) return;          // uniform per wave
+  const long r0 = (long)seq * group_rows;
+  float sd = 0.f, sl = 0.f;           // Σ (logp − q), Σ logp
+  int c = 0;
+  for (int k = lane; k < group_rows; k += 64) {
+    const long r = r0 + k;
+    if (targets[r] == ignore_index) continue;
+    const float logp = row_stats[r * 8 + RS_LOGP];
+    sd += logp - old_lp[r];
+    sl += logp;
+    ++c;
+  }
+  sd = wave_sum(sd);
+  sl = wave_sum(sl);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  float* gs = group_stats + (long)seq * 4;
+  if (c == 0) {                       // uniform per wave
+    if (lane < 4) gs[lane] = 0.f;
+    return;
+  }
+  const float w = by_mean ? 1.0f / (float)c : 1.0f;
+  const float s = w * sd;
+  float gsum = 0.f;                   // Σ −A_j·ratio_G·[active_j]
+  for (int k = lane; k < group_rows; k += 64) {
+    const long r = r0 + k;
+    if (targets[r] == ignore_index) continue;
+    gsum += surrogate_terms(s, adv[r], P).g;
+  }
+  gsum = wave_sum(gsum);
+  for (int k = lane; k < group_rows; k += 64) {
+    const long r = r0 + k;
+    if (targets[r] == ignore_index) continue;
+    float* rs = row_stats + r * 8;
+    RowTerms t = surrogate_terms(s, adv[r], P);
+    t.g = w * gsum;
+    kl_terms(rs[RS_LOGP], ref_lp, (int)r, P, t.kl, t.g);
+    rs[RS_RATIO] = t.ratio;
+    rs[RS_LOSS] = row_loss_of(t, rs[RS_H], P);
+    rs[RS_CLIPPED] = t.active ? 0.f : 1.f;
+    rs[RS_G] = t.g;
+  }
+  if (lane == 0) {                    // lane 0 may hold no valid row: the ratio again, from the same s
+    gs[0] = s;
+    gs[1] = expf(s);
+    gs[2] = (float)c;
+    gs[3] = sl;
+  }
+}
+
+// the 8 step statistics: means over valid rows (single workgroup, fixed summation order → deterministic). The log-ratio
+// of a row is its own (group_stats NULL) or its group's, as policy_group_kernel left it in group_stats.
+__device__ __forceinline__ void stats_body(const float* row_stats, const int64_t* targets, long ignore_index, const float* adv,
+                                           const float* old_lp, const float* ref_lp, const PolicyParams& P, int rows,
+                                           const float* group_stats, int group_rows, float* out) {
   __shared__ float rsum[4][7];
   __shared__ int rc[4];
   float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // row_loss, pg, H, kl, clipped, approx KL, ratio
@@ -157,7 +237,13 @@ __global__ __launch_bounds__(256) void policy_stats_kernel(const float* row_stat
   for (int i = threadIdx.x; i < rows; i += 256) {
     if (targets[i] == ignore_index) continue;
     const float* rs = row_stats + (long)i * 8;
-    const RowTerms t = row_terms(rs[RS_LOGP], adv[i], old_lp[i], ref_lp, i, P);
+    RowTerms t;
+    if (group_stats) {
+      t = surrogate_terms(group_stats[(long)(i / group_rows) * 4], adv[i], P);
+      kl_terms(rs[RS_LOGP], ref_lp, i, P, t.kl, t.g);
+    } else {
+      t = row_terms(rs[RS_LOGP], adv[i], old_lp[i], ref_lp, i, P);
+    }
     a[0] += rs[RS_LOSS];
     a[1] += t.pg;
     a[2] += rs[RS_H];
@@ -184,6 +270,17 @@ __global__ __launch_bounds__(256) void policy_stats_kernel(const float* row_stat
     out[k == 0 ? 0 : k + 1] = mean;
     if (k == 0) out[1] = (float)cnt;
   }
+}
+__global__ __launch_bounds__(256) void policy_stats_kernel(const float* row_stats, const int64_t* targets, long ignore_index,
+                                                           const float* adv, const float* old_lp, const float* ref_lp,
+                                                           PolicyParams P, int rows, float* out) {
+  stats_body(row_stats, targets, ignore_index, adv, old_lp, ref_lp, P, rows, nullptr, 1, out);
+}
+__global__ __launch_bounds__(256) void policy_stats_grouped_kernel(const float* row_stats, const int64_t* targets,
+                                                                   long ignore_index, const float* adv, const float* ref_lp,
+                                                                   PolicyParams P, int rows, const float* group_stats,
+                                                                   int group_rows, float* out) {
+  stats_body(row_stats, targets, ignore_index, adv, nullptr, ref_lp, P, rows, group_stats, group_rows, out);
 }
 
 __device__ __forceinline__ u32x4_t pack8(const float* v) {
@@ -236,16 +333,21 @@ static bool bad_range(int32_t n, int32_t first, int32_t count) {
   return n <= 0 || (n % 8) || first < 0 || count <= 0 || (first % 8) || (count % 8) || (int64_t)first + count > n;
 }
 
-// by_wave: a range of at most 256 columns goes to the wave-per-row kernel. The unranged entry point never asks for it.
-static int policy_forward(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
-                          int64_t ignore_index, const float* advantages, const float* old_logprob, const float* ref_logprob,
-                          float temperature, float clip_low, float clip_high, float entropy_coef, float kl_coef,
-                          float* row_stats, float* stats, int32_t vocab_first, int32_t vocab_count, bool by_wave, void* stream) {
+static int policy_forward_check(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                const float* advantages, const float* old_logprob, float temperature, float clip_low,
+                                float clip_high, const float* row_stats, const float* stats, int32_t vocab_first,
+                                int32_t vocab_count) {
   if (!logits || !targets || !advantages || !old_logprob || !row_stats || !stats) return BL_E_ARG;
   if (!(temperature > 0.f) || !(clip_low >= 0.f) || !(clip_high >= 0.f)) return BL_E_ARG;
   if (rows <= 0 || bad_range(n, vocab_first, vocab_count) || (ld % 4) || ld < n) return BL_E_SHAPE;
   if (!bl_aligned16(logits)) return BL_E_ALIGN;
-  const PolicyParams P = {1.0f / temperature, clip_low, clip_high, entropy_coef, ref_logprob ? kl_coef : 0.f};
+  return BL_OK;
+}
+
+// by_wave: a range of at most 256 columns goes to the wave-per-row kernel. The unranged entry point never asks for it.
+static void launch_rows(const float* logits, int64_t ld, int32_t rows, const int64_t* targets, int64_t ignore_index,
+                        const float* advantages, const float* old_logprob, const float* ref_logprob, const PolicyParams& P,
+                        float* row_stats, int32_t vocab_first, int32_t vocab_count, bool by_wave, void* stream) {
   if (by_wave && vocab_count <= 256)
     hipLaunchKernelGGL(policy_rows_wave_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, (long)ld,
                        vocab_first, vocab_count, rows, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P,
@@ -253,8 +355,43 @@ static int policy_forward(const float* logits, int64_t ld, int32_t rows, int32_t
   else
     hipLaunchKernelGGL(policy_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, vocab_first,
                        vocab_count, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P, row_stats);
+}
+
+static int policy_forward(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                          int64_t ignore_index, const float* advantages, const float* old_logprob, const float* ref_logprob,
+                          float temperature, float clip_low, float clip_high, float entropy_coef, float kl_coef,
+                          float* row_stats, float* stats, int32_t vocab_first, int32_t vocab_count, bool by_wave, void* stream) {
+  const int bad = policy_forward_check(logits, ld, rows, n, targets, advantages, old_logprob, temperature, clip_low, clip_high,
+                                       row_stats, stats, vocab_first, vocab_count);
+  if (bad != BL_OK) return bad;
+  const PolicyParams P = {1.0f / temperature, clip_low, clip_high, entropy_coef, ref_logprob ? kl_coef : 0.f};
+  launch_rows(logits, ld, rows, targets, ignore_index, advantages, old_logprob, ref_logprob, P, row_stats, vocab_first,
+              vocab_count, by_wave, stream);
   hipLaunchKernelGGL(policy_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, row_stats, targets, (long)ignore_index,
                      advantages, old_logprob, ref_logprob, P, rows, stats);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
+extern "C" int bl_policy_loss_grouped_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                          int64_t ignore_index, const float* advantages, const float* old_logprob,
+                                          const float* ref_logprob, float temperature, float clip_low, float clip_high,
+                                          float entropy_coef, float kl_coef, float* row_stats, float* stats,
+                                          int32_t vocab_first, int32_t vocab_count, int32_t group_rows, int32_t ratio_norm,
+                                          float* group_stats, void* stream) {
+  const int bad = policy_forward_check(logits, ld, rows, n, targets, advantages, old_logprob, temperature, clip_low, clip_high,
+                                       row_stats, stats, vocab_first, vocab_count);
+  if (bad != BL_OK) return bad;
+  if (!group_stats) return BL_E_ARG;
+  if (group_rows <= 0 || (rows % group_rows) || (ratio_norm != 0 && ratio_norm != 1)) return BL_E_SHAPE;
+  const PolicyParams P = {1.0f / temperature, clip_low, clip_high, entropy_coef, ref_logprob ? kl_coef : 0.f};
+  const int groups = rows / group_rows;
+  launch_rows(logits, ld, rows, targets, ignore_index, advantages, old_logprob, ref_logprob, P, row_stats, vocab_first,
+              vocab_count, true, stream);
+  hipLaunchKernelGGL(policy_group_kernel, dim3((groups + 3) / 4), dim3(256), 0, (hipStream_t)stream, row_stats, group_rows,
+                     groups, ratio_norm, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P, group_stats);
+  hipLaunchKernelGGL(policy_stats_grouped_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, row_stats, targets,
+                     (long)ignore_index, advantages, ref_logprob, P, rows, group_stats, group_rows, stats);
   BL_CHECK_LAUNCH();
   return BL_OK;
 }

@@ -42,23 +42,38 @@ def _policy_rows(logits, targets, row_stats, stats, what: str):
 
 
 def policy_loss(logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats, cfg, ignore_index: int = -100,
-                run: bool = True) -> Op:
+                run: bool = True, group_rows: Optional[int] = None, group_stats: Optional[torch.Tensor] = None) -> Op:
     """Clipped-surrogate policy-gradient loss over fp32 logits [rows, n] (training/policy_loss.py is the definition; `cfg` a
     PolicyLossConfig). advantages / old_logprob / ref_logprob (None: no KL term) fp32 [rows]; row_stats fp32 [rows, 8] and
     stats fp32 [8] receive policy_loss.ROW_STAT_NAMES / STAT_NAMES. With cfg.token_range the policy is over that token
-    range alone (bl_policy_loss_range_f32)."""
+    range alone (bl_policy_loss_range_f32). With cfg.ratio_level == "action" the ratio is per sequence of `group_rows`
+    consecutive rows (bl_policy_loss_grouped_f32) and group_stats fp32 [rows / group_rows, 4] receives
+    policy_loss.GROUP_STAT_NAMES; at token level both are ignored."""
     rows, n = _policy_rows(logits, targets, row_stats, stats, "policy_loss")
     for t, what in ((advantages, "advantages"), (old_logprob, "old_logprob"), (ref_logprob, "ref_logprob")):
         if t is not None and (_f32(t, what).numel() != rows or not t.is_contiguous()):
             raise ValueError(f"policy_loss: {what} fp32 [{rows}] contiguous")
     rng = getattr(cfg, "token_range", None)
+    head = (_f32(logits, "logits").data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
+            advantages.data_ptr(), old_logprob.data_ptr(), ref_logprob.data_ptr() if ref_logprob is not None else None,
+            float(cfg.temperature), float(cfg.clip_low), float(cfg.clip_high), float(cfg.entropy_coef), float(cfg.kl_coef),
+            row_stats.data_ptr(), stats.data_ptr())
+    keep = (logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats)
+    nbytes = 8.0 * rows * (n if rng is None else rng[1])
+    if getattr(cfg, "ratio_level", "token") == "action":
+        if group_rows is None or int(group_rows) != group_rows or group_rows < 1 or rows % int(group_rows):
+            raise ValueError(f"policy_loss: ratio_level='action' needs group_rows >= 1 dividing the {rows} rows, got {group_rows!r}")
+        groups = rows // int(group_rows)
+        if group_stats is None:
+            raise ValueError(f"policy_loss: ratio_level='action' needs group_stats fp32 [{groups}, 4]")
+        if tuple(_f32(group_stats, "group_stats").shape) != (groups, 4) or not group_stats.is_contiguous():
+            raise ValueError(f"policy_loss: group_stats fp32 [{groups}, 4] contiguous")
+        first, count = (0, n) if rng is None else (int(rng[0]), int(rng[1]))
+        return _op("bl_policy_loss_grouped_f32",
+                   head + (first, count, int(group_rows), 1 if cfg.ratio_norm == "mean" else 0, group_stats.data_ptr()),
+                   keep + (group_stats,), run, nbytes=nbytes + 64.0 * rows)
     return _op("bl_policy_loss_f32" if rng is None else "bl_policy_loss_range_f32",
-               (_f32(logits, "logits").data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
-                advantages.data_ptr(), old_logprob.data_ptr(), ref_logprob.data_ptr() if ref_logprob is not None else None,
-                float(cfg.temperature), float(cfg.clip_low), float(cfg.clip_high), float(cfg.entropy_coef), float(cfg.kl_coef),
-                row_stats.data_ptr(), stats.data_ptr()) + (() if rng is None else (int(rng[0]), int(rng[1]))),
-               (logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats), run,
-               nbytes=8.0 * rows * (n if rng is None else rng[1]))
+               head + (() if rng is None else (int(rng[0]), int(rng[1]))), keep, run, nbytes=nbytes)
 
 
 def policy_loss_backward(logits, targets, row_stats, stats, dlogits, cfg, ignore_index: int = -100, run: bool = True) -> Op:

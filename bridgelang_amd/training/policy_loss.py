@@ -35,6 +35,30 @@ column outside it, and no logit outside it is read. A valid row whose target lie
 action has probability 0 and the loss is undefined. Sampler, scorer and loss must describe ONE distribution or the ratio
 of an on-policy step is not 1: `temperature` and `token_range` here must be the rollout's (`action_tokens_only=True` on
 `sample_actions` / `score_actions` ↔ `token_range = model.action_token_range()`).
+
+The ratio LEVEL is part of it too. An OpenVLA action is the n consecutive action tokens of a sequence: drawn together,
+rewarded together, given one advantage. With `PolicyLossConfig.ratio_level = "action"` (`bl_policy_loss_grouped_f32`) the
+importance ratio is the action's, π(a)/π_old(a), clipped once, instead of one ratio per token. `group_rows` consecutive
+rows are one sequence and its group G is the set of its valid rows (labels cover exactly the sampled action, and the shift
+never crosses a sequence, so no index tensor is needed). With δ_r = logp_r − q_r, n_G = |G| and c = 1 (`ratio_norm =
+"sum"`, PPO's action ratio) or 1 / n_G (`"mean"`, the geometric mean of the token ratios: GSPO's sequence ratio):
+
+    s_G      = c · Σ_{r∈G} δ_r                 (summed in row order)
+    ratio_G  = exp(s_G)
+    for r ∈ G:
+      pg_r     = −min(ratio_G·A_r, clip(ratio_G, 1 − clip_low, 1 + clip_high)·A_r)
+      active_r = (A_r ≥ 0 and ratio_G ≤ 1 + clip_high) or (A_r < 0 and ratio_G ≥ 1 − clip_low)
+      kl_r, H_r as above (per token)
+      row_loss_r = pg_r − entropy_coef·H_r + kl_coef·kl_r
+      g_r      = c · Σ_{j∈G} (−A_j · ratio_G · [active_j]) + kl_coef·(1 − exp(ref_r − logp_r))
+    loss, dlogits as above (a token mean; dlogits with this g_r)
+
+`ratio` holds ratio_G on every row of G, `clipped` is valid and not active_r, the statistics `ratio`, `approx_kl` and
+`clip_frac` are means over valid rows of ratio_G, expm1(s_G) − s_G and not active_r, and `group_stats` reports
+GROUP_STAT_NAMES per sequence (zeros for a sequence without a valid row, which contributes nothing). Groups of one row are
+the token-level loss exactly. With `"sum"` and the token-mean loss a group's surrogate is counted n_G times: harmless when
+every action has the same number of tokens (OpenVLA: 7), but with ragged groups longer actions weigh more — `"mean"`, or
+advantages scaled by 1 / n_G, if that is not wanted.
 """
 from __future__ import annotations
 
@@ -49,6 +73,8 @@ IGNORE_INDEX = -100
 STAT_NAMES = ("loss", "n_valid", "pg", "entropy", "kl", "clip_frac", "approx_kl", "ratio")
 # the per-row statistics (fp32 [rows, 8]): five reported values, then what the backward kernel needs
 ROW_STAT_NAMES = ("logp", "entropy", "ratio", "row_loss", "clipped", "m", "log_s", "g")
+# the per-sequence statistics of the action-level ratio (fp32 [groups, 4]): s_G, ratio_G, n_G, Σ_G logp
+GROUP_STAT_NAMES = ("log_ratio", "ratio", "n", "logp")
 
 
 @dataclass(frozen=True)
@@ -59,8 +85,16 @@ class PolicyLossConfig:
     entropy_coef: float = 0.0
     kl_coef: float = 0.0
     token_range: Optional[Tuple[int, int]] = None    # (first, count): the policy is over these tokens alone
+    ratio_level: str = "token"                       # "token": one ratio per token; "action": one per sequence's labelled tokens
+    ratio_norm: str = "sum"                          # action level: exp(Σ δ) ("sum") or exp(Σ δ / n_G) ("mean")
 
     def __post_init__(self):
+        if self.ratio_level not in ("token", "action"):
+            raise ValueError(f"PolicyLossConfig: ratio_level is 'token' or 'action', got {self.ratio_level!r}")
+        if self.ratio_norm not in ("sum", "mean"):
+            raise ValueError(f"PolicyLossConfig: ratio_norm is 'sum' or 'mean', got {self.ratio_norm!r}")
+        if self.ratio_norm == "mean" and self.ratio_level != "action":
+            raise ValueError("PolicyLossConfig: ratio_norm='mean' goes with ratio_level='action' (a token is its own mean)")
         if self.token_range is not None:
             try:
                 first, count = (int(v) for v in self.token_range)
@@ -107,13 +141,35 @@ class PolicyLossResult:
     loss: float
     stats: np.ndarray         # [8] fp64, STAT_NAMES
     dlogits: np.ndarray       # [rows, n] fp64
+    group_stats: Optional[np.ndarray] = None      # [groups, 4] fp64, GROUP_STAT_NAMES (action level only)
+
+
+def _group_sums(v, valid, group_rows: int):
+    """[rows] → ([groups] sums of v over each group's valid rows, accumulated in row order; [groups] valid counts)."""
+    groups = v.shape[0] // group_rows
+    sums, counts = np.zeros(groups), np.zeros(groups, dtype=np.int64)
+    for k in range(groups):
+        sl = slice(k * group_rows, (k + 1) * group_rows)
+        vk = v[sl][valid[sl]]
+        counts[k] = vk.size
+        if vk.size:
+            sums[k] = np.add.accumulate(vk)[-1]
+    return sums, counts
 
 
 def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cfg: Optional[PolicyLossConfig] = None,
-                ignore_index: int = IGNORE_INDEX) -> PolicyLossResult:
+                ignore_index: int = IGNORE_INDEX, group_rows: Optional[int] = None) -> PolicyLossResult:
+    """`group_rows`: rows per sequence, needed (and dividing the row count) with cfg.ratio_level == "action"; ignored at
+    token level."""
     cfg = cfg or PolicyLossConfig()
+    by_action = cfg.ratio_level == "action"
+    if by_action:
+        rows = np.shape(logits)[0]
+        if group_rows is None or int(group_rows) != group_rows or group_rows < 1 or rows % int(group_rows):
+            raise ValueError(f"policy_loss: ratio_level='action' needs group_rows >= 1 dividing the {rows} rows, got {group_rows!r}")
+        group_rows = int(group_rows)
     if cfg.token_range is not None:
-        return _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, cfg, ignore_index)
+        return _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, cfg, ignore_index, group_rows)
     l = np.asarray(logits, dtype=np.float64)
     tg = np.asarray(targets, dtype=np.int64)
     rows, n = l.shape
@@ -135,11 +191,22 @@ def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cf
     H = -(p * logp_all).sum(axis=1)               # p = 0 (underflow) times a finite logp is 0
     a = np.where(valid, tg, 0)
     logp = logp_all[np.arange(rows), a]
-    ratio = np.exp(logp - q)
+    lr = logp - q
+    group_stats = None
+    if by_action:                                 # every valid row takes its group's log-ratio s_G = c·Σ δ
+        sums, n_g = _group_sums(lr, valid, group_rows)
+        c_g = 1.0 / np.maximum(n_g, 1) if cfg.ratio_norm == "mean" else np.ones(len(n_g))
+        s_g = c_g * sums
+        lr = np.where(valid, np.repeat(s_g, group_rows), 0.0)
+        group_stats = np.stack([s_g, np.where(n_g > 0, np.exp(s_g), 0.0), n_g.astype(np.float64),
+                                _group_sums(logp, valid, group_rows)[0]], axis=1)
+    ratio = np.exp(lr)
     lo, hi = 1.0 - cfg.clip_low, 1.0 + cfg.clip_high
     pg = -np.minimum(ratio * A, np.clip(ratio, lo, hi) * A)
     active = ((A >= 0) & (ratio <= hi)) | ((A < 0) & (ratio >= lo))
     g = np.where(active, -A * ratio, 0.0)
+    if by_action:                                 # … and its group's surrogate gradient c·Σ_j −A_j·ratio_G·[active_j]
+        g = np.repeat(c_g * _group_sums(g, valid, group_rows)[0], group_rows)
     kl = np.zeros(rows)
     if ref is not None:
         d = ref - logp
@@ -155,14 +222,15 @@ def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cf
         dl[~valid] = 0.0
     zero = lambda v: np.where(valid, v, 0.0)
     mean = lambda v: float(v[valid].sum() / nv) if nv else 0.0
-    lr = logp - q
     stats = np.array([mean(row_loss), nv, mean(pg), mean(H), mean(kl), mean((~active).astype(np.float64)),
                       mean(np.expm1(lr) - lr), mean(ratio)], dtype=np.float64)
     return PolicyLossResult(logp=zero(logp), entropy=zero(H), ratio=zero(ratio), pg=zero(pg), kl=zero(kl), row_loss=zero(row_loss),
-                            clipped=valid & ~active, valid=valid, g=zero(g), loss=stats[0], stats=stats, dlogits=dl)
+                            clipped=valid & ~active, valid=valid, g=zero(g), loss=stats[0], stats=stats, dlogits=dl,
+                            group_stats=group_stats)
 
 
-def _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, cfg: PolicyLossConfig, ignore_index: int) -> PolicyLossResult:
+def _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, cfg: PolicyLossConfig, ignore_index: int,
+                       group_rows: Optional[int] = None) -> PolicyLossResult:
     """`policy_loss` on logits[:, first : first + count] with the targets shifted by `first`; dlogits widened with zeros."""
     import dataclasses
     first, count = cfg.token_range
@@ -177,7 +245,7 @@ def _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, 
                          f"(first at row {int(np.argmax(outside))}): that action has probability 0 under the restricted policy")
     sliced = np.asarray(logits)[:, first:first + count]           # only the range is looked at, also by the finiteness check
     res = policy_loss(sliced, np.where(valid, tg - first, ignore_index), advantages, old_logprobs, ref_logprobs,
-                      dataclasses.replace(cfg, token_range=None), ignore_index)
+                      dataclasses.replace(cfg, token_range=None), ignore_index, group_rows)
     dl = np.zeros((sliced.shape[0], n), dtype=np.float64)
     dl[:, first:first + count] = res.dlogits
     res.dlogits = dl

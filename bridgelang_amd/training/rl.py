@@ -1,6 +1,11 @@
 """Glue between rollouts (`sample_actions` / `score_actions`) and the policy-loss training step
 (`TrainStep(loss="policy")`): GRPO's group-normalised advantages, and the training batch of sampled action tokens.
-Host-side tensor layout only; the loop that uses it is the caller's."""
+Host-side tensor layout only; the loop that uses it is the caller's.
+
+`policy_batch` serves both ratio levels of the loss unchanged. It gives every sequence one advantage and labels on
+exactly its n action tokens, and those labelled tokens are what `PolicyLossConfig(ratio_level="action")` takes as the
+sequence's group: the action's ratio π(a)/π_old(a) is formed from the n `old_logprobs` of the row, and
+`TrainStep.action_stats()` reports it per sequence."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple

@@ -32,7 +32,7 @@ from ..engine import rope_tables
 from ..ops import (EPI_BIAS, EPI_BIAS_GELU_KEEP, EPI_F32, EPI_F32_BF16R, EPI_GELU_BWD, EPI_NONE, EPI_RES, EPI_SWIGLU_BWD,
                    EPI_SWIGLU_KEEP, Op)
 from ..weights import PackedGroup, VLAWeights, _block_view, _unpack
-from .policy_loss import STAT_NAMES, PolicyLossConfig
+from .policy_loss import GROUP_STAT_NAMES, STAT_NAMES, PolicyLossConfig
 from .sharding import ShardComm, ShardLayout, bucket_key, comm_order
 
 IGNORE_INDEX = -100
@@ -390,7 +390,9 @@ class TrainStep:
         fed by `set_policy_batch` after `set_batch`. Only the two ops at the loss boundary differ; everything below the
         logits, and every other option, is shared. With `policy.token_range=(first, count)` the two ops are the ranged
         entry points: the policy — and with it `token_logprobs()` and `policy_stats()` — is the softmax over that token range
-        alone, as rollouts drawn with `action_tokens_only=True` need, and dlogits is 0 outside it."""
+        alone, as rollouts drawn with `action_tokens_only=True` need, and dlogits is 0 outside it. With
+        `policy.ratio_level="action"` the forward's loss op is the grouped entry point: one importance ratio per sequence
+        (its labelled tokens are the action), reported by `action_stats()`; the backward plan is the same."""
         if loss not in ("ce", "policy"):
             raise ValueError(f"loss must be 'ce' or 'policy', got {loss!r}")
         if policy is not None and loss != "policy":
@@ -504,6 +506,8 @@ class TrainStep:
             self.advantages, self.old_logprob, self.ref_logprob = (z(Tn, dtype=torch.float32) for _ in range(3))
             self.row_stats, self.stats = z(Tn, 8, dtype=torch.float32), z(8, dtype=torch.float32)
             self.row_loss, self.mean_cnt = self.row_stats[:, 3], self.stats[:2]
+            if self.policy.ratio_level == "action":      # one group per sequence: its S rows
+                self.group_stats = z(B, 4, dtype=torch.float32)
             self._batch_len = prompt_len
         self.cos, self.sin = rope_tables(d.head_dim, d.max_pos, d.rope_theta, dev)
         # ---- backward scratch ----
@@ -1036,7 +1040,8 @@ class TrainStep:
         else:
             plan.append(T.policy_loss(self.logits, self.targets, self.advantages, self.old_logprob,
                                       self.ref_logprob if self.policy.kl_coef != 0.0 else None, self.row_stats, self.stats,
-                                      self.policy, IGNORE_INDEX, run=False))
+                                      self.policy, IGNORE_INDEX, run=False, group_rows=self.S,
+                                      group_stats=getattr(self, "group_stats", None)))
         return plan
 
     def _layer_forward(self, l: int, with_down: bool = True) -> List[Op]:
@@ -1422,6 +1427,13 @@ class TrainStep:
         if self.policy is None:
             raise RuntimeError("policy_stats needs TrainStep(loss='policy')")
         return {name: self.stats[i] for i, name in enumerate(STAT_NAMES)}
+
+    def action_stats(self) -> Dict[str, torch.Tensor]:
+        """The per-sequence statistics of the last forward under policy.ratio_level="action" (policy_loss.GROUP_STAT_NAMES)
+        as device tensors [B]: the action's log-ratio, its ratio, its number of labelled tokens and its log π."""
+        if self.policy is None or self.policy.ratio_level != "action":
+            raise RuntimeError("action_stats needs TrainStep(loss='policy') with policy.ratio_level='action'")
+        return {name: self.group_stats[:, i] for i, name in enumerate(GROUP_STAT_NAMES)}
 
     def token_logprobs(self) -> torch.Tensor:
         """log π(token) of the last forward at the labelled positions, [B, l] aligned with `labels` (0 elsewhere): the row

@@ -350,6 +350,26 @@ int bl_policy_loss_backward_range_f32(const float* logits, int64_t ld, int32_t r
                                       int64_t ignore_index, const float* row_stats, const float* stats, float temperature,
                                       float entropy_coef, bl_bf16* dlogits, int64_t ldd, int32_t vocab_first,
                                       int32_t vocab_count, void* stream);
+/* bl_policy_loss_range_f32 with the importance ratio taken per ACTION instead of per token (training/policy_loss.py with
+ * PolicyLossConfig.ratio_level = "action"). Rows [k*group_rows, (k+1)*group_rows) are one sequence and its valid rows are
+ * one group G: s_G = c * sum_G (logp - old_logprob), c = 1 (ratio_norm 0, sum) or 1 / n_G (ratio_norm 1, mean),
+ * ratio_G = exp(s_G) is clipped once for the group, and every valid row gets
+ *   row_stats ratio = ratio_G, clipped = its advantage's side of the clip, row_loss with the group's surrogate, and
+ *   d row_loss / d logp = c * sum_{j in G} (-A_j * ratio_G * [active_j]) - kl_coef * expm1(ref_logprob - logp).
+ * Entropy and KL stay per token and loss stays the mean over valid rows. stats keeps its layout: mean ratio, clipped
+ * fraction and mean (ratio - 1) - log ratio are over valid rows of the group values. group_stats fp32 [rows / group_rows, 4]
+ * = (s_G, ratio_G, n_G, sum_G logp), zeros for a sequence without a valid row. Three launches on `stream` (rows, groups,
+ * statistics), deterministic. (vocab_first, vocab_count) = (0, n) is the unranged loss. There is no grouped backward:
+ * bl_policy_loss_backward_f32 / bl_policy_loss_backward_range_f32 read H, max z, log sum and d row_loss / d logp from
+ * row_stats and n_valid from stats[1], all of which this forward leaves in place. Constraints as
+ * bl_policy_loss_range_f32; group_stats NULL is BL_E_ARG; group_rows <= 0, rows % group_rows != 0 or ratio_norm outside
+ * {0, 1} is BL_E_SHAPE; nothing is launched on a rejection. */
+int bl_policy_loss_grouped_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                               int64_t ignore_index, const float* advantages, const float* old_logprob,
+                               const float* ref_logprob, float temperature, float clip_low, float clip_high,
+                               float entropy_coef, float kl_coef, float* row_stats, float* stats, int32_t vocab_first,
+                               int32_t vocab_count, int32_t group_rows, int32_t ratio_norm, float* group_stats,
+                               void* stream);
 /* LlamaRMSNorm backward: dx = rstd*(w*dy - xhat*mean(w*dy*xhat)) [+ dres: the residual stream's own gradient];
  * dw[j] = sum_rows dy*bf16(xhat). partial_ws >= ceil(rows/64)*dim floats. */
 int bl_rmsnorm_backward_bf16(const bl_bf16* x, int64_t ldx, const bl_bf16* w, const bl_bf16* dy, int64_t lddy,
