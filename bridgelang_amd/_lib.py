@@ -50,6 +50,13 @@ class BatchOpDesc(C.Structure):
                 ("src", C.c_void_p), ("dst", C.c_void_p), ("scale", C.c_float), ("pad", C.c_int32)]
 
 
+class LoraMergeDesc(C.Structure):
+    """One entry of bl_lora_merge_batched_bf16's device table (struct LoraMergeEntry in csrc/lora_merge.hip)."""
+    _fields_ = [("w", C.c_void_p), ("A", C.c_void_p), ("B", C.c_void_p), ("out", C.c_void_p), ("scale", C.c_float),
+                ("n", C.c_int32), ("k", C.c_int32), ("R", C.c_int32), ("rp", C.c_int32), ("members", C.c_int32),
+                ("interleave", C.c_int32), ("n_items", C.c_int32), ("first_item", C.c_int64)]
+
+
 class AttnDesc(C.Structure):
     """struct bl_attn_desc."""
     _fields_ = [
@@ -133,6 +140,8 @@ SIGNATURES = {
     "bl_gemm_tn_small_bf16": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _f32, _vp, _i64, _vp]),
     "bl_scale_bf16": (C.c_int, [_vp, _f32, _vp, _i64, _vp]),
     "bl_lora_block_mask_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "bl_lora_merge_bf16": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "bl_lora_merge_batched_bf16": (C.c_int, [_vp, _i32, _vp]),
     "bl_axpy_f32": (C.c_int, [_vp, _vp, _f32, _i64, _vp]),
     "bl_cast_f32_bf16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "bl_cast_bf16_f32": (C.c_int, [_vp, _vp, _i64, _vp]),

@@ -210,8 +210,11 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
 
     def engine(self, batch: int, prompt_len: int, n_new: int = 7, padded: bool = False, cached: bool = False,
                sample: bool = False, score: bool = False, score_range: Optional[Tuple[int, int]] = None,
-               vocab_range: Optional[Tuple[int, int]] = None) -> OpenVLAEngine:
-        """`cached=True`: the engine behind a `forward(..., use_cache=True)` KV-cache handle — keyed apart from the engines
+               vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None) -> OpenVLAEngine:
+        """`use_adapters` (see `attach_adapters`): None = the adapted weights if adapters are attached, False = the base
+        model, True = the adapted weights or an error. Part of the cache key; adapted engines are built over
+        `lora.adapted_weights()`.
+        `cached=True`: the engine behind a `forward(..., use_cache=True)` KV-cache handle — keyed apart from the engines
         `predict_action` / `generate` use, so an interleaved action prediction of the same shape does not invalidate the
         caller's cache (each kind has its own LRU slot; a second cached prefill of the same shape still does).
         `score=True` (with `score_range`) is a kind of its own again: the engines that score given tokens. `vocab_range`
@@ -219,11 +222,76 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         fp8 = bool(getattr(self, "fp8", False))       # `model.fp8 = True`: W8A8 e4m3 Llama prefill projections (extension)
         if vocab_range is not None:
             vocab_range = (int(vocab_range[0]), int(vocab_range[1]))
+        adapted = self._resolve_adapters(use_adapters)
+        if adapted and fp8:
+            raise NotImplementedError("fp8=True with attached adapters: the derived e4m3 weight copies would go stale on every "
+                                      "refresh of the adapted weights")
+        weights = self._adapters.adapted_weights() if adapted else self.weights
         key = (batch, prompt_len, n_new, fp8, padded, cached, sample) + (("score", score_range) if score else ()) + \
-            (("vocab", vocab_range) if vocab_range is not None else ())
+            (("vocab", vocab_range) if vocab_range is not None else ()) + (("adapted",) if adapted else ())
         return self._lru(self._engines, key,
-                         lambda: OpenVLAEngine(self.weights, batch, prompt_len, n_new=n_new, fp8=fp8 and not padded, padded=padded,
+                         lambda: OpenVLAEngine(weights, batch, prompt_len, n_new=n_new, fp8=fp8 and not padded, padded=padded,
                                                sample=sample, score=score, score_range=score_range, vocab_range=vocab_range))
+
+    # ---- LoRA adapters: inference under merged weights beside the frozen base (training/lora.py) ----
+    _adapters = None           # the attached training.lora.LoraAdapters
+
+    def _resolve_adapters(self, use_adapters: Optional[bool]) -> bool:
+        if use_adapters and self._adapters is None:
+            raise ValueError("use_adapters=True, but no adapters are attached (attach_adapters / load_adapter)")
+        return self._adapters is not None and use_adapters is not False
+
+    def attach_adapters(self, lora) -> "PrismaticForConditionalGeneration":
+        """Run `engine` / `generate` / `predict_action` / `sample_actions` / `score_actions` under `lora` (a
+        training.lora.LoraAdapters over THIS model's weights): their engines read `lora.adapted_weights()`, the adapters
+        merged into a second set of packed GEMM weights (W' = bf16(W + bf16(s·B)·A), refreshed here and by `lora.refresh()` —
+        or after every optimizer step by `TrainStep(..., lora=lora, refresh_adapted=True)`). `use_adapters=False` on those
+        calls is the base policy, whose weights are never written. `forward()` (the all-position HF branches) reads the
+        base weights."""
+        if lora.w is not self.weights:
+            raise ValueError("attach_adapters: the adapters were built over another model's weights")
+        if self._adapters is not None and self._adapters is not lora:
+            self.detach_adapters()
+        self._adapters = lora
+        if self.weights.embed.is_cuda:       # a CPU-allocated model (layout tests) runs no kernel: its adapted weights stay copies
+            lora.refresh()
+        return self
+
+    def detach_adapters(self) -> "PrismaticForConditionalGeneration":
+        """Back to the base model; the engines built over the adapted weights are dropped."""
+        self._adapters = None
+        for key in [k for k in self._engines if "adapted" in k]:
+            del self._engines[key]
+        return self
+
+    def load_adapter(self, adapter_dir, seed: int = 0) -> "PrismaticForConditionalGeneration":
+        """Attach the PEFT-named adapter that `training.finetune.save_checkpoint` writes (finetune.py:322-330):
+        `adapter_model.safetensors` (base_model.model.<module>.lora_{A,B}.weight) + `adapter_config.json`, from which `r`,
+        `lora_alpha` and `lora_dropout` are taken. A module this model has no GEMM group for, or a module of an adapted
+        group that the file lacks, is a ValueError."""
+        import json
+        from pathlib import Path
+        from safetensors.torch import load_file
+        from ...training.lora import LoraAdapters
+        d = Path(adapter_dir)
+        cfg_path, st_path = d / "adapter_config.json", d / "adapter_model.safetensors"
+        if not cfg_path.is_file() or not st_path.is_file():
+            raise FileNotFoundError(f"{d}: adapter_config.json and adapter_model.safetensors expected")
+        cfg = json.loads(cfg_path.read_text())
+        if cfg.get("peft_type", "LORA") != "LORA" or "r" not in cfg:
+            raise ValueError(f"{cfg_path}: a PEFT LoRA config with `r` expected")
+        r = int(cfg["r"])
+        lora = LoraAdapters(self.weights, r=r, alpha=cfg.get("lora_alpha"), seed=seed, dropout=float(cfg.get("lora_dropout", 0.0)))
+        sd = load_file(str(st_path))
+        known = {f"base_model.model.{mod}.lora_{ab}.weight" for ad in lora.adapters for mod in ad.modules for ab in "AB"}
+        unknown = sorted(k for k in sd if k not in known)
+        if unknown:
+            raise ValueError(f"{st_path}: {len(unknown)} tensors of modules this model has no adapter group for, e.g. {unknown[:3]}")
+        missing = sorted(known - set(sd))
+        if missing:
+            raise ValueError(f"{st_path}: {len(missing)} adapter tensors are missing, e.g. {missing[:3]}")
+        lora.load_state_dict(sd)
+        return self.attach_adapters(lora)
 
     # ---- forward: the reference's three branches (modeling_prismatic.py:322-415) ----
     cache_new_tokens = 7       # tokens a `forward(..., use_cache=True)` KV cache is sized for (prefill token + 6 cached steps)
@@ -307,8 +375,9 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
                  attention_mask: Optional[torch.Tensor] = None, do_sample: bool = False, use_cache: bool = True,
                  sampling: Optional[SamplingParams] = None, return_weights: bool = False,
                  forced_ids: Optional[torch.Tensor] = None, score_range: Optional[Tuple[int, int]] = None,
-                 vocab_range: Optional[Tuple[int, int]] = None, **_: Any):
-        """Greedy decoding, returns [B, L + max_new_tokens] like GenerationMixin (prompt ‖ new tokens). `use_cache` is
+                 vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None, **_: Any):
+        """`use_adapters`: see `engine` (None: the attached adapters if any; False: the base model).
+        Greedy decoding, returns [B, L + max_new_tokens] like GenerationMixin (prompt ‖ new tokens). `use_cache` is
         accepted and ignored: the KV cache is always used (use_cache=False in the fork's demo re-runs the vision towers
         7 times, run_openvla_demo.py:43 — same result, 7× the work). A batch whose attention_mask has zeros is taken as
         RIGHT-padded prompts: pads are hidden from attention and every sequence continues from its own last token.
@@ -336,7 +405,8 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         if forced_ids is not None:
             forced = torch.as_tensor(forced_ids).to(self.device, torch.int64)
             padded = attention_mask is not None and not bool(attention_mask.bool().all())
-            eng = self.engine(B, L, max_new_tokens, padded=padded, score=True, score_range=score_range, vocab_range=vocab_range)
+            eng = self.engine(B, L, max_new_tokens, padded=padded, score=True, score_range=score_range, vocab_range=vocab_range,
+                              use_adapters=use_adapters)
             eng.set_sampling(sampling if sampling is not None else SamplingParams())
             if padded:
                 eng.set_forced_ids(forced)
@@ -352,14 +422,14 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             sampling = SamplingParams(temperature=0.0, seed=0)
         sample = sampling is not None
         if attention_mask is not None and not bool(attention_mask.bool().all()):
-            eng = self.engine(B, L, max_new_tokens, padded=True, sample=sample, vocab_range=vocab_range)
+            eng = self.engine(B, L, max_new_tokens, padded=True, sample=sample, vocab_range=vocab_range, use_adapters=use_adapters)
             if sample:
                 eng.set_sampling(sampling)
             eng.set_padded_inputs(ids, pv, attention_mask)
             eng.run_eager()
             new = eng.gen_ids.t()
         else:
-            eng = self.engine(B, L, max_new_tokens, sample=sample, vocab_range=vocab_range)
+            eng = self.engine(B, L, max_new_tokens, sample=sample, vocab_range=vocab_range, use_adapters=use_adapters)
             new = eng.generate(ids, pv, sampling)
         out = torch.cat([ids, new], dim=1)
         return (out, eng.gen_wt.permute(1, 0, 2).clone()) if return_weights else out
@@ -384,13 +454,15 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         return int(self.vocab_size) - n_bins, n_bins
 
     def predict_action(self, input_ids: Optional[torch.LongTensor] = None, unnorm_key: Union[str, Sequence[Optional[str]], None] = None,
-                       action_tokens_only: bool = False, **kwargs: Any) -> np.ndarray:
-        """ids → 7 greedy action tokens → bin centres → un-normalised 7-DoF action (reference :506-536). `unnorm_key` may
+                       action_tokens_only: bool = False, use_adapters: Optional[bool] = None, **kwargs: Any) -> np.ndarray:
+        """`use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy).
+        ids → 7 greedy action tokens → bin centres → un-normalised 7-DoF action (reference :506-536). `unnorm_key` may
         be a list with one key per sequence (extension: a server batch that mixes datasets of one action dimension);
         the result is then always [B, n]. `action_tokens_only=True` decodes under the policy restricted to
         `action_token_range()`: with `sampling=` every draw is an action token, without it the call is constrained greedy
         decoding (the argmax over the action tokens)."""
         input_ids = input_ids.to(self.device)
+        kwargs["use_adapters"] = use_adapters
         if action_tokens_only:
             kwargs["vocab_range"] = self.action_token_range()
         keys = list(unnorm_key) if isinstance(unnorm_key, (list, tuple)) else None
@@ -435,8 +507,10 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
     def sample_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor,
                        unnorm_key: Union[str, Sequence[Optional[str]], None] = None, sampling: Optional[SamplingParams] = None,
                        num_samples: int = 1, attention_mask: Optional[torch.Tensor] = None,
-                       action_tokens_only: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """`num_samples` sampled actions per sequence with their log-probabilities (RL rollouts, best-of-N, uncertainty):
+                       action_tokens_only: bool = False,
+                       use_adapters: Optional[bool] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy).
+        `num_samples` sampled actions per sequence with their log-probabilities (RL rollouts, best-of-N, uncertainty):
         → (actions [B, num_samples, n], token_ids int64 [B, num_samples, n], logprobs fp64 [B, num_samples, n]). The batch
         is repeated `num_samples` times (several copies per engine run while the run stays within 16 sequences); copy j of a sequence with seed s draws with
         seed s + 0x9E3779B97F4A7C15·j mod 2^64 (`sampling.derive_seed`), so copy j equals that one call. logprobs[b, j, t] =
@@ -460,7 +534,8 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             a, tok, wt = self.predict_action(input_ids.repeat(c, 1), keys * c if keys is not None else unnorm_key,
                                              pixel_values=pixel_values.repeat(c, 1, 1, 1),
                                              attention_mask=None if attention_mask is None else attention_mask.repeat(c, 1),
-                                             sampling=sp, return_weights=True, action_tokens_only=action_tokens_only)
+                                             sampling=sp, return_weights=True, action_tokens_only=action_tokens_only,
+                                             use_adapters=use_adapters)
             acts.append(np.asarray(a).reshape(c, B, -1))
             toks.append(tok.reshape(c, B, -1))
             lps.append(logprob(wt).reshape(c, B, -1))
@@ -469,8 +544,10 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
     def score_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor, token_ids=None, actions=None,
                       unnorm_key: Optional[str] = None, sampling: Optional[SamplingParams] = None,
                       attention_mask: Optional[torch.Tensor] = None, return_bins: bool = False,
-                      action_tokens_only: bool = False):
-        """Log-probabilities of GIVEN actions under the policy `sample_actions` draws from (a PPO / GRPO learner's
+                      action_tokens_only: bool = False, use_adapters: Optional[bool] = None):
+        """`use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy — with adapters
+        attached, an RL learner's reference policy).
+        Log-probabilities of GIVEN actions under the policy `sample_actions` draws from (a PPO / GRPO learner's
         log π(a | s), a reranker's score of a planner's proposal): exactly one of `token_ids` (int64) and `actions`
         (tokenised by `token_ids_from_actions` with `unnorm_key`), shaped [B, n] or [B, K, n] with K candidates per
         sequence → logprobs fp64 [B, K, n] (K = 1 for [B, n]), -inf where a token lies outside the support that
@@ -510,7 +587,8 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             forced = torch.from_numpy(np.ascontiguousarray(tok[:, j0:j0 + c].transpose(1, 0, 2)).reshape(c * B, n))
             out = self.generate(ids.repeat(c, 1), n, pixel_values=pixel_values.repeat(c, 1, 1, 1),
                                 attention_mask=None if m is None else m.repeat(c, 1), sampling=sp, forced_ids=forced,
-                                score_range=rng, vocab_range=self.action_token_range() if action_tokens_only else None)
+                                score_range=rng, vocab_range=self.action_token_range() if action_tokens_only else None,
+                                use_adapters=use_adapters)
             wts.append(out[1].cpu().numpy().reshape(c, B, n, 2))
             if return_bins:
                 bins.append(out[2].cpu().numpy().reshape(c, B, n, n_bins))

@@ -126,7 +126,11 @@ class OpenVLAServer:
     `predict_action(..., sampling=SamplingParams(per-row arrays), return_weights=True) -> (actions, token ids, wt [B, 7, 2])`.
     `sample=True, action_tokens_only=True` draws (and, for a greedy request, takes the argmax) under the policy restricted
     to `vla.action_token_range()`: every answered action was decoded from action tokens, and a reported log-probability
-    is the one under that restricted policy."""
+    is the one under that restricted policy.
+    `adapter=` (a directory written by `training.finetune.save_checkpoint`, or a training.lora.LoraAdapters over `vla`'s
+    weights) serves the model under those LoRA adapters: they are attached (`vla.load_adapter` / `vla.attach_adapters`)
+    before any pipeline is built, and the pipelines read the adapted weights. A learner that refreshes the adapted weights
+    while the server runs must let the pipelines drain first (`LoraAdapters.refresh`, ordering contract)."""
 
     _BASE_KEYS = ("image", "instruction", "unnorm_key")
     _SAMPLING_KEYS = ("temperature", "top_k", "top_p", "seed", "return_logprob")
@@ -134,8 +138,13 @@ class OpenVLAServer:
     def __init__(self, vla: Any, processor: Any, openvla_path: Union[str, Path] = "openvla/openvla-7b",
                  max_batch: int = 16, max_wait_ms: float = 2.0, norm_stats_path: Optional[Union[str, Path]] = None,
                  pipeline_batch: Optional[int] = None, max_pipelines: int = 2, pad_to: Optional[int] = None,
-                 sample: bool = False, action_tokens_only: bool = False):
+                 sample: bool = False, action_tokens_only: bool = False, adapter: Any = None):
         self.vla, self.processor, self.openvla_path = vla, processor, str(openvla_path)
+        if adapter is not None:
+            if isinstance(adapter, (str, Path)):
+                vla.load_adapter(adapter)
+            else:
+                vla.attach_adapters(adapter)
         self.sample = bool(sample)
         if action_tokens_only and not sample:
             raise ValueError("action_tokens_only goes with sample=True")
@@ -272,10 +281,15 @@ class OpenVLAServer:
     def _live(self) -> List[Tuple[Any, Dict[int, Any]]]:
         return ([self._pad_pipe] if self._pad_pipe is not None else []) + list(self._pipes.values())
 
+    def _weights(self):
+        """The weights the pipelines read: the adapted ones when adapters are attached to the model."""
+        lora = getattr(self.vla, "_adapters", None)
+        return lora.adapted_weights() if lora is not None else self.vla.weights
+
     def _padded_pipe(self):
         from .pipeline import StaggeredDecodePipeline
         if self._pad_pipe is None:
-            pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, self.pad_to, padded=True, sample=self.sample,
+            pipe = StaggeredDecodePipeline(self._weights(), self.pipeline_batch, self.pad_to, padded=True, sample=self.sample,
                                            vocab_range=self.vocab_range)
             pipe.capture()
             self.pipelines_built += 1
@@ -293,7 +307,7 @@ class OpenVLAServer:
             del self._pipes[old_len]
             del old
             torch.cuda.empty_cache()
-        pipe = StaggeredDecodePipeline(self.vla.weights, self.pipeline_batch, L, sample=self.sample, vocab_range=self.vocab_range)
+        pipe = StaggeredDecodePipeline(self._weights(), self.pipeline_batch, L, sample=self.sample, vocab_range=self.vocab_range)
         pipe.capture()
         self.pipelines_built += 1
         self._pipes[L] = (pipe, {})

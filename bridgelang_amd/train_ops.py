@@ -405,6 +405,79 @@ def batched(entries, device, run: bool = True) -> Op:
     return _op("bl_batched_ops", (table.data_ptr(), block_start.data_ptr(), len(descs), tot), (table, block_start) + keep, run, nbytes=nbytes)
 
 
+# ---- LoRA merge: W' = bf16(W + bf16(s·B)·A) on the packed layout (csrc/lora_merge.hip; training/lora.py::merged_reference) ----
+LORA_MERGE_MAX_SPAN = 128      # ranks one row may see (LM_MAX_R): two interleaved members of padded rank 64
+
+
+def lora_merge_items(n: int, k: int, R: int, rp: int, members: int, interleave: bool) -> int:
+    """Work items of one group in the merge kernel (lm_shape in csrc/lora_merge.hip): four k-strips x up to 16 row tiles
+    each; stacked members that own whole 16-row tiles are walked member by member (their own rank block only)."""
+    skip = (not interleave) and members > 1 and n % (16 * members) == 0
+    meff = members if skip else 1
+    tpm = (n // 16) // meff
+    return ((k // 32 + 3) // 4) * meff * ((tpm + 15) // 16)
+
+
+def _lora_merge_check(w_packed, A, B, out_packed, rp: int, members: int, interleave: bool):
+    R, k = A.shape
+    n = B.shape[0]
+    for t, what in ((w_packed, "w_packed"), (A, "A"), (B, "B"), (out_packed, "out_packed")):
+        if not _bf16(t, what).is_contiguous():
+            raise ValueError(f"lora_merge: {what} must be contiguous")
+    if B.shape[1] != R or R != rp * members or n % 16 or k % 32 or R % 32 or rp % 32 or n % members:
+        raise ValueError(f"lora_merge: A{tuple(A.shape)} B{tuple(B.shape)} rp={rp} members={members}")
+    if w_packed.numel() != n * k or out_packed.numel() != n * k:
+        raise ValueError(f"lora_merge: packed weights of {n} x {k} elements expected")
+    skip = (not interleave) and members > 1 and n % (16 * members) == 0
+    if (rp if skip else R) > LORA_MERGE_MAX_SPAN:
+        raise ValueError(f"lora_merge: a row sees more than {LORA_MERGE_MAX_SPAN} ranks")
+    if any(t.data_ptr() & 15 for t in (w_packed, A, B, out_packed)):
+        raise ValueError("lora_merge: 16-byte aligned tensors")
+    lo, hi = w_packed.data_ptr(), out_packed.data_ptr()
+    if lo < hi + 2 * n * k and hi < lo + 2 * n * k:
+        raise ValueError("lora_merge: out_packed must not overlap w_packed")
+    return n, k, R
+
+
+def lora_merge(w_packed, A, B, scale: float, out_packed, rp: int, members: int = 1, interleave: bool = False, run: bool = True) -> Op:
+    """out_packed = packed bf16(W + bf16(scale·B)·A) from packed W [n/16, k/32, 64, 8], A [R, k], B [n, R] (bl_lora_merge_bf16).
+    Shapes are the library's to check (error codes); only dtypes / devices are checked here."""
+    R, k = A.shape
+    n = B.shape[0]
+    return _op("bl_lora_merge_bf16",
+               (_bf16(w_packed, "w_packed").data_ptr(), _bf16(A, "A").data_ptr(), _bf16(B, "B").data_ptr(), float(scale),
+                _bf16(out_packed, "out_packed").data_ptr(), n, k, R, rp, members, int(interleave)), (w_packed, A, B, out_packed), run,
+               nbytes=4.0 * n * k, flops=2.0 * n * k * R)
+
+
+def be_lora_merge(w_packed, A, B, scale: float, out_packed, rp: int, members: int = 1, interleave: bool = False):
+    """Table entry of `lora_merge_batched`: the work of `lora_merge`, validated here (the device table cannot be)."""
+    from ._lib import LoraMergeDesc
+    n, k, R = _lora_merge_check(w_packed, A, B, out_packed, rp, members, interleave)
+    d = LoraMergeDesc(w=w_packed.data_ptr(), A=A.data_ptr(), B=B.data_ptr(), out=out_packed.data_ptr(), scale=float(scale), n=n, k=k,
+                      R=R, rp=rp, members=members, interleave=int(interleave),
+                      n_items=lora_merge_items(n, k, R, rp, members, interleave), first_item=0)
+    return d, (w_packed, A, B, out_packed)
+
+
+def lora_merge_batched(entries, device, run: bool = False) -> Op:
+    """ONE launch (bl_lora_merge_batched_bf16) for the table entries made by be_lora_merge: every adapted group of a model.
+    The entries must be independent (no entry reads what another one writes). Bit-identical to one `lora_merge` per entry."""
+    import numpy as np
+    from ._lib import LoraMergeDesc
+    if not entries:
+        raise ValueError("lora_merge_batched: no entries")
+    descs, tot = [e[0] for e in entries], 0
+    for d in descs:
+        d.first_item = tot
+        tot += d.n_items
+    arr = (LoraMergeDesc * len(descs))(*descs)
+    table = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(device)
+    keep = tuple(t for e in entries for t in e[1])
+    return _op("bl_lora_merge_batched_bf16", (table.data_ptr(), len(descs)), (table,) + keep, run,
+               nbytes=float(sum(4 * d.n * d.k for d in descs)), flops=float(sum(2 * d.n * d.k * d.R for d in descs)))
+
+
 def cast(src: torch.Tensor, dst: torch.Tensor, run: bool = True) -> Op:
     """fp32 → bf16 (round to nearest even) or bf16 → fp32 of flat contiguous buffers (gradient wire format)."""
     assert src.is_contiguous() and dst.is_contiguous() and src.numel() == dst.numel()

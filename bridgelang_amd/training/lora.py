@@ -19,16 +19,32 @@ dA = dtᵀ·x through the small-output TN GEMM (bl_gemm_tn_small_bf16: dy / x re
 `lora_dropout` = p > 0 (round 4): t = dropout(x)·Aᵀ from a masked copy of x (bl_dropout_bf16: counter-based mask, recomputed in
 the backward pass), dA = dtᵀ·dropout(x), and the fused input gradient dy·W + dt·A is corrected to dy·W + mask/(1-p) ⊙ (dt·A)
 with u = dt·A from one more rank-R GEMM (bl_dropout_grad_fix_bf16). p = 0 plans are unchanged.
+
+Inference under the adapters: merged weights (the reference deploys LoRA with `merge_and_unload()` into the bf16 base,
+finetune.py:331-341). `merged_reference` is the definition, per packed group with logical [n, k] matrix W:
+    sB      = bf16(fp32(s) · B_all)               the operand the learner multiplies by (be_pack(scale = s): fp32 product, one RNE)
+    Δ[n,k]  = Σ_r sB[n,r] · A_all[r,k]            exact products, fp64 sum
+    W'[n,k] = bf16_rne(W[n,k] + Δ[n,k])           ONE rounding;  W'[n,k] = W[n,k] (same bits) where Δ[n,k] == 0
+  * B = 0 or s = 0 gives W' = W bit for bit (PEFT's initial state; the Δ == 0 rule also keeps a −0 of W).
+  * An update below half a bf16 ulp of W is absorbed: inherent to merging, and the same as the reference's deployment — the
+    learner's own forward (one rounding of the OUTPUT) still sees such an update, the merged model does not.
+  * K-padding columns stay 0, because A's padding columns are 0.
+`bl_lora_merge_bf16` (csrc/lora_merge.hip) computes it on the packed layout with Δ accumulated in fp32 on the MFMA and W + Δ
+formed in fp32: identical where those sums are exact, else within the fp32 accumulation error of Δ plus a possible flip of
+the final rounding next to a tie (tests/test_lora_merge_gpu.py states the bound). `adapted_weights()` is a second set of
+packed weights beside the frozen base (`VLAWeights.adapted_view`), `refresh()` the ONE batched launch that rewrites it from
+the live A / B; the base stays resident and untouched — an RL learner's reference policy.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from .. import ops
-from ..weights import PackedGroup, VLAWeights
+from ..weights import PackedGroup, VLAWeights, _pack, _unpack
 
 RP = 64          # padded rank
 
@@ -57,6 +73,33 @@ class Adapter:
             return torch.arange(out) * m + j
         base = (self.group.n // m) * j if self.mode == "concat" else 0
         return torch.arange(out) + base
+
+
+def bf16_rne_bits(x) -> np.ndarray:
+    """fp64 → bf16 bit patterns (uint16) with ONE round-to-nearest-even (torch's double → bfloat16 goes through fp32: two
+    roundings). Finite values inside the bf16 normal range."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    assert np.isfinite(x).all()
+    as_f64 = lambda bits: bits.astype(np.uint32).view(np.float32).astype(np.float64)
+    lo = np.ascontiguousarray(x.astype(np.float32)).view(np.uint32) & np.uint32(0xFFFF0000)     # a bf16 value next to x …
+    lo = np.where(np.abs(as_f64(lo)) > np.abs(x), lo - np.uint32(0x10000), lo).astype(np.uint32)   # … not above |x| (fp32 may round up)
+    hi = (lo + np.uint32(0x10000)).astype(np.uint32)                                              # the next one away from zero
+    d_lo, d_hi = np.abs(x - as_f64(lo)), np.abs(as_f64(hi) - x)                                  # both differences are exact
+    up = (d_hi < d_lo) | ((d_hi == d_lo) & (((lo >> np.uint32(16)) & np.uint32(1)) == 1))
+    return (np.where(up, hi, lo) >> np.uint32(16)).astype(np.uint16)
+
+
+def merged_reference(W: torch.Tensor, A: torch.Tensor, B: torch.Tensor, s: float, exact: bool = False):
+    """The definition of the merge for one group (module docstring): logical W [n, k], A_all [R, k], B_all [n, R] (bf16, any
+    device) and s = alpha / r → W' bf16 [n, k] on the CPU; `exact=True` → (W', W + Δ in fp64, sB bf16)."""
+    W, A, B = (t.detach().cpu() for t in (W, A, B))
+    assert W.dtype == A.dtype == B.dtype == torch.bfloat16
+    sB = (B.float() * float(np.float32(s))).to(torch.bfloat16)
+    delta = sB.double() @ A.double()
+    total = W.double() + delta
+    bits = torch.from_numpy(bf16_rne_bits(total.numpy()).view(np.int16).copy())
+    out = torch.where(delta == 0, W.contiguous().view(torch.int16), bits).view(torch.bfloat16)
+    return (out, total, sB) if exact else out
 
 
 class LoraAdapters:
@@ -92,6 +135,8 @@ class LoraAdapters:
             ad.index = len(self.adapters)
             self.adapters.append(ad)
             self.by_packed[g.packed.data_ptr()] = ad
+        self._adapted: Optional[VLAWeights] = None       # adapted_weights(): built on first use
+        self._refresh_ops: Optional[List[ops.Op]] = None
         self.init_gaussian(seed)
 
     def get(self, packed: torch.Tensor) -> Optional[Adapter]:
@@ -140,8 +185,8 @@ class LoraAdapters:
 
     def repack(self) -> None:
         for ad in self.adapters:
-            ops.pack_weight(ad.A, ad.A_p)
-            ops.pack_weight(ad.B, ad.B_p)
+            _pack(ad.A, ad.A_p)
+            _pack(ad.B, ad.B_p)
 
     def plain_units(self) -> List[Tuple[str, torch.Tensor, bool, str]]:
         """(name, live bf16 tensor, weight-decayed, bucket) for the ParamStore: finetune.py:188 builds one AdamW group
@@ -168,3 +213,35 @@ class LoraAdapters:
                 wt = sd[mod + ".weight"]
                 sd[mod + ".weight"] = (wt.float() + self.scaling * (b @ a)).to(wt.dtype)
         return sd
+
+    # ---- inference under the adapters: merged weights beside the frozen base (module docstring) ----
+    def merged_reference(self, ad: Adapter) -> torch.Tensor:
+        """W' bf16 [n, k] (CPU) of one adapter's group from the live A / B: the specification `refresh()` is tested against."""
+        return merged_reference(_unpack(ad.group.packed), ad.A, ad.B, self.scaling)
+
+    def adapted_weights(self) -> VLAWeights:
+        """`self.w.adapted_view(<every adapted group>)`, built once: the weights of the model WITH the adapters. They hold
+        copies of the base until the first `refresh()`."""
+        if self._adapted is None:
+            self._adapted = self.w.adapted_view([ad.group for ad in self.adapters])
+        return self._adapted
+
+    def refresh_ops(self) -> List[ops.Op]:
+        """The prepared refresh: ONE `bl_lora_merge_batched_bf16` launch over all adapted groups (replayable, graph-capturable)."""
+        from .. import train_ops as T
+        view = self.adapted_weights()
+        if self._refresh_ops is None:
+            index = {id(g): i for i, g in enumerate(self.w.groups)}
+            entries = [T.be_lora_merge(ad.group.packed, ad.A, ad.B, self.scaling, view.groups[index[id(ad.group)]].packed, RP,
+                                       len(ad.modules), ad.mode == "interleave") for ad in self.adapters]
+            self._refresh_ops = [T.lora_merge_batched(entries, self.w.embed.device, run=False)]
+        return self._refresh_ops
+
+    def refresh(self) -> None:
+        """Rewrite `adapted_weights()` from the live A / B and the frozen base: W' = bf16(W + bf16(s·B)·A) per group.
+        Ordering contract: this is an op on the CURRENT stream, ordered like any other launch there. Engines that read the
+        adapted weights on that stream (`predict_action`, `sample_actions`, `score_actions`, `OpenVLAEngine`) see the new
+        weights from their next run on; a `StaggeredDecodePipeline` has batches in flight across calls and must be
+        `flush()`ed before the refresh. Captured engine graphs stay valid: the buffers are rewritten in place, no pointer
+        changes. `TrainStep(..., lora=self, refresh_adapted=True)` runs it after every optimizer step."""
+        ops.run_all(self.refresh_ops())

@@ -367,8 +367,12 @@ class TrainStep:
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, store: Optional[ParamStore] = None,
                  world: int = 1, rank: int = 0, group=None, reduce_dtype: torch.dtype = torch.float32, lora=None,
                  force_comm: bool = False, recompute: bool = False, shard_params: bool = False, fp8: bool = False,
-                 fp8_wgrad: bool = False, loss: str = "ce", policy: Optional[PolicyLossConfig] = None):
+                 fp8_wgrad: bool = False, loss: str = "ce", policy: Optional[PolicyLossConfig] = None,
+                 refresh_adapted: bool = False):
         """`lora`: a training.lora.LoraAdapters → stage "lora": the base model is frozen and only the adapters train.
+        `refresh_adapted` (with `lora`): the re-pack plan that follows every optimizer step ends with the ONE batched merge
+        launch of `lora.refresh_ops()`, so `lora.adapted_weights()` — the weights an inference engine of the model the adapters
+        are attached to reads — are the learner's after every step, eager or graph replay. Off by default: plans unchanged.
         `recompute`: keep only each decoder layer's input and replay its forward inside the backward pass.
         `shard_params`: FSDP FULL_SHARD for every FSDP unit — decoder layers, ViT blocks and stems, projector, token
         embeddings, lm_head (fsdp.py:84-87) — every rank keeps 1/world of each unit's bf16 weights; a unit is all-gathered
@@ -406,6 +410,8 @@ class TrainStep:
                                  f"[0, {weights.dims.vocab})")
         if (lora is not None) != (stage == "lora"):
             raise ValueError("stage 'lora' and the `lora` adapters go together")
+        if refresh_adapted and lora is None:
+            raise ValueError("refresh_adapted goes with stage 'lora' and its `lora` adapters")
         if (recompute or shard_params or fp8) and lora is not None:
             raise ValueError("activation recomputation / parameter sharding / fp8 GEMMs are planned for the full-parameter stages only")
         if fp8 and (weights.dims.llm_dim % 128 or weights.dims.llm_inter % 128):
@@ -538,6 +544,9 @@ class TrainStep:
             self._setup_fp8()
         if lora is not None:
             self._build_extended_weights()
+            if refresh_adapted:                 # after the adapter refresh in the re-pack plan: reads the written-back A / B
+                self._adapter_ops = self._adapter_ops + lora.refresh_ops()
+                ops.run_all(self._adapter_ops[-1:])
         # execution order of the vision units (forward; the backward visits each tower's blocks top down, then its stem)
         vkey = lambda tw, i: f"vision.{tw.dims.prefix.split('.')[1]}." + ("stem" if i < 0 else f"block{i:02d}")
         self._vkey = vkey

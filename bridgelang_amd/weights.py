@@ -18,7 +18,7 @@ parameter-sharded training, and the small plain tensors):
 from __future__ import annotations
 
 import zlib
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Callable, Dict, Iterator, List, Optional, Tuple
 
 import torch
@@ -398,6 +398,40 @@ class VLAWeights:
     # towers) and "head" (projector, token embeddings, lm_head).
     unit_arenas: Dict[str, Arena] = field(default_factory=dict)
     _unit_views: List[tuple] = field(default_factory=list)  # (pool, unit key, path to the attribute, group index | None, view index, HF name | None)
+    adapted_arena: Optional[Arena] = None     # adapted_view(): the one allocation behind the replaced groups' packed tensors
+
+    # ---- a second set of GEMM weights beside the model's own (LoRA adapters merged on the device, training/lora.py) ---------
+    def adapted_view(self, groups) -> "VLAWeights":
+        """A VLAWeights that shares every tensor with this one — embeddings, norms, biases, lm_head, patch embeddings, the
+        pass-through tensors — EXCEPT the packed tensors of `groups` (PackedGroup objects or indices into `self.groups`):
+        those are new buffers in one new Arena (`adapted_arena`), initialised with copies of the originals and reachable
+        through the same routes as here (`layers[i].qkv_w` …, tower blocks, the projector, `groups[i].packed`, the members'
+        `placements`). The containers (layer / block / tower records, groups, placements) are copies, so neither side sees the
+        other re-point a tensor; derived caches (the e4m3 layer copies of engine.py) are not carried over. Meant to be read
+        by inference engines: the view shares `unit_arenas` and must not be released or restored."""
+        index = {id(g): i for i, g in enumerate(self.groups)}
+        want = sorted({g if isinstance(g, int) else index[id(g)] for g in groups})
+        if any(not 0 <= gi < len(self.groups) for gi in want):
+            raise IndexError(f"adapted_view: group indices {want} outside 0..{len(self.groups) - 1}")
+        v = replace(self)
+        v.__dict__.pop("_fp8_layers", None)
+        tower = lambda t: replace(t, blocks=[replace(b) for b in t.blocks])
+        v.dino, v.siglip, v.layers = tower(self.dino), tower(self.siglip), [replace(l) for l in self.layers]
+        v.groups = [PackedGroup(g.packed, g.n, g.k, list(g.members)) for g in self.groups]
+        v.placements = {name: pl if pl.group is None else replace(pl, group=v.groups[index[id(pl.group)]])
+                        for name, pl in self.placements.items()}
+        v.passthrough, v._unit_views = dict(self.passthrough), list(self._unit_views)
+        paths = {gi: path for _, _, path, gi, _, _ in self._unit_views if gi is not None}
+        arena = v.adapted_arena = Arena(self.embed.device)
+        slots = {gi: arena.reserve(tuple(self.groups[gi].packed.shape)) for gi in want}
+        arena.commit()
+        for gi in want:
+            t = arena.view(slots[gi])
+            t.copy_(self.groups[gi].packed)
+            obj, attr = v._attr_of(paths[gi])
+            setattr(obj, attr, t)
+            v.groups[gi].packed = t
+        return v
 
     # ---- parameter-sharded training (training/step.py, shard_params): the units' weights leave the device ------------------
     @property

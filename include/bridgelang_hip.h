@@ -456,6 +456,25 @@ int bl_gemm_tn_small_bf16(const bl_bf16* P, int64_t ldp, const bl_bf16* Q, int64
  * members), or n % members when the members' rows are interleaved). */
 int bl_scale_bf16(const bl_bf16* x, float s, bl_bf16* out, int64_t n, void* stream);
 int bl_lora_block_mask_f32(float* g, int32_t n_rows, int32_t R, int32_t rp, int32_t members, int32_t interleave, void* stream);
+/* LoRA deployment by merging (vla-scripts/finetune.py:331-341, PEFT `merge_and_unload()`), on the device and on the packed
+ * layout: out[n, k] = bf16(W[n, k] + sum_r bf16(scale * B[n, r]) * A[r, k]), w_packed and out_packed both fragment-major
+ * [n/16, k/32, 64, 8] (bl_pack_weight_bf16), A [R, k] and B [n, R] row-major bf16 with R = members * rp (the fused members'
+ * adapters side by side, B block structured: row n of B only sees member(n)'s rp columns, member(n) = n / (n / members), or
+ * n % members with interleave != 0). The update is accumulated in fp32 over R on the MFMA, added to W in fp32 and rounded
+ * once; an element whose update is exactly zero keeps its bits, so B = 0 or scale = 0 copies W bit for bit. Stacked members
+ * that own whole 16-row tiles read only their own rp columns of B / rows of A (the rest are zeros by construction).
+ * n % 16 == 0, k % 32 == 0, R % 32 == 0, rp % 32 == 0, the rank span of one row (rp for such stacked members, else R) <= 128, 16-byte aligned pointers, and
+ * out_packed must not overlap w_packed (BL_E_ARG). No atomics, no workspace; definition: training/lora.py::merged_reference. */
+int bl_lora_merge_bf16(const bl_bf16* w_packed, const bl_bf16* A, const bl_bf16* B, float scale, bl_bf16* out_packed, int64_t n,
+                       int64_t k, int32_t R, int32_t rp, int32_t members, int32_t interleave, void* stream);
+/* ONE launch for a device table of the above — every adapted group of a model after an optimizer step. table: device array of
+ *   struct { const bl_bf16 *w, *A, *B; bl_bf16* out; float scale; int32 n, k, R, rp, members, interleave, n_items;
+ *            int64 first_item; }
+ * n_items = ceil(k / 128) * m * ceil(n / 16 / m / 16) work items of the group (m = members when they are stacked and
+ * n % (16 * members) == 0, else 1), first_item = prefix sum of n_items. The entries are NOT validated (the table is on the
+ * device): build them with train_ops.lora_merge_batched, which checks what bl_lora_merge_bf16 checks. Same device code and
+ * summation order as bl_lora_merge_bf16: bit-identical results. */
+int bl_lora_merge_batched_bf16(const void* table, int32_t n_groups, void* stream);
 /* y += a * x on flat fp32 buffers: gradient accumulation over micro-batches with the loss normalised by the number of
  * accumulation steps (vla-scripts/finetune.py:256-262, 307-310). */
 int bl_axpy_f32(float* y, const float* x, float a, int64_t n, void* stream);
