@@ -237,6 +237,14 @@ __global__ __launch_bounds__(512) void gemm256s_fp8_kernel(GemmArgs p) {
 #endif
 }
 
+// A row (or channel) whose amax lies below FP8_AMAX_MIN = 2^-100 is quantised as a zero row: scale 1, inv 1, so every code is a
+// signed zero (|x| < 2^-100 is far below half the smallest e4m3 subnormal, 2^-10). Without the rule 448 / amax overflows to
+// +inf for 0 < amax < 448 / FLT_MAX ≈ 1.3e-36 — values bf16 holds — and the zeros of such a row become 0·inf = NaN codes,
+// which turn whole GEMM output rows into NaN. 2^-100 ≈ 7.9e-31 lies 2^18 above that range; rows at or above it are
+// quantised exactly as before (the same two divisions), and for every finite bf16 row the scale is finite and positive,
+// no NaN code is written and |decode·scale| <= 2·amax.
+constexpr float FP8_AMAX_MIN = 0x1p-100f;
+
 // Row-resident form of the kernel below for cols <= 512·NCH: the lane's NCH 16-byte chunks of the row are requested at once
 // and stay in registers between the amax pass and the conversion — the row crosses the memory system once, with NCH loads in
 // flight per lane instead of one (training-step quantisations 19 → 13 ms per step). Same arithmetic, same results.
@@ -259,8 +267,9 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_resident_kernel(const u
 #pragma unroll
     for (int i = 0; i < 4; ++i) amax = fmaxf(amax, fmaxf(fabsf(bflo(t[k][i])), fabsf(bfhi(t[k][i]))));
   amax = wave_max(amax);
-  const float inv = amax > 0.f ? __fdiv_rn(448.0f, amax) : 1.0f;
-  if (lane == 0) scales[row] = amax > 0.f ? __fdiv_rn(amax, 448.0f) : 1.0f;
+  const bool live = amax >= FP8_AMAX_MIN;
+  const float inv = live ? __fdiv_rn(448.0f, amax) : 1.0f;
+  if (lane == 0) scales[row] = live ? __fdiv_rn(amax, 448.0f) : 1.0f;
   uint8_t* qr = q + (long)row * ldq;
 #pragma unroll
   for (int k = 0; k < NCH; ++k)       // keep the row PACKED between the passes (hipcc would carry the 8 unpacked floats per chunk)
@@ -282,7 +291,8 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_resident_kernel(const u
   }
 }
 
-// x bf16 [rows, cols] → q fp8 e4m3 [rows, cols] + scale[row] = amax / 448 (1 for an all-zero row): one wave per row.
+// x bf16 [rows, cols] → q fp8 e4m3 [rows, cols] + scale[row] = amax / 448 (1 for an all-zero row and for amax < FP8_AMAX_MIN):
+// one wave per row.
 __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const uint16_t* x, long ldx, int rows, int cols, uint8_t* q,
                                                                 long ldq, float* scales) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -295,8 +305,9 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const uint16_t* 
     for (int i = 0; i < 4; ++i) amax = fmaxf(amax, fmaxf(fabsf(bflo(t[i])), fabsf(bfhi(t[i]))));
   }
   amax = wave_max(amax);
-  const float inv = amax > 0.f ? __fdiv_rn(448.0f, amax) : 1.0f;
-  if (lane == 0) scales[row] = amax > 0.f ? __fdiv_rn(amax, 448.0f) : 1.0f;
+  const bool live = amax >= FP8_AMAX_MIN;
+  const float inv = live ? __fdiv_rn(448.0f, amax) : 1.0f;
+  if (lane == 0) scales[row] = live ? __fdiv_rn(amax, 448.0f) : 1.0f;
   uint8_t* qr = q + (long)row * ldq;
   for (int c = lane * 8; c < cols; c += 512) {
     const u32x4_t t = *(const u32x4_t*)(xr + c);
@@ -376,8 +387,9 @@ __global__ __launch_bounds__(256) void transpose_quantize_fp8_kernel(const uint1
   if (tid < 64) {
     const int c = c0 + tid;
     const float a = c < cols ? amax[c] : 0.f;
-    inv_s[tid] = a > 0.f ? __fdiv_rn(448.0f, a) : 1.0f;
-    if (blockIdx.y == 0 && c < cols) scales[c] = a > 0.f ? __fdiv_rn(a, 448.0f) : 1.0f;
+    const bool live = a >= FP8_AMAX_MIN;                          // the zero-row rule of the row quantiser
+    inv_s[tid] = live ? __fdiv_rn(448.0f, a) : 1.0f;
+    if (blockIdx.y == 0 && c < cols) scales[c] = live ? __fdiv_rn(a, 448.0f) : 1.0f;
   }
   const int ch = lane & 15, g = lane >> 4;                       // this lane's channel (within the wave's 16) and 16-token group
   const int cw = wave * 16 + ch;                                 // channel within the tile

@@ -231,18 +231,20 @@ def gemm_last_form() -> str:
 
 # ---- FP8 (e4m3) GEMM family — BASELINE configs[4]; no reference counterpart -----------------------------------------
 FP8_MAX = 448.0
+FP8_AMAX_MIN = 2.0 ** -100     # a row whose amax lies below this is quantised as a zero row (csrc/gemm_fp8.hip)
 
 
 def quantize_weight_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """nn.Linear weight [N, K] (bf16, N % 16 == 0, K % 128 == 0) → (packed e4m3 weight, fp32 scale [N]): per output
-    channel scale = amax / 448, RNE cast, then the fragment-major packing of pack_weight on the bytes viewed as bf16
-    pairs (bl_gemm_fp8 reads the same byte layout as bl_gemm_bf16). Load-time work, torch ops."""
+    channel scale = amax / 448 (1 for a channel with amax < 2^-100, whose codes are all zero: the kernels' zero-row rule),
+    RNE cast, then the fragment-major packing of pack_weight on the bytes viewed as bf16 pairs (bl_gemm_fp8 reads the
+    same byte layout as bl_gemm_bf16). Load-time work, torch ops."""
     N, K = w.shape
     if N % 16 or K % 128:
         raise ValueError("quantize_weight_fp8: N % 16 == 0 and K % 128 == 0")
     wf = w.float()
     amax = wf.abs().amax(dim=1)
-    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    scale = torch.where(amax >= FP8_AMAX_MIN, amax / FP8_MAX, torch.ones_like(amax))
     q = (wf / scale[:, None]).to(torch.float8_e4m3fn)
     packed = pack_weight(q.view(torch.uint8).view(N, K // 2, 2).view(torch.bfloat16).reshape(N, K // 2).contiguous())
     return packed, scale.contiguous()
@@ -268,10 +270,11 @@ def quantize_rows_fp8(x: torch.Tensor, q: Optional[torch.Tensor] = None, scales:
 
 
 def gemm_fp8(A8: torch.Tensor, scale_a: torch.Tensor, W8: torch.Tensor, scale_w: torch.Tensor, out: torch.Tensor,
-             epilogue: int = EPI_NONE, *, bias: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
+             epilogue: int = EPI_NONE, *, bias: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+             res: Optional[torch.Tensor] = None, res_row_mod: int = 0, out_map: Optional[Tuple[int, int, int]] = None,
              run: bool = True) -> Op:
     """out = epilogue(scale_a[m] · scale_w[n] · (A8 @ W8.T)) on the fp8 MFMA path (bl_gemm_fp8). A8 uint8 e4m3 codes
-    [M, K]; W8 = quantize_weight_fp8(...)[0]."""
+    [M, K]; W8 = quantize_weight_fp8(...)[0]. `scale` (LayerScale, EPI_BIAS_RES), `res_row_mod` and `out_map` as in gemm."""
     lib = _lib.load()
     if A8.dtype != torch.uint8 or not A8.is_cuda or A8.stride(1) != 1:
         raise TypeError("gemm_fp8: A8 must be a CUDA/HIP uint8 matrix of e4m3 codes")
@@ -294,8 +297,13 @@ def gemm_fp8(A8: torch.Tensor, scale_a: torch.Tensor, W8: torch.Tensor, scale_w:
     keep = [A8, W8, out, scale_a, scale_w]
     if bias is not None:
         d.bias = _bf16(bias, "bias").data_ptr(); keep.append(bias)
+    if scale is not None:
+        d.scale = _bf16(scale, "scale").data_ptr(); keep.append(scale)
     if res is not None:
         d.res, d.ldres = _bf16(res, "res").data_ptr(), _rows(res, "res"); keep.append(res)
+    d.res_row_mod = res_row_mod
+    if out_map is not None:
+        d.out_group, d.out_stride, d.out_offset = out_map
     n_out = N // 2 if epilogue == EPI_SWIGLU else N
     esz = 4 if epilogue in (EPI_F32, EPI_F32_BF16R) else 2
     op = Op("bl_gemm_fp8", lib.bl_gemm_fp8, (C.byref(d), scale_a.data_ptr(), scale_w.data_ptr()), (d, *keep),

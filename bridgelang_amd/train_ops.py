@@ -146,7 +146,9 @@ def transpose_pad(a, out, rows_pad: int, run: bool = True) -> Op:
 
 
 def colamax(x: torch.Tensor, amax: torch.Tensor, run: bool = True) -> Op:
-    """amax[c] = max(amax[c], max_t |x[t, c]|) (fp32; zero it first): per-channel scales of the e4m3 weight-gradient operands."""
+    """amax[c] = max(amax[c], max_t |x[t, c]|) (fp32): per-channel scales of the e4m3 weight-gradient operands. The kernel
+    accumulates into amax with an atomic max over the bits of non-negative floats, so amax must be zeroed first (or hold a
+    non-negative running maximum); columns of zeros leave it untouched."""
     rows, cols = x.shape
     assert amax.dtype == torch.float32 and amax.numel() >= cols
     return _op("bl_colamax_bf16", (_bf16(x, "x").data_ptr(), _rows(x, "x"), rows, cols, amax.data_ptr()), (x, amax), run,
@@ -156,7 +158,7 @@ def colamax(x: torch.Tensor, amax: torch.Tensor, run: bool = True) -> Op:
 def transpose_quantize_fp8(x: torch.Tensor, amax: torch.Tensor, q: torch.Tensor, scales: torch.Tensor, tokens_pad: int, packed: bool,
                            run: bool = True) -> Op:
     """x bf16 [tokens, channels] → e4m3 codes, token-contiguous per channel (tokens zero-padded to tokens_pad) + scales[c] =
-    amax[c] / 448: q uint8 [channels, tokens_pad] row-major, or (packed) in bl_gemm_fp8's weight-operand packing
+    amax[c] / 448 (1, with all-zero codes, for amax[c] < 2^-100): q uint8 [channels, tokens_pad] row-major, or (packed) in bl_gemm_fp8's weight-operand packing
     [channels / 16, tokens_pad / 64, 64, 16]. One pass: 2 B read + 1 B written per element."""
     rows, cols = x.shape
     assert q.dtype == torch.uint8 and q.is_contiguous() and q.numel() == cols * tokens_pad and scales.numel() >= cols

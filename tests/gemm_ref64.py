@@ -27,6 +27,7 @@ Bit-exact outputs (`linear_ref`; every element, no tolerance). x is the exact pr
 * EPI_F32_BF16R      out = bf16(x): one rounding of an exact value, the same from fp32 and from fp64.
 * EPI_NONE           out = bf16(x), likewise.
 * EPI_BIAS           x + b is a multiple of 2^-7 below 2^17 (the asserted condition): the fp32 add is exact; out = bf16(x + b).
+                     (The reference rounds the sum to fp32 first, as the kernel's fp32 add does: the identity here.)
 * EPI_RES            t = bf16(x) is a multiple of 2^-7 (rounding a multiple of 2^-7 to fewer bits keeps it one) with
                      |t| <= 2^17 - 4; t + r is a multiple of 2^-7 below 2^17: exact; out = bf16(t + r).
 * EPI_BIAS_RES       t = bf16(x + b) as above, t + r exact as for EPI_RES.
@@ -189,13 +190,19 @@ def out_rows(M: int, out_map, device):
 
 
 # ---- references -------------------------------------------------------------------------------------------------------------
+def _f32(v: torch.Tensor) -> torch.Tensor:
+    """The fp32 add of the specification: one rounding of the exact fp64 sum, which is what an IEEE fp32 add returns. The
+    identity for the dyadic cases (their sums are fp32 values); it matters where x is an arbitrary fp32 value (fp8_ref64.py)."""
+    return v.float().double()
+
+
 def linear_ref(epi: int, x, bias=None, scale=None, res=None, res_row_mod: int = 0) -> torch.Tensor:
     """The six linear epilogues on the exact product x (fp64), as fp64 values that are bf16 (fp32 for EPI_F32) numbers."""
     if epi == EPI_F32:
         return x
     if epi in (EPI_F32_BF16R, EPI_NONE):
         return rb64(x)
-    t = x + bias.double() if epi in HAS_BIAS else x
+    t = _f32(x + bias.double()) if epi in HAS_BIAS else x
     t = rb64(t)
     if epi == EPI_BIAS:
         return t
@@ -209,7 +216,7 @@ def linear_ref(epi: int, x, bias=None, scale=None, res=None, res_row_mod: int = 
 
 def preact_ref(epi: int, x, bias=None) -> torch.Tensor:
     """Pre-activation kept by the *_KEEP forms, and the argument of every activation epilogue: bf16(x [+ b])."""
-    return rb64(x + bias.double()) if epi in HAS_BIAS else rb64(x)
+    return rb64(_f32(x + bias.double())) if epi in HAS_BIAS else rb64(x)
 
 
 def assert_exact(got: torch.Tensor, ref: torch.Tensor, what: str) -> None:
