@@ -27,37 +27,6 @@
 namespace bl_gemm_bf16_impl {
 using namespace blgemm;
 
-constexpr int GROUP_M = 4;   // round 3 same-box A/B: 4 beats 8 by 0.75 % end to end (gate||up -1.7 %), 2 / 3 tie, 9 … 18 lose
-
-// linear tile index → (row tile, column tile): groups of GROUP_M row-tiles walked column by column
-__device__ __forceinline__ void lin_to_tile(const GemmArgs& p, int lin, int& tm, int& tn) {
-  const int width = GROUP_M * p.tiles_n, grp = lin / width, first = grp * GROUP_M;
-  const int gsz = min(p.tiles_m - first, GROUP_M), rem = lin - grp * width;
-  tm = first + rem % gsz;
-  tn = rem / gsz;
-}
-
-__device__ __forceinline__ void tile_coords(const GemmArgs& p, int& tm, int& tn) {
-  // XCD-contiguous ordering over the LAUNCHED blocks (speed only; any bijective mapping is correct). The grid may
-  // cover only the first gridDim.x tiles of the tiles_m x tiles_n grid (whole rounds; a leftover round goes to gemm_ring8_kernel).
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-  const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  const int width = GROUP_M * p.tiles_n, grp = lin / width, first = grp * GROUP_M;
-  const int gsz = min(p.tiles_m - first, GROUP_M), rem = lin - grp * width;
-  tm = first + rem % gsz;
-  tn = rem / gsz;
-}
-
-// the same mapping for a VIRTUAL block index vb of nwg (persistent kernels: a workgroup walks vb = blockIdx.x + r·gridDim.x;
-// with gridDim.x a multiple of 8 every tile of a workgroup belongs to its own XCD's contiguous run)
-__device__ __forceinline__ void tile_coords_v(const GemmArgs& p, int vb, int nwg, int& tm, int& tn) {
-  const int xcd = vb & 7, q = nwg >> 3, r = nwg & 7;
-  const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-  lin_to_tile(p, lin, tm, tn);
-}
-
-#define BL_GLDS(RS, LDSP, VOFF, SOFF) __builtin_amdgcn_raw_ptr_buffer_load_lds(RS, LDS_PTR(LDSP), 16, VOFF, SOFF, 0, 0)
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;   // result of ds_read_b64_tr_b16
 
 // ======================================================================================================================
@@ -1390,35 +1359,10 @@ __global__ __launch_bounds__(512) void gemm_splitk_reduce_kernel(GemmArgs p) {
 #define BL_TN_KERNELS(X, EPI) \
   X(kid(KN_GEMM256S, 1), (gemm256s_kernel<BL_EPI_F32, true>)) X(kid(KN_TILE_REDUCE, 1), (gemm_splitk_reduce_kernel<BL_EPI_F32, true>))
 
-enum { FAM_TILE, FAM_ROWS, FAM_TN };   // bl_gemm_bf16, bl_gemm_skinny_rows_bf16, bl_gemm_tn_bf16
-
-// Carries a plan out: per launch the caller's arguments with the launch's overrides, on the kernel its id names. Decides
-// nothing. The LDS attributes of the family's kernels are set once per EPI.
-template <int EPI, int FAM>
-int launch_plan(const GemmPlan& plan, const GemmArgs& a, hipStream_t s) {
-#define BL_ATTR(ID, KERNEL) ok = ok && lds_attr(KERNEL, lds_bytes(ID));
-#define BL_CASE(ID, KERNEL) case ID: launch_kernel(KERNEL, l, p, s); break;
-  static const int attr_rc = [] {
-    bool ok = true;
-    if constexpr (FAM == FAM_TILE) { BL_TILE_KERNELS(BL_ATTR, EPI) }
-    else if constexpr (FAM == FAM_ROWS) { BL_ROWS_KERNELS(BL_ATTR, EPI) }
-    else { BL_TN_KERNELS(BL_ATTR, EPI) }
-    return ok ? BL_OK : BL_E_LAUNCH;
-  }();
-  if (attr_rc != BL_OK) return attr_rc;
-  for (int i = 0; i < plan.n; ++i) {
-    const Launch& l = plan.l[i];
-    const GemmArgs p = with_overrides(a, l);
-    if constexpr (FAM == FAM_TILE) switch (l.kernel) { BL_TILE_KERNELS(BL_CASE, EPI) default: return BL_E_LAUNCH; }
-    else if constexpr (FAM == FAM_ROWS) switch (l.kernel) { BL_ROWS_KERNELS(BL_CASE, EPI) default: return BL_E_LAUNCH; }
-    else switch (l.kernel) { BL_TN_KERNELS(BL_CASE, EPI) default: return BL_E_LAUNCH; }
-  }
-#undef BL_ATTR
-#undef BL_CASE
-  if (plan.n) gemm_last_form() = plan.form;
-  BL_CHECK_LAUNCH();
-  return BL_OK;
-}
+// bl_gemm_bf16, bl_gemm_skinny_rows_bf16, bl_gemm_tn_bf16: launch_plan (gemm_common.h) carries their plans out on these
+BL_KERNEL_FAMILY(TileKernels, BL_TILE_KERNELS)
+BL_KERNEL_FAMILY(RowsKernels, BL_ROWS_KERNELS)
+BL_KERNEL_FAMILY(TnKernels, BL_TN_KERNELS)
 
 }  // namespace bl_gemm_bf16_impl
 using namespace bl_gemm_bf16_impl;
@@ -1433,7 +1377,7 @@ extern "C" int bl_gemm_bf16(const bl_gemm_desc* d, void* stream) {
   if (d->a_norm_weight) return BL_E_ARG;   // the fused A-operand RMSNorm exists only in the skinny kernel
   const GemmPlan plan = plan_gemm(gemm_shape(a));
   return with_epilogue<ALL_EPIS>(d->epilogue, [&](auto epi) {
-    return launch_plan<decltype(epi)::value, FAM_TILE>(plan, a, (hipStream_t)stream);
+    return launch_plan<TileKernels<decltype(epi)::value>>(plan, a, (hipStream_t)stream);
   });
 }
 
@@ -1447,7 +1391,7 @@ extern "C" int bl_gemm_skinny_rows_bf16(const bl_gemm_desc* d, void* stream) {
   const char* e_on = getenv("BL_ROWS_STREAM");   // read per call: BL_ROWS_STREAM=0 switches the rows-stream form off (A/B)
   const GemmPlan plan = plan_rows(gemm_shape(a, e_on ? atoi(e_on) != 0 : true));
   return with_epilogue<SKINNY_EPIS>(d->epilogue, [&](auto epi) {
-    return launch_plan<decltype(epi)::value, FAM_ROWS>(plan, a, (hipStream_t)stream);
+    return launch_plan<RowsKernels<decltype(epi)::value>>(plan, a, (hipStream_t)stream);
   });
 }
 
@@ -1466,5 +1410,5 @@ extern "C" int bl_gemm_tn_bf16(const bl_gemm_desc* d, void* stream) {
   a.M = d->M; a.N = d->N; a.K = d->K;
   a.tail_base = -1;
   a.slab = (float*)d->workspace; a.slab_bytes = d->workspace_bytes; a.splitk = 1;
-  return launch_plan<BL_EPI_F32, FAM_TN>(plan_gemm_tn(gemm_shape(a)), a, (hipStream_t)stream);
+  return launch_plan<TnKernels<BL_EPI_F32>>(plan_gemm_tn(gemm_shape(a)), a, (hipStream_t)stream);
 }

@@ -1,6 +1,6 @@
-// gemm_common.h — argument block and fused epilogues shared by the tiled GEMM (gemm_bf16.hip) and the skinny
-// weight-streaming GEMM (gemm_skinny.hip). Both kernels compute the MFMA tile TRANSPOSED, so a lane owns 4 consecutive
-// output columns n..n+3 of one row m; the epilogue below is written for that layout.
+// gemm_common.h — argument block, fused epilogues, tile order and plan launcher shared by the tiled GEMMs (gemm_bf16.hip,
+// gemm_fp8.hip) and the skinny weight-streaming GEMM (gemm_skinny.hip). All kernels compute the MFMA tile TRANSPOSED, so a
+// lane owns 4 consecutive output columns n..n+3 of one row m; the epilogue below is written for that layout.
 #pragma once
 #include "bl_common.h"
 #include "gemm_plan.h"
@@ -275,7 +275,41 @@ __device__ __forceinline__ void epilogue_tile(const GemmArgs& p, int mrow, const
     for (int j = 0; j < NJ; ++j) epilogue_store4<EPI>(p, mrow + j * 16, ncol[i], acc[i][j]);
 }
 
-// host side: the kernel form the calling thread's last bf16 GEMM entry point took (bl_gemm_last_form; 0 = none launched):
+// ---- tile order of the tile kernels (bf16 and e4m3): a 1-D grid remapped so that each XCD (private L2) receives a contiguous run
+// of tiles, walked in groups of GM row-tiles so concurrently resident tiles share weight panels ----
+constexpr int GROUP_M = 4;   // round 3 same-box A/B: 4 beats 8 by 0.75 % end to end (gate||up -1.7 %), 2 / 3 tie, 9 … 18 lose
+constexpr int GROUP_M_E4M3 = 8;   // gemm256s_fp8_kernel keeps the order it was measured with
+
+// linear tile index → (row tile, column tile): groups of GM row-tiles walked column by column
+template <int GM = GROUP_M>
+__device__ __forceinline__ void lin_to_tile(const GemmArgs& p, int lin, int& tm, int& tn) {
+  const int width = GM * p.tiles_n, grp = lin / width, first = grp * GM;
+  const int gsz = min(p.tiles_m - first, GM), rem = lin - grp * width;
+  tm = first + rem % gsz;
+  tn = rem / gsz;
+}
+
+// the same for a VIRTUAL block index vb of nwg: XCD-contiguous ordering (speed only; any bijective mapping is correct).
+// Persistent kernels: a workgroup walks vb = blockIdx.x + r·gridDim.x; with gridDim.x a multiple of 8 every tile of a
+// workgroup belongs to its own XCD's contiguous run.
+template <int GM = GROUP_M>
+__device__ __forceinline__ void tile_coords_v(const GemmArgs& p, int vb, int nwg, int& tm, int& tn) {
+  const int xcd = vb & 7, q = nwg >> 3, r = nwg & 7;
+  const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
+  lin_to_tile<GM>(p, lin, tm, tn);
+}
+
+// … over the LAUNCHED blocks. The grid may cover only the first gridDim.x tiles of the tiles_m x tiles_n grid (whole rounds; a
+// leftover round goes to gemm_ring8_kernel).
+template <int GM = GROUP_M>
+__device__ __forceinline__ void tile_coords(const GemmArgs& p, int& tm, int& tn) {
+  tile_coords_v<GM>(p, blockIdx.x, gridDim.x, tm, tn);
+}
+
+// one 1-KiB LDS-DMA piece: 16 bytes per lane from buffer offset VOFF (per lane) + SOFF (uniform) to LDSP + 16 · lane
+#define BL_GLDS(RS, LDSP, VOFF, SOFF) __builtin_amdgcn_raw_ptr_buffer_load_lds(RS, LDS_PTR(LDSP), 16, VOFF, SOFF, 0, 0)
+
+// host side: the kernel form the calling thread's last GEMM entry point, bf16 or e4m3, took (bl_gemm_last_form; 0 = none launched):
 // the form code of the plan the launcher carried out (gemm_plan.h), read only by tests.
 inline int& gemm_last_form() {
   static thread_local int form = 0;
@@ -314,6 +348,35 @@ inline void launch_kernel(void (*kernel)(GemmArgs), const Launch& l, const GemmA
 // the weight-streaming kernels also take the count of 16-row weight tiles
 inline void launch_kernel(void (*kernel)(GemmArgs, int), const Launch& l, const GemmArgs& p, hipStream_t s) {
   hipLaunchKernelGGL(kernel, dim3(l.grid_x, l.grid_y), dim3(l.block), l.lds, s, p, p.N / 16);
+}
+// A kernel family is one entry point's list LIST(X, EPI) of X(kernel id, instantiation) pairs. The LDS attributes and the
+// launcher's switch both walk it, and both take the LDS bytes from lds_bytes(id).
+#define BL_FAMILY_ATTR(ID, KERNEL) ok = ok && lds_attr(KERNEL, lds_bytes(ID));
+#define BL_FAMILY_CASE(ID, KERNEL) case ID: launch_kernel(KERNEL, l, p, s); break;
+#define BL_KERNEL_FAMILY(NAME, LIST)                                                      \
+  template <int EPI>                                                                      \
+  struct NAME {                                                                           \
+    static bool lds_attrs() {                                                             \
+      bool ok = true;                                                                     \
+      LIST(BL_FAMILY_ATTR, EPI)                                                           \
+      return ok;                                                                          \
+    }                                                                                     \
+    static bool launch(const Launch& l, const GemmArgs& p, hipStream_t s) {               \
+      switch (l.kernel) { LIST(BL_FAMILY_CASE, EPI) default: return false; }              \
+      return true;                                                                        \
+    }                                                                                     \
+  };
+// Carries a plan out: per launch the caller's arguments with the launch's overrides, on the kernel its id names. Decides
+// nothing. The LDS attributes of the family's kernels are set once per family and EPI.
+template <typename Family>
+int launch_plan(const GemmPlan& plan, const GemmArgs& a, hipStream_t s) {
+  static const int attr_rc = Family::lds_attrs() ? BL_OK : BL_E_LAUNCH;
+  if (attr_rc != BL_OK) return attr_rc;
+  for (int i = 0; i < plan.n; ++i)
+    if (!Family::launch(plan.l[i], with_overrides(a, plan.l[i]), s)) return BL_E_LAUNCH;
+  if (plan.n) gemm_last_form() = plan.form;
+  BL_CHECK_LAUNCH();
+  return BL_OK;
 }
 // a workspace pointer with no bytes behind it still counts as a workspace (it bars the M > 320 mid2 form)
 inline GemmShape gemm_shape(const GemmArgs& a, bool rows_stream = true) {

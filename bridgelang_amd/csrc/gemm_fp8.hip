@@ -9,7 +9,9 @@
 // its row for BOTH operands — a permutation of k inside the 128-wide step, which a dot product does not see (checked with
 // exact integer data, tools/micro/fp8_mfma_check.hip). Per-token activation scales sa and per-output-channel weight
 // scales sw (fp32) are applied to the fp32 accumulators before the usual fused epilogue. Quantisation of the activations:
-// bl_quantize_rows_fp8 below (amax / 448 per row, hardware RNE conversion).
+// bl_quantize_rows_fp8 below (amax / 448 per row, hardware RNE conversion). bl_gemm_fp8 plans with plan_gemm_fp8 (gemm_plan.h:
+// one launch for every shape) and launches with launch_plan (gemm_common.h), like the bf16 entry points; folding the kernel
+// into gemm256s_kernel itself was measured and is not done.
 #include "gemm_common.h"
 
 namespace bl_gemm_fp8_impl {
@@ -17,28 +19,14 @@ using namespace blgemm;
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-constexpr int BK = 64;          // K-tile in 2-byte units = 128 fp8 values = 128 B per row
-constexpr int ROW_BYTES = 128;
-constexpr int GROUP_M = 8;
 constexpr int ONE_E8M0 = 0x7F7F7F7F;   // block scale 2^0 in every byte
 
-__device__ __forceinline__ void lin_to_tile(const GemmArgs& p, int lin, int& tm, int& tn) {
-  const int width = GROUP_M * p.tiles_n, grp = lin / width, first = grp * GROUP_M;
-  const int gsz = min(p.tiles_m - first, GROUP_M), rem = lin - grp * width;
-  tm = first + rem % gsz;
-  tn = rem / gsz;
-}
-
-__device__ __forceinline__ void tile_coords(const GemmArgs& p, int& tm, int& tn) {   // XCD-contiguous, grouped (gemm_bf16.hip)
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-  const int lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  lin_to_tile(p, lin, tm, tn);
-}
-
-#define BL_GLDS(RS, LDSP, VOFF, SOFF) __builtin_amdgcn_raw_ptr_buffer_load_lds(RS, LDS_PTR(LDSP), 16, VOFF, SOFF, 0, 0)
-
-// p.K, p.lda are in 2-byte units (the host entry point halves the fp8 counts), so every address below is the bf16 kernel's.
+// p.K, p.lda are in 2-byte units (the host entry point halves the fp8 counts; BK = 64 of them = 128 fp8 values = 128 B per row),
+// so every address below is the bf16 kernel's. plan_gemm_fp8 (gemm_plan.h) gives every shape one launch with one tile per
+// workgroup and splitk = 1, so the `p.splitk > 1` branches below never run. They stay because the register allocation
+// of the two K loops hangs on them: every epilogue's loops are free of scratch accesses with them, and with them taken
+// out (or with the whole body folded into gemm256s_kernel's) loops of several epilogues reload spilled registers behind
+// an `s_waitcnt vmcnt(0)` that drains the LDS-DMA stream — down_proj's shape +22 %.
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm256s_fp8_kernel(GemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -50,12 +38,12 @@ __global__ __launch_bounds__(512) void gemm256s_fp8_kernel(GemmArgs p) {
   const int nk_all = p.K / BK;
   int kt_begin = 0, nk = nk_all;
   if (p.splitk > 1) {
-    lin_to_tile(p, p.tail_base + blockIdx.x / p.splitk, tm, tn);
+    lin_to_tile<GROUP_M_E4M3>(p, p.tail_base + blockIdx.x / p.splitk, tm, tn);
     const int slice = blockIdx.x % p.splitk;
     kt_begin = (int)(((long)slice * nk_all) / p.splitk) & ~1;
     nk = slice + 1 == p.splitk ? nk_all : ((int)(((long)(slice + 1) * nk_all) / p.splitk) & ~1);
   } else {
-    tile_coords(p, tm, tn);
+    tile_coords<GROUP_M_E4M3>(p, tm, tn);
   }
   const int m0 = tm * BM, n0 = tn * BN;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -148,7 +136,7 @@ __global__ __launch_bounds__(512) void gemm256s_fp8_kernel(GemmArgs p) {
 #define BL_EPILOGUE()                                                                                     \
   do {                                                                                                    \
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                      \
-    if (p.splitk > 1) {                                                                                   \
+    if (p.splitk > 1) {                 /* never taken (see above) */                                     \
       float* dst = p.slab + ((long)blockIdx.x * 32 * 512 + tid) * 4;                                      \
       _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                       \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) *(f32x4_t*)(dst + (long)(i * 8 + j) * 512 * 4) = acc[i][j]; \
@@ -427,23 +415,14 @@ __global__ __launch_bounds__(256) void transpose_quantize_fp8_kernel(const uint1
   }
 }
 
-template <int EPI>
-int launch_fp8(const GemmArgs& a, hipStream_t s) {
-  constexpr int lds = lds_bytes(kid(KN_GEMM256S_FP8));
-  static const int attr_rc = lds_attr(gemm256s_fp8_kernel<EPI>, lds) ? BL_OK : BL_E_LAUNCH;
-  if (attr_rc != BL_OK) return attr_rc;
-  GemmArgs p = a;
-  p.tiles_m = (p.M + 255) / 256;
-  p.tiles_n = (p.N + 255) / 256;
-  hipLaunchKernelGGL((gemm256s_fp8_kernel<EPI>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds, s, p);
-  BL_CHECK_LAUNCH();
-  return BL_OK;
-}
+#define BL_FP8_KERNELS(X, EPI) X(kid(KN_GEMM256S_FP8), (gemm256s_fp8_kernel<EPI>))
+BL_KERNEL_FAMILY(Fp8Kernels, BL_FP8_KERNELS)
 
 }  // namespace bl_gemm_fp8_impl
 using namespace bl_gemm_fp8_impl;
 
 extern "C" int bl_gemm_fp8(const bl_gemm_desc* d, const float* scale_a, const float* scale_w, void* stream) {
+  gemm_last_form() = 0;
   if (!d || !scale_a || !scale_w) return BL_E_ARG;
   if ((d->K % 128) || (d->lda % 16) || d->ldw != d->K || d->a_norm_weight || d->workspace) return BL_E_SHAPE;
   if ((((uintptr_t)scale_w) & 15) || (((uintptr_t)scale_a) & 3)) return BL_E_ALIGN;
@@ -453,7 +432,10 @@ extern "C" int bl_gemm_fp8(const bl_gemm_desc* d, const float* scale_a, const fl
   const int rc = fill_gemm_args(&h, a);
   if (rc != BL_OK) return rc;
   a.qa = scale_a; a.qw = scale_w;
-  return with_epilogue<INFER_EPIS>(d->epilogue, [&](auto epi) { return launch_fp8<decltype(epi)::value>(a, (hipStream_t)stream); });
+  const GemmPlan plan = plan_gemm_fp8(gemm_shape(a));
+  return with_epilogue<INFER_EPIS>(d->epilogue, [&](auto epi) {
+    return launch_plan<Fp8Kernels<decltype(epi)::value>>(plan, a, (hipStream_t)stream);
+  });
 }
 
 extern "C" int bl_quantize_rows_fp8(const bl_bf16* x, int64_t ldx, int32_t rows, int32_t cols, uint8_t* q, int64_t ldq,

@@ -1,8 +1,8 @@
-// gemm_plan.h — which kernels a bf16 GEMM shape gets: plain host C++17, no HIP. Every threshold the project has measured (tile
+// gemm_plan.h — which kernels a GEMM shape gets, bf16 or e4m3: plain host C++17, no HIP. Every threshold the project has measured (tile
 // sizes, K slicing, tails, 288-row tiles, the persistent form) lives here, next to its measurement. A planner (one per entry
 // point) turns a GemmShape into a GemmPlan: up to three launches (main, tail, reduce), each with kernel id, grid, block, dynamic
-// LDS bytes and the GemmArgs scalars it sets, plus the form code bl_gemm_last_form reports. launch_plan (gemm_bf16.hip,
-// gemm_skinny.hip) carries a plan out and decides nothing. tests/test_gemm_plan_cpu.py compiles this header alone.
+// LDS bytes and the GemmArgs scalars it sets, plus the form code bl_gemm_last_form reports. launch_plan (gemm_common.h for the
+// tile, rows, TN and e4m3 families; gemm_skinny.hip) carries a plan out and decides nothing. tests/test_gemm_plan_cpu.py compiles this header alone.
 #pragma once
 #include <cstdint>
 
@@ -14,7 +14,7 @@ constexpr int CUS = 256;   // MI355X compute units: the 256-row tile kernels run
 // ---- kernels: id = family | a, b, c (kid), the kernel's template parameters after EPI in their order; the launchers' lists map
 // an id to its instantiation. KN_TILE_REDUCE gemm_splitk_reduce_kernel (the split-K tail's slabs), KN_SLAB_REDUCE
 // gemm128_splitk_reduce_kernel (the K-sliced forms' [M, N] slabs), KN_ROWS_STREAM_HALVES gemm_rows_stream_kernel<BL_EPI_NONE, …>
-// (K-halves to the slab), KN_SKINNY <KS = a, GS = b, EPI, NORM = c>, KN_GEMM256S_FP8: gemm_fp8.hip's one form
+// (K-halves to the slab), KN_SKINNY <KS = a, GS = b, EPI, NORM = c>, KN_GEMM256S_FP8 gemm256s_fp8_kernel (gemm_fp8.hip)
 enum { KN_GEMM128 = 1, KN_RING8, KN_MID, KN_MID2, KN_GEMM288S, KN_GEMM256S, KN_TILE_REDUCE, KN_SLAB_REDUCE, KN_ROWS_STREAM,
        KN_ROWS_STREAM_HALVES, KN_TREE_REDUCE, KN_SKINNY, KN_GEMM256S_FP8 };
 constexpr int kid(int family, int a = 0, int b = 0, int c = 0) { return family | (a << 8) | (b << 16) | (c << 24); }
@@ -72,7 +72,7 @@ struct GemmPlan {
 enum {
   GF_GEMM128 = 1, GF_RING160 = 2, GF_RING128_KSLICED = 3, GF_MID = 4, GF_MID2 = 5, GF_GEMM288S = 6, GF_GEMM256S = 7,
   GF_GEMM256S_PERSISTENT = 8, GF_ROWS_STREAM = 10, GF_ROWS_MID = 11, GF_SKINNY = 12, GF_TN = 13, GF_TN_PERSISTENT = 14,
-  GF_TN_ALL_SPLIT = 15
+  GF_TN_ALL_SPLIT = 15, GF_GEMM256S_FP8 = 16
 };
 enum { GT_NONE = 0, GT_SUB64X64 = 1, GT_SUB128X64 = 2, GT_SUB128X128 = 3, GT_SPLITK = 4 };
 constexpr int pack_form(int kind, int a = 0, int b = 0, int s = 0, int tail = GT_NONE, int tail_s = 0) {
@@ -91,6 +91,7 @@ inline int form_code(const GemmPlan& pl) {
     case KN_GEMM288S: return pack_form(GF_GEMM288S);
     case KN_ROWS_STREAM: case KN_ROWS_STREAM_HALVES: return pack_form(GF_ROWS_STREAM, kid_a(k), kid_b(k));
     case KN_SKINNY: return pack_form(GF_SKINNY, kid_c(k), 0, kid_a(k));
+    case KN_GEMM256S_FP8: return pack_form(GF_GEMM256S_FP8);
     case KN_GEMM256S: break;
     default: return 0;
   }
@@ -332,6 +333,17 @@ inline GemmPlan plan_gemm_tn(const GemmShape& g) {
     add256(pl, true, tiles, persist_ok, p);
   }
   return finish(pl);
+}
+
+// bl_gemm_fp8 (g.K and g.lda in 2-byte units, as the kernel counts them): ONE launch of gemm256s_fp8_kernel for every shape,
+// a 256 × 256 tile per workgroup — no tail treatment, no K slices (a workspace changes nothing), no persistent
+// walk, no 288-row tiles: none of them has been measured for e4m3.
+inline GemmPlan plan_gemm_fp8(const GemmShape& g) {
+  GemmPlan pl;
+  GemmOverrides p;
+  p.tiles_m = (g.M + 255) / 256, p.tiles_n = (g.N + 255) / 256;
+  detail::add(pl, kid(KN_GEMM256S_FP8), p.tiles_m * p.tiles_n, 1, 512, p);
+  return detail::finish(pl);
 }
 
 // K → the skinny kernel's KS and GS (BL_SKINNY_TABLE); false = no instantiation for this K

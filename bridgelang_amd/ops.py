@@ -208,7 +208,7 @@ _GF_TAIL = {0: "", 1: "+tail64x64", 2: "+tail128x64", 3: "+tail128x128"}
 def gemm_form_name(code: int) -> str:
     """Name of a bl_gemm_last_form code (csrc/gemm_plan.h): the main kernel with its template form and K slices, then
     the tail treatment — e.g. "gemm128", "mid<4,4>/S8", "mid2<2,2>", "gemm256s_persistent+tail64x64",
-    "gemm256s+splitk4", "rows_stream<8,4>+tree", "rows_mid<SK=2>+tree", "skinny<KS=43>", "tn+splitk2"."""
+    "gemm256s+splitk4", "rows_stream<8,4>+tree", "rows_mid<SK=2>+tree", "skinny<KS=43>", "tn+splitk2", "gemm256s_fp8"."""
     kind, a, b, S = code & 0xFF, (code >> 8) & 0xF, (code >> 12) & 0xF, (code >> 16) & 0x3F
     tail, tail_s = (code >> 22) & 0x7, (code >> 25) & 0x1F
     if kind == 0:
@@ -217,15 +217,15 @@ def gemm_form_name(code: int) -> str:
     main = {1: "gemm128", 2: "ring160x128", 3: f"ring128x128{sl}", 4: f"mid<{a},{b}>{sl}",
             5: f"mid2<{a},{b}>" if b else f"mid2<{a}>", 6: "gemm288s", 7: "gemm256s", 8: "gemm256s_persistent",
             10: f"rows_stream<{a},{b}>" + ("+tree" if b == 4 else ""), 11: f"rows_mid<SK={b}>" + ("+tree" if b == 2 else ""),
-            12: f"skinny<KS={S}>" + ("+norm" if a else ""), 13: "tn", 14: "tn_persistent", 15: "tn_all_split"}.get(kind)
+            12: f"skinny<KS={S}>" + ("+norm" if a else ""), 13: "tn", 14: "tn_persistent", 15: "tn_all_split", 16: "gemm256s_fp8"}.get(kind)
     if main is None:
         raise ValueError(f"gemm_form_name: unknown form code {code:#x}")
     return main + (f"+splitk{tail_s}" if tail == 4 else _GF_TAIL[tail])
 
 
 def gemm_last_form() -> str:
-    """The kernel form the calling thread's last bf16 GEMM launch took (bl_gemm_bf16, bl_gemm_skinny_bf16,
-    bl_gemm_skinny_rows_bf16, bl_gemm_tn_bf16), by name: a host-side record for tests, no part of dispatch."""
+    """The kernel form the calling thread's last GEMM launch took (bl_gemm_bf16, bl_gemm_skinny_bf16,
+    bl_gemm_skinny_rows_bf16, bl_gemm_tn_bf16, bl_gemm_fp8), by name: a host-side record for tests, no part of dispatch."""
     return gemm_form_name(_lib.load().bl_gemm_last_form())
 
 

@@ -129,7 +129,7 @@ int bl_gemm_skinny_rows_bf16(const bl_gemm_desc* d, void* stream);
 int bl_gemm_tn_bf16(const bl_gemm_desc* d, void* stream);
 
 /* Which kernel form the calling thread's last bl_gemm_bf16 / bl_gemm_skinny_bf16 / bl_gemm_skinny_rows_bf16 /
- * bl_gemm_tn_bf16 call launched (0: none — the call returned an error before launching). A host-side, thread-local
+ * bl_gemm_tn_bf16 / bl_gemm_fp8 call launched (0: none — the call returned an error before launching). A host-side, thread-local
  * record for tests; it takes no part in dispatch. Bits 0-7 main kernel, 8-11 and 12-15 its template parameters,
  * 16-21 K slices (skinny kernel: k-steps per wave), 22-24 tail treatment, 25-29 split-K tail slices; the codes are in
  * csrc/gemm_plan.h and decoded by ops.gemm_last_form(). */
@@ -147,7 +147,8 @@ int bl_rmsnorm_skinny_bf16(const bl_bf16* x, int64_t ldx, const bl_bf16* w, bl_b
  * bf16 MFMA rate). d->A: e4m3 codes [M, K] (lda in bytes, % 16), d->W: e4m3 weight in the fragment-major packing of
  * bl_pack_weight_bf16 applied to the [N, K/2] matrix of byte pairs, K % 128 == 0; scale_a fp32 [M] (per token),
  * scale_w fp32 [N] (per output channel, 16-byte aligned). Epilogues, bias / residual / output as bl_gemm_bf16; no
- * workspace, no fused A-norm. */
+ * workspace, no fused A-norm. One form for every shape (gemm256s_fp8_kernel, planned by plan_gemm_fp8), which
+ * bl_gemm_last_form reports as "gemm256s_fp8". */
 int bl_gemm_fp8(const bl_gemm_desc* d, const float* scale_a, const float* scale_w, void* stream);
 /* x bf16 [rows, cols] (cols % 8 == 0) -> q e4m3 [rows, cols] (ldq bytes) + scales[row] = amax(row) / 448;
  * q = RNE_e4m3(x * (448 / amax)). A row with amax < 2^-100 counts as a zero row: scale 1, every code a signed zero (448 / amax

@@ -117,6 +117,20 @@ def test_gemm_integer(dev, M, N, K, kind):
     assert bool(o.sabuf[M:].isnan().all()) and bool((o.abuf[M:] == 0x7F).all()) and bool((o.abuf[:, K:] == 0x7F).all())
 
 
+@pytest.mark.parametrize("M,N,K", [(1, 16, 128), (300, 528, 384)], ids=["1x16x128", "300x528x384"])
+def test_gemm_reports_its_form(dev, M, N, K):
+    """bl_gemm_fp8 goes through the planner and the launcher of the bf16 entry points: bl_gemm_last_form names its one form,
+    not the form of the bf16 call before it."""
+    from bridgelang_amd import ops
+    a = torch.zeros(64, 64, dtype=bf16, device=dev)
+    ops.gemm(a, ops.pack_weight(a), torch.empty(64, 64, dtype=bf16, device=dev), ops.EPI_NONE)
+    assert ops.gemm_last_form() == "gemm128"
+    o = Operands(dev, *gemm_operands(M, N, K, "pow2"))
+    C, _ = run_fp8(ops, dev, o, EPI_F32)
+    assert ops.gemm_last_form() == "gemm256s_fp8"
+    F.check_gemm("fp8 form f32", EPI_F32, o.A8, o.W8, o.sa, o.sw, C, x=o.x)
+
+
 # ---- selector instrument ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("M,N,K", SELECTOR_SHAPES, ids=[f"{M}x{N}x{K}" for M, N, K in SELECTOR_SHAPES])
 def test_gemm_selector(dev, M, N, K):

@@ -25,13 +25,13 @@ MIB = 1 << 20
 LDS_PER_CU = 160 * 1024                     # CDNA4
 # kernel families of gemm_plan.h (the KN_* enum)
 (KN_GEMM128, KN_RING8, KN_MID, KN_MID2, KN_GEMM288S, KN_GEMM256S, KN_TILE_REDUCE, KN_SLAB_REDUCE, KN_ROWS_STREAM,
- KN_ROWS_STREAM_HALVES, KN_TREE_REDUCE, KN_SKINNY) = range(1, 13)
+ KN_ROWS_STREAM_HALVES, KN_TREE_REDUCE, KN_SKINNY, KN_GEMM256S_FP8) = range(1, 14)
 
 MAIN = r"""
 #include "gemm_plan.h"
 #include <cstdio>
 #include <cstring>
-int main() {   // tile | rows | skinny: M N K lda ws flag    tn: T M N lda ldw ws    (ws < 0: none)
+int main() {   // tile | rows | skinny | fp8: M N K lda ws flag    tn: T M N lda ldw ws    (ws < 0: none)
   char what[16];
   long long v[6];
   while (scanf("%15s %lld %lld %lld %lld %lld %lld", what, v, v + 1, v + 2, v + 3, v + 4, v + 5) == 7) {
@@ -39,7 +39,8 @@ int main() {   // tile | rows | skinny: M N K lda ws flag    tn: T M N lda ldw w
     const bool tn = !strcmp(what, "tn");
     const GemmShape g = tn ? GemmShape{(int)v[1], (int)v[2], (int)v[0], v[3], v[4], v[5] < 0 ? 0 : v[5], true}
                            : GemmShape{(int)v[0], (int)v[1], (int)v[2], v[3], v[2], v[4] < 0 ? 0 : v[4], v[5] != 0};
-    const GemmPlan p = tn ? plan_gemm_tn(g) : what[0] == 't' ? plan_gemm(g) : what[0] == 'r' ? plan_rows(g) : plan_skinny(g, v[5] != 0);
+    const GemmPlan p = tn ? plan_gemm_tn(g) : what[0] == 't' ? plan_gemm(g) : what[0] == 'r' ? plan_rows(g) : what[0] == 'f' ? plan_gemm_fp8(g)
+                                                                                                     : plan_skinny(g, v[5] != 0);
     printf("%d", p.form);
     for (int i = 0; i < p.n; ++i) {
       const Launch& l = p.l[i];
@@ -87,6 +88,11 @@ def rows(M, N, K, ws=-1, stream=1, lda=None):
 
 def tn(T, M, N, ws=-1, lda=None, ldw=None):
     return ("tn", T, M, N, lda or M, ldw or N, ws)
+
+
+def fp8(M, N, K, ws=-1, lda=None):
+    """K and lda count e4m3 codes; bl_gemm_fp8 plans, as its kernel addresses, in 2-byte units."""
+    return ("fp8", M, N, K // 2, (lda or K) // 2, ws, 1)
 
 
 # ---- every shape → form statement of the repository -------------------------------------------------------------------------
@@ -138,6 +144,20 @@ def test_shape_to_form_tables(planner):
     assert not any(form.startswith("mid") for form, _ in planner([tile(700, N, K) for _, N, K in MID_ROWS_FORMS]))
 
 
+# ---- bl_gemm_fp8: one launch of gemm256s_fp8_kernel, whatever the shape -------------------------------------------
+FP8_SHAPES = [(1, 16, 128), (256, 256, 256), (300, 528, 384), (2344, 512, 128), (4608, 22016, 4096)]
+
+
+def test_fp8_plan_is_one_launch(planner):
+    for ws in (-1, 64 * MIB):                                    # bl_gemm_fp8 takes no workspace; a size changes nothing
+        plans = planner([fp8(M, N, K, ws, K + 16) for M, N, K in FP8_SHAPES])
+        for (M, N, K), (form, launches) in zip(FP8_SHAPES, plans):
+            tm, tn_ = (M + 255) // 256, (N + 255) // 256
+            assert form == "gemm256s_fp8", (M, N, K, ws)
+            assert launches == [dict(family=KN_GEMM256S_FP8, a=0, b=0, c=0, grid_x=tm * tn_, grid_y=1, block=512, lds=131072,
+                                     tiles_m=tm, tiles_n=tn_, tail_base=-1, splitk=1, ptiles=0)], (M, N, K, ws)
+
+
 # ---- the sweep: both sides of every threshold ---------------------------------------------------------------------------------
 SWEEP_M = [1, 16, 17, 32, 33, 96, 97, 128, 129, 256, 257, 320, 321, 640, 641, 700, 2048, 2081, 2290, 4100, 4353, 4608, 8192, 8352, 18432]
 SWEEP_K = [64, 448, 512, 576, 1024, 1088, 2112, 4096, 4160, 8192, 8256, 11008, 13824]
@@ -176,6 +196,9 @@ def sweep():
                                                       (32064, 4096)}
     for T in (33, 1000, 8200, 4096, 4176, 4608, 8352):
         shapes += [tn(T, M, N, ws, M + pad, N + 2 * pad) for M, N in sorted(tn_mn) for ws in SWEEP_WS for pad in (0, 8)]
+    # e4m3: every M and N of the sweep (the plan depends on nothing else), K a multiple of 128 codes
+    shapes += [fp8(M, N, 2 * K, ws) for M in ms for N in ns for K in SWEEP_K[::4] for ws in (-1, 64 * MIB)]
+    shapes += [fp8(M, N, K, ws, K + 16) for M, N, K in FP8_SHAPES for ws in SWEEP_WS]
     return shapes
 
 
@@ -230,12 +253,21 @@ def test_plan_invariants_over_the_sweep(swept):
                     assert l["family"] == KN_TILE_REDUCE and l["grid_x"] == 32 * (covered - l["tail_base"]), what
             big = ((M + 255) // 256) * ((N + 255) // 256)
             assert covered == big and launches[0]["tiles_m"] * launches[0]["tiles_n"] == big, what
+        # the e4m3 form: one launch, one workgroup per big tile, nothing else for any shape
+        if shape[0] == "fp8":
+            big = ((M + 255) // 256) * ((N + 255) // 256)
+            (l,) = launches
+            assert form == "gemm256s_fp8" and l["family"] == KN_GEMM256S_FP8 and l["grid_x"] == big == l["tiles_m"] * l["tiles_n"], what
+            assert (l["grid_y"], l["block"], l["lds"], l["tail_base"], l["splitk"], l["ptiles"]) == (1, 512, 131072, -1, 1, 0), what
+        else:
+            assert all(l["family"] != KN_GEMM256S_FP8 for l in launches), what
 
 
 def test_sweep_reaches_the_forms_that_have_a_per_element_case(swept):
     """Slice counts aside, the forms the tile, rows and TN planners produce over the sweep are the ones ALL_FORMS of
-    tests/test_gemm_ref_gpu.py lists (each has a per-element case there): a form without one fails here, without a GPU."""
+    tests/test_gemm_ref_gpu.py lists (each has a per-element case there): a form without one fails here, without a GPU.
+    (The e4m3 planner's one form has its per-element cases in tests/test_fp8_ref_gpu.py.)"""
     norm = lambda f: re.sub(r"\+splitk\d+", "+splitk", re.sub(r"/S\d+", "/S", f))
-    reached = {norm(form) for shape, (form, _) in zip(*swept)}
+    reached = {norm(form) for shape, (form, _) in zip(*swept) if shape[0] != "fp8"}
     listed = {norm(f) for f in ALL_FORMS if not f.startswith("skinny")}
     assert reached == listed, f"no per-element case: {sorted(reached - listed)}; listed but never planned: {sorted(listed - reached)}"
