@@ -57,6 +57,13 @@ class LoraMergeDesc(C.Structure):
                 ("interleave", C.c_int32), ("n_items", C.c_int32), ("first_item", C.c_int64)]
 
 
+class WeightQuantDesc(C.Structure):
+    """One entry of bl_quantize_weight_fp8_packed_batched's device table (struct WeightQuantEntry in
+    csrc/quantize_weight_fp8.hip)."""
+    _fields_ = [("w", C.c_void_p), ("w8", C.c_void_p), ("scale", C.c_void_p), ("n", C.c_int32), ("k", C.c_int32),
+                ("n_items", C.c_int32), ("pad", C.c_int32), ("first_item", C.c_int64)]
+
+
 class AttnDesc(C.Structure):
     """struct bl_attn_desc."""
     _fields_ = [
@@ -142,6 +149,8 @@ SIGNATURES = {
     "bl_lora_block_mask_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "bl_lora_merge_bf16": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "bl_lora_merge_batched_bf16": (C.c_int, [_vp, _i32, _vp]),
+    "bl_quantize_weight_fp8_packed": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "bl_quantize_weight_fp8_packed_batched": (C.c_int, [_vp, _i32, _vp]),
     "bl_axpy_f32": (C.c_int, [_vp, _vp, _f32, _i64, _vp]),
     "bl_cast_f32_bf16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "bl_cast_bf16_f32": (C.c_int, [_vp, _vp, _i64, _vp]),

@@ -223,9 +223,10 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         if vocab_range is not None:
             vocab_range = (int(vocab_range[0]), int(vocab_range[1]))
         adapted = self._resolve_adapters(use_adapters)
-        if adapted and fp8:
+        if adapted and fp8 and not self._adapters.fp8_enabled:
             raise NotImplementedError("fp8=True with attached adapters: the derived e4m3 weight copies would go stale on every "
-                                      "refresh of the adapted weights")
+                                      "refresh of the adapted weights. Opt in with attach_adapters(lora, fp8=True) / "
+                                      "load_adapter(dir, fp8=True) or lora.enable_fp8(): the refresh then requantises them on the device")
         weights = self._adapters.adapted_weights() if adapted else self.weights
         key = (batch, prompt_len, n_new, fp8, padded, cached, sample) + (("score", score_range) if score else ()) + \
             (("vocab", vocab_range) if vocab_range is not None else ()) + (("adapted",) if adapted else ())
@@ -241,15 +242,20 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             raise ValueError("use_adapters=True, but no adapters are attached (attach_adapters / load_adapter)")
         return self._adapters is not None and use_adapters is not False
 
-    def attach_adapters(self, lora) -> "PrismaticForConditionalGeneration":
+    def attach_adapters(self, lora, fp8: bool = False) -> "PrismaticForConditionalGeneration":
         """Run `engine` / `generate` / `predict_action` / `sample_actions` / `score_actions` under `lora` (a
         training.lora.LoraAdapters over THIS model's weights): their engines read `lora.adapted_weights()`, the adapters
         merged into a second set of packed GEMM weights (W' = bf16(W + bf16(s·B)·A), refreshed here and by `lora.refresh()` —
         or after every optimizer step by `TrainStep(..., lora=lora, refresh_adapted=True)`). `use_adapters=False` on those
         calls is the base policy, whose weights are never written. `forward()` (the all-position HF branches) reads the
-        base weights."""
+        base weights.
+        `fp8=True` is `lora.enable_fp8()`: the opt-in that lets `model.fp8 = True` (e4m3 prefill) run under the adapters —
+        every refresh then requantises the adapted weights' e4m3 copies on the device. It must come before a
+        `TrainStep(..., refresh_adapted=True)` over `lora` is built (LoraAdapters.enable_fp8)."""
         if lora.w is not self.weights:
             raise ValueError("attach_adapters: the adapters were built over another model's weights")
+        if fp8:
+            lora.enable_fp8()                # may raise: before anything attached is dropped
         if self._adapters is not None and self._adapters is not lora:
             self.detach_adapters()
         self._adapters = lora
@@ -264,11 +270,11 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             del self._engines[key]
         return self
 
-    def load_adapter(self, adapter_dir, seed: int = 0) -> "PrismaticForConditionalGeneration":
+    def load_adapter(self, adapter_dir, seed: int = 0, fp8: bool = False) -> "PrismaticForConditionalGeneration":
         """Attach the PEFT-named adapter that `training.finetune.save_checkpoint` writes (finetune.py:322-330):
         `adapter_model.safetensors` (base_model.model.<module>.lora_{A,B}.weight) + `adapter_config.json`, from which `r`,
         `lora_alpha` and `lora_dropout` are taken. A module this model has no GEMM group for, or a module of an adapted
-        group that the file lacks, is a ValueError."""
+        group that the file lacks, is a ValueError. `fp8`: as in `attach_adapters`."""
         import json
         from pathlib import Path
         from safetensors.torch import load_file
@@ -291,7 +297,7 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         if missing:
             raise ValueError(f"{st_path}: {len(missing)} adapter tensors are missing, e.g. {missing[:3]}")
         lora.load_state_dict(sd)
-        return self.attach_adapters(lora)
+        return self.attach_adapters(lora, fp8=fp8)
 
     # ---- forward: the reference's three branches (modeling_prismatic.py:322-415) ----
     cache_new_tokens = 7       # tokens a `forward(..., use_cache=True)` KV cache is sized for (prefill token + 6 cached steps)

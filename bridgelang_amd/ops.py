@@ -20,7 +20,7 @@ from ._lib import (AttnDesc, GemmDesc, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_KE
                    EPI_NONE, EPI_SWIGLU_BWD, EPI_SWIGLU_KEEP,
                    EPI_RES, EPI_SWIGLU)
 
-__all__ = ["Op", "gemm", "gemm_last_form", "gemm_form_name", "gemm_fp8", "quantize_rows_fp8", "quantize_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
+__all__ = ["Op", "gemm", "gemm_last_form", "gemm_form_name", "gemm_fp8", "quantize_rows_fp8", "quantize_weight_fp8", "quantize_packed_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
            "argmax", "sample", "score", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
            "EPI_NONE", "EPI_BIAS", "EPI_BIAS_GELU", "EPI_BIAS_RES", "EPI_RES", "EPI_SWIGLU", "EPI_F32", "EPI_F32_BF16R",
            "EPI_SWIGLU_KEEP", "EPI_BIAS_GELU_KEEP", "EPI_SWIGLU_BWD", "EPI_GELU_BWD"]
@@ -248,6 +248,36 @@ def quantize_weight_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     q = (wf / scale[:, None]).to(torch.float8_e4m3fn)
     packed = pack_weight(q.view(torch.uint8).view(N, K // 2, 2).view(torch.bfloat16).reshape(N, K // 2).contiguous())
     return packed, scale.contiguous()
+
+
+def quantize_packed_weight_fp8(wp: torch.Tensor, w8: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                               run: bool = True):
+    """Packed bf16 weight [N/16, K/32, 64, 8] (pack_weight; K % 128 == 0) → (packed e4m3 weight as bf16 [N/16, K/64, 64, 8], fp32
+    scale [N]) in the shapes quantize_weight_fp8 returns, on the device and without a row-major copy
+    (bl_quantize_weight_fp8_packed): the kernels' quantiser specification per output channel — it multiplies by
+    fl32(448 / amax) where quantize_weight_fp8 divides by the scale, so a few codes per 10^5 differ between the two; the
+    scales are equal. Writes every byte of w8 / scale in place (replayable; captured graphs that read them stay valid).
+    Returns (w8, scale, op)."""
+    lib = _lib.load()
+    _bf16(wp, "wp")
+    if wp.dim() != 4 or wp.shape[2:] != (64, 8) or not wp.is_contiguous():
+        raise ValueError("quantize_packed_weight_fp8: wp must come from pack_weight")
+    N, K = wp.shape[0] * 16, wp.shape[1] * 32
+    if N == 0 or K == 0 or K % 128:
+        raise ValueError("quantize_packed_weight_fp8: N % 16 == 0 and K % 128 == 0")
+    if w8 is None:
+        w8 = torch.empty(N // 16, K // 64, 64, 8, dtype=torch.bfloat16, device=wp.device)
+    if scale is None:
+        scale = torch.empty(N, dtype=torch.float32, device=wp.device)
+    if not w8.is_contiguous() or w8.numel() * w8.element_size() != N * K or not w8.is_cuda:
+        raise ValueError(f"quantize_packed_weight_fp8: w8 must hold the {N * K} bytes of [N/16, K/64, 64, 16]")
+    if scale.dtype != torch.float32 or scale.numel() != N or not scale.is_contiguous() or not scale.is_cuda:
+        raise ValueError(f"quantize_packed_weight_fp8: scale fp32 [{N}]")
+    op = Op("bl_quantize_weight_fp8_packed", lib.bl_quantize_weight_fp8_packed,
+            (wp.data_ptr(), N, K, w8.data_ptr(), scale.data_ptr()), (wp, w8, scale), nbytes=3.0 * N * K)
+    if run:
+        op.run()
+    return w8, scale, op
 
 
 def quantize_rows_fp8(x: torch.Tensor, q: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,

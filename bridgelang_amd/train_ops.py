@@ -480,6 +480,56 @@ def lora_merge_batched(entries, device, run: bool = False) -> Op:
                nbytes=float(sum(4 * d.n * d.k for d in descs)), flops=float(sum(2 * d.n * d.k * d.R for d in descs)))
 
 
+# ---- packed bf16 weight → packed e4m3 weight + per-channel scales (csrc/quantize_weight_fp8.hip; ops.quantize_packed_weight_fp8) ----
+def quantize_packed_items(n: int, k: int) -> int:
+    """Work items of one weight in the packed quantiser: one per 16-row tile (a tile's k columns stay in one workgroup, whose
+    threads reduce the sixteen channels' amax among themselves)."""
+    return n // 16
+
+
+def be_quantize_packed(wp, w8, scale):
+    """Table entry of `quantize_packed_batched`: the work of `ops.quantize_packed_weight_fp8`, validated here (the device
+    table cannot be)."""
+    from ._lib import WeightQuantDesc
+    if wp.dim() != 4 or tuple(wp.shape[2:]) != (64, 8) or not _bf16(wp, "wp").is_contiguous():
+        raise ValueError("quantize_packed: wp must be a packed bf16 weight [n/16, k/32, 64, 8]")
+    n, k = wp.shape[0] * 16, wp.shape[1] * 32
+    if n <= 0 or k <= 0 or k % 128 or n > 1 << 24 or k > 1 << 24:
+        raise ValueError(f"quantize_packed: n = {n}, k = {k}: k % 128 == 0 expected")
+    if not w8.is_cuda or not w8.is_contiguous() or w8.numel() * w8.element_size() != n * k:
+        raise ValueError(f"quantize_packed: w8 must hold the {n * k} bytes of [n/16, k/64, 64, 16]")
+    if _f32(scale, "scale").numel() != n or not scale.is_contiguous():
+        raise ValueError(f"quantize_packed: scale fp32 [{n}]")
+    if any(t.data_ptr() & 15 for t in (wp, w8, scale)):
+        raise ValueError("quantize_packed: 16-byte aligned tensors")
+    spans = [(wp.data_ptr(), 2 * n * k), (w8.data_ptr(), n * k), (scale.data_ptr(), 4 * n)]
+    for i, (a, an) in enumerate(spans):
+        for b, bn in spans[i + 1:]:
+            if a < b + bn and b < a + an:
+                raise ValueError("quantize_packed: wp, w8 and scale must not overlap")
+    d = WeightQuantDesc(w=wp.data_ptr(), w8=w8.data_ptr(), scale=scale.data_ptr(), n=n, k=k, n_items=quantize_packed_items(n, k),
+                        pad=0, first_item=0)
+    return d, (wp, w8, scale)
+
+
+def quantize_packed_batched(entries, device, run: bool = False) -> Op:
+    """ONE launch (bl_quantize_weight_fp8_packed_batched) for the table entries made by be_quantize_packed: every e4m3 copy of
+    a model's adapted weights. Bit-identical to one `ops.quantize_packed_weight_fp8` per entry."""
+    import numpy as np
+    from ._lib import WeightQuantDesc
+    if not entries:
+        raise ValueError("quantize_packed_batched: no entries")
+    descs, tot = [e[0] for e in entries], 0
+    for d in descs:
+        d.first_item = tot
+        tot += d.n_items
+    arr = (WeightQuantDesc * len(descs))(*descs)
+    table = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(device)
+    keep = tuple(t for e in entries for t in e[1])
+    return _op("bl_quantize_weight_fp8_packed_batched", (table.data_ptr(), len(descs)), (table,) + keep, run,
+               nbytes=float(sum(3 * d.n * d.k for d in descs)))
+
+
 def cast(src: torch.Tensor, dst: torch.Tensor, run: bool = True) -> Op:
     """fp32 → bf16 (round to nearest even) or bf16 → fp32 of flat contiguous buffers (gradient wire format)."""
     assert src.is_contiguous() and dst.is_contiguous() and src.numel() == dst.numel()

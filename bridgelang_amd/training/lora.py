@@ -34,6 +34,8 @@ formed in fp32: identical where those sums are exact, else within the fp32 accum
 the final rounding next to a tie (tests/test_lora_merge_gpu.py states the bound). `adapted_weights()` is a second set of
 packed weights beside the frozen base (`VLAWeights.adapted_view`), `refresh()` the ONE batched launch that rewrites it from
 the live A / B; the base stays resident and untouched — an RL learner's reference policy.
+`enable_fp8()` adds e4m3 copies of the adapted decoder-layer weights for the e4m3 prefill (`OpenVLAEngine(fp8=True)`); the
+refresh then ends with one `bl_quantize_weight_fp8_packed_batched` launch (csrc/quantize_weight_fp8.hip) that rewrites them.
 """
 from __future__ import annotations
 
@@ -44,9 +46,10 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..weights import PackedGroup, VLAWeights, _pack, _unpack
+from ..weights import Arena, PackedGroup, VLAWeights, _pack, _unpack
 
 RP = 64          # padded rank
+FP8_NAMES = ("qkv_w", "o_w", "gu_w", "down_w")     # the decoder-layer weights engine._fp8_layers keeps e4m3 copies of
 
 
 @dataclass(eq=False)
@@ -137,6 +140,9 @@ class LoraAdapters:
             self.by_packed[g.packed.data_ptr()] = ad
         self._adapted: Optional[VLAWeights] = None       # adapted_weights(): built on first use
         self._refresh_ops: Optional[List[ops.Op]] = None
+        self._plan_handed_out = False                    # refresh_ops() gave the plan to a caller who may keep a copy (TrainStep)
+        self._fp8: Optional[List[Dict[str, Tuple[torch.Tensor, torch.Tensor]]]] = None   # enable_fp8(): the adapted view's e4m3 copies
+        self._fp8_arena: Optional[Arena] = None
         self.init_gaussian(seed)
 
     def get(self, packed: torch.Tensor) -> Optional[Adapter]:
@@ -226,22 +232,77 @@ class LoraAdapters:
             self._adapted = self.w.adapted_view([ad.group for ad in self.adapters])
         return self._adapted
 
-    def refresh_ops(self) -> List[ops.Op]:
-        """The prepared refresh: ONE `bl_lora_merge_batched_bf16` launch over all adapted groups (replayable, graph-capturable)."""
+    # ---- e4m3 prefill under the adapters: the adapted view's e4m3 copies, requantised with every refresh ----
+    @property
+    def fp8_enabled(self) -> bool:
+        return self._fp8 is not None
+
+    def enable_fp8(self) -> "LoraAdapters":
+        """Give `adapted_weights()` e4m3 copies (+ per-channel scales) of every decoder layer's qkv_w / o_w / gu_w / down_w, in
+        one Arena, installed as that view's `_fp8_layers` cache in the shape engine._fp8_layers returns ([{name: (packed,
+        scale)}] per layer), so `OpenVLAEngine(adapted, fp8=True)` reads them unchanged. They are filled here once and
+        from then on rewritten IN PLACE by every refresh: `refresh_ops()` becomes the merge launch followed by ONE
+        `bl_quantize_weight_fp8_packed_batched` launch (csrc/quantize_weight_fp8.hip: the kernels' quantiser specification —
+        not bit-identical to the base model's load-time ops.quantize_weight_fp8, which divides by the scale).
+        Call it BEFORE a `TrainStep(..., lora=self, refresh_adapted=True)` is built: the step copies `refresh_ops()`, and a
+        copy made earlier would keep refreshing the bf16 weights only — so enabling after `refresh_ops()` has handed the
+        plan out raises RuntimeError. llm_dim and llm_inter must be multiples of 128 (bl_gemm_fp8's K), else ValueError."""
+        if self._fp8 is not None:
+            return self
+        if self._plan_handed_out:
+            raise RuntimeError("enable_fp8() after refresh_ops() was handed out (a TrainStep(refresh_adapted=True) holds a copy that "
+                               "refreshes the bf16 weights only): enable fp8 before building the step")
+        d = self.w.dims
+        if d.llm_dim % 128 or d.llm_inter % 128:
+            raise ValueError("fp8 prefill needs llm_dim and llm_inter to be multiples of 128")
+        view = self.adapted_weights()
+        arena = Arena(self.w.embed.device)
+        slots = []
+        for lw in view.layers:
+            row = {}
+            for name in FP8_NAMES:
+                wp = getattr(lw, name)
+                n, k = wp.shape[0] * 16, wp.shape[1] * 32
+                row[name] = (arena.reserve((n // 16, k // 64, 64, 8)), arena.reserve((2 * n,)))      # fp32 [n] as 2n bf16 slots
+            slots.append(row)
+        arena.commit()
+        self._fp8 = [{name: (arena.view(a), arena.view(b).view(torch.float32)) for name, (a, b) in row.items()} for row in slots]
+        self._fp8_arena = arena
+        view.__dict__["_fp8_layers"] = self._fp8
+        self._refresh_ops = None                         # rebuilt with the quantise launch
+        if self.w.embed.is_cuda:                         # a CPU-allocated model (layout tests) runs no kernel
+            ops.run_all(self._plan()[1:])
+        return self
+
+    def _plan(self) -> List[ops.Op]:
         from .. import train_ops as T
         view = self.adapted_weights()
         if self._refresh_ops is None:
             index = {id(g): i for i, g in enumerate(self.w.groups)}
+            dev = self.w.embed.device
             entries = [T.be_lora_merge(ad.group.packed, ad.A, ad.B, self.scaling, view.groups[index[id(ad.group)]].packed, RP,
                                        len(ad.modules), ad.mode == "interleave") for ad in self.adapters]
-            self._refresh_ops = [T.lora_merge_batched(entries, self.w.embed.device, run=False)]
+            plan = [T.lora_merge_batched(entries, dev, run=False)]
+            if self._fp8 is not None:
+                plan.append(T.quantize_packed_batched([T.be_quantize_packed(getattr(lw, name), *row[name])
+                                                       for lw, row in zip(view.layers, self._fp8) for name in FP8_NAMES], dev, run=False))
+            self._refresh_ops = plan
         return self._refresh_ops
 
+    def refresh_ops(self) -> List[ops.Op]:
+        """The prepared refresh (replayable, graph-capturable): ONE `bl_lora_merge_batched_bf16` launch over all adapted groups,
+        followed — after `enable_fp8()` — by ONE `bl_quantize_weight_fp8_packed_batched` launch over the decoder layers' e4m3
+        copies. A caller may keep the list (TrainStep does): from here on `enable_fp8()` raises."""
+        plan = self._plan()
+        self._plan_handed_out = True
+        return plan
+
     def refresh(self) -> None:
-        """Rewrite `adapted_weights()` from the live A / B and the frozen base: W' = bf16(W + bf16(s·B)·A) per group.
+        """Rewrite `adapted_weights()` from the live A / B and the frozen base: W' = bf16(W + bf16(s·B)·A) per group; after
+        `enable_fp8()` also their e4m3 copies and scales.
         Ordering contract: this is an op on the CURRENT stream, ordered like any other launch there. Engines that read the
         adapted weights on that stream (`predict_action`, `sample_actions`, `score_actions`, `OpenVLAEngine`) see the new
         weights from their next run on; a `StaggeredDecodePipeline` has batches in flight across calls and must be
         `flush()`ed before the refresh. Captured engine graphs stay valid: the buffers are rewritten in place, no pointer
         changes. `TrainStep(..., lora=self, refresh_adapted=True)` runs it after every optimizer step."""
-        ops.run_all(self.refresh_ops())
+        ops.run_all(self._plan())

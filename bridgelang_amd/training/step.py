@@ -545,8 +545,9 @@ class TrainStep:
         if lora is not None:
             self._build_extended_weights()
             if refresh_adapted:                 # after the adapter refresh in the re-pack plan: reads the written-back A / B
-                self._adapter_ops = self._adapter_ops + lora.refresh_ops()
-                ops.run_all(self._adapter_ops[-1:])
+                plan = lora.refresh_ops()       # the merge launch; after lora.enable_fp8() also the e4m3 requantisation
+                self._adapter_ops = self._adapter_ops + plan
+                ops.run_all(plan)
         # execution order of the vision units (forward; the backward visits each tower's blocks top down, then its stem)
         vkey = lambda tw, i: f"vision.{tw.dims.prefix.split('.')[1]}." + ("stem" if i < 0 else f"block{i:02d}")
         self._vkey = vkey

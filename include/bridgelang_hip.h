@@ -477,6 +477,21 @@ int bl_lora_merge_bf16(const bl_bf16* w_packed, const bl_bf16* A, const bl_bf16*
  * device): build them with train_ops.lora_merge_batched, which checks what bl_lora_merge_bf16 checks. Same device code and
  * summation order as bl_lora_merge_bf16: bit-identical results. */
 int bl_lora_merge_batched_bf16(const void* table, int32_t n_groups, void* stream);
+/* Packed bf16 GEMM weight → the W8 operand of bl_gemm_fp8 and its per-channel scales, on the device (csrc/
+ * quantize_weight_fp8.hip): w_packed fragment-major [n/16, k/32, 64, 8] (bl_pack_weight_bf16, bl_lora_merge_bf16), w8_packed the
+ * n·k bytes of [n/16, k/64, 64 lanes, 16 B], scale fp32 [n]. Per output channel, the quantiser specification of
+ * bl_quantize_rows_fp8: amax = max |w|; scale = amax / 448 and inv = 448 / amax when amax >= 2^-100, else scale = inv = 1;
+ * code = e4m3_rne_sat(fl32(w * inv)). e4m3 lane L of fragment (nt, ks8) = row 16·nt + (L & 15), columns 64·ks8 + 16·(L >> 4) + 0…15
+ * = the 16 bytes of bf16 fragment (nt, 2·ks8 + (L >> 5)), lane (L & 15) + 32·((L >> 4) & 1), then those of the lane 16 above.
+ * n % 16 == 0, k % 128 == 0 (bl_gemm_fp8's limit), 16-byte aligned pointers, no buffer overlapping another (BL_E_ARG). Every
+ * output byte is written whatever the buffers held; no atomics, no workspace. */
+int bl_quantize_weight_fp8_packed(const bl_bf16* w_packed, int64_t n, int64_t k, void* w8_packed, float* scale, void* stream);
+/* ONE launch for a device table of the above — every e4m3 copy of a model's adapted weights after a refresh. table: device array of
+ *   struct { const bl_bf16* w; void* w8; float* scale; int32 n, k, n_items, pad; int64 first_item; }
+ * n_items = n / 16 (one work item per 16-row tile), first_item = prefix sum of n_items. The entries are NOT validated (the
+ * table is on the device): build them with train_ops.quantize_packed_batched, which checks what the single call checks.
+ * Same device code as bl_quantize_weight_fp8_packed: bit-identical results. */
+int bl_quantize_weight_fp8_packed_batched(const void* table, int32_t n_entries, void* stream);
 /* y += a * x on flat fp32 buffers: gradient accumulation over micro-batches with the loss normalised by the number of
  * accumulation steps (vla-scripts/finetune.py:256-262, 307-310). */
 int bl_axpy_f32(float* y, const float* x, float a, int64_t n, void* stream);
