@@ -10,12 +10,14 @@ only, modeling_prismatic.py:326,460-463); per-sample results equal independent b
 """
 from __future__ import annotations
 
+import functools
 from typing import List, Optional, Tuple
 
 import torch
 
 from . import ops
-from .ops import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_F32_BF16R, EPI_NONE, EPI_RES, EPI_SWIGLU, Op
+from .llm_plan import decode_fused, decode_layer, head, head_fused, prefill_layer
+from .ops import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_F32_BF16R, EPI_NONE, EPI_RES, EPI_SWIGLU, Fp8Weight, Op
 from .weights import TowerW, VLAWeights
 
 
@@ -28,13 +30,13 @@ def rope_tables(head_dim: int, max_pos: int, theta: float, device) -> tuple:
 
 
 def _fp8_layers(weights: VLAWeights) -> list:
-    """e4m3 copies (+ per-channel scales) of the Llama projection weights, quantised once per weight set from the packed
+    """e4m3 copies ([{name: ops.Fp8Weight}] per layer) of the Llama projection weights, quantised once per weight set from the packed
     bf16 arena (ops.quantize_weight_fp8) and kept on the weights object: shared by every engine built over these weights.
     (Quantised from the weights as they are NOW: call `weights.__dict__.pop("_fp8_layers", None)` after loading others.)"""
     cache = weights.__dict__.get("_fp8_layers")
     if cache is None:
-        cache = [{n: ops.quantize_weight_fp8(ops.unpack_weight(getattr(lw, n))) for n in ("qkv_w", "o_w", "gu_w", "down_w")}
-                 for lw in weights.layers]
+        cache = [{n: Fp8Weight(*ops.quantize_weight_fp8(ops.unpack_weight(getattr(lw, n))))
+                  for n in ("qkv_w", "o_w", "gu_w", "down_w")} for lw in weights.layers]
         weights.__dict__["_fp8_layers"] = cache
     return cache
 
@@ -242,156 +244,129 @@ class OpenVLAEngine:
         a batch range is a contiguous slice of each; results do not depend on the range a sequence is run in."""
         d, w, S = self.dims, self.w, self.S
         b1 = self.B if b1 is None else b1
-        B = b1 - b0
-        D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
-        rows = slice(b0 * S, b1 * S)
-        x3 = self.x[b0:b1]
-        x = x3.view(B * S, D)
-        h, qkv, ao, act = self.h[rows], self.qkv[rows], self.ao[rows], self.act[rows]
-        xd, hdd, aod, actd = self.xd[b0:b1], self.hd[b0:b1], self.aod[b0:b1], self.actd[b0:b1]
+        B, D, H, hd = b1 - b0, d.llm_dim, d.llm_heads, d.head_dim
+        rows, x3 = slice(b0 * S, b1 * S), self.x[b0:b1]
+        x, h, qkv, ao, act = x3.view(B * S, D), self.h[rows], self.qkv[rows], self.ao[rows], self.act[rows]
         key_mask = self.key_mask[b0:b1] if self.key_mask is not None else None
+        cs = (H * self.cache_len * hd, self.cache_len * hd, hd)
+        rope_in_attention = hd == 128 and S <= 320
+        fp8 = self.fp8 and rope_in_attention       # the e4m3 linears are built for the layers of the fused attention
+
+        def lin(l, x, name, out, epi, **kw):
+            if not fp8:
+                return [self._g(x, getattr(w.layers[l], name), out, epi, run=False, **kw)]
+            q8 = (self.act8 if name == "down_w" else self.h8)[rows]
+            return ops.linear_fp8(x, q8, self.sq[rows], *self.w8[l][name], out, epi, **kw)
+
+        def attn(l):
+            kc, vc = self.k_cache[l][b0:b1], self.v_cache[l][b0:b1]
+            if rope_in_attention:   # RoPE and the KV-cache write ride inside the attention kernel's q / k / v loads
+                return [ops.attention_rope(qkv, kc, vc, ao, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, pos0=0,
+                                           key_mask=key_mask, run=False)]
+            return [ops.rope_kvcache(qkv, self.cos, self.sin, kc, vc, B=B, S=S, H=H, head_dim=hd, pos0=0, run=False),
+                    ops.attention(qkv, kc, vc, ao, B=B, H=H, Sq=S, Skv=S, head_dim=hd, q_strides=(S * 3 * D, hd, 3 * D),
+                                  k_strides=cs, v_strides=cs, o_strides=(S * D, hd, D), causal=True, key_mask=key_mask,
+                                  run=False)]
+
         plan = [ops.embed_splice(self.input_ids[b0:b1], w.embed, x3, self.n_patches, run=False)]
         self.layer_ends: List[int] = []       # len(plan) after each decoder layer (hidden-state taps of the all_rows plan)
-        cs = (H * self.cache_len * hd, self.cache_len * hd, hd)
         # Generation consumes only the last position of the last layer (the reference materialises all S rows of every
-        # layer, SURVEY App. C.5): that layer still projects K/V for every position (the decode steps attend to them),
-        # but its attention, o_proj, MLP run on the B last rows only — single-query attention + weight-streaming GEMMs.
+        # layer, SURVEY App. C.5): _plan_last_rows.
         last_rows_only = not self.all_rows and d.llm_layers > 1
-        for l, lw in enumerate(w.layers):
-            kc, vc = self.k_cache[l][b0:b1], self.v_cache[l][b0:b1]
-            plan.append(ops.rmsnorm(x, lw.ln1, h, d.rms_eps, run=False))
-            plan.append(self._g(h, lw.qkv_w, qkv, EPI_NONE, run=False))
-            last = last_rows_only and l == d.llm_layers - 1
-            if self.fp8 and not last and hd == 128 and S <= 320:
-                w8, h8, act8, sq = self.w8[l], self.h8[rows], self.act8[rows], self.sq[rows]
-                q8 = lambda src, dst: ops.quantize_rows_fp8(src, dst, sq, run=False)[2]
-                plan[-1] = q8(h, h8)                                           # replaces the bf16 qkv GEMM appended above
-                plan.append(ops.gemm_fp8(h8, sq, *w8["qkv_w"], qkv, EPI_NONE, run=False))
-                plan.append(ops.attention_rope(qkv, kc, vc, ao, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, pos0=0,
-                                               key_mask=key_mask, run=False))
-                plan.append(q8(ao, h8))
-                plan.append(ops.gemm_fp8(h8, sq, *w8["o_w"], x, EPI_RES, res=x, run=False))
-                plan.append(ops.rmsnorm(x, lw.ln2, h, d.rms_eps, run=False))
-                plan.append(q8(h, h8))
-                plan.append(ops.gemm_fp8(h8, sq, *w8["gu_w"], act, EPI_SWIGLU, run=False))
-                plan.append(q8(act, act8))
-                plan.append(ops.gemm_fp8(act8, sq, *w8["down_w"], x, EPI_RES, res=x, run=False))
-                self.layer_ends.append(len(plan))
-                continue
-            if not last and hd == 128 and S <= 320:
-                # RoPE and the KV-cache write ride inside the attention kernel's q / k / v loads
-                plan.append(ops.attention_rope(qkv, kc, vc, ao, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, pos0=0,
-                                               key_mask=key_mask, run=False))
-                plan.append(self._g(ao, lw.o_w, x, EPI_RES, res=x, run=False))
-                plan.append(ops.rmsnorm(x, lw.ln2, h, d.rms_eps, run=False))
-                plan.append(self._g(h, lw.gu_w, act, EPI_SWIGLU, run=False))
-                plan.append(self._g(act, lw.down_w, x, EPI_RES, res=x, run=False))
-                self.layer_ends.append(len(plan))
-                continue
-            plan.append(ops.rope_kvcache(qkv, self.cos, self.sin, kc, vc, B=B, S=S, H=H, head_dim=hd, pos0=0, run=False))
-            if last and self.padded:
-                # each sequence's last REAL position: gather its (rotated) q row and residual row (bl_gather_rows_bf16: a
-                # copy, no arithmetic), then the same single-query attention / weight-streaming GEMMs as the un-padded plan
-                q_last, x_last, last_row = self.q_last[b0:b1], self.x_last[b0:b1], self.last_row[b0:b1]
-                plan.append(ops.gather_rows(qkv.view(B, S, 3 * D)[:, :, :D], last_row, q_last, run=False))   # the q third
-                plan.append(ops.gather_rows(x3, last_row, x_last, run=False))
-                plan.append(ops.attention_decode(q_last, kc, vc, aod, B=B, H=H, Skv=S, head_dim=hd,
-                                                 q_strides=(D, hd, D), k_strides=cs, v_strides=cs,
-                                                 o_strides=(D, hd, D), key_mask=self.cache_mask[b0:b1], run=False))
-            elif last:
-                q_last = qkv.view(B, S, 3 * D)[:, S - 1]                       # roped in place; row stride S·3D
-                x_last = x3[:, S - 1, :]
-                plan.append(ops.attention_decode(q_last, kc, vc, aod, B=B, H=H, Skv=S, head_dim=hd,
-                                                 q_strides=(S * 3 * D, hd, 3 * D), k_strides=cs, v_strides=cs,
-                                                 o_strides=(D, hd, D), run=False))
-            if last:
-                plan.append(self._g(aod, lw.o_w, xd, EPI_RES, res=x_last, run=False))
-                if ops.skinny_supported(B, D, EPI_SWIGLU):
-                    plan.append(self._g(xd, lw.gu_w, actd, EPI_SWIGLU, a_norm=(lw.ln2, d.rms_eps), run=False))
-                else:
-                    plan.append(ops.rmsnorm(xd, lw.ln2, hdd, d.rms_eps, run=False))
-                    plan.append(self._g(hdd, lw.gu_w, actd, EPI_SWIGLU, run=False))
-                plan.append(self._g(actd, lw.down_w, xd, EPI_RES, res=xd, run=False))
-                return plan + self._head(xd, 0, b0, b1)
-            plan.append(ops.attention(qkv, kc, vc, ao, B=B, H=H, Sq=S, Skv=S, head_dim=hd,
-                                      q_strides=(S * 3 * D, hd, 3 * D), k_strides=cs, v_strides=cs,
-                                      o_strides=(S * D, hd, D), causal=True, key_mask=key_mask, run=False))
-            plan.append(self._g(ao, lw.o_w, x, EPI_RES, res=x, run=False))
-            plan.append(ops.rmsnorm(x, lw.ln2, h, d.rms_eps, run=False))
-            plan.append(self._g(h, lw.gu_w, act, EPI_SWIGLU, run=False))
-            plan.append(self._g(act, lw.down_w, x, EPI_RES, res=x, run=False))
+        for l in range(d.llm_layers - int(last_rows_only)):
+            plan += prefill_layer(w.layers[l], x, h, qkv, ao, act, d.rms_eps, functools.partial(lin, l), attn(l))
             self.layer_ends.append(len(plan))
+        if last_rows_only:
+            return plan + self._plan_last_rows(b0, b1)
         if self.all_rows:   # HF semantics: logits for every position (what forward()/training consume)
-            plan.append(ops.rmsnorm(x, w.norm, h, d.rms_eps, run=False))
-            plan.append(self._g(h, w.lm_head, self.logits_all[rows], EPI_F32_BF16R, run=False))
-            return plan
+            return plan + [ops.rmsnorm(x, w.norm, h, d.rms_eps, run=False),
+                           self._g(h, w.lm_head, self.logits_all[rows], EPI_F32_BF16R, run=False)]
         # final norm + lm_head on the last position only (the reference materialises all S rows, SURVEY App. C.5)
-        plan += self._head(x3[:, S - 1, :], 0, b0, b1)
-        return plan
+        return plan + self._head(x3[:, S - 1, :], 0, b0, b1)
+
+    def _plan_last_rows(self, b0: int, b1: int) -> List[Op]:
+        """The last decoder layer of a generation prefill + the first token: it still projects K/V for every position (the
+        decode steps attend to them), but its attention, o_proj and MLP run on the B last rows only — single-query
+        attention + weight-streaming GEMMs."""
+        d, S, B, lw = self.dims, self.S, b1 - b0, self.w.layers[-1]
+        D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
+        x3, xd, aod, actd = self.x[b0:b1], self.xd[b0:b1], self.aod[b0:b1], self.actd[b0:b1]
+        h, qkv = self.h[b0 * S:b1 * S], self.qkv[b0 * S:b1 * S]
+        kc, vc = self.k_cache[-1][b0:b1], self.v_cache[-1][b0:b1]
+        cs = (H * self.cache_len * hd, self.cache_len * hd, hd)
+        plan = [ops.rmsnorm(x3.view(B * S, D), lw.ln1, h, d.rms_eps, run=False), self._g(h, lw.qkv_w, qkv, EPI_NONE, run=False),
+                ops.rope_kvcache(qkv, self.cos, self.sin, kc, vc, B=B, S=S, H=H, head_dim=hd, pos0=0, run=False)]
+        if self.padded:
+            # each sequence's last REAL position: gather its (rotated) q row and residual row (bl_gather_rows_bf16: a
+            # copy, no arithmetic), then the same single-query attention / weight-streaming GEMMs as the un-padded plan
+            q_last, x_last, last_row = self.q_last[b0:b1], self.x_last[b0:b1], self.last_row[b0:b1]
+            q_strides, mask = (D, hd, D), self.cache_mask[b0:b1]
+            plan += [ops.gather_rows(qkv.view(B, S, 3 * D)[:, :, :D], last_row, q_last, run=False),   # the q third
+                     ops.gather_rows(x3, last_row, x_last, run=False)]
+        else:
+            q_last, x_last = qkv.view(B, S, 3 * D)[:, S - 1], x3[:, S - 1, :]      # roped in place; row stride S·3D
+            q_strides, mask = (S * 3 * D, hd, 3 * D), None
+        plan.append(ops.attention_decode(q_last, kc, vc, aod, B=B, H=H, Skv=S, head_dim=hd, q_strides=q_strides,
+                                         k_strides=cs, v_strides=cs, o_strides=(D, hd, D), key_mask=mask, run=False))
+        plan.append(self._g(aod, lw.o_w, xd, EPI_RES, res=x_last, run=False))
+        plan += self._norm_lin(xd, lw.ln2, lw.gu_w, actd, EPI_SWIGLU, ops.skinny_supported(B, D, EPI_SWIGLU), b0, b1)
+        return plan + [self._g(actd, lw.down_w, xd, EPI_RES, res=xd, run=False)] + self._head(xd, 0, b0, b1)
+
+    def _norm_lin(self, x, norm_w, W, out, epi, fused: bool, b0: int = 0, b1: Optional[int] = None) -> List[Op]:
+        """A linear on B rows with an RMSNorm in front: fused into the weight-streaming GEMM (`a_norm`), or a launch of
+        its own into `hd` ahead of the GEMM."""
+        if fused:
+            return [self._g(x, W, out, epi, a_norm=(norm_w, self.dims.rms_eps), run=False)]
+        return [ops.rmsnorm(x, norm_w, self.hd[b0:b1], self.dims.rms_eps, run=False), self._g(self.hd[b0:b1], W, out, epi, run=False)]
 
     def _head(self, x_rows: torch.Tensor, t: int, b0: int = 0, b1: Optional[int] = None) -> List[Op]:
-        """final RMSNorm → lm_head (bf16-rounded fp32 logits) → greedy argmax (sample=True: the seeded draw; score=True:
-        the score of the forced token), for generation step t."""
-        d, w = self.dims, self.w
-        b1 = self.B if b1 is None else b1
-        logits, ids, hdd = self.logits[t][b0:b1], self.gen_ids[t][b0:b1], self.hd[b0:b1]
-        if ops.skinny_supported(b1 - b0, d.llm_dim, EPI_F32_BF16R):   # RMSNorm fused into the weight-streaming GEMM
-            plan = [self._g(x_rows, w.lm_head, logits, EPI_F32_BF16R, a_norm=(w.norm, d.rms_eps), run=False)]
-        else:
-            plan = [ops.rmsnorm(x_rows, w.norm, hdd, d.rms_eps, run=False),
-                    self._g(hdd, w.lm_head, logits, EPI_F32_BF16R, run=False)]
-        if self.sample:
-            plan.append(ops.sample(logits, self.samp_temperature[b0:b1], self.samp_top_k[b0:b1], self.samp_top_p[b0:b1],
-                                   self.samp_seed[b0:b1], t, ids, self.gen_wt[t][b0:b1], run=False, vocab=self.vocab_range))
-        elif self.score_mode:
-            plan.append(ops.score(logits, self.samp_temperature[b0:b1], self.samp_top_k[b0:b1], self.samp_top_p[b0:b1], ids,
-                                  self.gen_wt[t][b0:b1], *self._score_range_args(t, b0, b1), run=False,
-                                  vocab=self.vocab_range))
-        else:
-            plan.append(ops.argmax(logits, ids, run=False))
-        return plan
+        """final RMSNorm → lm_head (bf16-rounded fp32 logits) → the token of generation step t."""
+        logits = self.logits[t][b0:b1]
+        norm_lin = functools.partial(self._norm_lin, fused=head_fused(logits.shape[0], self.dims), b0=b0, b1=b1)
+        return head(self.w, x_rows, logits, norm_lin, [self._pick(logits, t, b0, b1)])
 
-    def _score_range_args(self, t: int, b0: int = 0, b1: Optional[int] = None) -> tuple:
-        """(range_first, range_wt) of ops.score for generation step t; no range: (0, None)."""
-        if self.score_range is None:
-            return 0, None
-        return self.score_range[0], self.gen_range_wt[t][b0:b1]
+    def _pick(self, logits: torch.Tensor, t: int, b0: int = 0, b1: Optional[int] = None) -> Op:
+        """Generation step t's token from its logits: greedy argmax (sample=True: the seeded draw; score=True: the score
+        of the forced token). The pipeline calls it with its own logits rows for this engine's batch."""
+        ids = self.gen_ids[t][b0:b1]
+        if self.sample:
+            return ops.sample(logits, self.samp_temperature[b0:b1], self.samp_top_k[b0:b1], self.samp_top_p[b0:b1],
+                              self.samp_seed[b0:b1], t, ids, self.gen_wt[t][b0:b1], run=False, vocab=self.vocab_range)
+        if self.score_mode:
+            rng = (0, None) if self.score_range is None else (self.score_range[0], self.gen_range_wt[t][b0:b1])
+            return ops.score(logits, self.samp_temperature[b0:b1], self.samp_top_k[b0:b1], self.samp_top_p[b0:b1], ids,
+                             self.gen_wt[t][b0:b1], *rng, run=False, vocab=self.vocab_range)
+        return ops.argmax(logits, ids, run=False)
+
+    def _decode_attn(self, l: int, t: int, qkv, ao, fused: bool, rope: Optional[tuple] = None) -> List[Op]:
+        """Attention of decode step t in layer l: this batch's token at position S+t-1 against its own KV cache, from
+        qkv [B, 3D] into ao [B, D] (the pipeline passes its rows for this batch, and one pair of rope tables for all)."""
+        d, B, pos = self.dims, self.B, self.S + t - 1
+        D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
+        (cos, sin), kc, vc = rope or (self.cos, self.sin), self.k_cache[l], self.v_cache[l]
+        if fused:
+            # padded: every sequence appends at its own position (over its pad rows): the cache layout, and with
+            # it every sum, is the one of the sequence's un-padded run
+            pad_kw = dict(rope_pos=self.rope_pos[t]) if self.padded else {}
+            return [ops.attention_decode_rope(qkv, kc, vc, ao, cos, sin, B=B, H=H, head_dim=hd, pos=pos, run=False, **pad_kw)]
+        cs = (H * self.cache_len * hd, self.cache_len * hd, hd)
+        return [ops.rope_kvcache(qkv, cos, sin, kc, vc, B=B, S=1, H=H, head_dim=hd, pos0=pos, run=False),
+                ops.attention_decode(qkv, kc, vc, ao, B=B, H=H, Skv=pos + 1, head_dim=hd, q_strides=(3 * D, hd, 3 * D),
+                                     k_strides=cs, v_strides=cs, o_strides=(D, hd, D), run=False)]
 
     def _plan_decode(self, t: int) -> List[Op]:
         """Cached-generation step t (modeling_prismatic.py:325-341): token gen_ids[t-1] at position S+t-1. Five
-        launches per layer: qkv (RMSNorm fused) → attention (RoPE + KV append fused) → o_proj+residual → gate/up
-        (RMSNorm + SwiGLU fused) → down+residual."""
-        d, w, B = self.dims, self.w, self.B
-        D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
-        pos = self.S + t - 1
-        fused = ops.skinny_supported(B, D, EPI_NONE) and hd == 128
-        cs = (H * self.cache_len * hd, self.cache_len * hd, hd)
+        launches per layer when B rows fit the skinny kernel: qkv (RMSNorm fused) → attention (RoPE + KV append fused) →
+        o_proj+residual → gate/up (RMSNorm + SwiGLU fused) → down+residual."""
+        B, D, w = self.B, self.dims.llm_dim, self.w
+        fused = decode_fused(B, self.dims)
+        norm_lin = functools.partial(self._norm_lin, fused=fused)
+        lin = lambda x, W, out, epi, res: [self._g(x, W, out, epi, res=res, run=False)]
+        attn = lambda l: self._decode_attn(l, t, self.qkvd, self.aod, fused)
         plan = [ops.embed_splice(self.gen_ids[t - 1].view(B, 1), w.embed, self.xd.view(B, 1, D), 0, run=False)]
         for l, lw in enumerate(w.layers):
-            if fused:
-                plan.append(self._g(self.xd, lw.qkv_w, self.qkvd, EPI_NONE, a_norm=(lw.ln1, d.rms_eps), run=False))
-                # padded: every sequence appends at its own position (over its pad rows): the cache layout, and with
-                # it every sum, is the one of the sequence's un-padded run
-                pad_kw = dict(rope_pos=self.rope_pos[t]) if self.padded else {}
-                plan.append(ops.attention_decode_rope(self.qkvd, self.k_cache[l], self.v_cache[l], self.aod, self.cos,
-                                                      self.sin, B=B, H=H, head_dim=hd, pos=pos, run=False, **pad_kw))
-            else:
-                plan.append(ops.rmsnorm(self.xd, lw.ln1, self.hd, d.rms_eps, run=False))
-                plan.append(self._g(self.hd, lw.qkv_w, self.qkvd, EPI_NONE, run=False))
-                plan.append(ops.rope_kvcache(self.qkvd, self.cos, self.sin, self.k_cache[l], self.v_cache[l], B=B, S=1,
-                                             H=H, head_dim=hd, pos0=pos, run=False))
-                plan.append(ops.attention_decode(self.qkvd, self.k_cache[l], self.v_cache[l], self.aod, B=B, H=H,
-                                                 Skv=pos + 1, head_dim=hd, q_strides=(3 * D, hd, 3 * D), k_strides=cs,
-                                                 v_strides=cs, o_strides=(D, hd, D), run=False))
-            plan.append(self._g(self.aod, lw.o_w, self.xd, EPI_RES, res=self.xd, run=False))
-            if fused:
-                plan.append(self._g(self.xd, lw.gu_w, self.actd, EPI_SWIGLU, a_norm=(lw.ln2, d.rms_eps), run=False))
-            else:
-                plan.append(ops.rmsnorm(self.xd, lw.ln2, self.hd, d.rms_eps, run=False))
-                plan.append(self._g(self.hd, lw.gu_w, self.actd, EPI_SWIGLU, run=False))
-            plan.append(self._g(self.actd, lw.down_w, self.xd, EPI_RES, res=self.xd, run=False))
-        plan += self._head(self.xd, t)
-        return plan
+            plan += decode_layer(l, lw, self.xd, self.qkvd, self.aod, self.actd, norm_lin, lin, attn)
+        return plan + self._head(self.xd, t)
 
     # ---- execution ------------------------------------------------------------------------------------------------
     def all_ops(self) -> List[Op]:

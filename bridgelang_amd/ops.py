@@ -11,7 +11,7 @@ import functools
 import math
 
 import ctypes as C
-from typing import Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -20,7 +20,7 @@ from ._lib import (AttnDesc, GemmDesc, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_KE
                    EPI_NONE, EPI_SWIGLU_BWD, EPI_SWIGLU_KEEP,
                    EPI_RES, EPI_SWIGLU)
 
-__all__ = ["Op", "gemm", "gemm_last_form", "gemm_form_name", "gemm_fp8", "quantize_rows_fp8", "quantize_weight_fp8", "quantize_packed_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
+__all__ = ["Op", "gemm", "gemm_last_form", "gemm_form_name", "gemm_fp8", "linear_fp8", "Fp8Weight", "quantize_rows_fp8", "quantize_weight_fp8", "quantize_packed_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
            "argmax", "sample", "score", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
            "EPI_NONE", "EPI_BIAS", "EPI_BIAS_GELU", "EPI_BIAS_RES", "EPI_RES", "EPI_SWIGLU", "EPI_F32", "EPI_F32_BF16R",
            "EPI_SWIGLU_KEEP", "EPI_BIAS_GELU_KEEP", "EPI_SWIGLU_BWD", "EPI_GELU_BWD"]
@@ -341,6 +341,19 @@ def gemm_fp8(A8: torch.Tensor, scale_a: torch.Tensor, W8: torch.Tensor, scale_w:
     if run:
         op.run()
     return op
+
+
+class Fp8Weight(NamedTuple):
+    """One weight's e4m3 copy as bl_gemm_fp8 reads it: the packed codes and the fp32 scale per output channel."""
+    w8: torch.Tensor
+    scale: torch.Tensor
+
+
+def linear_fp8(x: torch.Tensor, q: torch.Tensor, sx: torch.Tensor, w8: torch.Tensor, sw: torch.Tensor, out: torch.Tensor,
+               epilogue: int = EPI_NONE, **kw) -> List[Op]:
+    """The e4m3 linear as a plan fragment (nothing runs): quantise the rows of x into q / sx, then
+    out = epilogue(sx[m] · sw[n] · (q @ w8.T)); `kw` as gemm_fp8's (bias, scale, res, …)."""
+    return [quantize_rows_fp8(x, q, sx, run=False)[2], gemm_fp8(q, sx, w8, sw, out, epilogue, run=False, **kw)]
 
 
 def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor, eps: float = 1e-6,

@@ -12,13 +12,15 @@ Each of the two stage pairings is captured once as a HIP graph with fork/join st
 """
 from __future__ import annotations
 
+import functools
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
 from .engine import OpenVLAEngine
-from .ops import EPI_F32_BF16R, EPI_NONE, EPI_RES, EPI_SWIGLU, Op
+from .llm_plan import decode_fused, decode_layer, head, head_fused
+from .ops import Op
 from .weights import VLAWeights
 
 
@@ -136,75 +138,49 @@ class StaggeredDecodePipeline:
         self._tick = 0
 
     def _plan_merged(self, k: int) -> List[Op]:
-        """Decode iteration g = 1 … n_new-1 of the batch in slot (k - g) mod n_new, all in one pass over the weights
-        (the per-batch steps of OpenVLAEngine._plan_decode, modeling_prismatic.py:325-341, stacked on the row axis).
+        """Decode iteration g = 1 … n_new-1 of the batch in slot (k - g) mod n_new, all in one pass over the weights:
+        llm_plan.decode_layer and llm_plan.head — the layer and head OpenVLAEngine._plan_decode emits for ONE batch —
+        over the stacked rows, with the launch forms below."""
+        d, w, B, D, e0, M = self.dims, self.w, self.B, self.dims.llm_dim, self.engines[0], self.xd.shape[0]
+        fused = decode_fused(B, d)
+        groups = [(g, self.engines[(k - g - self.lag) % self.slots], slice((g - 1) * B, g * B)) for g in range(1, self.n_new)]
 
-        Every op mirrors the kernel choice OpenVLAEngine._plan_decode makes for ONE batch, in its many-rows form with the
-        same arithmetic: where the engine streams weights through bl_gemm_skinny_bf16 (B <= 16), the stacked rows go
-        through bl_gemm_skinny_rows_bf16 (same 8-way K partition and combine order) and the fused a_norm becomes
-        bl_rmsnorm_skinny_bf16; where the engine falls back to the tiled kernels, so does this plan (no split-K workspace:
-        the tiled kernels' K order does not depend on the row count). Hence ids and logits equal the plain engine's bit
-        for bit (tests/test_pipeline_gpu.py, tests/test_full_size_gpu.py)."""
-        d, w, B = self.dims, self.w, self.B
-        D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
-        e0 = self.engines[0]
-        fused = ops.skinny_supported(B, D, EPI_NONE) and hd == 128       # OpenVLAEngine._plan_decode's condition
-        M = self.xd.shape[0]
-
-        def gm(A, W, out, epi, res=None):
-            """one Linear over the stacked rows, in the arithmetic the engine uses for B rows"""
+        def lin(A, W, out, epi, res=None):
+            """One Linear over the stacked rows, in the arithmetic the engine uses for B rows: where the engine streams
+            weights through bl_gemm_skinny_bf16 (B <= 16), the stacked rows go through bl_gemm_skinny_rows_bf16 in slices
+            of 128 rows (same 8-way K partition and combine order); where the engine falls back to the tiled kernels, so
+            does this plan (no split-K workspace: the tiled kernels' K order does not depend on the row count)."""
             if not ops.skinny_supported(B, A.shape[1], epi):
                 return [ops.gemm(A, W, out, epi, res=res, skinny=False, run=False)]
             return [ops.gemm(A[r0:r0 + 128], W, out[r0:r0 + 128], epi, res=None if res is None else res[r0:r0 + 128],
                              skinny_rows=True, workspace=self.ws, run=False) for r0 in range(0, M, 128)]
 
-        def norm(x, wn, out, fused_in_engine):
-            return (ops.rmsnorm_skinny if fused_in_engine else ops.rmsnorm)(x, wn, out, d.rms_eps, run=False)
+        def norm_lin(x, norm_w, W, out, epi, fused=fused):
+            """The engine's fused a_norm becomes bl_rmsnorm_skinny_bf16 (its arithmetic) ahead of the linear; its separate
+            RMSNorm stays bl_rmsnorm_bf16. Hence ids and logits equal the plain engine's bit for bit
+            (tests/test_pipeline_gpu.py, tests/test_full_size_gpu.py)."""
+            return [(ops.rmsnorm_skinny if fused else ops.rmsnorm)(x, norm_w, self.hd, d.rms_eps, run=False)] + lin(self.hd, W, out, epi)
 
-        groups = [(g, self.engines[(k - g - self.lag) % self.slots], slice((g - 1) * B, g * B)) for g in range(1, self.n_new)]
+        def attn(l):
+            """Own KV cache, own position: attention runs per batch, as each slot engine's own (against the one pair of
+            rope tables) — or, for up to 8 fused iterations, all of them in one launch."""
+            if not (fused and len(groups) <= 8):
+                return [op for g, e, r in groups for op in e._decode_attn(l, g, self.qkvd[r], self.aod[r], fused, (e0.cos, e0.sin))]
+            # padded: group g's sequences sit at their own positions, row g of the slot engine's device-side rope_pos
+            at = (dict(rope_pos=[e.rope_pos[g] for g, e, _ in groups]) if self.padded else
+                  dict(pos=[e.S + g - 1 for g, e, _ in groups]))
+            return [ops.attention_decode_rope_grouped(
+                self.qkvd, [e.k_cache[l] for _, e, _ in groups], [e.v_cache[l] for _, e, _ in groups], self.aod,
+                e0.cos, e0.sin, B=B, H=d.llm_heads, head_dim=d.head_dim, run=False, **at)]
+
         plan = [ops.embed_splice(e.gen_ids[g - 1].view(B, 1), w.embed, self.xd[r].view(B, 1, D), 0, run=False)
                 for g, e, r in groups]
         for l, lw in enumerate(w.layers):
-            plan.append(norm(self.xd, lw.ln1, self.hd, fused))
-            plan += gm(self.hd, lw.qkv_w, self.qkvd, EPI_NONE)
-            grouped = fused and len(groups) <= 8
-            if grouped:     # all decode iterations' attention in one launch
-                # padded: group g's sequences sit at their own positions, row g of the slot engine's device-side rope_pos
-                at = (dict(rope_pos=[e.rope_pos[g] for g, e, _ in groups]) if self.padded else
-                      dict(pos=[e.S + g - 1 for g, e, _ in groups]))
-                plan.append(ops.attention_decode_rope_grouped(
-                    self.qkvd, [e.k_cache[l] for _, e, _ in groups], [e.v_cache[l] for _, e, _ in groups], self.aod,
-                    e0.cos, e0.sin, B=B, H=H, head_dim=hd, run=False, **at))
-            for g, e, r in groups:
-                pos = e.S + g - 1
-                if grouped:
-                    continue
-                if fused:
-                    pad_kw = dict(rope_pos=e.rope_pos[g]) if self.padded else {}
-                    plan.append(ops.attention_decode_rope(self.qkvd[r], e.k_cache[l], e.v_cache[l], self.aod[r], e0.cos, e0.sin,
-                                                          B=B, H=H, head_dim=hd, pos=pos, run=False, **pad_kw))
-                else:
-                    cs = (H * e.cache_len * hd, e.cache_len * hd, hd)
-                    plan.append(ops.rope_kvcache(self.qkvd[r], e0.cos, e0.sin, e.k_cache[l], e.v_cache[l], B=B, S=1, H=H,
-                                                 head_dim=hd, pos0=pos, run=False))
-                    plan.append(ops.attention_decode(self.qkvd[r], e.k_cache[l], e.v_cache[l], self.aod[r], B=B, H=H,
-                                                     Skv=pos + 1, head_dim=hd, q_strides=(3 * D, hd, 3 * D), k_strides=cs,
-                                                     v_strides=cs, o_strides=(D, hd, D), run=False))
-            plan += gm(self.aod, lw.o_w, self.xd, EPI_RES, res=self.xd)
-            plan.append(norm(self.xd, lw.ln2, self.hd, fused))
-            plan += gm(self.hd, lw.gu_w, self.actd, EPI_SWIGLU)
-            plan += gm(self.actd, lw.down_w, self.xd, EPI_RES, res=self.xd)
-        plan.append(norm(self.xd, w.norm, self.hd, ops.skinny_supported(B, D, EPI_F32_BF16R)))   # OpenVLAEngine._head
-        plan += gm(self.hd, w.lm_head, self.logits, EPI_F32_BF16R)
-        if self.sample:     # iteration g of a batch draws with ITS slot's settings at Philox counter g, as its engine would
-            plan += [ops.sample(self.logits[r], e.samp_temperature, e.samp_top_k, e.samp_top_p, e.samp_seed, g, e.gen_ids[g],
-                                e.gen_wt[g], run=False, vocab=self.vocab_range) for g, e, r in groups]
-        elif self.score:    # … or scores ITS slot's forced token g, which the next iteration's embedding consumes unchanged
-            plan += [ops.score(self.logits[r], e.samp_temperature, e.samp_top_k, e.samp_top_p, e.gen_ids[g], e.gen_wt[g],
-                               *e._score_range_args(g), run=False, vocab=self.vocab_range) for g, e, r in groups]
-        else:
-            plan += [ops.argmax(self.logits[r], e.gen_ids[g], run=False) for g, e, r in groups]
-        return plan
+            plan += decode_layer(l, lw, self.xd, self.qkvd, self.aod, self.actd, norm_lin, lin, attn)
+        # iteration g of a batch draws with ITS slot's settings at Philox counter g, as its engine would — or scores ITS
+        # slot's forced token g, which the next iteration's embedding consumes unchanged
+        return plan + head(w, self.xd, self.logits, functools.partial(norm_lin, fused=head_fused(B, d)),
+                           [e._pick(self.logits[r], g) for g, e, r in groups])
 
     def _run_tick(self, k: int) -> None:
         """stage 1 of slot k ‖ the merged decode iteration over the other slots."""

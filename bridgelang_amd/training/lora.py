@@ -239,8 +239,8 @@ class LoraAdapters:
 
     def enable_fp8(self) -> "LoraAdapters":
         """Give `adapted_weights()` e4m3 copies (+ per-channel scales) of every decoder layer's qkv_w / o_w / gu_w / down_w, in
-        one Arena, installed as that view's `_fp8_layers` cache in the shape engine._fp8_layers returns ([{name: (packed,
-        scale)}] per layer), so `OpenVLAEngine(adapted, fp8=True)` reads them unchanged. They are filled here once and
+        one Arena, installed as that view's `_fp8_layers` cache in the shape engine._fp8_layers returns ([{name:
+        ops.Fp8Weight}] per layer), so `OpenVLAEngine(adapted, fp8=True)` reads them unchanged. They are filled here once and
         from then on rewritten IN PLACE by every refresh: `refresh_ops()` becomes the merge launch followed by ONE
         `bl_quantize_weight_fp8_packed_batched` launch (csrc/quantize_weight_fp8.hip: the kernels' quantiser specification —
         not bit-identical to the base model's load-time ops.quantize_weight_fp8, which divides by the scale).
@@ -266,7 +266,8 @@ class LoraAdapters:
                 row[name] = (arena.reserve((n // 16, k // 64, 64, 8)), arena.reserve((2 * n,)))      # fp32 [n] as 2n bf16 slots
             slots.append(row)
         arena.commit()
-        self._fp8 = [{name: (arena.view(a), arena.view(b).view(torch.float32)) for name, (a, b) in row.items()} for row in slots]
+        self._fp8 = [{name: ops.Fp8Weight(arena.view(a), arena.view(b).view(torch.float32)) for name, (a, b) in row.items()}
+                     for row in slots]
         self._fp8_arena = arena
         view.__dict__["_fp8_layers"] = self._fp8
         self._refresh_ops = None                         # rebuilt with the quantise launch

@@ -30,7 +30,7 @@ import torch
 from .. import ops, train_ops as T
 from ..engine import rope_tables
 from ..ops import (EPI_BIAS, EPI_BIAS_GELU_KEEP, EPI_F32, EPI_F32_BF16R, EPI_GELU_BWD, EPI_NONE, EPI_RES, EPI_SWIGLU_BWD,
-                   EPI_SWIGLU_KEEP, Op)
+                   EPI_SWIGLU_KEEP, Fp8Weight, Op)
 from ..weights import PackedGroup, VLAWeights, _block_view, _unpack
 from .policy_loss import GROUP_STAT_NAMES, STAT_NAMES, PolicyLossConfig
 from .sharding import ShardComm, ShardLayout, bucket_key, comm_order
@@ -441,7 +441,7 @@ class TrainStep:
         dev = weights.embed.device
         self.device = dev
         self._wT: Dict[int, torch.Tensor] = {}       # transposed packed weights for dgrad
-        self._w8: Dict[int, dict] = {}              # packed bf16 weight (data_ptr) → its e4m3 forward / dgrad copies + scales
+        self._w8: Dict[int, Tuple[Fp8Weight, Fp8Weight]] = {}   # packed bf16 weight (data_ptr) → its e4m3 (forward, dgrad) copies
         self._cur_unit: Optional[str] = None   # unit (bucket key) whose ops are being planned (slot views are shared by a pool's units)
         self._units: Dict[str, dict] = {}      # parameter-sharded units (see _setup_unit_pools)
         self._params_updated = torch.cuda.Event()      # end of the last optimizer_step: parameter gathers wait for it
@@ -620,13 +620,13 @@ class TrainStep:
             self._t_tmp = torch.zeros(nmax, dtype=torch.bfloat16, device=self.device)
 
     @staticmethod
-    def _fp8_entry(n: int, k: int, dev) -> dict:
-        return dict(w8=torch.zeros(n // 16, k // 64, 64, 8, dtype=torch.bfloat16, device=dev),
-                    sw=torch.zeros(n, dtype=torch.float32, device=dev),
-                    wT8=torch.zeros(k // 16, n // 64, 64, 8, dtype=torch.bfloat16, device=dev),
-                    swT=torch.zeros(k, dtype=torch.float32, device=dev))
+    def _fp8_entry(n: int, k: int, dev) -> Tuple[Fp8Weight, Fp8Weight]:
+        """(forward copy: scale per output channel n, transposed copy for dgrad: scale per input channel k) of a weight [n, k]."""
+        one = lambda r, c: Fp8Weight(torch.zeros(r // 16, c // 64, 64, 8, dtype=torch.bfloat16, device=dev),
+                                     torch.zeros(r, dtype=torch.float32, device=dev))
+        return one(n, k), one(k, n)
 
-    def _fp8_weight_ops(self, rm: torch.Tensor, e: dict) -> List[Op]:
+    def _fp8_weight_ops(self, rm: torch.Tensor, e: Tuple[Fp8Weight, Fp8Weight]) -> List[Op]:
         """Logical bf16 weight [n, k] → e4m3 forward copy (scale per output channel n) and e4m3 transposed copy for dgrad
         (scale per input channel k), both in the fragment-major packing bl_gemm_fp8 reads."""
         n, k = rm.shape
@@ -634,9 +634,10 @@ class TrainStep:
         qT = self._q_tmp[:n * k].view(k, n)
         t = self._t_tmp[:n * k].view(k, n)
         as_pairs = lambda c: c.view(torch.bfloat16)                    # e4m3 codes as 2-byte units: [r, c] → [r, c / 2]
-        return [ops.quantize_rows_fp8(rm, q, e["sw"], run=False)[2], T.pack(as_pairs(q), e["w8"], run=False),
-                T.transpose_pad(rm, t, n, run=False), ops.quantize_rows_fp8(t, qT, e["swT"], run=False)[2],
-                T.pack(as_pairs(qT), e["wT8"], run=False)]
+        fwd, bwd = e
+        return [ops.quantize_rows_fp8(rm, q, fwd.scale, run=False)[2], T.pack(as_pairs(q), fwd.w8, run=False),
+                T.transpose_pad(rm, t, n, run=False), ops.quantize_rows_fp8(t, qT, bwd.scale, run=False)[2],
+                T.pack(as_pairs(qT), bwd.w8, run=False)]
 
     # ---- parameter sharding (FSDP FULL_SHARD): decoder layers ("layers" pool), ViT blocks + patch embeddings ("vision"),
     #      projector / token embeddings / lm_head ("head") ----
@@ -923,9 +924,7 @@ class TrainStep:
         ad = self.lora.get(packed) if self.lora is not None else None
         e8 = self._w8.get(packed.data_ptr())
         if e8 is not None:                                 # decoder-layer linear on the e4m3 MFMA path
-            q = self._q8[x.shape[1]]
-            return [ops.quantize_rows_fp8(x, q, self._sx, run=False)[2],
-                    ops.gemm_fp8(q, self._sx, e8["w8"], e8["sw"], out, epilogue, run=False, **kw)]
+            return ops.linear_fp8(x, self._q8[x.shape[1]], self._sx, *e8[0], out, epilogue, **kw)
         if ad is None:
             return [self._g(x, packed, out, epilogue, **kw)]
         K, R = x.shape[1], ad.R
@@ -950,9 +949,7 @@ class TrainStep:
             plan = self._wgrad(dy, x, packed)
             e8 = self._w8.get(packed.data_ptr())
             if dx is not None and e8 is not None:          # dx = dy · W on the e4m3 path (dy per token row, Wᵀ per input channel)
-                q = self._q8_dy[:, :dy.shape[1]]
-                plan += [ops.quantize_rows_fp8(dy, q, self._sdy, run=False)[2],
-                         ops.gemm_fp8(q, self._sdy, e8["wT8"], e8["swT"], dx, EPI_NONE, run=False)]
+                plan += ops.linear_fp8(dy, self._q8_dy[:, :dy.shape[1]], self._sdy, *e8[1], dx, EPI_NONE)
             elif dx is not None:
                 plan.append(self._dgrad(dy, packed, dx, epilogue, **kw))
             return plan

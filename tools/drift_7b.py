@@ -52,13 +52,13 @@ else:
     show("projector out", eng.x[:, 1:257], unbits(z["proj"]))
     show("spliced embeddings", eng.x, unbits(z["x0"]))
     L = dims.llm_layers
-    per = 7
-    for l in range(L - 1):                       # the last layer runs on the last row only
-        ops.run_all(eng.prefill_ops[1 + l * per:1 + (l + 1) * per]); torch.cuda.synchronize()
+    ends = [1] + eng.layer_ends                  # the full-rows layers: the last layer runs on the last row only
+    for l in range(L - 1):
+        ops.run_all(eng.prefill_ops[ends[l]:ends[l + 1]]); torch.cuda.synchronize()
         if l % 4 == 3 or l < 3:
             ref = unbits(z["layers"][l])
             show(f"after layer {l}", eng.x, ref)
             show(f"   last row only", eng.x[:, -1], ref[:, -1])
-    ops.run_all(eng.prefill_ops[1 + (L - 1) * per:]); torch.cuda.synchronize()
+    ops.run_all(eng.prefill_ops[ends[L - 1]:]); torch.cuda.synchronize()
     show("last layer, last row", eng.xd, unbits(z["layers"][L - 1])[:, -1])
     show("logits (last row)", eng.logits[0, 0], unbits(z["logits"]))
