@@ -20,6 +20,10 @@
 // policy_group_kernel (one wave per sequence; it overwrites ratio, row_loss, clipped and g of the valid rows with the
 // group-level values and writes group_stats), then the statistics with the log-ratio read from group_stats. m, log S, H
 // and g stay where the backward kernel reads them, so the backward entry points serve both levels.
+//
+// bl_preference_loss_f32 is the preference-pair loss (DPO family; training/preference_loss.py) on the same rows: the row
+// pass without the surrogate, then preference_seq_kernel, preference_pair_kernel and preference_apply_kernel (below, with
+// their own comment). It leaves g per row, and the number of pairs in stats[1], for the same backward entry points.
 #include "bl_common.h"
 #include <math.h>
 
@@ -69,24 +73,35 @@ __device__ __forceinline__ float row_loss_of(const RowTerms& t, float H, const P
 }
 
 // what thread 0 / lane 0 does once S and W of a row are known. lr points at column `first`; tgt is relative to it.
+// SURR = false is the row pass of the preference loss: the same logp, H, m and log S, no surrogate (adv, old_lp and ref_lp
+// are not read); ratio, row_loss, clipped and g are written as zeros for preference_apply_kernel to fill.
+template <bool SURR>
 __device__ __forceinline__ void finish_row(const float* lr, int n, long tgt, float m, float S, float W, const float* adv,
                                            const float* old_lp, const float* ref_lp, int row, const PolicyParams& P, float* rs) {
   const float logS = logf(S);
   const float H = logS - W / S;                                       // −Σ p·logp, logp = (z − m) − log S
   const float za = (tgt >= 0 && tgt < n) ? lr[tgt] * P.inv_t : NAN;    // a token outside the row: NaN, never a stray read
   const float logp = za - m - logS;
-  const RowTerms t = row_terms(logp, adv[row], old_lp[row], ref_lp, row, P);
   rs[RS_LOGP] = logp;
   rs[RS_H] = H;
-  rs[RS_RATIO] = t.ratio;
-  rs[RS_LOSS] = row_loss_of(t, H, P);
-  rs[RS_CLIPPED] = t.active ? 0.f : 1.f;
   rs[RS_M] = m;
   rs[RS_LOGS] = logS;
-  rs[RS_G] = t.g;
+  if constexpr (SURR) {
+    const RowTerms t = row_terms(logp, adv[row], old_lp[row], ref_lp, row, P);
+    rs[RS_RATIO] = t.ratio;
+    rs[RS_LOSS] = row_loss_of(t, H, P);
+    rs[RS_CLIPPED] = t.active ? 0.f : 1.f;
+    rs[RS_G] = t.g;
+  } else {
+    rs[RS_RATIO] = 0.f;
+    rs[RS_LOSS] = 0.f;
+    rs[RS_CLIPPED] = 0.f;
+    rs[RS_G] = 0.f;
+  }
 }
 
 // one workgroup per row; the row is the n columns from column `first` on
+template <bool SURR>
 __global__ __launch_bounds__(256) void policy_rows_kernel(const float* logits, long ld, int first, int n, const int64_t* targets,
                                                           long ignore_index, const float* adv, const float* old_lp,
                                                           const float* ref_lp, PolicyParams P, float* row_stats) {
@@ -126,12 +141,13 @@ __global__ __launch_bounds__(256) void policy_rows_kernel(const float* logits, l
   if ((threadIdx.x & 63) == 0) { red_s[wave] = s; red_w[wave] = w; }
   __syncthreads();
   if (threadIdx.x == 0)
-    finish_row(lr, n, tgt - first, m, red_s[0] + red_s[1] + red_s[2] + red_s[3], red_w[0] + red_w[1] + red_w[2] + red_w[3],
+    finish_row<SURR>(lr, n, tgt - first, m, red_s[0] + red_s[1] + red_s[2] + red_s[3], red_w[0] + red_w[1] + red_w[2] + red_w[3],
                adv, old_lp, ref_lp, row, P, rs);
 }
 
 // n <= 256: one wave per row, four rows per workgroup, the lane's float4 stays in registers between the two passes. The
 // order of every sum is the workgroup kernel's on such a row (there waves 1–3 hold no column and add zeros).
+template <bool SURR>
 __global__ __launch_bounds__(256) void policy_rows_wave_kernel(const float* logits, long ld, int first, int n, int rows,
                                                                const int64_t* targets, long ignore_index, const float* adv,
                                                                const float* old_lp, const float* ref_lp, PolicyParams P,
@@ -161,7 +177,7 @@ __global__ __launch_bounds__(256) void policy_rows_wave_kernel(const float* logi
   }
   s = wave_sum(s);
   w = wave_sum(w);
-  if (lane == 0) finish_row(lr, n, tgt - first, m, s + 0.f + 0.f + 0.f, w + 0.f + 0.f + 0.f, adv, old_lp, ref_lp, row, P, rs);
+  if (lane == 0) finish_row<SURR>(lr, n, tgt - first, m, s + 0.f + 0.f + 0.f, w + 0.f + 0.f + 0.f, adv, old_lp, ref_lp, row, P, rs);
 }
 
 // The action-level ratio. One wave per sequence (its group_rows consecutive rows), four sequences per workgroup, no barrier.
@@ -326,6 +342,169 @@ __global__ __launch_bounds__(256) void policy_backward_kernel(const float* logit
   }
 }
 
+// ---- the preference-pair loss (training/preference_loss.py): the row pass above without the surrogate, then three small
+// kernels over what it left. Sequences are runs of group_rows rows as for policy_group_kernel; pair[b] = +k / −k / 0 puts
+// sequence b on the chosen / rejected side of pair k or in none. g of every valid row is rewritten so that the policy
+// backward kernel (entropy_coef = 0, stats[1] = P) writes this loss's dlogits.
+enum { PREF_SIGMOID = 0, PREF_IPO = 1, PREF_HINGE = 2 };
+struct PrefParams {
+  float beta, margin, eps, alpha;
+  int kind, by_mean;
+};
+
+// P: the host's count, or the device scalar's (a captured graph serves batches with another number of pairs), kept inside
+// [1, cap] — cap is how many rows pair_stats has
+__device__ __forceinline__ int pref_pairs(int cap, const int32_t* n_pairs_dev) {
+  const int P = n_pairs_dev ? *n_pairs_dev : cap;
+  return P < 1 ? 1 : (P > cap ? cap : P);
+}
+// the signed pair id of sequence b, 0 for an id outside ±P: nothing is indexed by an unchecked id
+__device__ __forceinline__ int pref_id(const int32_t* pair, int b, int P) {
+  const long v = pair[b];
+  const long k = v < 0 ? -v : v;
+  return (k >= 1 && k <= P) ? (int)v : 0;
+}
+__device__ __forceinline__ float softplusf(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+
+// One wave per sequence, four sequences per workgroup, no barrier: n_b, δ_b = c_b·Σ (logp − ref) and Σ logp over the
+// sequence's valid rows, lanes striding the rows in ascending order as policy_group_kernel. seq_stats[b] = (δ_b, n_b,
+// Σ logp, 0); slot 3 is preference_apply_kernel's.
+__global__ __launch_bounds__(256) void preference_seq_kernel(const float* row_stats, int group_rows, int groups, int by_mean,
+                                                             const int64_t* targets, long ignore_index, const float* ref_lp,
+                                                             float* seq_stats) {
+  const int seq = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (seq >= groups) return;          // uniform per wave
+  const long r0 = (long)seq * group_rows;
+  float sd = 0.f, sl = 0.f;           // Σ (logp − ref), Σ logp
+  int c = 0;
+  for (int k = lane; k < group_rows; k += 64) {
+    const long r = r0 + k;
+    if (targets[r] == ignore_index) continue;
+    const float logp = row_stats[r * 8 + RS_LOGP];
+    sd += ref_lp ? logp - ref_lp[r] : logp;
+    sl += logp;
+    ++c;
+  }
+  sd = wave_sum(sd);
+  sl = wave_sum(sl);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if (lane == 0) {
+    float* ss = seq_stats + (long)seq * 4;
+    ss[0] = c == 0 ? 0.f : (by_mean ? 1.0f / (float)c : 1.0f) * sd;
+    ss[1] = (float)c;
+    ss[2] = sl;
+    ss[3] = 0.f;
+  }
+}
+
+// The pair level and the 8 step statistics, ONE workgroup: thread t takes pairs t, t + 256, … and walks the sequences in
+// ascending b for each (Δ_k, N_k, nll_k; O(P·B / 256) steps per thread, a few hundred at training batches), writes
+// pair_stats[k] = (h_k, ℓ_k, ℓ'_k, nll_k) — zeros for the rows [P, cap) — and the statistics are the means over the pairs,
+// summed per thread in ascending k, then wave_sum, then the four waves in order. stats[1] = P. A pair without a chosen
+// token (the host refuses it) gets nll 0, not a division by zero.
+__global__ __launch_bounds__(256) void preference_pair_kernel(const float* seq_stats, const int32_t* pair, int groups, int cap,
+                                                              const int32_t* n_pairs_dev, PrefParams Q, float* pair_stats,
+                                                              float* out) {
+  __shared__ float rsum[4][7];
+  const int P = pref_pairs(cap, n_pairs_dev);
+  float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // ℓ + α·nll, ℓ, [Δ > 0], β·Δ, β·chosen, β·rejected, nll
+  for (int k = threadIdx.x; k < cap; k += 256) {
+    float* ps = pair_stats + (long)k * 4;
+    if (k >= P) {
+      ps[0] = ps[1] = ps[2] = ps[3] = 0.f;
+      continue;
+    }
+    float rc = 0.f, rr = 0.f, lp = 0.f, N = 0.f;
+    for (int b = 0; b < groups; ++b) {
+      const int id = pref_id(pair, b, P);
+      if (id == k + 1) {
+        rc += seq_stats[(long)b * 4];
+        N += seq_stats[(long)b * 4 + 1];
+        lp += seq_stats[(long)b * 4 + 2];
+      } else if (id == -(k + 1)) {
+        rr += seq_stats[(long)b * 4];
+      }
+    }
+    const float nll = N > 0.f ? -lp / N : 0.f;
+    const float delta = rc - rr;
+    const float h = Q.beta * delta - Q.margin;
+    float l, dl;
+    if (Q.kind == PREF_SIGMOID) {
+      const float e = expf(-fabsf(h));
+      l = (1.0f - Q.eps) * softplusf(-h) + Q.eps * softplusf(h);
+      dl = (h >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e)) - (1.0f - Q.eps);
+    } else if (Q.kind == PREF_IPO) {
+      const float u = h / Q.beta - 1.0f / (2.0f * Q.beta);
+      l = u * u;
+      dl = 2.0f * u / Q.beta;
+    } else {
+      l = fmaxf(0.f, 1.0f - h);
+      dl = h < 1.0f ? -1.0f : 0.f;
+    }
+    ps[0] = h;
+    ps[1] = l;
+    ps[2] = dl;
+    ps[3] = nll;
+    a[0] += l + Q.alpha * nll;
+    a[1] += l;
+    a[2] += delta > 0.f ? 1.f : 0.f;
+    a[3] += Q.beta * delta;
+    a[4] += Q.beta * rc;
+    a[5] += Q.beta * rr;
+    a[6] += nll;
+  }
+#pragma unroll
+  for (int k = 0; k < 7; ++k) a[k] = wave_sum(a[k]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k) rsum[threadIdx.x >> 6][k] = a[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 7) {
+    const int k = threadIdx.x;
+    out[k == 0 ? 0 : k + 1] = (rsum[0][k] + rsum[1][k] + rsum[2][k] + rsum[3][k]) / (float)P;
+    if (k == 0) out[1] = (float)P;
+  }
+}
+
+// One wave per sequence again: g_r = ℓ'_k·β·sign(pair[b])·c_b − [pair[b] > 0]·α / N_k into RS_G of the sequence's valid rows
+// (0 for a sequence in no pair) and the first term into seq_stats[b][3]. N_k is recounted here from the n_b of the pair's
+// chosen sequences: small integers in fp32, exact in any order. RS_RATIO, RS_LOSS and RS_CLIPPED stay the zeros of the row
+// pass; RS_M, RS_LOGS and RS_H stay where the backward kernel reads them.
+__global__ __launch_bounds__(256) void preference_apply_kernel(float* row_stats, int group_rows, int groups, int cap,
+                                                               const int32_t* n_pairs_dev, const int32_t* pair,
+                                                               const int64_t* targets, long ignore_index, PrefParams Q,
+                                                               const float* pair_stats, float* seq_stats) {
+  const int seq = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (seq >= groups) return;          // uniform per wave
+  const int P = pref_pairs(cap, n_pairs_dev);
+  const int id = pref_id(pair, seq, P);
+  float* ss = seq_stats + (long)seq * 4;
+  float g_seq = 0.f, g = 0.f;
+  if (id != 0) {                      // uniform per wave
+    const int k = id > 0 ? id : -id;
+    const float c = ss[1];
+    const float w = (Q.by_mean && c > 0.f) ? 1.0f / c : 1.0f;
+    g_seq = pair_stats[(long)(k - 1) * 4 + 2] * Q.beta * (id > 0 ? 1.0f : -1.0f) * w;
+    g = g_seq;
+    if (id > 0 && Q.alpha != 0.f) {
+      float N = 0.f;
+      for (int b = lane; b < groups; b += 64)
+        if (pref_id(pair, b, P) == id) N += seq_stats[(long)b * 4 + 1];
+      N = wave_sum(N);
+      if (N > 0.f) g -= Q.alpha / N;
+    }
+  }
+  const long r0 = (long)seq * group_rows;
+  for (int j = lane; j < group_rows; j += 64) {
+    const long r = r0 + j;
+    if (targets[r] == ignore_index) continue;
+    row_stats[r * 8 + RS_G] = g;
+  }
+  if (lane == 0) ss[3] = g_seq;
+}
+
 }  // namespace bl_policy_impl
 using namespace bl_policy_impl;
 
@@ -345,15 +524,16 @@ static int policy_forward_check(const float* logits, int64_t ld, int32_t rows, i
 }
 
 // by_wave: a range of at most 256 columns goes to the wave-per-row kernel. The unranged entry point never asks for it.
+template <bool SURR = true>
 static void launch_rows(const float* logits, int64_t ld, int32_t rows, const int64_t* targets, int64_t ignore_index,
                         const float* advantages, const float* old_logprob, const float* ref_logprob, const PolicyParams& P,
                         float* row_stats, int32_t vocab_first, int32_t vocab_count, bool by_wave, void* stream) {
   if (by_wave && vocab_count <= 256)
-    hipLaunchKernelGGL(policy_rows_wave_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, (long)ld,
+    hipLaunchKernelGGL(policy_rows_wave_kernel<SURR>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, (long)ld,
                        vocab_first, vocab_count, rows, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P,
                        row_stats);
   else
-    hipLaunchKernelGGL(policy_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, vocab_first,
+    hipLaunchKernelGGL(policy_rows_kernel<SURR>, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, vocab_first,
                        vocab_count, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P, row_stats);
 }
 
@@ -434,4 +614,33 @@ extern "C" int bl_policy_loss_backward_f32(const float* logits, int64_t ld, int3
                                            void* stream) {
   return bl_policy_loss_backward_range_f32(logits, ld, rows, n, targets, ignore_index, row_stats, stats, temperature,
                                            entropy_coef, dlogits, ldd, 0, n, stream);
+}
+
+extern "C" int bl_preference_loss_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                      int64_t ignore_index, const int32_t* pair, const float* ref_logprob, int32_t n_pairs,
+                                      const int32_t* n_pairs_dev, int32_t group_rows, int32_t kind, int32_t seq_norm,
+                                      float beta, float label_smoothing, float margin, float sft_coef, float temperature,
+                                      float* row_stats, float* stats, float* pair_stats, float* seq_stats,
+                                      int32_t vocab_first, int32_t vocab_count, void* stream) {
+  if (!logits || !targets || !pair || !row_stats || !stats || !pair_stats || !seq_stats) return BL_E_ARG;
+  if (!(temperature > 0.f) || !(beta > 0.f) || !(label_smoothing >= 0.f && label_smoothing < 0.5f) || !(margin >= 0.f) ||
+      !(sft_coef >= 0.f) || n_pairs < 1)
+    return BL_E_ARG;
+  if (rows <= 0 || bad_range(n, vocab_first, vocab_count) || (ld % 4) || ld < n) return BL_E_SHAPE;
+  if (group_rows <= 0 || (rows % group_rows) || (seq_norm != 0 && seq_norm != 1)) return BL_E_SHAPE;
+  if (kind != PREF_SIGMOID && kind != PREF_IPO && kind != PREF_HINGE) return BL_E_SHAPE;
+  if (!bl_aligned16(logits)) return BL_E_ALIGN;
+  const PolicyParams P = {1.0f / temperature, 0.f, 0.f, 0.f, 0.f};
+  const PrefParams Q = {beta, margin, label_smoothing, sft_coef, kind, seq_norm};
+  const int groups = rows / group_rows;
+  launch_rows<false>(logits, ld, rows, targets, ignore_index, nullptr, nullptr, nullptr, P, row_stats, vocab_first, vocab_count,
+                     true, stream);
+  hipLaunchKernelGGL(preference_seq_kernel, dim3((groups + 3) / 4), dim3(256), 0, (hipStream_t)stream, row_stats, group_rows,
+                     groups, seq_norm, targets, (long)ignore_index, ref_logprob, seq_stats);
+  hipLaunchKernelGGL(preference_pair_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, seq_stats, pair, groups, n_pairs,
+                     n_pairs_dev, Q, pair_stats, stats);
+  hipLaunchKernelGGL(preference_apply_kernel, dim3((groups + 3) / 4), dim3(256), 0, (hipStream_t)stream, row_stats, group_rows,
+                     groups, n_pairs, n_pairs_dev, pair, targets, (long)ignore_index, Q, pair_stats, seq_stats);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
 }

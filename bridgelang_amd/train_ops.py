@@ -88,6 +88,44 @@ def policy_loss_backward(logits, targets, row_stats, stats, dlogits, cfg, ignore
                (logits, targets, row_stats, stats, dlogits), run, nbytes=(2.0 * n + 4.0 * (n if rng is None else rng[1])) * rows)
 
 
+def preference_loss(logits, targets, pair, ref_logprob, row_stats, stats, pair_stats, seq_stats, cfg, group_rows: int,
+                    n_pairs: Optional[torch.Tensor] = None, ignore_index: int = -100, run: bool = True) -> Op:
+    """Preference-pair loss (DPO family) over fp32 logits [rows, n] (training/preference_loss.py is the definition; `cfg` a
+    PreferenceLossConfig). pair int32 [rows / group_rows]: +k / −k / 0 per sequence of `group_rows` rows; ref_logprob fp32
+    [rows] (None: reference-free). row_stats fp32 [rows, 8], stats fp32 [8], pair_stats fp32 [cap, 4] and seq_stats fp32
+    [rows / group_rows, 4] receive policy_loss.ROW_STAT_NAMES and preference_loss.PREF_STAT_NAMES / PAIR_STAT_NAMES /
+    SEQ_STAT_NAMES. The number of pairs P is `cap`, or the int32 device scalar `n_pairs` (read by the kernels, so a captured
+    op serves any P <= cap). `policy_loss_backward` with cfg.backward_config() is the gradient."""
+    from .training.preference_loss import KINDS, SEQ_NORMS
+    rows, n = _policy_rows(logits, targets, row_stats, stats, "preference_loss")
+    if int(group_rows) != group_rows or group_rows < 1 or rows % int(group_rows):
+        raise ValueError(f"preference_loss: needs group_rows >= 1 dividing the {rows} rows, got {group_rows!r}")
+    groups = rows // int(group_rows)
+    if pair.dtype != torch.int32 or not pair.is_cuda or pair.numel() != groups or not pair.is_contiguous():
+        raise TypeError(f"preference_loss: pair int32 [{groups}] contiguous on the device")
+    if (ref_logprob is None) != bool(cfg.reference_free):
+        raise ValueError("preference_loss: ref_logprob is given unless cfg.reference_free")
+    if ref_logprob is not None and (_f32(ref_logprob, "ref_logprob").numel() != rows or not ref_logprob.is_contiguous()):
+        raise ValueError(f"preference_loss: ref_logprob fp32 [{rows}] contiguous")
+    if _f32(pair_stats, "pair_stats").dim() != 2 or pair_stats.shape[0] < 1 or pair_stats.shape[1] != 4 or not pair_stats.is_contiguous():
+        raise ValueError("preference_loss: pair_stats fp32 [cap >= 1, 4] contiguous")
+    if tuple(_f32(seq_stats, "seq_stats").shape) != (groups, 4) or not seq_stats.is_contiguous():
+        raise ValueError(f"preference_loss: seq_stats fp32 [{groups}, 4] contiguous")
+    if n_pairs is not None and (n_pairs.dtype != torch.int32 or not n_pairs.is_cuda or n_pairs.numel() != 1):
+        raise TypeError("preference_loss: n_pairs is an int32 device scalar")
+    rng = cfg.token_range
+    first, count = (0, n) if rng is None else (int(rng[0]), int(rng[1]))
+    return _op("bl_preference_loss_f32",
+               (_f32(logits, "logits").data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
+                pair.data_ptr(), ref_logprob.data_ptr() if ref_logprob is not None else None, int(pair_stats.shape[0]),
+                n_pairs.data_ptr() if n_pairs is not None else None, int(group_rows), KINDS.index(cfg.kind),
+                SEQ_NORMS.index(cfg.seq_norm), float(cfg.beta), float(cfg.label_smoothing), float(cfg.margin), float(cfg.sft_coef),
+                float(cfg.temperature), row_stats.data_ptr(), stats.data_ptr(), pair_stats.data_ptr(), seq_stats.data_ptr(),
+                first, count),
+               (logits, targets, pair, ref_logprob, row_stats, stats, pair_stats, seq_stats, n_pairs), run,
+               nbytes=8.0 * rows * count + 64.0 * rows)
+
+
 def rmsnorm_backward(x, w, dy, dx, dw, ws, eps: float, dres: Optional[torch.Tensor] = None, run: bool = True) -> Op:
     rows, dim = x.shape
     return _op("bl_rmsnorm_backward_bf16",

@@ -157,6 +157,33 @@ def _group_sums(v, valid, group_rows: int):
     return sums, counts
 
 
+def row_softmax(l, T: float):
+    """z = l / T → (logp_i [rows, n], p_i [rows, n], H [rows]) of the definition above, for every row of fp64 `l`."""
+    z = l / T
+    m = z.max(axis=1, keepdims=True)
+    S = np.exp(z - m).sum(axis=1, keepdims=True)
+    logp_all = z - m - np.log(S)
+    p = np.exp(logp_all)
+    H = -(p * logp_all).sum(axis=1)               # p = 0 (underflow) times a finite logp is 0
+    return logp_all, p, H
+
+
+def slice_range(logits, targets, token_range, ignore_index: int, what: str):
+    """The rows restricted to token_range = (first, count): (logits[:, first : first + count], targets shifted by first).
+    ValueError if the range leaves the row or a valid target lies outside it."""
+    first, count = token_range
+    n = np.shape(logits)[1]
+    if first + count > n:
+        raise ValueError(f"{what}: token_range [{first}, {first + count}) leaves [0, {n})")
+    tg = np.asarray(targets, dtype=np.int64)
+    valid = tg != ignore_index
+    outside = valid & ((tg < first) | (tg >= first + count))
+    if outside.any():
+        raise ValueError(f"{what}: {int(outside.sum())} target(s) outside token_range [{first}, {first + count}) "
+                         f"(first at row {int(np.argmax(outside))}): that action has probability 0 under the restricted policy")
+    return np.asarray(logits)[:, first:first + count], np.where(valid, tg - first, ignore_index)
+
+
 def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cfg: Optional[PolicyLossConfig] = None,
                 ignore_index: int = IGNORE_INDEX, group_rows: Optional[int] = None) -> PolicyLossResult:
     """`group_rows`: rows per sequence, needed (and dividing the row count) with cfg.ratio_level == "action"; ignored at
@@ -183,12 +210,7 @@ def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cf
     q = np.where(valid, np.asarray(old_logprobs, dtype=np.float64), 0.0)
     ref = None if ref_logprobs is None else np.where(valid, np.asarray(ref_logprobs, dtype=np.float64), 0.0)
     T = float(cfg.temperature)
-    z = l / T
-    m = z.max(axis=1, keepdims=True)
-    S = np.exp(z - m).sum(axis=1, keepdims=True)
-    logp_all = z - m - np.log(S)
-    p = np.exp(logp_all)
-    H = -(p * logp_all).sum(axis=1)               # p = 0 (underflow) times a finite logp is 0
+    logp_all, p, H = row_softmax(l, T)
     a = np.where(valid, tg, 0)
     logp = logp_all[np.arange(rows), a]
     lr = logp - q
@@ -235,16 +257,8 @@ def _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, 
     import dataclasses
     first, count = cfg.token_range
     n = np.shape(logits)[1]
-    if first + count > n:
-        raise ValueError(f"policy_loss: token_range [{first}, {first + count}) leaves [0, {n})")
-    tg = np.asarray(targets, dtype=np.int64)
-    valid = tg != ignore_index
-    outside = valid & ((tg < first) | (tg >= first + count))
-    if outside.any():
-        raise ValueError(f"policy_loss: {int(outside.sum())} target(s) outside token_range [{first}, {first + count}) "
-                         f"(first at row {int(np.argmax(outside))}): that action has probability 0 under the restricted policy")
-    sliced = np.asarray(logits)[:, first:first + count]           # only the range is looked at, also by the finiteness check
-    res = policy_loss(sliced, np.where(valid, tg - first, ignore_index), advantages, old_logprobs, ref_logprobs,
+    sliced, shifted = slice_range(logits, targets, cfg.token_range, ignore_index, "policy_loss")     # only the range is looked at
+    res = policy_loss(sliced, shifted, advantages, old_logprobs, ref_logprobs,
                       dataclasses.replace(cfg, token_range=None), ignore_index, group_rows)
     dl = np.zeros((sliced.shape[0], n), dtype=np.float64)
     dl[:, first:first + count] = res.dlogits

@@ -5,7 +5,10 @@ Host-side tensor layout only; the loop that uses it is the caller's.
 `policy_batch` serves both ratio levels of the loss unchanged. It gives every sequence one advantage and labels on
 exactly its n action tokens, and those labelled tokens are what `PolicyLossConfig(ratio_level="action")` takes as the
 sequence's group: the action's ratio π(a)/π_old(a) is formed from the n `old_logprobs` of the row, and
-`TrainStep.action_stats()` reports it per sequence."""
+`TrainStep.action_stats()` reports it per sequence.
+
+`pairs_from_rewards` and `preference_batch` are the same glue for `TrainStep(loss="preference")`: the best rollout of a
+prompt against the worst, laid out as consecutive chosen / rejected sequences by `policy_batch`."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
@@ -102,3 +105,58 @@ def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pa
         out_adv[b, s:s + n] = float(adv[b])
         out_lp[b, s:s + n] = lp[b].to(torch.float32)
     return {"input_ids": out_ids, "attention_mask": out_m, "labels": labels, "advantages": out_adv, "old_logprobs": out_lp}
+
+
+def pairs_from_rewards(rewards, min_gap: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Preference pairs from rewards [B, K] of K rollouts per prompt: the best rollout against the worst. → (chosen index
+    int64 [B], rejected index int64 [B], keep bool [B]); among equal rewards the lowest index wins on either side, and a
+    prompt whose best and worst rewards tie, or lie closer than `min_gap`, is not kept."""
+    r = _cpu(rewards, torch.float64)
+    if r.dim() != 2 or r.shape[1] < 1:
+        raise ValueError(f"pairs_from_rewards: rewards [B, K], got shape {tuple(r.shape)}")
+    if not bool(torch.isfinite(r).all()):
+        raise ValueError("pairs_from_rewards: rewards must be finite")
+    if not min_gap >= 0:
+        raise ValueError("pairs_from_rewards: min_gap must be >= 0")
+    K = r.shape[1]
+    first = lambda hit: torch.where(hit, torch.arange(K).expand_as(r), torch.full_like(r, K, dtype=torch.int64)).min(dim=1).values
+    hi, lo = r.max(dim=1, keepdim=True).values, r.min(dim=1, keepdim=True).values
+    gap = (hi - lo)[:, 0]
+    return first(r == hi), first(r == lo), (gap > 0) & (gap >= min_gap)
+
+
+def preference_batch(prompt_ids, attention_mask, chosen_ids, rejected_ids, ref_chosen=None, ref_rejected=None,
+                     pad_to: Optional[int] = None, token_range: Optional[Tuple[int, int]] = None, groups=None) -> Dict[str, torch.Tensor]:
+    """The training batch of loss="preference" from one chosen and one rejected action per prompt: prompt_ids [B, lp] with
+    attention_mask as for `policy_batch`, chosen_ids / rejected_ids int64 [B, n]. Sequence 2k is prompt k with its chosen
+    action and sequence 2k + 1 the same prompt with the rejected one, each laid out by `policy_batch`. ref_chosen /
+    ref_rejected [B, n] are the reference policy's log-probabilities of those tokens as `score_actions(...,
+    use_adapters=False)` reports them (both or neither: neither is the reference-free form). `groups` int [B] (ids dense
+    in 1…P, default 1…B) gives prompts that share an id ONE pair — the trajectory form: the chosen actions of all its
+    steps against the rejected ones. → dict of CPU tensors `input_ids`, `attention_mask`, `labels` [2B, l] (for
+    `set_batch`, with the images repeated twice, `repeat_interleave(2, 0)`), `pair` int32 [2B] and `ref_logprobs` fp32
+    [2B, l] or None (for `set_preference_batch`)."""
+    ids, ch, rj = _cpu(prompt_ids, torch.int64), _cpu(chosen_ids, torch.int64), _cpu(rejected_ids, torch.int64)
+    if ids.dim() != 2 or ch.dim() != 2 or ch.shape != rj.shape or ch.shape[0] != ids.shape[0]:
+        raise ValueError(f"preference_batch: prompt_ids [B, lp], chosen_ids and rejected_ids [B, n], got {tuple(ids.shape)}, "
+                         f"{tuple(ch.shape)} and {tuple(rj.shape)}")
+    B, n = ch.shape
+    if (ref_chosen is None) != (ref_rejected is None):
+        raise ValueError("preference_batch: ref_chosen and ref_rejected go together")
+    if groups is None:
+        gid = torch.arange(1, B + 1, dtype=torch.int64)
+    else:
+        gid = _cpu(groups, torch.int64)
+        seen = torch.unique(gid)
+        if tuple(gid.shape) != (B,) or seen[0] != 1 or seen[-1] != len(seen):
+            raise ValueError(f"preference_batch: groups int [{B}] with ids dense in 1…P")
+    two = lambda a, b: torch.stack([a, b], dim=1).reshape(2 * B, *a.shape[1:])           # rows 2k, 2k + 1 = a[k], b[k]
+    twice = lambda a: None if a is None else a.repeat_interleave(2, 0)
+    have_ref = ref_chosen is not None
+    ref = two(_cpu(ref_chosen, torch.float64), _cpu(ref_rejected, torch.float64)) if have_ref else torch.zeros(2 * B, n, dtype=torch.float64)
+    if tuple(ref.shape) != (2 * B, n):
+        raise ValueError(f"preference_batch: ref_chosen and ref_rejected [{B}, {n}]")
+    batch = policy_batch(twice(ids), twice(None if attention_mask is None else _cpu(attention_mask, torch.bool)), two(ch, rj), ref,
+                         torch.zeros(2 * B), pad_to=pad_to, token_range=token_range)
+    return {"input_ids": batch["input_ids"], "attention_mask": batch["attention_mask"], "labels": batch["labels"],
+            "pair": two(gid, -gid).to(torch.int32), "ref_logprobs": batch["old_logprobs"] if have_ref else None}

@@ -33,6 +33,7 @@ from ..ops import (EPI_BIAS, EPI_BIAS_GELU_KEEP, EPI_F32, EPI_F32_BF16R, EPI_GEL
                    EPI_SWIGLU_KEEP, Fp8Weight, Op)
 from ..weights import PackedGroup, VLAWeights, _block_view, _unpack
 from .policy_loss import GROUP_STAT_NAMES, STAT_NAMES, PolicyLossConfig
+from .preference_loss import PAIR_STAT_NAMES, PREF_STAT_NAMES, SEQ_STAT_NAMES, PreferenceLossConfig, check_pairs
 from .sharding import ShardComm, ShardLayout, bucket_key, comm_order
 
 IGNORE_INDEX = -100
@@ -368,7 +369,7 @@ class TrainStep:
                  world: int = 1, rank: int = 0, group=None, reduce_dtype: torch.dtype = torch.float32, lora=None,
                  force_comm: bool = False, recompute: bool = False, shard_params: bool = False, fp8: bool = False,
                  fp8_wgrad: bool = False, loss: str = "ce", policy: Optional[PolicyLossConfig] = None,
-                 refresh_adapted: bool = False):
+                 refresh_adapted: bool = False, preference: Optional[PreferenceLossConfig] = None):
         """`lora`: a training.lora.LoraAdapters → stage "lora": the base model is frozen and only the adapters train.
         `refresh_adapted` (with `lora`): the re-pack plan that follows every optimizer step ends with the ONE batched merge
         launch of `lora.refresh_ops()`, so `lora.adapted_weights()` — the weights an inference engine of the model the adapters
@@ -396,17 +397,26 @@ class TrainStep:
         entry points: the policy — and with it `token_logprobs()` and `policy_stats()` — is the softmax over that token range
         alone, as rollouts drawn with `action_tokens_only=True` need, and dlogits is 0 outside it. With
         `policy.ratio_level="action"` the forward's loss op is the grouped entry point: one importance ratio per sequence
-        (its labelled tokens are the action), reported by `action_stats()`; the backward plan is the same."""
-        if loss not in ("ce", "policy"):
-            raise ValueError(f"loss must be 'ce' or 'policy', got {loss!r}")
+        (its labelled tokens are the action), reported by `action_stats()`; the backward plan is the same.
+        `loss="preference"`: the preference-pair loss of training/preference_loss.py (DPO, IPO, hinge; cDPO, SimPO and RPO
+        by its options) over the same rows, configured by `preference` (a PreferenceLossConfig; its defaults if None) and fed
+        by `set_preference_batch` after `set_batch`: every sequence is the chosen or the rejected side of a pair, or in
+        none. The forward's loss op is bl_preference_loss_f32; the backward's is the policy loss's, which divides by the
+        number of pairs in `mean_cnt[1]`. `token_range` as for the policy loss."""
+        if loss not in ("ce", "policy", "preference"):
+            raise ValueError(f"loss must be 'ce', 'policy' or 'preference', got {loss!r}")
         if policy is not None and loss != "policy":
             raise ValueError("`policy` configures loss='policy'")
+        if preference is not None and loss != "preference":
+            raise ValueError("`preference` configures loss='preference'")
         self.loss_kind = loss
         self.policy = (policy or PolicyLossConfig()) if loss == "policy" else None
-        if self.policy is not None and self.policy.token_range is not None:
-            first, count = self.policy.token_range
+        self.preference = (preference or PreferenceLossConfig()) if loss == "preference" else None
+        self._row_cfg = self.policy or self.preference           # whichever loss keeps row_stats: its T and token range
+        if self._row_cfg is not None and self._row_cfg.token_range is not None:
+            first, count = self._row_cfg.token_range
             if first % 8 or count % 8 or first + count > weights.dims.vocab:
-                raise ValueError(f"policy.token_range {self.policy.token_range}: multiples of 8 inside the vocabulary "
+                raise ValueError(f"{loss}.token_range {self._row_cfg.token_range}: multiples of 8 inside the vocabulary "
                                  f"[0, {weights.dims.vocab})")
         if (lora is not None) != (stage == "lora"):
             raise ValueError("stage 'lora' and the `lora` adapters go together")
@@ -506,7 +516,14 @@ class TrainStep:
         self.delta = z(B * d.llm_heads * pad, dtype=torch.float32)
         self.hn = z(Tn, D)
         self.logits = z(Tn, V, dtype=torch.float32)
-        if self.policy is None:
+        if self.preference is not None:         # mean_cnt = (loss, P): the backward kernel divides by the number of pairs
+            self.ref_logprob = z(Tn, dtype=torch.float32)
+            self.row_stats, self.stats = z(Tn, 8, dtype=torch.float32), z(8, dtype=torch.float32)
+            self.row_loss, self.mean_cnt = self.row_stats[:, 3], self.stats[:2]
+            self.pair, self.n_pairs = z(B, dtype=torch.int32), torch.ones(1, dtype=torch.int32, device=dev)
+            self.pair_stats_buf, self.seq_stats_buf = z(max(B // 2, 1), 4, dtype=torch.float32), z(B, 4, dtype=torch.float32)
+            self._batch_len, self._pairs_set = prompt_len, False
+        elif self.policy is None:
             self.row_loss, self.mean_cnt = z(Tn, dtype=torch.float32), z(2, dtype=torch.float32)
         else:                                   # per-row inputs and statistics of the policy loss; mean_cnt = (loss, n_valid)
             self.advantages, self.old_logprob, self.ref_logprob = (z(Tn, dtype=torch.float32) for _ in range(3))
@@ -1042,7 +1059,12 @@ class TrainStep:
             plan.append(self._u_await("llm.lm_head"))
         plan += [ops.rmsnorm(self.x[-1], w.norm, self.hn, d.rms_eps, run=False),
                  g(self.hn, w.lm_head, self.logits, EPI_F32_BF16R)]
-        if self.policy is None:
+        if self.preference is not None:
+            plan.append(T.preference_loss(self.logits, self.targets, self.pair,
+                                          None if self.preference.reference_free else self.ref_logprob, self.row_stats,
+                                          self.stats, self.pair_stats_buf, self.seq_stats_buf, self.preference, group_rows=self.S,
+                                          n_pairs=self.n_pairs, ignore_index=IGNORE_INDEX, run=False))
+        elif self.policy is None:
             plan.append(ops.cross_entropy(self.logits, self.targets, self.row_loss, self.mean_cnt, IGNORE_INDEX, run=False))
         else:
             plan.append(T.policy_loss(self.logits, self.targets, self.advantages, self.old_logprob,
@@ -1077,9 +1099,9 @@ class TrainStep:
         D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
         lm = "language_model.model"
         plan: List[Op] = [T.cross_entropy_backward(self.logits, self.targets, self.mean_cnt, self.dlogits, IGNORE_INDEX, run=False)
-                          if self.policy is None else
-                          T.policy_loss_backward(self.logits, self.targets, self.row_stats, self.stats, self.dlogits, self.policy,
-                                                 IGNORE_INDEX, run=False)]
+                          if self._row_cfg is None else
+                          T.policy_loss_backward(self.logits, self.targets, self.row_stats, self.stats, self.dlogits,
+                                                 self.policy or self.preference.backward_config(), IGNORE_INDEX, run=False)]
         head = "projector" in self._units
         if head:
             plan.append(self._u_await_grad("llm.lm_head"))
@@ -1390,16 +1412,19 @@ class TrainStep:
         self.key_mask[:, :1] = m[:, :1]
         self.key_mask[:, 1:1 + P] = 1
         self.key_mask[:, 1 + P:] = m[:, 1:]
-        if self.policy is not None and self.policy.token_range is not None:
-            first, count = self.policy.token_range
+        if self._row_cfg is not None and self._row_cfg.token_range is not None:
+            first, count = self._row_cfg.token_range
             outside = (lab != IGNORE_INDEX) & ((lab < first) | (lab >= first + count))
             if bool(outside.any()):
-                raise ValueError(f"labels: {int(outside.sum())} labelled token(s) outside policy.token_range [{first}, {first + count}): "
+                raise ValueError(f"labels: {int(outside.sum())} labelled token(s) outside {self.loss_kind}.token_range [{first}, {first + count}): "
                                  "that action has probability 0 under the restricted policy — draw rollouts with "
                                  "action_tokens_only=True")
         self.targets.copy_(shift_to_rows(lab, P, IGNORE_INDEX).view(-1))
-        if self.policy is not None:
+        if self._row_cfg is not None:
             self._batch_len = l
+        if self.preference is not None:         # the pair assignment belongs to a batch: the next one brings its own
+            self.pair.zero_()
+            self._pairs_set = False
 
     def set_policy_batch(self, advantages: torch.Tensor, old_logprobs: torch.Tensor, ref_logprobs: Optional[torch.Tensor] = None) -> None:
         """Per-token inputs of loss="policy", [B, l] aligned with the `labels` of the preceding `set_batch`: the advantage
@@ -1442,12 +1467,66 @@ class TrainStep:
             raise RuntimeError("action_stats needs TrainStep(loss='policy') with policy.ratio_level='action'")
         return {name: self.group_stats[:, i] for i, name in enumerate(GROUP_STAT_NAMES)}
 
+    def set_preference_batch(self, pair, ref_logprobs: Optional[torch.Tensor] = None) -> None:
+        """The pair assignment of loss="preference" for the batch of the preceding `set_batch`: `pair` int [B] holds +k for
+        a sequence on the chosen side of pair k, −k on the rejected side, 0 for one in no pair, with k dense in 1…P.
+        `ref_logprobs` [B, l] are the reference policy's log-probabilities of the labelled tokens, aligned with the labels
+        as `set_policy_batch` takes them (`score_actions(use_adapters=False)` through `rl.preference_batch`, or this
+        step's own `token_logprobs()` before the first update); needed iff not `preference.reference_free`. ValueError
+        for ids that are not dense, a pair without a labelled token on either side, or a non-finite reference on a
+        labelled token of a paired sequence. P goes to the loss op through the device scalar `n_pairs`, so a captured
+        graph serves any assignment."""
+        if self.preference is None:
+            raise RuntimeError("set_preference_batch needs TrainStep(loss='preference')")
+        if (ref_logprobs is None) != self.preference.reference_free:
+            raise ValueError("ref_logprobs is given unless preference.reference_free")
+        dev, B, L, P_, l = self.device, self.B, self.L, self.dims.n_patches, self._batch_len
+        pr = torch.as_tensor(pair).detach().cpu()
+        if pr.dim() != 1 or pr.shape[0] != B or pr.dtype.is_floating_point or pr.dtype == torch.bool:
+            raise ValueError(f"pair: an integer vector [{B}], got {pr.dtype} {tuple(pr.shape)}")
+        valid = (self.targets != IGNORE_INDEX).view(B, self.S)
+        n_pairs = check_pairs(pr.to(torch.int64).numpy(), valid.sum(dim=1).cpu().numpy())
+        if ref_logprobs is not None:
+            src = torch.as_tensor(ref_logprobs)
+            if tuple(src.shape) != (B, l):
+                raise ValueError(f"ref_logprobs: shape {tuple(src.shape)}, expected {(B, l)} (aligned with the labels of set_batch)")
+            pad = torch.zeros(B, L, dtype=torch.float32, device=dev)
+            pad[:, :l] = src.to(dev, dtype=torch.float32)
+            rows = shift_to_rows(pad, P_, 0.0)
+            bad = valid & (pr != 0).to(dev)[:, None] & ~torch.isfinite(rows)
+            if bool(bad.any()):
+                raise ValueError(f"ref_logprobs: {int(bad.sum())} non-finite value(s) on labelled positions of paired sequences — a "
+                                 "token outside a top-k / top-p support scores -inf; score the reference with temperature only")
+            self.ref_logprob.copy_(torch.where(valid, rows, torch.zeros_like(rows)).view(-1))
+        self.pair.copy_(pr.to(torch.int32))
+        self.n_pairs.fill_(n_pairs)
+        self._pairs_set = True
+
+    def preference_stats(self) -> Dict[str, torch.Tensor]:
+        """The 8 step statistics of the last forward (preference_loss.PREF_STAT_NAMES) as device scalars."""
+        if self.preference is None:
+            raise RuntimeError("preference_stats needs TrainStep(loss='preference')")
+        return {name: self.stats[i] for i, name in enumerate(PREF_STAT_NAMES)}
+
+    def pair_stats(self) -> Dict[str, torch.Tensor]:
+        """The per-pair statistics of the last forward (preference_loss.PAIR_STAT_NAMES) as device tensors [B // 2]; the
+        entries from the batch's number of pairs on are 0."""
+        if self.preference is None:
+            raise RuntimeError("pair_stats needs TrainStep(loss='preference')")
+        return {name: self.pair_stats_buf[:, i] for i, name in enumerate(PAIR_STAT_NAMES)}
+
+    def sequence_stats(self) -> Dict[str, torch.Tensor]:
+        """The per-sequence statistics of the last forward (preference_loss.SEQ_STAT_NAMES) as device tensors [B]."""
+        if self.preference is None:
+            raise RuntimeError("sequence_stats needs TrainStep(loss='preference')")
+        return {name: self.seq_stats_buf[:, i] for i, name in enumerate(SEQ_STAT_NAMES)}
+
     def token_logprobs(self) -> torch.Tensor:
         """log π(token) of the last forward at the labelled positions, [B, l] aligned with `labels` (0 elsewhere): the row
         statistics shifted back. This is how a learner gets on-policy `old_logprobs`, or a frozen model's `ref_logprobs`,
         from the training forward itself."""
-        if self.policy is None:
-            raise RuntimeError("token_logprobs needs TrainStep(loss='policy')")
+        if self._row_cfg is None:
+            raise RuntimeError("token_logprobs needs TrainStep(loss='policy') or TrainStep(loss='preference')")
         return shift_from_rows(self.row_stats[:, 0].view(self.B, self.S), self.dims.n_patches)[:, :self._batch_len]
 
     @contextlib.contextmanager
@@ -1509,6 +1588,8 @@ class TrainStep:
         """Hand-written backward into the flat fp32 gradient buffer. Sharded runs (world > 1) issue each bucket's
         reduce-scatter on a side stream as soon as its last wgrad is enqueued (overlapping the rest of the backward)."""
         st, lay = self.store, self.store.layout
+        if self.preference is not None and not self._pairs_set:
+            raise RuntimeError("loss='preference': set_preference_batch comes after set_batch and before the backward pass")
         if not self.comm.active:
             if self._vis2 and getattr(self, "_bwd_tower_at", None) and len(self._bwd_tower_at) == 2:
                 a, b = self._bwd_tower_at

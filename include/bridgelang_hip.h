@@ -372,6 +372,31 @@ int bl_policy_loss_grouped_f32(const float* logits, int64_t ld, int32_t rows, in
                                float entropy_coef, float kl_coef, float* row_stats, float* stats, int32_t vocab_first,
                                int32_t vocab_count, int32_t group_rows, int32_t ratio_norm, float* group_stats,
                                void* stream);
+/* The preference-pair loss (DPO family; training/preference_loss.py is the definition) over the same rows. Rows
+ * [b*group_rows, (b+1)*group_rows) are sequence b; pair int32 [rows / group_rows] holds +k (chosen side of pair k), -k
+ * (rejected side) or 0 (in no pair), k in 1..P; an id outside +-P counts as 0 on the device. With delta_b = c_b * sum over
+ * the sequence's valid rows of (logp - ref_logprob) (ref_logprob NULL: reference-free; c_b = 1 for seq_norm 0, 1 / n_b for
+ * seq_norm 1), Delta_k = sum_chosen delta_b - sum_rejected delta_b and h_k = beta * Delta_k - margin, the pair's loss is
+ *   kind 0 (sigmoid): -(1 - eps) log sigma(h) - eps log sigma(-h), eps = label_smoothing;  kind 1 (ipo): (h / beta -
+ *   1 / (2 beta))^2;  kind 2 (hinge): max(0, 1 - h);  plus sft_coef * nll_k, the chosen side's token-mean NLL,
+ * and the loss is the mean over the P pairs. P is n_pairs, or *n_pairs_dev (int32 on the device, read by the kernels, kept
+ * inside [1, n_pairs]) when that is not NULL: n_pairs is then the capacity of pair_stats and a captured launch serves
+ * batches with any number of pairs up to it. Outputs, every element written: row_stats fp32 [rows, 8] as
+ * bl_policy_loss_f32 with logp, entropy, max z, log sum, zeros for ratio / row_loss / clipped, and d loss * P / d logp in
+ * slot 7; stats fp32 [8] = (loss, P, mean pair loss, accuracy, margin, chosen reward, rejected reward, nll); pair_stats
+ * fp32 [n_pairs, 4] = (h, loss, d loss / d h, nll), zeros from row P on; seq_stats fp32 [rows / group_rows, 4] = (delta_b,
+ * n_b, sum logp, the sequence's d / d logp without the sft term). Four launches on `stream` (rows, sequences, pairs and
+ * statistics, gradient factors), deterministic. The gradient is bl_policy_loss_backward_f32 /
+ * bl_policy_loss_backward_range_f32 with entropy_coef = 0: they divide by stats[1] = P. NULL logits / targets / pair / an
+ * output, beta <= 0, temperature <= 0, label_smoothing outside [0, 0.5), margin < 0, sft_coef < 0 or n_pairs < 1 is
+ * BL_E_ARG; a bad range, rows % group_rows != 0, kind outside {0, 1, 2} or seq_norm outside {0, 1} is BL_E_SHAPE;
+ * alignment as bl_policy_loss_range_f32; nothing is launched on a rejection. */
+int bl_preference_loss_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                           int64_t ignore_index, const int32_t* pair, const float* ref_logprob, int32_t n_pairs,
+                           const int32_t* n_pairs_dev, int32_t group_rows, int32_t kind, int32_t seq_norm, float beta,
+                           float label_smoothing, float margin, float sft_coef, float temperature, float* row_stats,
+                           float* stats, float* pair_stats, float* seq_stats, int32_t vocab_first, int32_t vocab_count,
+                           void* stream);
 /* LlamaRMSNorm backward: dx = rstd*(w*dy - xhat*mean(w*dy*xhat)) [+ dres: the residual stream's own gradient];
  * dw[j] = sum_rows dy*bf16(xhat). partial_ws >= ceil(rows/64)*dim floats. */
 int bl_rmsnorm_backward_bf16(const bl_bf16* x, int64_t ldx, const bl_bf16* w, const bl_bf16* dy, int64_t lddy,
