@@ -126,6 +126,73 @@ def preference_loss(logits, targets, pair, ref_logprob, row_stats, stats, pair_s
                nbytes=8.0 * rows * count + 64.0 * rows)
 
 
+def value_index_slots(rows: int, level: str, group_rows: Optional[int]) -> int:
+    """Capacity of the value-row list: one slot per row at token level, one per sequence of `group_rows` rows at action level."""
+    if level == "token":
+        return rows
+    if level != "action":
+        raise ValueError(f"value head: level is 'action' or 'token', got {level!r}")
+    if group_rows is None or int(group_rows) != group_rows or group_rows < 1 or rows % int(group_rows):
+        raise ValueError(f"value head: level='action' needs group_rows >= 1 dividing the {rows} rows, got {group_rows!r}")
+    return rows // int(group_rows)
+
+
+def _value_common(hn, w, value_rows, index, count, cfg, group_rows, what: str):
+    rows, dim = hn.shape
+    cap = value_index_slots(rows, cfg.level, group_rows)
+    if _bf16(w, "w").numel() != dim or not w.is_contiguous():
+        raise ValueError(f"{what}: w bf16 [{dim}] contiguous")
+    if tuple(_f32(value_rows, "value_rows").shape) != (rows, 4) or not value_rows.is_contiguous():
+        raise ValueError(f"{what}: value_rows fp32 [{rows}, 4] contiguous")
+    for t, n, name in ((index, cap, "index"), (count, 1, "count")):
+        if t.dtype != torch.int32 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
+            raise TypeError(f"{what}: {name} int32 [{n}] contiguous on the device")
+    return rows, dim, cap, (int(group_rows) if cfg.level == "action" else 0), (1 if cfg.level == "action" else 0)
+
+
+def value_head(hn, targets, w, b, returns, old_values, cfg, index, count, value_rows, stats, policy_stats=None,
+               group_rows: Optional[int] = None, ignore_index: int = -100, run: bool = True) -> Op:
+    """The value head and PPO's clipped value loss over the bf16 final-norm rows hn [rows, dim] (training/value_loss.py is
+    the definition; `cfg` a ValueLossConfig): w bf16 [dim], b bf16 [1], returns / old_values fp32 [rows] (old_values None
+    only with cfg.clip None). The value rows are found on the device from `targets`; index int32 [value_index_slots(...)]
+    and count int32 [1] receive their ascending list, value_rows fp32 [rows, 4] and stats fp32 [8] receive
+    value_loss.VALUE_ROW_NAMES / VALUE_STAT_NAMES. `policy_stats` (the policy loss's stats, or None) supplies the loss that
+    `total` adds to."""
+    rows, dim, cap, gr, level = _value_common(hn, w, value_rows, index, count, cfg, group_rows, "value_head")
+    if targets.dtype != torch.int64 or targets.numel() != rows:
+        raise TypeError(f"value_head: targets int64 [{rows}]")
+    if _bf16(b, "b").numel() != 1 or _f32(stats, "stats").numel() != 8:
+        raise ValueError("value_head: b bf16 [1] and stats fp32 [8]")
+    if (old_values is None) != (cfg.clip is None):
+        raise ValueError("value_head: old_values is given unless cfg.clip is None")
+    for t, what in ((returns, "returns"), (old_values, "old_values")):
+        if t is not None and (_f32(t, what).numel() != rows or not t.is_contiguous()):
+            raise ValueError(f"value_head: {what} fp32 [{rows}] contiguous")
+    return _op("bl_value_head_f32",
+               (_bf16(hn, "hn").data_ptr(), _rows(hn, "hn"), rows, dim, targets.data_ptr(), ignore_index, gr, level, w.data_ptr(),
+                b.data_ptr(), returns.data_ptr(), old_values.data_ptr() if old_values is not None else None, float(cfg.coef),
+                float(cfg.clip) if cfg.clip is not None else -1.0, _f32(policy_stats, "policy_stats").data_ptr() if policy_stats is not None else None,
+                index.data_ptr(), count.data_ptr(), value_rows.data_ptr(), stats.data_ptr()),
+               (hn, targets, w, b, returns, old_values, policy_stats, index, count, value_rows, stats), run,
+               nbytes=8.0 * rows + 2.0 * cap * dim)
+
+
+def value_head_backward(hn, w, value_rows, index, count, dw, db, dh, cfg, group_rows: Optional[int] = None,
+                        inv_world: float = 1.0, run: bool = True) -> Op:
+    """Gradient of `value_head` from what it left: dw fp32 [dim] and db fp32 [1] are overwritten, dv_r·w is added into the
+    value rows of the bf16 dh [rows, dim] — unless dh is None (cfg.detach). `inv_world` scales dv (the data-parallel mean)."""
+    rows, dim, cap, gr, level = _value_common(hn, w, value_rows, index, count, cfg, group_rows, "value_head_backward")
+    if _f32(dw, "dw").numel() != dim or not dw.is_contiguous() or _f32(db, "db").numel() != 1:
+        raise ValueError(f"value_head_backward: dw fp32 [{dim}] contiguous and db fp32 [1]")
+    if dh is not None and tuple(_bf16(dh, "dh").shape) != (rows, dim):
+        raise ValueError(f"value_head_backward: dh bf16 [{rows}, {dim}]")
+    return _op("bl_value_head_backward_f32",
+               (_bf16(hn, "hn").data_ptr(), _rows(hn, "hn"), rows, dim, gr, level, w.data_ptr(), value_rows.data_ptr(),
+                index.data_ptr(), count.data_ptr(), float(inv_world), dw.data_ptr(), db.data_ptr(),
+                dh.data_ptr() if dh is not None else None, _rows(dh, "dh") if dh is not None else 0),
+               (hn, w, value_rows, index, count, dw, db, dh), run, nbytes=(2.0 if dh is None else 6.0) * cap * dim)
+
+
 def rmsnorm_backward(x, w, dy, dx, dw, ws, eps: float, dres: Optional[torch.Tensor] = None, run: bool = True) -> Op:
     rows, dim = x.shape
     return _op("bl_rmsnorm_backward_bf16",

@@ -7,6 +7,9 @@ exactly its n action tokens, and those labelled tokens are what `PolicyLossConfi
 sequence's group: the action's ratio π(a)/π_old(a) is formed from the n `old_logprobs` of the row, and
 `TrainStep.action_stats()` reports it per sequence.
 
+`gae` is PPO's estimator for trajectories with per-step rewards and a learned critic (`TrainStep(value=...)`): advantages
+for `set_policy_batch`, returns for `set_value_batch`.
+
 `pairs_from_rewards` and `preference_batch` are the same glue for `TrainStep(loss="preference")`: the best rollout of a
 prompt against the worst, laid out as consecutive chosen / rejected sequences by `policy_batch`."""
 from __future__ import annotations
@@ -36,6 +39,42 @@ def group_advantages(rewards, eps: float = 1e-6) -> torch.Tensor:
     mean = r.mean(dim=1, keepdim=True)
     std = (r - mean).pow(2).mean(dim=1, keepdim=True).sqrt()
     return ((r - mean) / (std + eps)).to(torch.float32)
+
+
+def gae(rewards, values, last_values=None, dones=None, gamma: float = 0.99, lam: float = 0.95) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Generalised advantage estimation over N trajectories of T steps: rewards and values [N, T] (V of the state each
+    action was taken in: the learner's `forward()` over the rollout batch, then `values()`), `last_values` [N] the value of
+    the state after the last step (None: 0, the trajectory ended there), `dones` [N, T] true where the episode ended WITH
+    step t (None: nowhere), so nothing is bootstrapped or carried across it:
+
+        δ_t = r_t + γ·V_{t+1}·(1 − done_t) − V_t          V_T = last_values
+        A_t = δ_t + γ·λ·(1 − done_t)·A_{t+1}              A_T = 0
+        returns = A + V
+
+    → fp32 (advantages, returns) [N, T], computed in fp64 on the host: the advantages feed `set_policy_batch` (one per
+    sequence, e.g. through `policy_batch`), the returns `set_value_batch`. ValueError on a shape mismatch or a non-finite
+    input."""
+    r, v = _cpu(rewards, torch.float64), _cpu(values, torch.float64)
+    if r.dim() != 2 or r.shape[1] < 1 or v.shape != r.shape:
+        raise ValueError(f"gae: rewards and values [N, T], got {tuple(r.shape)} and {tuple(v.shape)}")
+    N, T = r.shape
+    last = torch.zeros(N, dtype=torch.float64) if last_values is None else _cpu(last_values, torch.float64)
+    done = torch.zeros(N, T, dtype=torch.float64) if dones is None else _cpu(dones, torch.float64)
+    if tuple(last.shape) != (N,) or tuple(done.shape) != (N, T):
+        raise ValueError(f"gae: last_values [{N}] and dones [{N}, {T}], got {tuple(last.shape)} and {tuple(done.shape)}")
+    if not all(bool(torch.isfinite(t).all()) for t in (r, v, last, done)) or not (np.isfinite(gamma) and np.isfinite(lam)):
+        raise ValueError("gae: rewards, values, last_values, dones, gamma and lam must be finite")
+    if bool(((done != 0) & (done != 1)).any()):
+        raise ValueError("gae: dones holds 0 / 1 (or booleans)")
+    adv = torch.zeros(N, T, dtype=torch.float64)
+    nxt_v, nxt_a = last, torch.zeros(N, dtype=torch.float64)
+    for t in range(T - 1, -1, -1):
+        live = 1.0 - done[:, t]
+        delta = r[:, t] + gamma * nxt_v * live - v[:, t]
+        nxt_a = delta + gamma * lam * live * nxt_a
+        adv[:, t] = nxt_a
+        nxt_v = v[:, t]
+    return adv.to(torch.float32), (adv + v).to(torch.float32)
 
 
 def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pad_to: Optional[int] = None,

@@ -35,6 +35,8 @@ from ..weights import PackedGroup, VLAWeights, _block_view, _unpack
 from .policy_loss import GROUP_STAT_NAMES, STAT_NAMES, PolicyLossConfig
 from .preference_loss import PAIR_STAT_NAMES, PREF_STAT_NAMES, SEQ_STAT_NAMES, PreferenceLossConfig, check_pairs
 from .sharding import ShardComm, ShardLayout, bucket_key, comm_order
+from .value_head import ValueHead
+from .value_loss import VALUE_STAT_NAMES, ValueLossConfig
 
 IGNORE_INDEX = -100
 # SwiGLU / GELU forward ("f") and backward ("b") as GEMM epilogues (BL_EPI_*_KEEP / BL_EPI_*_BWD) instead of separate
@@ -369,7 +371,8 @@ class TrainStep:
                  world: int = 1, rank: int = 0, group=None, reduce_dtype: torch.dtype = torch.float32, lora=None,
                  force_comm: bool = False, recompute: bool = False, shard_params: bool = False, fp8: bool = False,
                  fp8_wgrad: bool = False, loss: str = "ce", policy: Optional[PolicyLossConfig] = None,
-                 refresh_adapted: bool = False, preference: Optional[PreferenceLossConfig] = None):
+                 refresh_adapted: bool = False, preference: Optional[PreferenceLossConfig] = None,
+                 value: Optional[ValueLossConfig] = None, value_head: Optional[ValueHead] = None):
         """`lora`: a training.lora.LoraAdapters → stage "lora": the base model is frozen and only the adapters train.
         `refresh_adapted` (with `lora`): the re-pack plan that follows every optimizer step ends with the ONE batched merge
         launch of `lora.refresh_ops()`, so `lora.adapted_weights()` — the weights an inference engine of the model the adapters
@@ -402,13 +405,29 @@ class TrainStep:
         by its options) over the same rows, configured by `preference` (a PreferenceLossConfig; its defaults if None) and fed
         by `set_preference_batch` after `set_batch`: every sequence is the chosen or the rejected side of a pair, or in
         none. The forward's loss op is bl_preference_loss_f32; the backward's is the policy loss's, which divides by the
-        number of pairs in `mean_cnt[1]`. `token_range` as for the policy loss."""
+        number of pairs in `mean_cnt[1]`. `token_range` as for the policy loss.
+        `value` (with loss="policy"; a training.value_loss.ValueLossConfig): a critic trains with the policy — the linear
+        `value_head` (a training.value_head.ValueHead on the final-norm output; a zero-initialised one is created when None,
+        `ts.value_head`) under PPO's clipped value loss, fed by `set_value_batch` after `set_batch`. The head's two tensors
+        join the store's extra units beside LoRA's (a caller's `store` must carry them). bl_value_head_f32 follows the
+        policy loss op in the forward plan and bl_value_head_backward_f32 sits between lm_head's input-gradient GEMM and the
+        final norm's backward, adding the value loss's gradient into `dh`; `forward()` then returns policy loss + coef ·
+        value loss. Without `value` both plans are what they were. Critic warm-up needs no mode of its own: advantages of 0
+        with entropy_coef = kl_coef = 0 make dlogits exactly 0, so every trunk gradient is the value path's."""
         if loss not in ("ce", "policy", "preference"):
             raise ValueError(f"loss must be 'ce', 'policy' or 'preference', got {loss!r}")
         if policy is not None and loss != "policy":
             raise ValueError("`policy` configures loss='policy'")
         if preference is not None and loss != "preference":
             raise ValueError("`preference` configures loss='preference'")
+        if value is not None and loss != "policy":
+            raise ValueError("`value` (the critic) trains with loss='policy'")
+        if value_head is not None and value is None:
+            raise ValueError("`value_head` goes with `value` (a ValueLossConfig)")
+        if value is not None and value_head is not None and value_head.dim != weights.dims.llm_dim:
+            raise ValueError(f"value_head.dim {value_head.dim} is not the model's llm_dim {weights.dims.llm_dim}")
+        self.value = value
+        self.value_head = (value_head or ValueHead(weights.dims.llm_dim, weights.embed.device)) if value is not None else None
         self.loss_kind = loss
         self.policy = (policy or PolicyLossConfig()) if loss == "policy" else None
         self.preference = (preference or PreferenceLossConfig()) if loss == "preference" else None
@@ -440,8 +459,14 @@ class TrainStep:
             raise ValueError(f"sequence of {self.S} positions exceeds the model's {d.max_pos} (model_max_length)")
         self.max_grad_norm, self.weight_decay, self.betas, self.eps = max_grad_norm, weight_decay, betas, eps
         if store is None:
-            store = ParamStore(weights, stage, world, rank, extra=lora.plain_units() if lora is not None else None,
-                               shard_params=shard_params, defer_grads=True)
+            extra = (lora.plain_units() if lora is not None else []) + (self.value_head.plain_units() if value is not None else [])
+            store = ParamStore(weights, stage, world, rank, extra=extra or None, shard_params=shard_params, defer_grads=True)
+        elif value is not None:
+            for name, live, _, _ in self.value_head.plain_units():
+                u = store.by_name.get(name)
+                if u is None or u.dst is None or u.dst.data_ptr() != live.data_ptr():
+                    raise ValueError(f"the given store does not carry this value head's `{name}`: build it with "
+                                     "extra=[... + value_head.plain_units()]")
         self.store = store
         assert self.store.stage == stage and self.store.shard_params == shard_params
         shard_params = self.shard_params = shard_params and bool(self.store.sharded_keys)      # frozen LLM: nothing to shard
@@ -532,6 +557,11 @@ class TrainStep:
             if self.policy.ratio_level == "action":      # one group per sequence: its S rows
                 self.group_stats = z(B, 4, dtype=torch.float32)
             self._batch_len = prompt_len
+            if value is not None:               # the critic: per-row inputs, the device's list of value rows, per-row outputs
+                self.returns, self.old_values = z(Tn, dtype=torch.float32), z(Tn, dtype=torch.float32)
+                self.value_rows, self.vstats = z(Tn, 4, dtype=torch.float32), z(8, dtype=torch.float32)
+                self.value_index = z(T.value_index_slots(Tn, value.level, S), dtype=torch.int32)
+                self.value_count = z(1, dtype=torch.int32)
         self.cos, self.sin = rope_tables(d.head_dim, d.max_pos, d.rope_theta, dev)
         # ---- backward scratch ----
         self.dlogits = z(Tn, V)
@@ -1071,6 +1101,12 @@ class TrainStep:
                                       self.ref_logprob if self.policy.kl_coef != 0.0 else None, self.row_stats, self.stats,
                                       self.policy, IGNORE_INDEX, run=False, group_rows=self.S,
                                       group_stats=getattr(self, "group_stats", None)))
+            if self.value is not None:
+                vh = self.value_head
+                plan.append(T.value_head(self.hn, self.targets, vh.weight, vh.bias, self.returns,
+                                         self.old_values if self.value.clip is not None else None, self.value, self.value_index,
+                                         self.value_count, self.value_rows, self.vstats, policy_stats=self.stats, group_rows=S,
+                                         ignore_index=IGNORE_INDEX, run=False))
         return plan
 
     def _layer_forward(self, l: int, with_down: bool = True) -> List[Op]:
@@ -1109,6 +1145,11 @@ class TrainStep:
         plan += self._wgrad(self.dlogits, self.hn, w.lm_head)
         self._ready.append((len(plan), "llm.lm_head"))
         plan.append(self._dgrad(self.dlogits, w.lm_head, self.dh))
+        if self.value is not None:                 # + the value loss's gradient on the value rows of dh; dw, db of the head
+            plan.append(T.value_head_backward(self.hn, self.value_head.weight, self.value_rows, self.value_index, self.value_count,
+                                              st.grad_view("value_head.weight"), st.grad_view("value_head.bias")[:1],
+                                              None if self.value.detach else self.dh, self.value, group_rows=S,
+                                              inv_world=1.0 / self.world if self.comm.active else 1.0, run=False))
         self._cur_unit = None
         if head:                                   # the projector's dgrad layouts travel under the whole decoder backward
             plan += [self._u_release("llm.lm_head"), self._u_flush("llm.lm_head"), self._u_gather("projector", backward=True)]
@@ -1454,6 +1495,56 @@ class TrainStep:
                                  "rollout's top-k / top-p support scores -inf; draw training rollouts with temperature only")
             dst.copy_(torch.where(valid, rows, torch.zeros_like(rows)).view(-1))
 
+    def set_value_batch(self, returns: torch.Tensor, old_values: Optional[torch.Tensor] = None) -> None:
+        """The critic's targets for the batch of the preceding `set_batch`: the return R of each value position and the
+        value the behaviour critic gave it (`values()` of a forward over the rollout batch before the update, as
+        `token_logprobs()` supplies on-policy `old_logprobs`). At value.level "action" both are [B], one per sequence; at
+        "token" they are [B, l] aligned with the labels, taking the path `set_policy_batch`'s inputs take. `old_values` is
+        needed unless value.clip is None. Non-finite values where a value row reads them raise ValueError."""
+        if self.value is None:
+            raise RuntimeError("set_value_batch needs TrainStep(loss='policy', value=ValueLossConfig(...))")
+        if (old_values is None) != (self.value.clip is None):
+            raise ValueError("old_values goes together with value.clip (None only for the unclipped loss)")
+        dev, B, L, P, l = self.device, self.B, self.L, self.dims.n_patches, self._batch_len
+        valid = (self.targets != IGNORE_INDEX).view(B, self.S)
+        by_action = self.value.level == "action"
+        for name, src, dst in (("returns", returns, self.returns), ("old_values", old_values, self.old_values)):
+            if src is None:
+                continue
+            src = torch.as_tensor(src)
+            want = (B,) if by_action else (B, l)
+            if tuple(src.shape) != want:
+                raise ValueError(f"{name}: shape {tuple(src.shape)}, expected {want}"
+                                 + ("" if by_action else " (aligned with the labels of set_batch)"))
+            if by_action:                       # one value row per sequence, found on the device: every row carries the sequence's
+                rows = src.to(dev, dtype=torch.float32)[:, None].expand(B, self.S)
+            else:
+                pad = torch.zeros(B, L, dtype=torch.float32, device=dev)
+                pad[:, :l] = src.to(dev, dtype=torch.float32)
+                rows = shift_to_rows(pad, P, 0.0)
+            bad = valid & ~torch.isfinite(rows)
+            if bool(bad.any()):
+                raise ValueError(f"{name}: {int(bad.any(dim=1).sum() if by_action else bad.sum())} non-finite value(s) "
+                                 f"on {'sequences with a label' if by_action else 'labelled positions'}")
+            dst.copy_(torch.where(valid, rows, torch.zeros_like(rows)).reshape(-1))
+
+    def values(self) -> torch.Tensor:
+        """V of the last forward: [B] at value.level "action" (the value at each sequence's first labelled position; 0 for
+        a sequence without one), [B, l] aligned with the labels at "token" (0 off the labels). This is how a learner values
+        its rollout states for `rl.gae`, and where `old_values` come from."""
+        if self.value is None:
+            raise RuntimeError("values needs TrainStep(loss='policy', value=ValueLossConfig(...))")
+        v = self.value_rows[:, 0].view(self.B, self.S)
+        if self.value.level == "action":        # at most one non-zero per sequence: the sum is that value, exactly
+            return v.sum(dim=1)
+        return shift_from_rows(v, self.dims.n_patches)[:, :self._batch_len]
+
+    def value_stats(self) -> Dict[str, torch.Tensor]:
+        """The 8 statistics of the value loss of the last forward (value_loss.VALUE_STAT_NAMES) as device scalars."""
+        if self.value is None:
+            raise RuntimeError("value_stats needs TrainStep(loss='policy', value=ValueLossConfig(...))")
+        return {name: self.vstats[i] for i, name in enumerate(VALUE_STAT_NAMES)}
+
     def policy_stats(self) -> Dict[str, torch.Tensor]:
         """The 8 step statistics of the last forward (policy_loss.STAT_NAMES) as device scalars."""
         if self.policy is None:
@@ -1572,7 +1663,8 @@ class TrainStep:
         gr.replay()
 
     def forward(self, graph: bool = False) -> torch.Tensor:
-        """Vision towers (frozen) → projector → decoder → loss. Returns the device scalar loss."""
+        """Vision towers (frozen) → projector → decoder → loss. Returns the device scalar loss (with a critic: policy loss +
+        value.coef · value loss, `value_stats()["total"]`)."""
         if self.lora is not None and self.lora.dropout > 0.0:
             self._drop_seed.add_(1)            # a fresh mask per forward pass; the backward pass recomputes it from the same value
         if self.train_vision and self._vis2:
@@ -1582,7 +1674,7 @@ class TrainStep:
         else:
             self._vis.run_vision()
         self._replay("fwd", self.forward_ops, graph)
-        return self.mean_cnt[0]
+        return self.mean_cnt[0] if self.value is None else self.vstats[7]
 
     def backward(self, graph: bool = False) -> None:
         """Hand-written backward into the flat fp32 gradient buffer. Sharded runs (world > 1) issue each bucket's

@@ -397,6 +397,33 @@ int bl_preference_loss_f32(const float* logits, int64_t ld, int32_t rows, int32_
                            float label_smoothing, float margin, float sft_coef, float temperature, float* row_stats,
                            float* stats, float* pair_stats, float* seq_stats, int32_t vocab_first, int32_t vocab_count,
                            void* stream);
+/* The critic of the policy step (training/value_loss.py is the definition): a linear value head on the bf16 final-norm
+ * rows hn [rows, dim] (leading dimension ld) and PPO's clipped value loss. The VALUE ROWS are found on the device from
+ * `targets` (the convention of bl_cross_entropy_f32): level 0 (token) every valid row, level 1 (action) the first valid row
+ * of each run of group_rows rows (group_rows is ignored at level 0). Per value row r, with w bf16 [dim] and b bf16 [1]:
+ *   v = sum_k hn[r,k]*w[k] + b,  e = v - returns[r],  ec = old_values[r] + clamp(v - old_values[r], -clip, clip) - returns[r],
+ *   l = max(e^2, ec^2) / 2,  dv = coef * (e^2 >= ec^2 ? e : 0) / n   (clip < 0: unclipped, old_values may be NULL).
+ * returns / old_values fp32 [rows] and hn are read on value rows only. Outputs, every element written: index int32 [cap]
+ * (cap = rows at level 0, rows / group_rows at level 1) = the value rows in ascending order, then -1; count int32 [1] = n;
+ * value_rows fp32 [rows, 4] = (v, l, clipped 0/1, dv), zeros elsewhere; stats fp32 [8] = (mean l, n, clipped fraction,
+ * mean v, mean return, explained variance, mean |e|, total) with total = policy_stats[0] + coef * mean l (policy_stats, the
+ * stats of bl_policy_loss_f32, may be NULL: 0). n = 0 gives zeros. The dot product is one chain per lane over its 8-column
+ * pieces in ascending k, then the wave's xor butterfly; the statistics are one workgroup in a fixed order. Four launches
+ * on `stream`, deterministic, no host-side knowledge of the labels. dim % 8 == 0, ld % 8 == 0, ld >= dim, a level outside
+ * {0, 1} or rows % group_rows != 0 at level 1: BL_E_SHAPE; hn, w, value_rows 16-byte aligned; a NULL pointer, coef < 0 or
+ * clip >= 0 without old_values: BL_E_ARG; nothing is launched on a rejection. */
+int bl_value_head_f32(const bl_bf16* hn, int64_t ld, int32_t rows, int32_t dim, const int64_t* targets, int64_t ignore_index,
+                      int32_t group_rows, int32_t level, const bl_bf16* w, const bl_bf16* b, const float* returns,
+                      const float* old_values, float coef, float clip, const float* policy_stats, int32_t* index,
+                      int32_t* count, float* value_rows, float* stats, void* stream);
+/* Its gradient from what it left (value_rows, index, count; same rows / group_rows / level): with dv_r = value_rows[r][3] *
+ * inv_world, dw fp32 [dim] = sum_r dv_r * hn[r,:] (a thread owns its columns and walks the value rows in ascending order),
+ * db fp32 [1] = sum_r dv_r, and dh[r,k] = bf16(float(dh[r,k]) + dv_r * w[k]) on the value rows only; dh NULL: the trunk gets no
+ * gradient from the value loss (detach) and dw / db are the same bits. dw and db are overwritten. Constraints as the
+ * forward; lddh % 8 == 0, lddh >= dim, dw and dh 16-byte aligned; inv_world <= 0 is BL_E_ARG. */
+int bl_value_head_backward_f32(const bl_bf16* hn, int64_t ld, int32_t rows, int32_t dim, int32_t group_rows, int32_t level,
+                               const bl_bf16* w, const float* value_rows, const int32_t* index, const int32_t* count,
+                               float inv_world, float* dw, float* db, bl_bf16* dh, int64_t lddh, void* stream);
 /* LlamaRMSNorm backward: dx = rstd*(w*dy - xhat*mean(w*dy*xhat)) [+ dres: the residual stream's own gradient];
  * dw[j] = sum_rows dy*bf16(xhat). partial_ws >= ceil(rows/64)*dim floats. */
 int bl_rmsnorm_backward_bf16(const bl_bf16* x, int64_t ldx, const bl_bf16* w, const bl_bf16* dy, int64_t lddy,
