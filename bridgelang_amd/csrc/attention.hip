@@ -34,27 +34,6 @@ struct AttnArgs {
   const uint16_t* cos_tab; const uint16_t* sin_tab; uint16_t* k_cache; uint16_t* v_cache; int cache_len, pos0;
 };
 
-// HF apply_rotary_pos_emb on one 8-element chunk pair (x1 = dims c..c+7, x2 = dims 64+c..): the arithmetic (three bf16
-// roundings per element) of rope_kvcache_kernel in glue.hip, bit for bit.
-__device__ __forceinline__ void rope_pair(const u32x4_t x1, const u32x4_t x2, const u32x4_t cq, const u32x4_t sq, u32x4_t& o1,
-                                          u32x4_t& o2) {
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    float r1[2], r2[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const float a = e ? bfhi(x1[w]) : bflo(x1[w]);
-      const float c2 = e ? bfhi(x2[w]) : bflo(x2[w]);
-      const float co = e ? bfhi(cq[w]) : bflo(cq[w]);
-      const float si = e ? bfhi(sq[w]) : bflo(sq[w]);
-      r1[e] = rbf(a * co) + rbf(-c2 * si);
-      r2[e] = rbf(c2 * co) + rbf(a * si);
-    }
-    o1[w] = pack2bf(r1[0], r1[1]);
-    o2[w] = pack2bf(r2[0], r2[1]);
-  }
-}
-
 constexpr int KV_CHUNK = 64;
 constexpr int VROW = KV_CHUNK * 2 + 16;   // bytes per V^T row (64 keys + 16 B pad → conflict-free ds_read_b64)
 

@@ -27,6 +27,29 @@ __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
 __device__ __forceinline__ float bflo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
 __device__ __forceinline__ float bfhi(uint32_t w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
 
+// ---- RoPE ----------------------------------------------------------------------------------------------------
+// HF apply_rotary_pos_emb on one 8-element chunk pair (x1 = dims c..c+7, x2 = dims 64+c..): the arithmetic (three bf16
+// roundings per element) of rope_kvcache_kernel in glue.hip, bit for bit.
+// Shared by the fused attention kernels (attention.hip) and the attention taps (attention_probs.hip).
+__device__ __forceinline__ void rope_pair(const u32x4_t x1, const u32x4_t x2, const u32x4_t cq, const u32x4_t sq, u32x4_t& o1,
+                                          u32x4_t& o2) {
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    float r1[2], r2[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const float a = e ? bfhi(x1[w]) : bflo(x1[w]);
+      const float c2 = e ? bfhi(x2[w]) : bflo(x2[w]);
+      const float co = e ? bfhi(cq[w]) : bflo(cq[w]);
+      const float si = e ? bfhi(sq[w]) : bflo(sq[w]);
+      r1[e] = rbf(a * co) + rbf(-c2 * si);
+      r2[e] = rbf(c2 * co) + rbf(a * si);
+    }
+    o1[w] = pack2bf(r1[0], r1[1]);
+    o2[w] = pack2bf(r2[0], r2[1]);
+  }
+}
+
 // ---- wave reductions (xor butterfly over 64 lanes) ------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

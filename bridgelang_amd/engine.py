@@ -16,6 +16,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import ops
+from .attention_taps import MAX_SEGMENTS, ActionAttention, AttnTaps, pad_bounds, prompt_segments
 from .llm_plan import decode_fused, decode_layer, head, head_fused, prefill_layer
 from .ops import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_F32_BF16R, EPI_NONE, EPI_RES, EPI_SWIGLU, Fp8Weight, Op
 from .weights import TowerW, VLAWeights
@@ -45,7 +46,8 @@ class OpenVLAEngine:
     def __init__(self, weights: VLAWeights, batch: int, prompt_len: int, n_new: int = 7, all_rows: bool = False,
                  use_mask: bool = False, splitk: bool = False, fp8: bool = False, padded: bool = False,
                  vision_only: bool = False, text_only: bool = False, sample: bool = False, score: bool = False,
-                 score_range: Optional[Tuple[int, int]] = None, vocab_range: Optional[Tuple[int, int]] = None):
+                 score_range: Optional[Tuple[int, int]] = None, vocab_range: Optional[Tuple[int, int]] = None,
+                 attn_taps: Optional[AttnTaps] = None):
         """all_rows=True builds the training/eval-style forward instead of generation: logits for every position
         (`logits_all` [B*S, vocab] fp32) and no decode steps. use_mask=True threads a [B, S] uint8 key-padding mask
         (`key_mask`, 1 = attend) through the Llama attention (modeling_prismatic.py:387-390). splitk=True lets
@@ -76,7 +78,14 @@ class OpenVLAEngine:
         vocab_range=(first, count), with sample=True or score=True, restricts the policy to that token range (the 256
         action bins): the plan ends in bl_sample_range_f32 / bl_score_range_f32, the softmax, top-k, top-p, the draw and a
         greedy sequence's argmax are taken over the range alone, and a score_range must lie inside it. Fixed per engine,
-        like score_range."""
+        like score_range.
+        attn_taps=AttnTaps(layers, full, segments) adds one read-only bl_attention_probs_f32 after the attention of every
+        tapped layer (attention_taps.py): in a generation plan on the query row of the token being produced (step 0: the
+        last prompt position), into `tap_probs` / `tap_seg` (`action_attention()`; the segment bounds are the device
+        tensor `seg_bounds`, filled by `set_segments`); in an all_rows plan on all S rows, into one [B, H, S, S] buffer
+        per tapped layer (`attention_maps()`). The taps read qkv and the KV cache and write nothing the plan reads: every
+        id, logit and weight is what the engine without them gives, and with attn_taps=None every plan is op for op the
+        one it was."""
         self.w, self.dims = weights, weights.dims
         self.vision_only, self.text_only = vision_only, text_only
         if text_only and (vision_only or padded or fp8):
@@ -179,6 +188,29 @@ class OpenVLAEngine:
             self.w8 = _fp8_layers(weights)
             self.h8, self.act8 = z(B * S, D, dtype=torch.uint8), z(B * S, I, dtype=torch.uint8)
             self.sq = z(B * S, dtype=torch.float32)
+        self.attn_taps, self.tap_slot = attn_taps, {}
+        if attn_taps is not None:
+            if vision_only:
+                raise ValueError("attn_taps tap the Llama attention: a vision_only engine has none")
+            if d.head_dim != 128 or self.cache_len > 2048:
+                raise NotImplementedError("attn_taps need head_dim 128 and a cache of at most 2048 rows")
+            self.tap_layers = attn_taps.resolve(d.llm_layers)
+            self.tap_slot = {l: i for i, l in enumerate(self.tap_layers)}
+            nt, Hh = len(self.tap_layers), d.llm_heads
+            self.tap_probs = self.tap_seg = self.tap_maps = self.tap_mask = None
+            if all_rows:
+                self.tap_maps = [z(B, Hh, S, S, dtype=torch.float32) for _ in range(nt)]
+            else:
+                # step-major so that one (step, layer) slab is the kernel's contiguous [B, H, 1, n]; action_attention() permutes
+                if attn_taps.full:
+                    self.tap_probs = z(n_new, nt, B, Hh, self.cache_len, dtype=torch.float32)
+                if attn_taps.segments:
+                    self.tap_seg = z(n_new, nt, B, Hh, MAX_SEGMENTS, dtype=torch.float32)
+                    self.seg_bounds = z(B, MAX_SEGMENTS + 1, dtype=torch.int32)
+                if padded:      # keys of decode step t: rows 0 .. rope_pos[t][b] of sequence b's cache
+                    self.tap_mask = z(n_new, B, self.cache_len, dtype=torch.uint8)
+                    self.q_tap = z(B, D)
+                self.set_segments(*prompt_segments(torch.ones(B, prompt_len, dtype=torch.int64), self.n_patches, n_new))
 
         self.dino_ops = [] if text_only else self._plan_tower(weights.dino, 0, self.vbuf[0])
         self.siglip_ops = [] if text_only else self._plan_tower(weights.siglip, d.dino.dim, self.vbuf[1])
@@ -239,6 +271,24 @@ class OpenVLAEngine:
                 self._g(self.p1, w.fc2_w, self.p2, EPI_BIAS_GELU, bias=w.fc2_b, run=False),
                 self._g(self.p2, w.fc3_w, self.x.view(B * S, D), EPI_BIAS, bias=w.fc3_b, out_map=(256, S, 1), run=False)]
 
+    def _tap(self, l: int, t: int, q: torch.Tensor, q_strides, Skv: int, rope: Optional[tuple], key_mask, b0: int = 0,
+             b1: Optional[int] = None) -> List[Op]:
+        """The attention tap of layer l for generation step t (nothing if the layer is not tapped): the probabilities of
+        the step's one query row per sequence over cache rows [0, Skv). rope = None: q is rotated in memory; else
+        (pos0, rope_pos): rotated on load. Writes every column of its tap_probs rows (zeros past Skv) and its tap_seg rows."""
+        if l not in self.tap_slot:
+            return []
+        if (b0, self.B if b1 is None else b1) != (0, self.B):
+            raise ValueError("attention taps are built for the whole batch (no batch ranges: the staggered pipeline has no taps)")
+        d, i = self.dims, self.tap_slot[l]
+        H, hd = d.llm_heads, d.head_dim
+        kw = {} if rope is None else dict(cos=self.cos, sin=self.sin, pos0=rope[0], rope_pos=rope[1])
+        return [ops.attention_probs(q, self.k_cache[l], B=self.B, H=H, Sq=1, Skv=Skv, head_dim=hd, q_strides=q_strides,
+                                    k_strides=(H * self.cache_len * hd, self.cache_len * hd, hd), causal=False, key_mask=key_mask,
+                                    probs=None if self.tap_probs is None else self.tap_probs[t, i].unsqueeze(2),
+                                    seg=None if self.tap_seg is None else self.tap_seg[t, i].unsqueeze(2),
+                                    seg_bounds=None if self.tap_seg is None else self.seg_bounds, run=False, **kw)]
+
     def _plan_prefill(self, b0: int = 0, b1: Optional[int] = None) -> List[Op]:
         """Llama prefill + first token for batch rows [b0, b1) (default: the whole batch). Every buffer is batch-major, so
         a batch range is a contiguous slice of each; results do not depend on the range a sequence is run in."""
@@ -258,15 +308,32 @@ class OpenVLAEngine:
             q8 = (self.act8 if name == "down_w" else self.h8)[rows]
             return ops.linear_fp8(x, q8, self.sq[rows], *self.w8[l][name], out, epi, **kw)
 
+        def tap(l):
+            """After layer l's attention: qkv still holds its q (un-rotated under the fused attention, rotated in place
+            otherwise) and k_cache[l] its rotated keys."""
+            if l not in self.tap_slot:
+                return []
+            if self.all_rows:       # every row, HF's `attentions` entry of the layer
+                kw = dict(cos=self.cos, sin=self.sin, pos0=0) if rope_in_attention else {}
+                return [ops.attention_probs(qkv, self.k_cache[l][b0:b1], B=B, H=H, Sq=S, Skv=S, head_dim=hd,
+                                            q_strides=(S * 3 * D, hd, 3 * D), k_strides=cs, causal=True, key_mask=key_mask,
+                                            probs=self.tap_maps[self.tap_slot[l]][b0:b1], run=False, **kw)]
+            if self.padded:         # the row that produces the first token is each sequence's last REAL one: gather it
+                rope = (0, self.rope_pos[0]) if rope_in_attention else None
+                return ([ops.gather_rows(qkv.view(B, S, 3 * D)[:, :, :D], self.last_row[b0:b1], self.q_tap[b0:b1], run=False)]
+                        + self._tap(l, 0, self.q_tap, (D, hd, D), S, rope, key_mask, b0, b1))
+            rope = (S - 1, None) if rope_in_attention else None
+            return self._tap(l, 0, qkv.view(B, S, 3 * D)[:, S - 1], (S * 3 * D, hd, 3 * D), S, rope, key_mask, b0, b1)
+
         def attn(l):
             kc, vc = self.k_cache[l][b0:b1], self.v_cache[l][b0:b1]
             if rope_in_attention:   # RoPE and the KV-cache write ride inside the attention kernel's q / k / v loads
                 return [ops.attention_rope(qkv, kc, vc, ao, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, pos0=0,
-                                           key_mask=key_mask, run=False)]
+                                           key_mask=key_mask, run=False)] + tap(l)
             return [ops.rope_kvcache(qkv, self.cos, self.sin, kc, vc, B=B, S=S, H=H, head_dim=hd, pos0=0, run=False),
                     ops.attention(qkv, kc, vc, ao, B=B, H=H, Sq=S, Skv=S, head_dim=hd, q_strides=(S * 3 * D, hd, 3 * D),
                                   k_strides=cs, v_strides=cs, o_strides=(S * D, hd, D), causal=True, key_mask=key_mask,
-                                  run=False)]
+                                  run=False)] + tap(l)
 
         plan = [ops.embed_splice(self.input_ids[b0:b1], w.embed, x3, self.n_patches, run=False)]
         self.layer_ends: List[int] = []       # len(plan) after each decoder layer (hidden-state taps of the all_rows plan)
@@ -308,6 +375,7 @@ class OpenVLAEngine:
             q_strides, mask = (S * 3 * D, hd, 3 * D), None
         plan.append(ops.attention_decode(q_last, kc, vc, aod, B=B, H=H, Skv=S, head_dim=hd, q_strides=q_strides,
                                          k_strides=cs, v_strides=cs, o_strides=(D, hd, D), key_mask=mask, run=False))
+        plan += self._tap(d.llm_layers - 1, 0, q_last, q_strides, S, None, mask, b0, b1)      # q_last is rotated
         plan.append(self._g(aod, lw.o_w, xd, EPI_RES, res=x_last, run=False))
         plan += self._norm_lin(xd, lw.ln2, lw.gu_w, actd, EPI_SWIGLU, ops.skinny_supported(B, D, EPI_SWIGLU), b0, b1)
         return plan + [self._g(actd, lw.down_w, xd, EPI_RES, res=xd, run=False)] + self._head(xd, 0, b0, b1)
@@ -348,11 +416,16 @@ class OpenVLAEngine:
             # padded: every sequence appends at its own position (over its pad rows): the cache layout, and with
             # it every sum, is the one of the sequence's un-padded run
             pad_kw = dict(rope_pos=self.rope_pos[t]) if self.padded else {}
-            return [ops.attention_decode_rope(qkv, kc, vc, ao, cos, sin, B=B, H=H, head_dim=hd, pos=pos, run=False, **pad_kw)]
+            tap = []
+            if l in self.tap_slot:      # qkv keeps the un-rotated q; padded: sequence b's keys are rows 0 .. rope_pos[t][b]
+                tap = self._tap(l, t, qkv, (3 * D, hd, 3 * D), pos + 1, (pos, pad_kw.get("rope_pos")),
+                                self.tap_mask[t] if self.padded else None)
+            return [ops.attention_decode_rope(qkv, kc, vc, ao, cos, sin, B=B, H=H, head_dim=hd, pos=pos, run=False, **pad_kw)] + tap
         cs = (H * self.cache_len * hd, self.cache_len * hd, hd)
         return [ops.rope_kvcache(qkv, cos, sin, kc, vc, B=B, S=1, H=H, head_dim=hd, pos0=pos, run=False),
                 ops.attention_decode(qkv, kc, vc, ao, B=B, H=H, Skv=pos + 1, head_dim=hd, q_strides=(3 * D, hd, 3 * D),
-                                     k_strides=cs, v_strides=cs, o_strides=(D, hd, D), run=False)]
+                                     k_strides=cs, v_strides=cs, o_strides=(D, hd, D), run=False)] \
+            + self._tap(l, t, qkv, (3 * D, hd, 3 * D), pos + 1, None, None)      # q was rotated in place
 
     def _plan_decode(self, t: int) -> List[Op]:
         """Cached-generation step t (modeling_prismatic.py:325-341): token gen_ids[t-1] at position S+t-1. Five
@@ -448,6 +521,40 @@ class OpenVLAEngine:
         self.cache_mask[:, 1 + P:self.S] = m[:, 1:].to(torch.uint8)          # column 0 (BOS) and the 256 patch columns stay on
         self.last_row.copy_(P + n_real - 1)
         self.rope_pos.copy_((P + n_real)[None, :].to(torch.int32) + torch.arange(self.n_new, device=self.device, dtype=torch.int32)[:, None] - 1)
+        if self.attn_taps is not None:
+            if self.tap_mask is not None:
+                self.tap_mask.copy_(torch.arange(self.cache_len, device=self.device)[None, None, :] <= self.rope_pos[:, :, None])
+            self.set_segments(*prompt_segments(m.cpu(), P, self.n_new))      # the default segments of these prompts
+
+    def set_segments(self, names, bounds: torch.Tensor) -> None:
+        """The key segments the taps sum over: `names` and int32 bounds [B, len(names) + 1] in cache rows
+        (attention_taps.prompt_segments). They live in the device tensor `seg_bounds`, which the taps read when they run,
+        so a captured graph serves any segments; they stay until the next call (set_padded_inputs resets them to the
+        defaults of its prompts)."""
+        if self.attn_taps is None or self.all_rows:
+            raise ValueError("engine was not built with attn_taps on a generation plan")
+        names, bounds = tuple(names), torch.as_tensor(bounds).to(torch.int32)
+        if tuple(bounds.shape) != (self.B, len(names) + 1):
+            raise ValueError(f"set_segments: bounds must be [{self.B}, {len(names) + 1}] for {len(names)} names, got {tuple(bounds.shape)}")
+        if bool((bounds[:, 1:] < bounds[:, :-1]).any()) or bool((bounds < 0).any()):
+            raise ValueError("set_segments: bounds must be non-negative and non-decreasing")
+        self.seg_names = names
+        if self.tap_seg is not None:
+            self.seg_bounds.copy_(pad_bounds(bounds.cpu(), MAX_SEGMENTS))
+
+    def action_attention(self) -> ActionAttention:
+        """What the taps of the last run recorded, as views of the static buffers (device tensors; no host sync)."""
+        if self.attn_taps is None or self.all_rows:
+            raise ValueError("engine was not built with attn_taps on a generation plan")
+        probs = None if self.tap_probs is None else self.tap_probs.permute(2, 0, 1, 3, 4)
+        seg = None if self.tap_seg is None else self.tap_seg.permute(2, 0, 1, 3, 4)[..., :len(self.seg_names)]
+        return ActionAttention(probs=probs, segments=seg, names=self.seg_names, layers=self.tap_layers)
+
+    def attention_maps(self) -> tuple:
+        """all_rows plan: HF's `attentions` — one entry per decoder layer, fp32 [B, H, S, S], None for a layer not tapped."""
+        if self.attn_taps is None or not self.all_rows:
+            raise ValueError("engine was not built with attn_taps on an all_rows plan")
+        return tuple(self.tap_maps[self.tap_slot[l]] if l in self.tap_slot else None for l in range(self.dims.llm_layers))
 
     def set_sampling(self, params) -> None:
         """Fill the per-sequence settings buffers from a `sampling.SamplingParams` (scalars or one value per sequence;

@@ -40,6 +40,7 @@ import numpy as np
 import torch
 from transformers import PreTrainedModel
 
+from ...attention_taps import ActionAttention, AttnTaps, prompt_segments
 from ...engine import OpenVLAEngine
 from ...sampling import SamplingParams, derive_seed, logprob
 from ...weights import TowerDims, VLADims, VLAWeights, allocate
@@ -210,8 +211,11 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
 
     def engine(self, batch: int, prompt_len: int, n_new: int = 7, padded: bool = False, cached: bool = False,
                sample: bool = False, score: bool = False, score_range: Optional[Tuple[int, int]] = None,
-               vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None) -> OpenVLAEngine:
-        """`use_adapters` (see `attach_adapters`): None = the adapted weights if adapters are attached, False = the base
+               vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None,
+               attn_taps: Optional[AttnTaps] = None) -> OpenVLAEngine:
+        """`attn_taps` (attention_taps.AttnTaps): an engine whose plan records where the action tokens attend; part of the
+        cache key only when given, so the engines of every other call are the ones they were.
+        `use_adapters` (see `attach_adapters`): None = the adapted weights if adapters are attached, False = the base
         model, True = the adapted weights or an error. Part of the cache key; adapted engines are built over
         `lora.adapted_weights()`.
         `cached=True`: the engine behind a `forward(..., use_cache=True)` KV-cache handle — keyed apart from the engines
@@ -229,10 +233,49 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
                                       "load_adapter(dir, fp8=True) or lora.enable_fp8(): the refresh then requantises them on the device")
         weights = self._adapters.adapted_weights() if adapted else self.weights
         key = (batch, prompt_len, n_new, fp8, padded, cached, sample) + (("score", score_range) if score else ()) + \
-            (("vocab", vocab_range) if vocab_range is not None else ()) + (("adapted",) if adapted else ())
+            (("vocab", vocab_range) if vocab_range is not None else ()) + (("adapted",) if adapted else ()) + \
+            ((("taps", attn_taps.key(self.dims.llm_layers)),) if attn_taps is not None else ())
         return self._lru(self._engines, key,
                          lambda: OpenVLAEngine(weights, batch, prompt_len, n_new=n_new, fp8=fp8 and not padded, padded=padded,
-                                               sample=sample, score=score, score_range=score_range, vocab_range=vocab_range))
+                                               sample=sample, score=score, score_range=score_range, vocab_range=vocab_range,
+                                               attn_taps=attn_taps))
+
+    # ---- where the action tokens attend (attention_taps.py) ----
+    @staticmethod
+    def _attn_taps(return_attention: Optional[str], attention_layers) -> Optional[AttnTaps]:
+        if return_attention is None:
+            if attention_layers is not None:
+                raise ValueError("attention_layers goes with return_attention=")
+            return None
+        if return_attention not in ("segments", "full", "both"):
+            raise ValueError(f'return_attention must be None, "segments", "full" or "both", got {return_attention!r}')
+        return AttnTaps(layers=None if attention_layers is None else tuple(int(l) for l in attention_layers),
+                        full=return_attention != "segments", segments=return_attention != "full")
+
+    @staticmethod
+    def _set_attention_segments(eng: OpenVLAEngine, attention_mask: Optional[torch.Tensor], text_splits) -> None:
+        """The segments of THIS call's prompts (after set_padded_inputs, which resets them, and before the plan runs)."""
+        mask = torch.ones(eng.B, eng.L, dtype=torch.int64) if attention_mask is None else attention_mask
+        eng.set_segments(*prompt_segments(mask, eng.n_patches, eng.n_new, text_splits))
+
+    @staticmethod
+    def _action_attention(eng: OpenVLAEngine) -> ActionAttention:
+        a = eng.action_attention()       # views of the engine's static buffers: hand out copies
+        return ActionAttention(probs=None if a.probs is None else a.probs.clone(),
+                               segments=None if a.segments is None else a.segments.clone(), names=a.names, layers=a.layers)
+
+    @torch.no_grad()
+    def attention_maps(self, input_ids: torch.LongTensor, pixel_values: Optional[torch.Tensor] = None,
+                       attention_mask: Optional[torch.Tensor] = None, layers=None) -> tuple:
+        """HF's `attentions` for the all-position forward of these inputs (multimodal, or language-only without
+        pixel_values): a tuple with one entry per decoder layer, fp32 [B, H, S, S] (S = 256 + L, or L), None for a layer
+        outside `layers` (None: all). Row i of an entry is query i's softmax over the keys it sees (causal, pads hidden);
+        computed by bl_attention_probs_f32 from the layer's own q and cached keys, never rounded to bf16."""
+        from ...forward_full import _all_rows_engine, forward_all_rows
+        taps = AttnTaps(layers=None if layers is None else tuple(int(l) for l in layers), full=True, segments=False)
+        forward_all_rows(self, input_ids, attention_mask, pixel_values, None, attn_taps=taps)
+        eng = _all_rows_engine(self, input_ids.shape[0], input_ids.shape[1], pixel_values is None, taps)
+        return tuple(None if m is None else m.clone() for m in eng.attention_maps())
 
     # ---- LoRA adapters: inference under merged weights beside the frozen base (training/lora.py) ----
     _adapters = None           # the attached training.lora.LoraAdapters
@@ -323,10 +366,11 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             current transformers) plus an opaque `past_key_values` handle bound to that engine's KV caches.
 
         `output_hidden_states=True` (all-position branches) returns HF's tuple: embeddings, every decoder layer's output,
-        the last one after the final norm. `output_attentions` cannot be served: the attention kernels never materialise
-        the probability matrix (neither does the reference under flash-attn). No gradients flow through this class."""
+        the last one after the final norm. `output_attentions` is not served here: the attention kernels never materialise
+        the probability matrix (neither does the reference under flash-attn); `attention_maps` computes it on request. No gradients flow through this class."""
         if output_attentions:
-            raise NotImplementedError("output_attentions: the fused attention kernels do not materialise attention weights")
+            raise NotImplementedError("output_attentions: the fused attention kernels do not materialise attention weights; "
+                                      "attention_maps(input_ids, pixel_values, attention_mask, layers) computes them on request")
         if input_ids is None and inputs_embeds is None:
             raise ValueError("Invalid PrismaticForConditionalGeneration `forward()` call: need input_ids (or inputs_embeds)")
         from ...forward_full import EngineKVCache, forward_all_rows, forward_cached_step, forward_prefill_cached
@@ -381,8 +425,15 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
                  attention_mask: Optional[torch.Tensor] = None, do_sample: bool = False, use_cache: bool = True,
                  sampling: Optional[SamplingParams] = None, return_weights: bool = False,
                  forced_ids: Optional[torch.Tensor] = None, score_range: Optional[Tuple[int, int]] = None,
-                 vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None, **_: Any):
+                 vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None,
+                 return_attention: Optional[str] = None, attention_layers=None, text_splits=None, **_: Any):
         """`use_adapters`: see `engine` (None: the attached adapters if any; False: the base model).
+        `return_attention="segments" | "full" | "both"` appends an `attention_taps.ActionAttention` to whatever the call
+        returns: for every new token, tapped layer (`attention_layers`, None = all) and head, the attention of the query that
+        produced it — summed over bos | image | text | generated ("segments"), over every cache row ("full"), or both.
+        `text_splits` [B, k] (indices into input_ids, BOS counted) cut the text into k + 1 pieces, e.g. task | description |
+        "\nOut:". With `forced_ids` it is the attention under the given tokens. The taps only read: ids, logits and weights
+        are those of the call without them.
         Greedy decoding, returns [B, L + max_new_tokens] like GenerationMixin (prompt ‖ new tokens). `use_cache` is
         accepted and ignored: the KV cache is always used (use_cache=False in the fork's demo re-runs the vision towers
         7 times, run_openvla_demo.py:43 — same result, 7× the work). A batch whose attention_mask has zeros is taken as
@@ -408,37 +459,54 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             raise ValueError("generate() needs pixel_values")
         B, L = input_ids.shape
         ids, pv = input_ids.to(self.device), pixel_values.to(self.device)
+        taps = self._attn_taps(return_attention, attention_layers)
+        if taps is None and text_splits is not None:
+            raise ValueError("text_splits goes with return_attention=")
         if forced_ids is not None:
             forced = torch.as_tensor(forced_ids).to(self.device, torch.int64)
             padded = attention_mask is not None and not bool(attention_mask.bool().all())
             eng = self.engine(B, L, max_new_tokens, padded=padded, score=True, score_range=score_range, vocab_range=vocab_range,
-                              use_adapters=use_adapters)
+                              use_adapters=use_adapters, attn_taps=taps)
             eng.set_sampling(sampling if sampling is not None else SamplingParams())
             if padded:
                 eng.set_forced_ids(forced)
                 eng.set_padded_inputs(ids, pv, attention_mask)
+                if taps is not None:
+                    self._set_attention_segments(eng, attention_mask, text_splits)
                 eng.run_eager()
             else:
+                if taps is not None:
+                    self._set_attention_segments(eng, None, text_splits)
                 eng.score(ids, pv, forced)
             out = (torch.cat([ids, forced], dim=1), eng.gen_wt.permute(1, 0, 2).clone())
-            return out if score_range is None else out + (eng.gen_range_wt.permute(1, 0, 2).clone(),)
+            out = out if score_range is None else out + (eng.gen_range_wt.permute(1, 0, 2).clone(),)
+            return out if taps is None else out + (self._action_attention(eng),)
         if score_range is not None:
             raise ValueError("score_range goes with forced_ids=")
         if vocab_range is not None and sampling is None:
             sampling = SamplingParams(temperature=0.0, seed=0)
         sample = sampling is not None
         if attention_mask is not None and not bool(attention_mask.bool().all()):
-            eng = self.engine(B, L, max_new_tokens, padded=True, sample=sample, vocab_range=vocab_range, use_adapters=use_adapters)
+            eng = self.engine(B, L, max_new_tokens, padded=True, sample=sample, vocab_range=vocab_range, use_adapters=use_adapters,
+                              attn_taps=taps)
             if sample:
                 eng.set_sampling(sampling)
             eng.set_padded_inputs(ids, pv, attention_mask)
+            if taps is not None:
+                self._set_attention_segments(eng, attention_mask, text_splits)
             eng.run_eager()
             new = eng.gen_ids.t()
         else:
-            eng = self.engine(B, L, max_new_tokens, sample=sample, vocab_range=vocab_range, use_adapters=use_adapters)
+            eng = self.engine(B, L, max_new_tokens, sample=sample, vocab_range=vocab_range, use_adapters=use_adapters,
+                              attn_taps=taps)
+            if taps is not None:
+                self._set_attention_segments(eng, None, text_splits)
             new = eng.generate(ids, pv, sampling)
         out = torch.cat([ids, new], dim=1)
-        return (out, eng.gen_wt.permute(1, 0, 2).clone()) if return_weights else out
+        out = (out, eng.gen_wt.permute(1, 0, 2).clone()) if return_weights else out
+        if taps is None:
+            return out
+        return (out if isinstance(out, tuple) else (out,)) + (self._action_attention(eng),)
 
 
 class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
@@ -466,7 +534,9 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         be a list with one key per sequence (extension: a server batch that mixes datasets of one action dimension);
         the result is then always [B, n]. `action_tokens_only=True` decodes under the policy restricted to
         `action_token_range()`: with `sampling=` every draw is an action token, without it the call is constrained greedy
-        decoding (the argmax over the action tokens)."""
+        decoding (the argmax over the action tokens). `return_attention=` / `attention_layers=` / `text_splits=` (see
+        `generate`) return the `ActionAttention` of the action tokens as an extra last element; `text_splits` index the
+        input_ids as given (the empty token this call appends joins the last text piece)."""
         input_ids = input_ids.to(self.device)
         kwargs["use_adapters"] = use_adapters
         if action_tokens_only:
@@ -481,7 +551,9 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             kwargs["attention_mask"] = m
         n = self.get_action_dim(unnorm_key)
         generated = self.generate(input_ids, max_new_tokens=n, **kwargs)
-        wt = None
+        wt = att = None
+        if kwargs.get("return_attention") is not None:   # the ActionAttention rides last
+            generated, att = (generated[0] if len(generated) == 2 else generated[:-1]), generated[-1]
         if isinstance(generated, tuple):                 # sampling= with return_weights=True
             generated, wt = generated
         tokens = generated[:, -n:].cpu().numpy()
@@ -489,7 +561,21 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             actions = np.stack([np.asarray(self.actions_from_token_ids(tokens[i:i + 1], k)).reshape(-1) for i, k in enumerate(keys)])
         else:
             actions = self.actions_from_token_ids(tokens, unnorm_key)
-        return actions if wt is None else (actions, tokens, wt.cpu().numpy())
+        out = actions if wt is None else (actions, tokens, wt.cpu().numpy())
+        if att is None:
+            return out
+        return (out if isinstance(out, tuple) else (out,)) + (att,)
+
+    @staticmethod
+    def _stack_attention(parts: Sequence[ActionAttention], B: int) -> ActionAttention:
+        """The ActionAttention of several engine runs over c·B rows each (copy-major, as sample_actions / score_actions batch
+        them) → one with tensors [B, copies, n_new, layers, H, ·]."""
+        def cat(ts):
+            if ts[0] is None:
+                return None
+            return torch.cat([t.reshape((t.shape[0] // B, B) + tuple(t.shape[1:])) for t in ts], dim=0).transpose(0, 1).contiguous()
+        return ActionAttention(probs=cat([a.probs for a in parts]), segments=cat([a.segments for a in parts]),
+                               names=parts[0].names, layers=parts[0].layers)
 
     def _action_prompt(self, input_ids: torch.LongTensor, m: Optional[torch.Tensor]):
         """The prompt with the empty token 29871 behind each sequence's last token → (input_ids, attention_mask)."""
@@ -514,7 +600,8 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
                        unnorm_key: Union[str, Sequence[Optional[str]], None] = None, sampling: Optional[SamplingParams] = None,
                        num_samples: int = 1, attention_mask: Optional[torch.Tensor] = None,
                        action_tokens_only: bool = False,
-                       use_adapters: Optional[bool] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                       use_adapters: Optional[bool] = None, return_attention: Optional[str] = None, attention_layers=None,
+                       text_splits=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """`use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy).
         `num_samples` sampled actions per sequence with their log-probabilities (RL rollouts, best-of-N, uncertainty):
         → (actions [B, num_samples, n], token_ids int64 [B, num_samples, n], logprobs fp64 [B, num_samples, n]). The batch
@@ -523,7 +610,9 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         log(w / total) of step t's weight pair: the token's log-probability under the warped (temperature / top-k /
         top-p) distribution. `action_tokens_only=True` draws from the policy restricted to `action_token_range()`: every
         token is an action token and its log-probability is the one under that restricted policy — what a learner with
-        `PolicyLossConfig(token_range=model.action_token_range())` trains against."""
+        `PolicyLossConfig(token_range=model.action_token_range())` trains against.
+        `return_attention=` (with `attention_layers=`, `text_splits=` [B, k]; see `generate`) appends the `ActionAttention` of
+        every copy: tensors [B, num_samples, n, layers, H, ·]."""
         if sampling is None:
             sampling = SamplingParams()
         if num_samples < 1:
@@ -532,26 +621,38 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         T, k, p, seed = sampling.resolve(B)
         keys = list(unnorm_key) if isinstance(unnorm_key, (list, tuple)) else None
         per_call = max(1, 16 // B)          # copies per engine run: batches up to 16 keep "a sequence's result is its batch-1 result"
-        acts, toks, lps = [], [], []
+        acts, toks, lps, atts = [], [], [], []
+        att_kw = {}
+        if return_attention is not None:
+            att_kw = dict(return_attention=return_attention, attention_layers=attention_layers)
         for j0 in range(0, num_samples, per_call):
             c = min(per_call, num_samples - j0)
             sp = SamplingParams(temperature=np.tile(T, c), top_k=np.tile(k, c), top_p=np.tile(p, c),
                                 seed=np.concatenate([derive_seed(seed, j) for j in range(j0, j0 + c)]))
-            a, tok, wt = self.predict_action(input_ids.repeat(c, 1), keys * c if keys is not None else unnorm_key,
-                                             pixel_values=pixel_values.repeat(c, 1, 1, 1),
-                                             attention_mask=None if attention_mask is None else attention_mask.repeat(c, 1),
-                                             sampling=sp, return_weights=True, action_tokens_only=action_tokens_only,
-                                             use_adapters=use_adapters)
+            if att_kw and text_splits is not None:
+                att_kw["text_splits"] = torch.as_tensor(text_splits).reshape(B, -1).repeat(c, 1)
+            res = self.predict_action(input_ids.repeat(c, 1), keys * c if keys is not None else unnorm_key,
+                                      pixel_values=pixel_values.repeat(c, 1, 1, 1),
+                                      attention_mask=None if attention_mask is None else attention_mask.repeat(c, 1),
+                                      sampling=sp, return_weights=True, action_tokens_only=action_tokens_only,
+                                      use_adapters=use_adapters, **att_kw)
+            a, tok, wt = res[:3]
+            if att_kw:
+                atts.append(res[3])
             acts.append(np.asarray(a).reshape(c, B, -1))
             toks.append(tok.reshape(c, B, -1))
             lps.append(logprob(wt).reshape(c, B, -1))
-        return tuple(np.concatenate(x, axis=0).transpose(1, 0, 2) for x in (acts, toks, lps))
+        out = tuple(np.concatenate(x, axis=0).transpose(1, 0, 2) for x in (acts, toks, lps))
+        return out + (self._stack_attention(atts, B),) if att_kw else out
 
     def score_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor, token_ids=None, actions=None,
                       unnorm_key: Optional[str] = None, sampling: Optional[SamplingParams] = None,
                       attention_mask: Optional[torch.Tensor] = None, return_bins: bool = False,
-                      action_tokens_only: bool = False, use_adapters: Optional[bool] = None):
-        """`use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy — with adapters
+                      action_tokens_only: bool = False, use_adapters: Optional[bool] = None,
+                      return_attention: Optional[str] = None, attention_layers=None, text_splits=None):
+        """`return_attention=` (with `attention_layers=`, `text_splits=` [B, k]; see `generate`) appends the `ActionAttention`
+        under the GIVEN actions, tensors [B, K, n, layers, H, ·], as an extra last element.
+        `use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy — with adapters
         attached, an RL learner's reference policy).
         Log-probabilities of GIVEN actions under the policy `sample_actions` draws from (a PPO / GRPO learner's
         log π(a | s), a reranker's score of a planner's proposal): exactly one of `token_ids` (int64) and `actions`
@@ -586,7 +687,10 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         rng = (self.vocab_size - n_bins, n_bins) if return_bins else None
         ids, m = self._action_prompt(input_ids.to(self.device), attention_mask)      # the prompt as predict_action prepares it
         per_call = max(1, 16 // B)          # candidates per engine run, as sample_actions batches its copies
-        wts, bins = [], []
+        wts, bins, atts = [], [], []
+        att_kw = {}
+        if return_attention is not None:
+            att_kw = dict(return_attention=return_attention, attention_layers=attention_layers)
         for j0 in range(0, K, per_call):
             c = min(per_call, K - j0)
             sp = SamplingParams(temperature=np.tile(T, c), top_k=np.tile(k, c), top_p=np.tile(p, c), seed=0)
@@ -594,13 +698,20 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             out = self.generate(ids.repeat(c, 1), n, pixel_values=pixel_values.repeat(c, 1, 1, 1),
                                 attention_mask=None if m is None else m.repeat(c, 1), sampling=sp, forced_ids=forced,
                                 score_range=rng, vocab_range=self.action_token_range() if action_tokens_only else None,
-                                use_adapters=use_adapters)
+                                use_adapters=use_adapters, **att_kw,
+                                **(dict(text_splits=torch.as_tensor(text_splits).reshape(B, -1).repeat(c, 1))
+                                   if att_kw and text_splits is not None else {}))
+            if att_kw:
+                atts.append(out[-1])
             wts.append(out[1].cpu().numpy().reshape(c, B, n, 2))
             if return_bins:
                 bins.append(out[2].cpu().numpy().reshape(c, B, n, n_bins))
         wt = np.concatenate(wts, axis=0).transpose(1, 0, 2, 3)
         lp = logprob(wt)
-        return (lp, wt, np.concatenate(bins, axis=0).transpose(1, 0, 2, 3)) if return_bins else lp
+        res = (lp, wt, np.concatenate(bins, axis=0).transpose(1, 0, 2, 3)) if return_bins else lp
+        if not att_kw:
+            return res
+        return (res if isinstance(res, tuple) else (res,)) + (self._stack_attention(atts, B),)
 
     def token_ids_from_actions(self, actions: np.ndarray, unnorm_key: Optional[str] = None) -> np.ndarray:
         """Un-normalised actions [..., n] → action token ids int64 [..., n]: the inverse of `actions_from_token_ids`, i.e.

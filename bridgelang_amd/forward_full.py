@@ -49,25 +49,29 @@ class EngineKVCache:
         return self.engine.n_new - 1
 
 
-def _all_rows_engine(model, B: int, L: int, text_only: bool) -> OpenVLAEngine:
+def _all_rows_engine(model, B: int, L: int, text_only: bool, attn_taps=None) -> OpenVLAEngine:
     # engines live on the model (LRU-bounded, PrismaticForConditionalGeneration._lru), never in a module global
-    return model._lru(model._forward_engines, (B, L, text_only),
-                      lambda: OpenVLAEngine(model.weights, B, L, all_rows=True, use_mask=True, text_only=text_only))
+    key = (B, L, text_only) + ((("taps", attn_taps.key(model.dims.llm_layers)),) if attn_taps is not None else ())
+    return model._lru(model._forward_engines, key,
+                      lambda: OpenVLAEngine(model.weights, B, L, all_rows=True, use_mask=True, text_only=text_only,
+                                            attn_taps=attn_taps))
 
 
 def forward_all_rows(model, input_ids: Optional[torch.Tensor], attention_mask: Optional[torch.Tensor],
                      pixel_values: Optional[torch.Tensor], labels: Optional[torch.Tensor],
-                     inputs_embeds: Optional[torch.Tensor] = None, output_hidden_states: bool = False):
+                     inputs_embeds: Optional[torch.Tensor] = None, output_hidden_states: bool = False, attn_taps=None):
     """Returns (loss or None, logits fp32 [B, S, vocab], projector features bf16 [B, 256, D] or None, hidden states or
     None). `pixel_values is None` is the reference's language-only branch (S = L); there `inputs_embeds` [B, L, D] may
-    stand in for `input_ids` (an extension: the reference asserts it away, modeling_prismatic.py:345)."""
+    stand in for `input_ids` (an extension: the reference asserts it away, modeling_prismatic.py:345). `attn_taps`
+    (attention_taps.AttnTaps) runs the plan with the attention taps of those layers; the maps are then the engine's
+    (`_all_rows_engine(model, B, L, text_only, attn_taps).attention_maps()`)."""
     dev = model.device
     text_only = pixel_values is None
     if inputs_embeds is not None and not text_only:
         raise ValueError("inputs_embeds replaces the token embeddings of the language-only forward; the multimodal forward "
                          "embeds input_ids itself (modeling_prismatic.py:380)")
     B, L = (inputs_embeds if input_ids is None else input_ids).shape[:2]
-    eng = _all_rows_engine(model, B, L, text_only)
+    eng = _all_rows_engine(model, B, L, text_only, attn_taps)
     P, S = eng.n_patches, eng.S
     if input_ids is not None:
         eng.set_inputs(input_ids.to(dev), None if text_only else pixel_values.to(dev))

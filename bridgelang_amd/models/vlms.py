@@ -109,6 +109,10 @@ class PrismaticVLM:
     def generate(self, input_ids: torch.LongTensor, pixel_values, max_new_tokens: int = 7, **kwargs: Any) -> torch.LongTensor:
         return self.hf.generate(input_ids, max_new_tokens=max_new_tokens, pixel_values=self._stack(pixel_values), **kwargs)
 
+    def attention_maps(self, input_ids: torch.LongTensor, pixel_values=None, attention_mask=None, layers=None) -> tuple:
+        """HF's `attentions` of the all-position forward (PrismaticForConditionalGeneration.attention_maps)."""
+        return self.hf.attention_maps(input_ids, None if pixel_values is None else self._stack(pixel_values), attention_mask, layers)
+
 
 class OpenVLA(PrismaticVLM):
     def __init__(self, *args, norm_stats: Dict[str, Dict[str, Dict[str, Dict[str, List[float]]]]], action_tokenizer, **kwargs) -> None:
@@ -118,7 +122,8 @@ class OpenVLA(PrismaticVLM):
     model_family = "openvla"
 
     def predict_action(self, image, instruction: str, unnorm_key: Optional[str] = None, **kwargs: str) -> np.ndarray:
-        """openvla.py:35-103: PIL image + instruction → un-normalised continuous action."""
+        """openvla.py:35-103: PIL image + instruction → un-normalised continuous action. `return_attention=` (with
+        `attention_layers=`, `text_splits=`; see the HF model's `generate`) returns (action, ActionAttention)."""
         image_transform, tokenizer = self.vision_backbone.image_transform, self.llm_backbone.tokenizer
         prompt_builder = self.get_prompt_builder()
         prompt_builder.add_turn(role="human", message=f"What action should the robot take to {instruction.lower()}?")
@@ -135,12 +140,16 @@ class OpenVLA(PrismaticVLM):
             raise ValueError(f"Unsupported `pixel_values` type = {type(pixel_values)}")
         n = self.get_action_dim(unnorm_key)
         generated_ids = self.generate(input_ids, pixel_values, max_new_tokens=n, **kwargs)
+        attention = None
+        if kwargs.get("return_attention") is not None:
+            generated_ids, attention = generated_ids[0], generated_ids[-1]
         predicted_action_token_ids = generated_ids[0, -n:]
         normalized_actions = self.action_tokenizer.decode_token_ids_to_actions(predicted_action_token_ids.cpu().numpy())
         action_norm_stats = self.get_action_stats(unnorm_key)
         mask = action_norm_stats.get("mask", np.ones_like(action_norm_stats["q01"], dtype=bool))
         action_high, action_low = np.array(action_norm_stats["q99"]), np.array(action_norm_stats["q01"])
-        return np.where(mask, 0.5 * (normalized_actions + 1) * (action_high - action_low) + action_low, normalized_actions)
+        action = np.where(mask, 0.5 * (normalized_actions + 1) * (action_high - action_low) + action_low, normalized_actions)
+        return action if attention is None else (action, attention)
 
     @staticmethod
     def _check_unnorm_key(norm_stats: Dict, unnorm_key: str) -> str:

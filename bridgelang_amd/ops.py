@@ -20,7 +20,7 @@ from ._lib import (AttnDesc, GemmDesc, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_KE
                    EPI_NONE, EPI_SWIGLU_BWD, EPI_SWIGLU_KEEP,
                    EPI_RES, EPI_SWIGLU)
 
-__all__ = ["Op", "gemm", "gemm_last_form", "gemm_form_name", "gemm_fp8", "linear_fp8", "Fp8Weight", "quantize_rows_fp8", "quantize_weight_fp8", "quantize_packed_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
+__all__ = ["Op", "gemm", "gemm_last_form", "gemm_form_name", "gemm_fp8", "linear_fp8", "Fp8Weight", "quantize_rows_fp8", "quantize_weight_fp8", "quantize_packed_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "attention_probs", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
            "argmax", "sample", "score", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
            "EPI_NONE", "EPI_BIAS", "EPI_BIAS_GELU", "EPI_BIAS_RES", "EPI_RES", "EPI_SWIGLU", "EPI_F32", "EPI_F32_BF16R",
            "EPI_SWIGLU_KEEP", "EPI_BIAS_GELU_KEEP", "EPI_SWIGLU_BWD", "EPI_GELU_BWD"]
@@ -489,6 +489,65 @@ def attention_decode_rope(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
         return op
     op = Op("bl_attention_decode_rope_bf16", lib.bl_attention_decode_rope_bf16,
             (C.byref(d), cos.data_ptr(), sin.data_ptr(), pos), (d, qkv, k_cache, v_cache, o, cos, sin, key_mask))
+    if run:
+        op.run()
+    return op
+
+
+def attention_probs(q: torch.Tensor, k: torch.Tensor, *, B: int, H: int, Sq: int, Skv: int, head_dim: int, q_strides, k_strides,
+                    causal: bool, scale: Optional[float] = None, key_mask: Optional[torch.Tensor] = None,
+                    cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None, pos0: int = 0,
+                    rope_pos: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None,
+                    seg: Optional[torch.Tensor] = None, seg_bounds: Optional[torch.Tensor] = None, run: bool = True) -> Op:
+    """The attention probabilities of q against ROTATED keys k (a KV-cache view), read-only (bl_attention_probs_f32).
+    q / k are strided [batch, head, row, head_dim] views, strides (batch, head, row) in elements. With cos / sin, q is
+    un-rotated and is rotated on load at pos0 + row (rope_pos[b] + row with an int32 [B] device tensor); without, q is
+    rotated in memory. probs: fp32 [B, H, Sq, p_cols >= Skv] view with a contiguous last dim — columns past Skv are zeroed;
+    seg: contiguous fp32 [B, H, Sq, n_seg] with seg_bounds int32 [B, n_seg + 1]. Either output may be None."""
+    lib = _lib.load()
+    scale = head_dim ** -0.5 if scale is None else scale
+    d = AttnDesc()
+    d.q, (d.q_bs, d.q_hs, d.q_rs) = _bf16(q, "q").data_ptr(), q_strides
+    d.k, (d.k_bs, d.k_hs, d.k_rs) = _bf16(k, "k").data_ptr(), k_strides
+    if key_mask is not None:
+        if key_mask.dtype != torch.uint8 or key_mask.dim() != 2 or key_mask.stride(1) != 1:
+            raise TypeError("key_mask must be a [B, Skv] uint8 tensor")
+        d.key_mask, d.mask_bs = key_mask.data_ptr(), key_mask.stride(0)
+    d.B, d.H, d.Sq, d.Skv, d.head_dim, d.causal, d.scale = B, H, Sq, Skv, head_dim, int(causal), float(scale)
+    if (cos is None) != (sin is None):
+        raise ValueError("attention_probs: cos and sin come together")
+    rope_rows = 0
+    if cos is not None:
+        for t, n in ((cos, "cos"), (sin, "sin")):
+            _bf16(t, n)
+            if not t.is_contiguous() or t.dim() != 2 or t.shape[1] != head_dim // 2:
+                raise ValueError(f"attention_probs: {n} must be a contiguous [positions, head_dim/2] table")
+        rope_rows = min(cos.shape[0], sin.shape[0])
+    if rope_pos is not None and (rope_pos.dtype != torch.int32 or not rope_pos.is_cuda or rope_pos.numel() != B
+                                 or not rope_pos.is_contiguous()):
+        raise TypeError("attention_probs: rope_pos must be a contiguous CUDA/HIP int32 tensor [B]")
+    p_ptr, p_str, p_cols = None, (0, 0, 0), 0
+    if probs is not None:
+        if probs.dtype != torch.float32 or not probs.is_cuda or probs.dim() != 4 or probs.stride(3) != 1 \
+                or tuple(probs.shape[:3]) != (B, H, Sq):
+            raise TypeError("attention_probs: probs must be a CUDA/HIP fp32 [B, H, Sq, cols] view with a contiguous last dim")
+        p_ptr, p_str, p_cols = probs.data_ptr(), probs.stride()[:3], probs.shape[3]
+    s_ptr, b_ptr, n_seg = None, None, 0
+    if seg is not None:
+        if seg.dtype != torch.float32 or not seg.is_cuda or not seg.is_contiguous() or seg.dim() != 4 \
+                or tuple(seg.shape[:3]) != (B, H, Sq):
+            raise TypeError("attention_probs: seg must be a contiguous CUDA/HIP fp32 [B, H, Sq, n_seg] tensor")
+        n_seg = seg.shape[3]
+        if seg_bounds is None or seg_bounds.dtype != torch.int32 or not seg_bounds.is_cuda or not seg_bounds.is_contiguous() \
+                or tuple(seg_bounds.shape) != (B, n_seg + 1):
+            raise TypeError("attention_probs: seg_bounds must be a contiguous CUDA/HIP int32 [B, n_seg + 1] tensor")
+        s_ptr, b_ptr = seg.data_ptr(), seg_bounds.data_ptr()
+    op = Op("bl_attention_probs_f32", lib.bl_attention_probs_f32,
+            (C.byref(d), None if cos is None else cos.data_ptr(), None if sin is None else sin.data_ptr(), rope_rows, pos0,
+             None if rope_pos is None else rope_pos.data_ptr(), p_ptr, p_str[0], p_str[1], p_str[2], p_cols, s_ptr, b_ptr, n_seg),
+            (d, q, k, key_mask, cos, sin, rope_pos, probs, seg, seg_bounds),
+            flops=2.0 * B * H * Sq * Skv * head_dim,
+            nbytes=2.0 * B * H * (Sq + Skv) * head_dim + 4.0 * B * H * Sq * (p_cols + n_seg))
     if run:
         op.run()
     return op

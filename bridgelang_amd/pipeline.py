@@ -100,13 +100,17 @@ class StaggeredDecodePipeline:
 
     def __init__(self, weights: VLAWeights, batch: int, prompt_len: int, n_new: int = 7, split_vision: bool = False,
                  fp8: bool = False, padded: bool = False, sample: bool = False, score: bool = False,
-                 score_range: Optional[Tuple[int, int]] = None, vocab_range: Optional[Tuple[int, int]] = None):
+                 score_range: Optional[Tuple[int, int]] = None, vocab_range: Optional[Tuple[int, int]] = None,
+                 attn_taps=None):
         """split_vision=True adds a third stage: the vision towers + projector of the batch submitted NOW run beside the
         Llama prefill of the batch submitted one step earlier (n_new + 1 slots, latency n_new + 1 steps).
         score=True (with score_range, as OpenVLAEngine's) scores given tokens instead of producing them: every slot is an
         `OpenVLAEngine(score=True)`, `step(..., forced_ids=, sampling=)` fills the slot's forced ids and settings, and the
         merged iteration ends in bl_score_f32 per group where a sampling pipeline draws. vocab_range=(first, count), with
         sample=True or score=True, is OpenVLAEngine's: every draw and score is under the policy restricted to that range."""
+        if attn_taps is not None:
+            raise ValueError("StaggeredDecodePipeline has no attention taps: its merged decode iteration runs several batches' "
+                             "rows in one launch; use OpenVLAEngine(attn_taps=...)")
         if n_new < 2:
             raise ValueError("StaggeredDecodePipeline needs at least one decode iteration (n_new >= 2)")
         if padded and fp8:

@@ -138,7 +138,10 @@ class OpenVLAServer:
     def __init__(self, vla: Any, processor: Any, openvla_path: Union[str, Path] = "openvla/openvla-7b",
                  max_batch: int = 16, max_wait_ms: float = 2.0, norm_stats_path: Optional[Union[str, Path]] = None,
                  pipeline_batch: Optional[int] = None, max_pipelines: int = 2, pad_to: Optional[int] = None,
-                 sample: bool = False, action_tokens_only: bool = False, adapter: Any = None):
+                 sample: bool = False, action_tokens_only: bool = False, adapter: Any = None, attn_taps: Any = None):
+        if attn_taps is not None:
+            raise ValueError("OpenVLAServer does not return attention: call the model's generate / predict_action with "
+                             "return_attention=...")
         self.vla, self.processor, self.openvla_path = vla, processor, str(openvla_path)
         if adapter is not None:
             if isinstance(adapter, (str, Path)):

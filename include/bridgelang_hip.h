@@ -210,6 +210,23 @@ int bl_attention_backward_bf16(const bl_attn_desc* d, const bl_bf16* dout, const
                                bl_bf16* dk, bl_bf16* dv, void* stream);
 /* Single-query decode attention over a KV cache; kv_len = number of valid keys (same for the whole batch). */
 int bl_attention_decode_bf16(const bl_attn_desc* d, void* stream);
+/* The attention probabilities themselves (what HF returns as `attentions`), read-only: P = softmax over the visible keys of
+ * q k^T * scale, in fp32, never rounded to bf16. Uses d->q (any strides that are multiples of 8, the fused-qkv row stride
+ * included), d->k (ROTATED keys, e.g. a KV-cache view), d->key_mask, B, H, Sq, Skv, scale, causal; d->v and d->o are ignored.
+ * head_dim 128 and Skv <= 2048, else BL_E_SHAPE. Key j is visible to query i iff key_mask[b][j] != 0 and (not causal or
+ * j <= i + Skv - Sq). K rows >= Skv are never read and rows of hidden keys may hold anything, NaN included.
+ *   q: cos_tab == sin_tab == NULL: already rotated in memory. Otherwise un-rotated: row i of sequence b is rotated on load at
+ *      position pos0 + i, or rope_pos[b] + i when rope_pos (device int32 [B]) is given, with the arithmetic of
+ *      bl_rope_kvcache_bf16 bit for bit; tables [rope_rows, 64] bf16 (a position outside them is clamped).
+ *   probs (or NULL): fp32, element strides p_bs / p_hs / p_rs, columns [0, Skv) = P (0 for hidden keys, a row without a
+ *      visible key is all 0), columns [Skv, p_cols) = 0: no memset needed, nothing outside [0, p_cols) is written.
+ *   seg (or NULL): fp32 [B, H, Sq, n_seg], n_seg <= 8: seg[b][h][i][s] = sum of P over keys [bounds[b][s], bounds[b][s+1]),
+ *      seg_bounds device int32 [B, n_seg + 1], non-decreasing, clipped to [0, Skv] by the kernel.
+ * A row's results do not depend on the other rows of the launch: Sq = S and S calls with Sq = 1 agree bit for bit.
+ * Definition: bridgelang_amd/attention_taps.py::probs_reference. */
+int bl_attention_probs_f32(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab, int32_t rope_rows, int32_t pos0,
+                           const int32_t* rope_pos, float* probs, int64_t p_bs, int64_t p_hs, int64_t p_rs, int32_t p_cols,
+                           float* seg, const int32_t* seg_bounds, int32_t n_seg, void* stream);
 
 /* Training forward: rotate q and k of the fused qkv rows IN PLACE (same arithmetic as bl_rope_kvcache_bf16, no cache). */
 int bl_rope_bf16(bl_bf16* qkv, int64_t ld, int32_t B, int32_t S, int32_t H, int32_t head_dim, const bl_bf16* cos_tab,
