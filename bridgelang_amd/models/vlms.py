@@ -13,7 +13,7 @@ import torch
 from ..extern.hf.configuration_prismatic import OpenVLAConfig
 from ..extern.hf.modeling_prismatic import OpenVLAForActionPrediction
 from ..training.checkpoint import from_model_state_dicts, to_model_state_dicts
-from ..training.step import STAGES
+from ..training.param_store import STAGES
 from ..weights import VLADims
 
 

@@ -19,8 +19,7 @@ from __future__ import annotations
 
 import contextlib
 
-from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import os
 
@@ -29,338 +28,18 @@ import torch
 
 from .. import ops, train_ops as T
 from ..engine import rope_tables
-from ..ops import (EPI_BIAS, EPI_BIAS_GELU_KEEP, EPI_F32, EPI_F32_BF16R, EPI_GELU_BWD, EPI_NONE, EPI_RES, EPI_SWIGLU_BWD,
-                   EPI_SWIGLU_KEEP, Fp8Weight, Op)
-from ..weights import PackedGroup, VLAWeights, _block_view, _unpack
+from ..ops import EPI_BIAS, EPI_F32_BF16R, EPI_NONE, EPI_RES, Op
+from ..weights import VLAWeights
+from .linears import Linears, Scratch, ScratchSet
+from .param_store import STAGES, ParamStore, no_decay, param_sharded_key, pool_of, trainable_names      # noqa: F401  (re-exported)
 from .policy_loss import GROUP_STAT_NAMES, STAT_NAMES, PolicyLossConfig
 from .preference_loss import PAIR_STAT_NAMES, PREF_STAT_NAMES, SEQ_STAT_NAMES, PreferenceLossConfig, check_pairs
-from .sharding import ShardComm, ShardLayout, bucket_key, comm_order
+from .sharding import ShardComm, comm_order
+from .unit_pools import UnitPools
 from .value_head import ValueHead
 from .value_loss import VALUE_STAT_NAMES, ValueLossConfig
 
 IGNORE_INDEX = -100
-# SwiGLU / GELU forward ("f") and backward ("b") as GEMM epilogues (BL_EPI_*_KEEP / BL_EPI_*_BWD) instead of separate
-# elementwise passes. ON by default since the tile GEMMs' whole-tile epilogue (round 4, gemm_common.h::epilogue_tile): same box,
-# alternating runs at 7B, B = 32: separate passes 409.8 ms / step, forward fused 408.7, backward fused 409.0, both 406.6. With the
-# per-store epilogue of rounds 1-3 the fused forms LOST 2-4 ms (442.2 vs 444.5-446.2): one workgroup per CU, so the extra
-# stores / exp / erf sat exposed in an epilogue that already cost more than the HBM-bound pass they remove.
-# BL_TRAIN_FUSED_ACT=0 (or any string without "f" / "b") selects the separate passes. Bit-identical either way (tested).
-_FA = os.environ.get("BL_TRAIN_FUSED_ACT", "fb")
-UNFUSED_FWD, UNFUSED_BWD = "f" not in _FA, "b" not in _FA
-
-# stage → (vision trainable, projector trainable, llm: "all" | "last" | "none")   — prismatic.py:129-241
-STAGES: Dict[str, Tuple[bool, bool, str]] = {
-    "align": (False, True, "none"),
-    "finetune": (False, True, "all"), "vla-train": (False, True, "all"),
-    "full-finetune": (True, True, "all"), "vla-full-train": (True, True, "all"),
-    "last-layer-finetune": (False, False, "last"), "vla-last-layer-train": (False, False, "last"),
-    "vla-sandwich-train": (True, True, "last"),
-    "lora": (False, False, "none"),          # vla-scripts/finetune.py: base frozen, adapters train (training/lora.py)
-}
-
-
-def trainable_names(w: VLAWeights, stage: str) -> List[str]:
-    """HF tensor names with requires_grad=True after `freeze_backbones(stage)`; "last" = embed_tokens, the final decoder
-    layer and lm_head (llama2.py:101-102; the final norm is not in that tuple and stays frozen)."""
-    if stage not in STAGES:
-        raise ValueError(f"Stage `{stage}` is not supported")
-    vision, proj, llm = STAGES[stage]
-    last = f"language_model.model.layers.{w.dims.llm_layers - 1}."
-    out = []
-    for name in w.placements:
-        if name.startswith("vision_backbone."):
-            ok = vision
-        elif name.startswith("projector."):
-            ok = proj
-        elif llm == "all":
-            ok = True
-        elif llm == "last":
-            ok = name.startswith(last) or name in ("language_model.model.embed_tokens.weight", "language_model.lm_head.weight")
-        else:
-            ok = False
-        if ok:
-            out.append(name)
-    return out
-
-
-def pl_is_plain(w: VLAWeights, name: str) -> bool:
-    return w.placements[name].group is None
-
-
-# buckets whose PARAMETERS are sharded under fsdp-full-shard: every FSDP unit of the reference — decoder layers, ViT blocks
-# (+ patch embeddings), projector, and the root's token embeddings / lm_head (prismatic.py:285-306, dinosiglip_vit.py:136-140,
-# base_llm.py:182-188, fsdp.py:160-168). Not sharded: the two buckets of small plain tensors.
-def param_sharded_key(key: str) -> bool:
-    return key.startswith(("llm.layer", "vision.", "projector", "llm.lm_head", "llm.embed"))
-
-
-def pool_of(key: str) -> str:
-    """Gather-slot pool of a parameter-sharded bucket: uniform decoder layers / the vision units / the three big singletons."""
-    return "layers" if key.startswith("llm.layer") else "vision" if key.startswith("vision.") else "head"
-
-
-def no_decay(name: str, shape: Tuple[int, ...]) -> bool:
-    """fsdp.py:208: `param.ndim <= 1 or name.endswith(".bias")` → weight_decay 0."""
-    return len(shape) <= 1 or name.endswith(".bias")
-
-
-@dataclass
-class Unit:
-    """One optimizer unit: a packed GEMM weight group (logical [n, k] matrix) or a plain tensor."""
-    key: str
-    offset: int                 # into the flat (bucket-padded) parameter space
-    numel: int
-    group: Optional[PackedGroup]
-    dst: Optional[torch.Tensor]        # plain: contiguous bf16 view of the live parameter
-    decay: bool
-    bucket: int
-    names: Tuple[str, ...] = ()
-
-
-class ParamStore:
-    """Trainable tensors as one flat parameter space (sharding.ShardLayout): full fp32 gradients and a full bf16 staging
-    copy on every rank, fp32 masters and AdamW moments for this rank's 1/world slice of every bucket only."""
-
-    def __init__(self, w: VLAWeights, stage: str, world: int = 1, rank: int = 0,
-                 extra: Optional[List[Tuple[str, torch.Tensor, bool, str]]] = None, only: Optional[Sequence[str]] = None,
-                 shard_params: bool = False, defer_grads: bool = False):
-        """`extra`: additional trainable bf16 tensors outside the model's own table — (name, flat live tensor, decayed,
-        bucket key), e.g. LoRA adapters. `only`: restrict the stage's trainable set to these HF names (whole fused groups;
-        diagnostics / tests: optimizer state for a handful of tensors instead of the model). `shard_params`: the buckets
-        of every FSDP unit (param_sharded_key) keep NO full bf16 copy — each rank holds its 1/world slice (`own`), the unit
-        is gathered around its use (FSDP FULL_SHARD, fsdp.py:84-87; TrainStep(shard_params=True))."""
-        self.w, self.stage = w, stage
-        specs = w._specs()
-        names = set(trainable_names(w, stage))
-        if only is not None:
-            keep = set(only)
-            for g in w.groups:
-                if keep & set(g.members):
-                    keep |= set(g.members)
-            names &= keep
-        self.names = names
-        self.units: List[Unit] = []
-        self.by_name: Dict[str, Unit] = {}
-        self.layout = lay = ShardLayout(world, rank)
-        cur = None
-        for gi, g in enumerate(w.groups):                       # GEMM weight groups (all decayed: ndim >= 2)
-            tr = [n in names for n in g.members]
-            if not any(tr):
-                continue
-            assert all(tr), f"group {g.members} is only partly trainable"
-            key = bucket_key(g.members[0])
-            if key != cur:
-                lay.begin(key, True)
-                cur = key
-            u = Unit(f"group{gi}", 0, g.n * g.k, g, None, True, len(lay.buckets) - 1, tuple(g.members))
-            u.offset = lay.add(u.numel, len(self.units))
-            self.units.append(u)
-            for n in g.members:
-                self.by_name[n] = u
-        EMBED = "language_model.model.embed_tokens.weight"
-        # (bucket key, decayed, names): the token embeddings are half of the reference's root FSDP unit (fsdp.py:160-168) and get
-        # a bucket of their own right behind the GEMM-weight buckets (parameter-sharded with them); the other plain tensors
-        # (norm scales, biases, LayerScale, position / class tokens: 0.1 % of the model) share one bucket per weight-decay class
-        plain_buckets = [("llm.embed", True, [EMBED])] if EMBED in names and pl_is_plain(w, EMBED) else []
-        for decay in (True, False):
-            plain_buckets.append(("plain.decay" if decay else "plain.nodecay", decay,
-                                  [n for n, pl in w.placements.items() if pl.group is None and n in names and n != EMBED
-                                   and (not no_decay(n, specs[n].shape)) == decay]))
-        for bkey, decay, members in plain_buckets:
-            todo = [(n, w.placements[n]) for n in members]
-            if not todo:
-                continue
-            lay.begin(bkey, decay)
-            for name, pl in todo:
-                assert pl.ld == pl.cols or pl.rows == 1
-                dst = pl.dst.view(-1)[pl.offset:pl.offset + pl.rows * pl.cols]
-                u = Unit(name, 0, dst.numel(), None, dst, decay, len(lay.buckets) - 1, (name,))
-                u.offset = lay.add(u.numel, len(self.units))
-                self.units.append(u)
-                self.by_name[name] = u
-        cur = None
-        for name, dst, decay, bkey in (extra or []):
-            if bkey != cur:
-                lay.begin(bkey, decay)
-                cur = bkey
-            assert dst.is_contiguous() and dst.dtype == torch.bfloat16 and lay.buckets[-1].decay == decay
-            u = Unit(name, 0, dst.numel(), None, dst.view(-1), decay, len(lay.buckets) - 1, (name,))
-            u.offset = lay.add(u.numel, len(self.units))
-            self.units.append(u)
-            self.by_name[name] = u
-        lay.close()
-        self.total = lay.total
-        self.n_params = sum(u.numel for u in self.units)
-        dev = w.embed.device
-        # Parameter-sharded buckets (FSDP FULL_SHARD units, param_sharded_key) occupy a contiguous range [lo, hi) of the
-        # flat space that is CUT OUT of the addressing of the replicated buffers — the bf16 staging copy of the updated
-        # parameters and the flat fp32 gradient: for those buckets a rank keeps only its 1/world slice of the parameters
-        # (`own`, bf16) and of the reduced gradient (`gshard`, fp32); the full gradient of ONE unit exists transiently in
-        # one of its pool's two slots (`gslots`) between that unit's weight-gradient GEMMs and its reduce-scatter, as FSDP
-        # frees a unit's full gradient after reduce-scatter (fsdp.py:160-168).
-        self.shard_params = shard_params
-        sh = [b for b in lay.buckets if shard_params and param_sharded_key(b.key)]
-        self.sharded_keys = {b.key for b in sh}
-        self._cut = (sh[0].offset, sh[-1].offset + sh[-1].numel) if sh else (lay.total, lay.total)
-        assert sum(b.numel for b in sh) == self._cut[1] - self._cut[0], "parameter-sharded buckets must be contiguous"
-        self._n_rep = n_rep = lay.total - (self._cut[1] - self._cut[0])
-        self.stage_bf16 = torch.zeros(max(n_rep, 8), dtype=torch.bfloat16, device=dev)
-        self.own_off, n_own = {}, 0
-        # gradient slots: per pool two transient fp32 buffers sized for the pool's largest bucket; a bucket uses slot
-        # (its index in the pool's forward order) % 2 — for the decoder layers that is layer % 2
-        self.grad_slot_of: Dict[str, Tuple[str, int]] = {}
-        self._slot_numel: Dict[str, int] = {}
-        seen: Dict[str, int] = {}
-        for b in sh:
-            self.own_off[b.key] = n_own
-            n_own += lay.shard_numel(b)
-            pool = pool_of(b.key)
-            self.grad_slot_of[b.key] = (pool, seen.get(pool, 0) % 2)
-            seen[pool] = seen.get(pool, 0) + 1
-            self._slot_numel[pool] = max(self._slot_numel.get(pool, 0), b.numel)
-        self._n_own = n_own
-        self.own = torch.zeros(max(n_own, 8), dtype=torch.bfloat16, device=dev) if sh else None
-        self.grad = self.gshard = None
-        self.gslots: Dict[str, List[torch.Tensor]] = {}
-        self.use_grad_slots = True          # TrainStep clears it when no collective runs (world 1): the "slice" is then the whole
-                                            # bucket and the weight-gradient GEMMs write the persistent buffer directly
-        if not defer_grads:                 # TrainStep defers: it first gives the model's own unit allocations back
-            self.alloc_grads()
-        f = lambda: torch.zeros(max(lay.local_total, 8), dtype=torch.float32, device=dev)
-        self.master, self.m, self.v = f(), f(), f()
-        for bi, b in enumerate(lay.buckets):                    # masters ← this rank's slice of the live bf16 weights
-            full = torch.zeros(b.numel, dtype=torch.float32, device=dev)
-            for ui in b.members:
-                u = self.units[ui]
-                sl = full[u.offset - b.offset:u.offset - b.offset + u.numel]
-                if u.group is not None:
-                    sl.view(u.group.n, u.group.k).copy_(_unpack(u.group.packed))
-                else:
-                    sl.copy_(u.dst)
-            lo, hi = lay.shard_range(b)
-            lo_l = lay.local_offset(b)
-            self.master[lo_l:lo_l + hi - lo].copy_(full[lo - b.offset:hi - b.offset])
-            if b.key in self.sharded_keys:
-                self.own_slice(b).copy_(full[lo - b.offset:hi - b.offset])
-            del full
-        self.blocks_per_bucket = 2048
-        self.partial = torch.zeros(self.blocks_per_bucket * max(len(lay.buckets), 1), dtype=torch.float32, device=dev)
-        self.norm_coef = torch.zeros(2, dtype=torch.float32, device=dev)     # [total norm, clip coefficient]
-        self.step_count = 0
-
-    def alloc_grads(self) -> None:
-        """The fp32 gradient buffers: flat for the replicated buckets; this rank's slices + two transient slots per pool
-        for the parameter-sharded ones."""
-        if self.grad is not None:
-            return
-        dev = self.w.embed.device
-        self.grad = torch.zeros(max(self._n_rep, 8), dtype=torch.float32, device=dev)
-        if self.sharded_keys:
-            self.gshard = torch.zeros(max(self._n_own, 8), dtype=torch.float32, device=dev)
-            if self.use_grad_slots:
-                self.gslots = {pool: [torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(2)]
-                               for pool, n in self._slot_numel.items()}
-
-    # ---- views ----
-    def _replicated(self, buf: torch.Tensor, offset: int, numel: int) -> torch.Tensor:
-        """View of flat range [offset, offset + numel) in a buffer that skips the parameter-sharded range."""
-        lo, hi = self._cut
-        assert offset + numel <= lo or offset >= hi, "parameter-sharded buckets have no replicated copy"
-        o = offset if offset < lo else offset - (hi - lo)
-        return buf[o:o + numel]
-
-    def stage_view(self, offset: int, numel: int) -> torch.Tensor:
-        """bf16 staging view of flat range [offset, offset + numel) (never inside the parameter-sharded range)."""
-        return self._replicated(self.stage_bf16, offset, numel)
-
-    def grad_range(self, offset: int, numel: int) -> torch.Tensor:
-        """fp32 gradient of flat range [offset, offset + numel) of the replicated buckets."""
-        return self._replicated(self.grad, offset, numel)
-
-    def own_slice(self, b) -> torch.Tensor:
-        """This rank's bf16 slice of a parameter-sharded bucket."""
-        o = self.own_off[b.key]
-        return self.own[o:o + self.layout.shard_numel(b)]
-
-    def grad_slot(self, b) -> torch.Tensor:
-        """The transient full-size fp32 gradient of parameter-sharded bucket b (decoder layer l uses slot l % 2 of the
-        layer pool; the vision / head units alternate inside their pools)."""
-        if not self.use_grad_slots:          # one rank, no collective: the rank's slice of the reduced gradient is the bucket itself
-            assert self.layout.world == 1
-            return self.reduced_grad(b)
-        pool, parity = self.grad_slot_of[b.key]
-        return self.gslots[pool][parity][:b.numel]
-
-    def reduced_grad(self, b) -> torch.Tensor:
-        """This rank's slice of bucket b's gradient once reduced: what the norm and AdamW read."""
-        if b.key in self.sharded_keys:
-            o = self.own_off[b.key]
-            return self.gshard[o:o + self.layout.shard_numel(b)]
-        lo, hi = self.layout.shard_range(b)
-        return self.grad_range(lo, hi - lo)
-
-    def _unit_grad(self, u: Unit) -> torch.Tensor:
-        b = self.layout.buckets[u.bucket]
-        if b.key in self.sharded_keys:
-            return self.grad_slot(b)[u.offset - b.offset:u.offset - b.offset + u.numel]
-        return self.grad_range(u.offset, u.numel)
-
-    def grad_view(self, name_or_unit) -> torch.Tensor:
-        """fp32 gradient of a unit: [n, k] for a group, flat for a plain tensor (for a parameter-sharded unit: the
-        transient slot its weight-gradient GEMMs write — valid until the slot's next unit overwrites it)."""
-        u = name_or_unit if isinstance(name_or_unit, Unit) else self.by_name[name_or_unit]
-        sl = self._unit_grad(u)
-        return sl.view(u.group.n, u.group.k) if u.group is not None else sl
-
-    def _named(self, flat: Optional[torch.Tensor], name: str, unit_slice: Optional[torch.Tensor] = None) -> torch.Tensor:
-        u = self.by_name[name]
-        sl = unit_slice if unit_slice is not None else flat[u.offset:u.offset + u.numel]
-        if name not in self.w.placements:                       # extra unit: flat
-            return sl
-        pl = self.w.placements[name]
-        shape = self.w._specs()[name].shape
-        if u.group is None:
-            return sl.view(shape)
-        return _block_view(sl, pl).reshape(shape)
-
-    def named_grad(self, name: str) -> torch.Tensor:
-        """Gradient under its HF name / shape (a copy for grouped tensors): the local, un-reduced gradient of a replicated
-        bucket. Parameter-sharded units have no such thing once collectives run — their full gradient lives in a transient
-        slot that the flush reduce-scatters in place and later units overwrite — so this raises for them; without
-        collectives (one rank) the rank's "slice" is the whole bucket and the call is valid."""
-        u = self.by_name[name]
-        if self.layout.buckets[u.bucket].key in self.sharded_keys and self.use_grad_slots:
-            raise RuntimeError(f"{name}: the full gradient of a parameter-sharded unit is transient (reduce-scattered in its slot, "
-                               "overwritten two units later); read store.reduced_grad(bucket) — this rank's reduced slice — instead")
-        return self._named(None, name, self._unit_grad(u))
-
-    def full_master(self, comm: Optional[ShardComm] = None) -> torch.Tensor:
-        """All fp32 masters in the flat layout (gathered over ranks when sharded) — checkpoints and tests."""
-        return (comm or ShardComm(self.layout)).gather_full(self.master)
-
-    def named_master(self, name: str, full: Optional[torch.Tensor] = None) -> torch.Tensor:
-        return self._named(self.full_master() if full is None else full, name)
-
-    def master_state_dict(self, comm: Optional[ShardComm] = None) -> Dict[str, torch.Tensor]:
-        full = self.full_master(comm)
-        return {n: self._named(full, n).clone() for n in self.by_name}
-
-    def trainable(self, name: str) -> bool:
-        return name in self.by_name
-
-    def unit_of_packed(self, packed: torch.Tensor) -> Optional[Unit]:
-        for u in self.units:
-            if u.group is not None and u.group.packed.data_ptr() == packed.data_ptr():
-                return u
-        return None
-
-
-def transposed_pack(packed: torch.Tensor, n: int, k: int, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Packed [n, k] weight → packed [k, n] (the dgrad operand)."""
-    rm = _unpack(packed).contiguous()
-    t = torch.empty(k, n, dtype=torch.bfloat16, device=packed.device)
-    T.transpose_pad(rm, t, n)
-    return ops.pack_weight(t)
 
 
 class TrainStep:
@@ -448,7 +127,6 @@ class TrainStep:
         if fp8_wgrad and not fp8:
             raise ValueError("fp8_wgrad extends fp8=True (e4m3 forward / dgrad) to the weight-gradient GEMMs")
         self.fp8, self.fp8_wgrad = fp8, fp8_wgrad
-        self.fp8_wgrad_gemms = [0, 0]          # planned weight-gradient GEMMs [on the e4m3 path, fallen back to bf16]
         self.recompute, self.shard_params = recompute, shard_params
         self.lora = lora
         self.train_vision = STAGES[stage][0] or lora is not None      # towers need their training-form forward
@@ -475,25 +153,22 @@ class TrainStep:
         self.world = st.layout.world
         dev = weights.embed.device
         self.device = dev
-        self._wT: Dict[int, torch.Tensor] = {}       # transposed packed weights for dgrad
-        self._w8: Dict[int, Tuple[Fp8Weight, Fp8Weight]] = {}   # packed bf16 weight (data_ptr) → its e4m3 (forward, dgrad) copies
-        self._cur_unit: Optional[str] = None   # unit (bucket key) whose ops are being planned (slot views are shared by a pool's units)
-        self._units: Dict[str, dict] = {}      # parameter-sharded units (see _setup_unit_pools)
-        self._params_updated = torch.cuda.Event()      # end of the last optimizer_step: parameter gathers wait for it
-        self._materialized = False
+        self._wide: Dict[int, torch.Tensor] = {}
+        self.lin = Linears(weights, st, lora, batch, batch * self.S, self._wide, fp8=fp8, fp8_wgrad=fp8_wgrad, shard_params=shard_params)
+        self.fp8_wgrad_gemms = self.lin.fp8_wgrad_gemms
+        self.pools: Optional[UnitPools] = None
         if shard_params:                       # first: the model's unit allocations are given back before anything else is reserved
-            self._setup_unit_pools()
+            self.pools = self.lin.pools = UnitPools(weights, st, self.comm, self.lin, recompute, fp8)
         if st.grad is None:
             st.use_grad_slots = self.comm.active
         st.alloc_grads()
         B, S, D, I, V, NL = batch, self.S, d.llm_dim, d.llm_inter, d.vocab, d.llm_layers
         Tn = B * S
-        self.T, self.Tp = Tn, (Tn + 63) // 64 * 64
+        self.T = Tn
         z = lambda *shape, dtype=torch.bfloat16: torch.zeros(*shape, dtype=dtype, device=dev)
         # LoRA K-concatenation: the input x of an adapted linear and the gradient dy of its output live in buffers that
         # are R columns wider than the tensor; t = x·Aᵀ / dt = dy·(sB) land in those columns, so y = [x | t]·[W | sB]ᵀ
         # and dx = [dy | dt]·[Wᵀ | Aᵀ]ᵀ are single GEMMs over K + R (no separate rank-R update pass over y / dx).
-        self._wide: Dict[int, torch.Tensor] = {}
         R_ = lambda packed: (lora.get(packed).R if (lora is not None and lora.get(packed) is not None) else 0)
 
         def za(rows: int, cols: int, extra: int) -> torch.Tensor:
@@ -513,7 +188,7 @@ class TrainStep:
         #      prompt_len 1, no decode) ----
         from ..engine import OpenVLAEngine
         self._vis = OpenVLAEngine(weights, batch, 1, n_new=1, vision_only=True)
-        if any(info["pool"] == "vision" for info in self._units.values()):
+        if self.pools is not None and "vision" in self.pools.slots:
             self._vis.dino_ops = self._vis.siglip_ops = self._vis.vision_ops = []      # the towers' weights live in gather slots
         self.pixel_values = self._vis.pixel_values
         self.feats = self._vis.feats if lora is None else za(B * 256, d.vision_dim, R_(weights.fc1_w))
@@ -570,31 +245,19 @@ class TrainStep:
         self.dqkv, self.dgu, self.dact = za(Tn, 3 * D, R_(L0.qkv_w)), za(Tn, 2 * I, R_(L0.gu_w)), z(Tn, I)
         self.dp3, self.dz2, self.dz1 = za(B * 256, D, R_(weights.fc3_w)), za(B * 256, D, R_(weights.fc2_w)), za(B * 256, Pv, R_(weights.fc1_w))
         self.dp2, self.dp1 = z(B * 256, D), z(B * 256, Pv)
-        nmax = max(V, 3 * D, 2 * I, Pv)
-        self.tA, self.tB, self.tBp = z(nmax * self.Tp), z(nmax * self.Tp), z(nmax * self.Tp)
         towers = (weights.dino, weights.siglip) if self.train_vision else ()
         mv = max((B * tw.dims.tokens for tw in towers), default=0)
         dv_ = max((tw.dims.dim for tw in towers), default=0)
-        self.norm_ws = z(max(((Tn + 15) // 16) * D, 2 * ((mv + 15) // 16) * dv_), dtype=torch.float32)
-        self.col_ws = z(max(((Tn + 31) // 32) * max(Pv, D), 256 * dv_, ((mv + 15) // 16) * dv_ * 4), dtype=torch.float32)
+        norm_ws = z(max(((Tn + 15) // 16) * D, 2 * ((mv + 15) // 16) * dv_), dtype=torch.float32)
+        col_ws = z(max(((Tn + 31) // 32) * max(Pv, D), 256 * dv_, ((mv + 15) // 16) * dv_ * 4), dtype=torch.float32)
         self._frozen_dw = z(2 * max(D, Pv, dv_), dtype=torch.float32)         # sink for vector grads of frozen tensors
-        self._lora_t: Dict[int, torch.Tensor] = {}                            # saved t = x·Aᵀ per adapted linear
-        self._Wext: Dict[int, torch.Tensor] = {}                              # packed [W | s·B]   per adapted linear
-        self._WText: Dict[int, torch.Tensor] = {}                             # packed [Wᵀ | Aᵀ]
-        self._BsT: Dict[int, torch.Tensor] = {}                               # packed (s·B)ᵀ: the dt = dy·(sB) operand
-        self._adapter_ops: List[Op] = []                                      # refresh of the adapter parts (repack plan)
         self.dfeats = z(B * 256, d.vision_dim) if self.train_vision else None
         self.vis = [self._alloc_tower(tw) for tw in towers]
-        # ---- transposed weights for dgrad ----
-        self.ws = torch.empty(64 << 20, dtype=torch.uint8, device=dev)
-        if fp8:
-            self._setup_fp8()
-        if lora is not None:
-            self._build_extended_weights()
-            if refresh_adapted:                 # after the adapter refresh in the re-pack plan: reads the written-back A / B
-                plan = lora.refresh_ops()       # the merge launch; after lora.enable_fp8() also the e4m3 requantisation
-                self._adapter_ops = self._adapter_ops + plan
-                ops.run_all(plan)
+        # ---- the scratch ops bind at plan time; the linears' own buffers and weight layouts ----
+        main = ScratchSet(torch.empty(64 << 20, dtype=torch.uint8, device=dev), col_ws, norm_ws,
+                          z(8 << 20, dtype=torch.float32) if lora is not None else None)
+        self.scratch = Scratch(main, main)
+        self.lin.allocate(max(V, 3 * D, 2 * I, Pv) * ((Tn + 63) // 64 * 64), fp8, refresh_adapted)
         # execution order of the vision units (forward; the backward visits each tower's blocks top down, then its stem)
         vkey = lambda tw, i: f"vision.{tw.dims.prefix.split('.')[1]}." + ("stem" if i < 0 else f"block{i:02d}")
         self._vkey = vkey
@@ -611,484 +274,71 @@ class TrainStep:
                       and (lora is None or lora.dropout == 0.0)      # the dropout buffers serve one adapted linear at a time
                       and os.environ.get("BL_TRAIN_VISION_STREAMS", "1") != "0")
         self._vis_stream = torch.cuda.Stream(device=dev) if self._vis2 else None
-        self._scratch2 = (dict(ws=torch.empty_like(self.ws), col_ws=torch.empty_like(self.col_ws), norm_ws=torch.empty_like(self.norm_ws))
-                          if self._vis2 else None)
+        if self._vis2:
+            self.scratch.side = main.like()
         self.vision_forward_ops: List[Op] = []
         self._vfwd_tower: List[List[Op]] = []
         for ti, (tw, sv, col) in enumerate(zip(towers, self.vis, (0, d.dino.dim))):
-            with self._side_scratch(ti == 1):
-                self._vfwd_tower.append(self._plan_tower_forward(tw, col, sv))
+            self._vfwd_tower.append(self._plan_tower_forward(tw, col, sv, self.scratch.side if ti else main))
             self.vision_forward_ops += self._vfwd_tower[-1]
         self.forward_ops = self._plan_forward()
-        self.tn_ws = z(8 << 20, dtype=torch.float32) if lora is not None else None
-        if self._vis2 and self.tn_ws is not None:
-            self._scratch2["tn_ws"] = torch.empty_like(self.tn_ws)
         self._ready: List[Tuple[int, str]] = []      # (number of backward ops enqueued, bucket key complete at that point)
         self.backward_ops = self._plan_backward()
         self.repack_ops = self._plan_repack()
         self._graphs: Dict[str, torch.cuda.CUDAGraph] = {}
         self._comm_stream = torch.cuda.Stream(device=dev) if (self.comm.active or shard_params) else None
-        self._rs_scratch = (z(max(st._slot_numel.values())) if shard_params and self.comm.active
-                            and reduce_dtype != torch.float32 else None)        # bf16 wire copy of one unit's gradients
-
-    # ---- helpers ------------------------------------------------------------------------------------------------
-    # ---- fp8 (e4m3) forward / dgrad GEMMs of the decoder layers ------------------------------------------------------
-    def _setup_fp8(self) -> None:
-        d, dev, Tn = self.dims, self.device, self.T
-        D, I = d.llm_dim, d.llm_inter
-        u8 = lambda *shape: torch.zeros(*shape, dtype=torch.uint8, device=dev)
-        self._q8 = {D: u8(Tn, D), I: u8(Tn, I)}                          # quantised GEMM inputs (one linear at a time)
-        self._q8_dy = u8(Tn, max(3 * D, 2 * I))                          # quantised output gradients
-        self._sx, self._sdy = (torch.zeros(Tn, dtype=torch.float32, device=dev) for _ in range(2))
-        if self.fp8_wgrad:                     # token-contiguous (transposed) operands of the e4m3 weight-gradient GEMM
-            Tq = (Tn + 127) // 128 * 128       # its contraction length: tokens, padded with zero columns to the MFMA's K = 128
-            nmx = max(3 * D, 2 * I)
-            self._Tq = Tq
-            self._wg_qA = u8(nmx * Tq)                                                 # dyᵀ codes [N, Tq] row-major
-            self._wg_pB = u8(I * Tq)                                                   # xᵀ codes [K, Tq] in the fragment-major packing
-            self._wg_sA = torch.zeros(nmx, dtype=torch.float32, device=dev)
-            self._wg_sB = torch.zeros(I, dtype=torch.float32, device=dev)
-            self._wg_amax = torch.zeros(nmx + I, dtype=torch.float32, device=dev)      # column |max| of dy (first N) and x (next K)
-        self._fp8_scratch()
-        if self.shard_params:                  # sharded layers are quantised in their gather (slots carry the e4m3 copies)
-            return
-        for _, _, gi, _ in self.w.unit_fields("layers"):
-            g = self.w.groups[gi]
-            self._w8[g.packed.data_ptr()] = e = self._fp8_entry(g.n, g.k, dev)
-            rm = ops.unpack_weight(g.packed).contiguous()                # start-up only; later the optimizer's bf16 copy
-            ops.run_all(self._fp8_weight_ops(rm, e))
-            del rm
-
-    def _fp8_scratch(self) -> None:
-        if not hasattr(self, "_q_tmp"):
-            D, I = self.dims.llm_dim, self.dims.llm_inter
-            nmax = max(3 * D * D, 2 * I * D)
-            self._q_tmp = torch.zeros(nmax, dtype=torch.uint8, device=self.device)
-            self._t_tmp = torch.zeros(nmax, dtype=torch.bfloat16, device=self.device)
-
-    @staticmethod
-    def _fp8_entry(n: int, k: int, dev) -> Tuple[Fp8Weight, Fp8Weight]:
-        """(forward copy: scale per output channel n, transposed copy for dgrad: scale per input channel k) of a weight [n, k]."""
-        one = lambda r, c: Fp8Weight(torch.zeros(r // 16, c // 64, 64, 8, dtype=torch.bfloat16, device=dev),
-                                     torch.zeros(r, dtype=torch.float32, device=dev))
-        return one(n, k), one(k, n)
-
-    def _fp8_weight_ops(self, rm: torch.Tensor, e: Tuple[Fp8Weight, Fp8Weight]) -> List[Op]:
-        """Logical bf16 weight [n, k] → e4m3 forward copy (scale per output channel n) and e4m3 transposed copy for dgrad
-        (scale per input channel k), both in the fragment-major packing bl_gemm_fp8 reads."""
-        n, k = rm.shape
-        q = self._q_tmp[:n * k].view(n, k)
-        qT = self._q_tmp[:n * k].view(k, n)
-        t = self._t_tmp[:n * k].view(k, n)
-        as_pairs = lambda c: c.view(torch.bfloat16)                    # e4m3 codes as 2-byte units: [r, c] → [r, c / 2]
-        fwd, bwd = e
-        return [ops.quantize_rows_fp8(rm, q, fwd.scale, run=False)[2], T.pack(as_pairs(q), fwd.w8, run=False),
-                T.transpose_pad(rm, t, n, run=False), ops.quantize_rows_fp8(t, qT, bwd.scale, run=False)[2],
-                T.pack(as_pairs(qT), bwd.w8, run=False)]
-
-    # ---- parameter sharding (FSDP FULL_SHARD): decoder layers ("layers" pool), ViT blocks + patch embeddings ("vision"),
-    #      projector / token embeddings / lm_head ("head") ----
-    def _setup_unit_pools(self) -> None:
-        """One machinery for every FSDP unit of the reference (prismatic.py:285-306, dinosiglip_vit.py:136-140,
-        fsdp.py:160-168): per pool TWO gather slots — the logical bf16 bucket + one buffer of forward layouts + one of dgrad
-        layouts, each sized for the pool's largest unit and carved into per-unit views — the model's tensors are re-pointed
-        at the views of slot (unit index % 2; decoder layer l: l % 2) and the pool's own allocation is freed. A unit is
-        all-gathered (and packed) into its slot one unit ahead of its use, on the communication stream; its weight gradients
-        go to one of two transient fp32 slots of the pool and are reduce-scattered into the rank's persistent slice right
-        after the unit's last weight-gradient GEMM. The token embeddings are a plain [vocab, D] tensor: read in place from the
-        gathered bucket. Under `fp8` a decoder layer's gather quantises instead of packing: the slot carries the e4m3
-        forward / dgrad copies (+ scales, `_w8`) and no bf16 dgrad layouts."""
-        w, st, lay, dev = self.w, self.store, self.store.layout, self.device
-        by_group = {id(u.group): u for u in st.units if u.group is not None}
-        by_key = {b.key: b for b in lay.buckets}
-        self._pool_slots: Dict[str, List[dict]] = {}
-        if self.fp8:
-            self._fp8_scratch()
-        for pool in ("layers", "vision", "head"):
-            fields = w.unit_fields(pool)                                   # (unit key, path, group index | None, HF name | None)
-            keys = list(dict.fromkeys(k for k, *_ in fields))
-            live = [k for k in keys if k in st.sharded_keys]
-            if not live:
-                continue
-            if len(live) != len(keys):
-                raise ValueError(f"parameter sharding needs every unit of the {pool} pool trainable or none "
-                                 f"({sorted(set(keys) - set(live))} frozen; the decoder layers: vla-full-train / vla-train)")
-            fp8 = self.fp8 and pool == "layers"
-            numel = lambda k: sum(w.groups[gi].n * w.groups[gi].k for kk, _, gi, _ in fields if kk == k and gi is not None)
-            flat_max, pk_max = max(by_key[k].numel for k in keys), max(max(numel(k) for k in keys), 8)
-            slots = [dict(flat=torch.zeros(flat_max, dtype=torch.bfloat16, device=dev),
-                          fwd=torch.zeros(pk_max, dtype=torch.bfloat16, device=dev),
-                          bwd=None if fp8 else torch.zeros(pk_max, dtype=torch.bfloat16, device=dev),
-                          ready=torch.cuda.Event(), free=torch.cuda.Event(), grads_flushed=torch.cuda.Event()) for _ in range(2)]
-            self._pool_slots[pool] = slots
-            views: Dict[tuple, torch.Tensor] = {}
-            for k in keys:
-                b = by_key[k]
-                parity = st.grad_slot_of[k][1]
-                slot, off = slots[parity], 0
-                info = dict(pool=pool, parity=parity, bucket=b, by_ptr={}, T={}, fwd_ops=[], bwd_ops=[], plain=[])
-                for kk, path, gi, name in fields:
-                    if kk != k:
-                        continue
-                    if gi is not None:
-                        u = by_group[id(w.groups[gi])]
-                        n, kd = u.group.n, u.group.k
-                        fv = slot["fwd"][off:off + n * kd].view(n // 16, kd // 32, 64, 8)
-                        rm = slot["flat"][u.offset - b.offset:u.offset - b.offset + u.numel].view(n, kd)
-                        if fp8:                                            # the units of one parity share the slot's e4m3 copies
-                            if fv.data_ptr() not in self._w8:
-                                self._w8[fv.data_ptr()] = self._fp8_entry(n, kd, dev)
-                            q = self._fp8_weight_ops(rm, self._w8[fv.data_ptr()])
-                            info["fwd_ops"] += q[:2]
-                            info["bwd_ops"] += q[2:]
-                        else:
-                            tv = slot["bwd"][off:off + n * kd].view(kd // 16, n // 32, 64, 8)
-                            info["fwd_ops"].append(T.pack(rm, fv, run=False))
-                            info["bwd_ops"].append(T.transpose_pack(rm, tv, n, run=False))
-                            info["T"][fv.data_ptr()] = tv
-                        off += n * kd
-                        info["by_ptr"][fv.data_ptr()] = u
-                        views[(k, path)] = fv
-                    else:                                                  # token embeddings: used where the gather lands them
-                        u = st.by_name[name]
-                        obj, attr = w._attr_of(path)
-                        views[(k, path)] = slot["flat"][u.offset - b.offset:u.offset - b.offset + u.numel].view(getattr(obj, attr).shape)
-                        info["plain"].append((path, u))
-                        u.dst = None                                       # the optimizer writes the rank's slice, nothing is copied back
-                if self.recompute and pool == "layers":                    # the backward pass replays the layer's forward
-                    info["bwd_ops"] = info["bwd_ops"] + info["fwd_ops"]
-                self._units[k] = info
-            if w.pool_resident(pool):
-                w.release_unit_weights(pool, views)
-            else:                                  # re-planned step over an already sharded model
-                w.repoint_unit_weights(pool, views)
-
-    def _u_slot(self, key: str) -> dict:
-        info = self._units[key]
-        return self._pool_slots[info["pool"]][info["parity"]]
-
-    def _u_gather(self, key: str, backward: bool = False, both: bool = False) -> Op:
-        """Issue unit `key`'s parameter gather + packing (forward layouts, dgrad layouts, or both) on the communication stream."""
-        def fn():
-            info, slot, side = self._units[key], self._u_slot(key), self._comm_stream
-            side.wait_event(self._params_updated)             # AdamW (main stream) has written the rank's slice
-            side.wait_event(slot["free"])                     # the unit that used this slot before is done with it
-            with torch.cuda.stream(side):
-                b = info["bucket"]
-                self.comm.all_gather_into(slot["flat"][:b.numel], self.store.own_slice(b))
-                if both or not backward:
-                    ops.run_all(info["fwd_ops"])
-                if both or backward:
-                    ops.run_all(info["bwd_ops"])
-                slot["ready"].record(side)
-        return ops.glue("gather_unit_params", fn, ())
-
-    def _u_await(self, key: str) -> Op:
-        return ops.glue("await_unit_params", lambda: torch.cuda.current_stream().wait_event(self._u_slot(key)["ready"]), ())
-
-    def _u_release(self, key: str) -> Op:
-        return ops.glue("release_unit_params", lambda: self._u_slot(key)["free"].record(torch.cuda.current_stream()), ())
-
-    def _u_await_grad(self, key: str) -> Op:
-        return ops.glue("await_unit_grad_slot", lambda: torch.cuda.current_stream().wait_event(self._u_slot(key)["grads_flushed"]), ())
-
-    def _u_flush(self, key: str) -> Op:
-        """After the unit's last weight gradient: reduce-scatter its transient fp32 slot, keep this rank's slice."""
-        def fn():
-            st, lay, side = self.store, self.store.layout, self._comm_stream
-            if not st.use_grad_slots:
-                return
-            b = self._units[key]["bucket"]
-            gs = st.grad_slot(b)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                scratch = self._rs_scratch[:b.numel] if self._rs_scratch is not None else None
-                self.comm.reduce_scatter_bucket(gs, b, scratch)
-                n = lay.shard_numel(b)
-                T.copy_f32(gs[lay.rank * n:(lay.rank + 1) * n], st.reduced_grad(b))
-                self._u_slot(key)["grads_flushed"].record(side)
-        return ops.glue("flush_unit_grads", fn, ())
-
-    def _u_seq(self, seq: List[str], j: int, backward: bool, body: List[Op], gather: bool = True, flush: bool = True) -> List[Op]:
-        """Ops of unit seq[j] wrapped in its parameter / gradient-slot protocol: wait for its gather, start the next unit's
-        gather (after this unit's release when both share a slot), and in the backward pass wait for the gradient slot and
-        flush it afterwards. Units that are not parameter-sharded pass through."""
-        key = seq[j]
-        if key not in self._units:
-            return body
-        nxt = seq[j + 1] if j + 1 < len(seq) and seq[j + 1] in self._units else None
-        same = nxt is not None and self._u_slot(nxt) is self._u_slot(key)
-        pre: List[Op] = []
-        if j == 0 and gather:
-            pre.append(self._u_gather(key, backward))
-        pre.append(self._u_await(key))
-        if nxt is not None and not same:
-            pre.append(self._u_gather(nxt, backward))
-        if backward:
-            pre.append(self._u_await_grad(key))
-        post = [self._u_release(key)]
-        if backward and flush:
-            post.append(self._u_flush(key))
-        if nxt is not None and same:
-            post.append(self._u_gather(nxt, backward))
-        return pre + body + post
-
-    def _unit_of(self, packed: torch.Tensor) -> Optional[Unit]:
-        if self._cur_unit is not None and packed.data_ptr() in self._units[self._cur_unit]["by_ptr"]:
-            return self._units[self._cur_unit]["by_ptr"][packed.data_ptr()]     # slot views are shared by the units of a pool
-        return self.store.unit_of_packed(packed)
+        if self.pools is not None:
+            self.pools.start(self._comm_stream, reduce_dtype)
 
     def materialize_params(self) -> None:
-        """Bring every parameter-sharded unit back into the model's own allocation (gather each unit, pack) — for inference,
-        `state_dict()` / `save_pretrained` after parameter-sharded training. The step's plans address the slots, so this
+        """Bring every parameter-sharded unit back into the model's own allocation (UnitPools.materialize_params); this
         step object cannot train afterwards."""
-        if not self.shard_params or self._materialized:
-            return
-        w, st = self.w, self.store
-        by_group = {id(u.group): u for u in st.units if u.group is not None}
-        for pool, slots in self._pool_slots.items():
-            w.restore_unit_weights(pool)
-            cur = None
-            for key, path, gi, name in w.unit_fields(pool):
-                info = self._units[key]
-                b, slot = info["bucket"], slots[info["parity"]]
-                if key != cur:
-                    torch.cuda.synchronize()                # a slot is re-used by the next unit of its parity
-                    self.comm.all_gather_into(slot["flat"][:b.numel], st.own_slice(b))
-                    cur = key
-                obj, attr = w._attr_of(path)
-                u = by_group[id(w.groups[gi])] if gi is not None else st.by_name[name]
-                rm = slot["flat"][u.offset - b.offset:u.offset - b.offset + u.numel]
-                if gi is not None:
-                    T.pack(rm.view(u.group.n, u.group.k), getattr(obj, attr))
-                else:
-                    getattr(obj, attr).view(-1).copy_(rm)
-        torch.cuda.synchronize()
-        self._materialized = True
+        if self.pools is not None:
+            self.pools.materialize_params()
 
-    def _g(self, *a, **k) -> Op:
-        """Prepared GEMM with the split-K scratch: training has no batch-slot invariance to keep (engine.py keeps it
-        off for inference), so ragged last rounds of K >= 8192 GEMMs are split along K."""
-        return ops.gemm(*a, workspace=self.ws, run=False, **k)
+    def _planning(self, key: str):
+        """Around the backward ops of unit `key`: a parameter-sharded unit's slot views are looked up under its name."""
+        return self.pools.planning(key) if self.pools is not None and key in self.pools.units else contextlib.nullcontext()
 
-    def wT(self, packed: torch.Tensor) -> torch.Tensor:
-        """[K, N]-packed transposed copy of a packed [N, K] weight (built on first use, refreshed by repack)."""
-        key = packed.data_ptr()
-        if self._cur_unit is not None and key in self._units[self._cur_unit]["T"]:
-            return self._units[self._cur_unit]["T"][key]
-        assert not any(key in info["T"] for info in self._units.values()), "slot weights are addressed while their unit is planned"
-        if key not in self._wT:
-            n, k = packed.shape[0] * 16, packed.shape[1] * 32
-            self._wT[key] = transposed_pack(packed, n, k)
-        return self._wT[key]
-
-    def _dgrad(self, dy: torch.Tensor, packed: torch.Tensor, out: torch.Tensor, epilogue: int = EPI_NONE, **kw) -> Op:
-        return self._g(dy, self.wT(packed), out, epilogue, **kw)
-
-    def _wgrad_into(self, dy: torch.Tensor, x: torch.Tensor, gview: torch.Tensor, fp8: bool = False) -> List[Op]:
-        """gview[N, K] (fp32) = dyᵀ[N, T] · x[T, K]: the TN GEMM reads dy and x where they lie (transposing LDS reads);
-        shapes with N % 8 or K % 8 take the round-1 form — the NT GEMM over token-padded transposed copies.
-        fp8=True: the e4m3 form (TrainStep(fp8_wgrad=True)) — transpose, quantise per channel, NT GEMM on bl_gemm_fp8."""
-        Tn, N = dy.shape
-        K = x.shape[1]
-        assert tuple(gview.shape) == (N, K), (dy.shape, x.shape, gview.shape)
-        if fp8:
-            Tq = self._Tq
-            qA = self._wg_qA[:N * Tq].view(N, Tq)
-            pB = self._wg_pB[:K * Tq].view(torch.bfloat16).view(K // 16, Tq // 64, 64, 8)
-            sA, sB = self._wg_sA[:N], self._wg_sB[:K]
-            # two passes per operand: column |max| (2 B read), then one transposing quantise(-and-pack) (2 B read, 1 B written)
-            am = self._wg_amax[:N + K]
-            return [T.fill_zero(am, run=False), T.colamax(dy, am[:N], run=False), T.colamax(x, am[N:], run=False),
-                    T.transpose_quantize_fp8(dy, am[:N], self._wg_qA[:N * Tq], sA, Tq, False, run=False),
-                    T.transpose_quantize_fp8(x, am[N:], self._wg_pB[:K * Tq], sB, Tq, True, run=False),
-                    ops.gemm_fp8(qA, sA, pB, sB, gview, EPI_F32, run=False)]
-        if N % 8 == 0 and K % 8 == 0:
-            return [T.gemm_tn(dy, x, gview, workspace=self.ws, run=False)]
-        Tp = (Tn + 63) // 64 * 64
-        assert max(N, K) * Tp <= self.tA.numel()
-        tA = self.tA[:N * Tp].view(N, Tp)
-        tB = self.tB[:K * Tp].view(K, Tp)
-        tBp = self.tBp[:K * Tp].view(K // 16, Tp // 32, 64, 8)
-        if K % 64 == 0:                        # one pass: transpose straight into the packed operand layout
-            prep = [T.transpose_pack(x, tBp, Tp, run=False)]
-        else:
-            prep = [T.transpose_pad(x, tB, Tp, run=False), T.pack(tB, tBp, run=False)]
-        return [T.transpose_pad(dy, tA, Tp, run=False)] + prep + [self._g(tA, tBp, gview, EPI_F32, algo_nk=(K, Tn))]
-
-    def _wgrad(self, dy: torch.Tensor, x: torch.Tensor, packed: torch.Tensor) -> List[Op]:
-        """Weight gradient of a base linear; [] when the weight is frozen."""
-        u = self._unit_of(packed)
-        if u is None:
-            return []
-        want = self.fp8_wgrad and packed.data_ptr() in self._w8
-        fp8 = want and dy.shape[1] % 16 == 0 and x.shape[1] % 16 == 0
-        if want:                               # how many weight-gradient GEMMs really run on the e4m3 path (bench.py reports it)
-            self.fp8_wgrad_gemms[0 if fp8 else 1] += 1
-            if not fp8 and self.fp8_wgrad_gemms[1] == 1:
-                import warnings
-                warnings.warn(f"fp8_wgrad: a weight gradient of shape [{dy.shape[1]}, {x.shape[1]}] is not a multiple of 16 in both "
-                              "dimensions and stays on the bf16 TN GEMM")
-        return self._wgrad_into(dy, x, self.store.grad_view(u), fp8=fp8)
-
-    def _build_extended_weights(self) -> None:
-        """LoRA: K-concatenated packed weights [W | s·B] (forward) and [Wᵀ | Aᵀ] (dgrad) per adapted linear. The frozen
-        part is copied once; the adapter columns are (re)written by `_adapter_ops` after every optimizer step."""
-        lora, s = self.lora, self.lora.scaling
-        dev = self.device
-        zb = lambda *shape: torch.zeros(*shape, dtype=torch.bfloat16, device=dev)
-        entries = []
-        self._ATp: Dict[int, torch.Tensor] = {}                             # packed Aᵀ [k, R]: the u = dt·A operand (lora_dropout > 0)
-        if lora.dropout > 0.0:
-            rows = max([self.T, self.B * 256] + [self.B * tw.dims.tokens for tw in (self.w.dino, self.w.siglip)])
-            kmax = max(ad.group.k for ad in lora.adapters)
-            self._xd, self._ud = zb(rows, kmax), zb(rows, kmax)            # dropout(x) and u = dt·A of ONE adapted linear at a time
-            self._drop_seed = torch.zeros(1, dtype=torch.int32, device=dev)     # bumped once per forward pass
-        for ad in lora.adapters:
-            packed, n, k, R = ad.group.packed, ad.group.n, ad.group.k, ad.R
-            KT, NT = (k + R) // 32, (n + R) // 32
-            We, WTe = zb(n // 16, KT, 64, 8), zb(k // 16, NT, 64, 8)
-            We.view(n // 16, KT, 512)[:, :k // 32].copy_(packed.view(n // 16, k // 32, 512))
-            WTe.view(k // 16, NT, 512)[:, :n // 32].copy_(transposed_pack(packed, n, k).view(k // 16, n // 32, 512))
-            BsT = zb(R // 16, n // 32, 64, 8)
-            key = packed.data_ptr()
-            self._Wext[key], self._WText[key], self._BsT[key] = We, WTe, BsT
-            # the adapter columns of the extended weights, from the live adapter tensors: [W | s·B], (s·B)ᵀ, A, [Wᵀ | Aᵀ] — table
-            # entries of ONE bl_batched_ops launch for all adapters (rounds 1-3: five launches per adapter, 1 650 per step)
-            entries += [T.be_pack(ad.B, We, KT, k // 32, scale=s), T.be_transpose_pack(ad.B, BsT, n, scale=s),
-                        T.be_pack(ad.A, ad.A_p), T.be_transpose_pack(ad.A, WTe, R, NT, n // 32)]
-            if lora.dropout > 0.0:
-                self._ATp[key] = zb(k // 16, R // 32, 64, 8)
-                entries.append(T.be_transpose_pack(ad.A, self._ATp[key], R))
-        self._adapter_ops = [T.batched(entries, dev, run=False)]
-        ops.run_all(self._adapter_ops)
-
-    def _lin(self, x: torch.Tensor, packed: torch.Tensor, out: torch.Tensor, epilogue: int = EPI_NONE, **kw) -> List[Op]:
-        """Forward of one nn.Linear. With an adapter: t = x·Aᵀ into the spare columns of x's buffer, then ONE GEMM
-        y = [x | t]·[W | s·B]ᵀ over K + R."""
-        ad = self.lora.get(packed) if self.lora is not None else None
-        e8 = self._w8.get(packed.data_ptr())
-        if e8 is not None:                                 # decoder-layer linear on the e4m3 MFMA path
-            return ops.linear_fp8(x, self._q8[x.shape[1]], self._sx, *e8[0], out, epilogue, **kw)
-        if ad is None:
-            return [self._g(x, packed, out, epilogue, **kw)]
-        K, R = x.shape[1], ad.R
-        wide = self._wide[x.data_ptr()]
-        assert wide.shape[1] >= K + R, "input buffer of an adapted linear lacks the adapter columns"
-        t = wide[:, K:K + R]
-        self._lora_t[packed.data_ptr()] = t
-        pre: List[Op] = []
-        xa = x
-        if self.lora.dropout > 0.0:            # PEFT: lora_A(dropout(x)); the base product below still reads the un-masked x
-            xa = self._xd[:x.shape[0], :K]
-            pre = [T.dropout(x, xa, self.lora.dropout, self._drop_seed, ad.index, run=False)]
-        return pre + [self._g(xa, ad.A_p, t, EPI_NONE), self._g(wide[:, :K + R], self._Wext[packed.data_ptr()], out, epilogue, **kw)]
-
-    def _lin_bwd(self, dy: torch.Tensor, x: torch.Tensor, packed: torch.Tensor, dx: Optional[torch.Tensor],
-                 epilogue: int = EPI_NONE, **kw) -> List[Op]:
-        """Backward of one nn.Linear given dy: base wgrad (if trainable) and dx = dy·W (if wanted); with an adapter:
-        dt = dy·(sB) into the spare columns of dy's buffer, dB = (s·tᵀ·dy)ᵀ and dA = dtᵀ·x through the small-output TN
-        GEMM (dy / x read once, untransposed), and dx = [dy | dt]·[Wᵀ | Aᵀ]ᵀ as ONE GEMM."""
-        ad = self.lora.get(packed) if self.lora is not None else None
-        if ad is None:
-            plan = self._wgrad(dy, x, packed)
-            e8 = self._w8.get(packed.data_ptr())
-            if dx is not None and e8 is not None:          # dx = dy · W on the e4m3 path (dy per token row, Wᵀ per input channel)
-                plan += ops.linear_fp8(dy, self._q8_dy[:, :dy.shape[1]], self._sdy, *e8[1], dx, EPI_NONE)
-            elif dx is not None:
-                plan.append(self._dgrad(dy, packed, dx, epilogue, **kw))
-            return plan
-        i, st, s, R, N = ad.index, self.store, self.lora.scaling, ad.R, dy.shape[1]
-        key = packed.data_ptr()
-        wide = self._wide[dy.data_ptr()]
-        assert wide.shape[1] >= N + R, "gradient buffer of an adapted linear lacks the adapter columns"
-        dt = wide[:, N:N + R]
-        t = self._lora_t[key]
-        gB = st.grad_view(f"lora.{i}.B").view(ad.group.n, R)
-        gA = st.grad_view(f"lora.{i}.A").view(R, ad.group.k)
-        plan = [self._g(dy, self._BsT[key], dt, EPI_NONE), T.gemm_tn_small(t, dy, gB, True, self.tn_ws, alpha=s, run=False)]
-        if len(ad.modules) > 1:
-            plan.append(T.lora_block_mask(gB, R // len(ad.modules), len(ad.modules), ad.mode == "interleave", run=False))
-        p = self.lora.dropout
-        xa = x
-        if p > 0.0:                            # the mask of the forward pass, recomputed (same device seed, same salt)
-            xa = self._xd[:x.shape[0], :x.shape[1]]
-            plan.append(T.dropout(x, xa, p, self._drop_seed, ad.index, run=False))
-        plan.append(T.gemm_tn_small(dt, xa, gA, False, self.tn_ws, run=False))
-        if dx is not None:
-            plan.append(self._g(wide[:, :N + R], self._WText[key], dx, epilogue, **kw))
-            if p > 0.0:                        # dx = dy·W + dt·A so far; dropout's backward masks the adapter's share
-                assert epilogue == EPI_NONE, "activation-backward epilogues are not combined with lora_dropout"
-                u = self._ud[:x.shape[0], :x.shape[1]]
-                plan += [self._g(dt, self._ATp[key], u, EPI_NONE), T.dropout_grad_fix(u, dx, p, self._drop_seed, ad.index, run=False)]
-        return plan
-
-    def _lin_act(self, x, packed, pre, act, kind: str, **kw) -> List[Op]:
-        """Linear + activation of the training forward with the PRE-activation kept (autograd's saved tensor): one GEMM
-        whose epilogue writes both (`kind` "swiglu": gate/up interleaved → silu(g)·u; "gelu": bias + exact-erf GELU). The
-        e4m3 path and BL_TRAIN_FUSED_ACT=0 (see above) keep the plain epilogue + an elementwise pass; both forms
-        give the same bits."""
-        fused = not UNFUSED_FWD and self._w8.get(packed.data_ptr()) is None
-        if kind == "swiglu":
-            if fused:
-                return self._lin(x, packed, pre, EPI_SWIGLU_KEEP, out2=act, **kw)
-            return self._lin(x, packed, pre, EPI_NONE, **kw) + [T.swiglu(pre, act, run=False)]
-        if fused:
-            return self._lin(x, packed, pre, EPI_BIAS_GELU_KEEP, out2=act, **kw)
-        return self._lin(x, packed, pre, EPI_BIAS, **kw) + [T.gelu(pre, act, run=False)]
-
-    def _lin_bwd_act(self, dy, x, packed, pre, dpre, dact, kind: str) -> List[Op]:
-        """Backward of `act(pre)` → Linear(packed) given dy of the linear: the input-gradient GEMM's epilogue applies the
-        activation's backward with the saved pre-activation, so d act never travels through HBM (dact is only used by the
-        unfused forms: e4m3 dgrad and BL_TRAIN_FUSED_ACT=0)."""
-        fused = not UNFUSED_BWD and self._w8.get(packed.data_ptr()) is None
-        if self.lora is not None and self.lora.dropout > 0.0 and self.lora.get(packed) is not None:
-            fused = False       # dropout's backward adds the masked adapter share to d act BEFORE the activation's backward
-        if not fused:
-            bwd = T.swiglu_backward(pre, dact, dpre, run=False) if kind == "swiglu" else T.gelu_backward(pre, dact, dpre, run=False)
-            return self._lin_bwd(dy, x, packed, dact) + [bwd]
-        return self._lin_bwd(dy, x, packed, dpre, epilogue=EPI_SWIGLU_BWD if kind == "swiglu" else EPI_GELU_BWD, res=pre)
+    def _seq(self, seq: List[str], j: int, backward: bool, body: List[Op]) -> List[Op]:
+        """Ops of unit seq[j], inside its gather / release / flush protocol when it is parameter-sharded (UnitPools.seq)."""
+        return body if self.pools is None else self.pools.seq(seq, j, backward, body)
 
     def _gvec(self, name: str, n: int) -> torch.Tensor:
         """fp32 gradient slot of a vector parameter, or a scratch sink when it is frozen."""
         return self.store.grad_view(name) if self.store.trainable(name) else self._frozen_dw[:n]
 
-    def _bias_grad(self, dy: torch.Tensor, name: str) -> List[Op]:
+    def _bias_grad(self, sc: ScratchSet, dy: torch.Tensor, name: str) -> List[Op]:
         """Bias gradient = column sums of dy; nothing when the bias is frozen."""
-        return [T.colsum(dy, self.store.grad_view(name), self.col_ws, run=False)] if self.store.trainable(name) else []
+        return [T.colsum(dy, self.store.grad_view(name), sc.col_ws, run=False)] if self.store.trainable(name) else []
 
     # ---- plans --------------------------------------------------------------------------------------------------
     def _plan_forward(self) -> List[Op]:
-        d, w, B, S = self.dims, self.w, self.B, self.S
-        D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
-        g = self._g
+        d, w, B, S, D, sc = self.dims, self.w, self.B, self.S, self.dims.llm_dim, self.scratch.main
         plan: List[Op] = []
-        head = "projector" in self._units          # the head pool is parameter-sharded: projector, token embeddings, lm_head
+        head =self.pools is not None and "projector" in self.pools.units          # the head pool is parameter-sharded: projector, token embeddings, lm_head
         if head:                                   # lm_head keeps its slot (both layouts) from here to its dgrad in the backward pass
-            plan += [self._u_gather("projector"), self._u_gather("llm.lm_head", both=True), self._u_await("projector")]
+            plan += [self.pools.gather("projector"), self.pools.gather("llm.lm_head", both=True), self.pools.await_("projector")]
         # projector with the pre-activations kept (modeling_prismatic.py:151-156)
-        lin = self._lin
-        plan += self._lin_act(self.feats, w.fc1_w, self.z1, self.p1, "gelu", bias=w.fc1_b)
-        plan += self._lin_act(self.p1, w.fc2_w, self.z2, self.p2, "gelu", bias=w.fc2_b)
-        plan += lin(self.p2, w.fc3_w, self.p3, EPI_BIAS, bias=w.fc3_b)
+        plan += self.lin.forward_act(sc, self.feats, w.fc1_w, self.z1, self.p1, "gelu", bias=w.fc1_b)
+        plan += self.lin.forward_act(sc, self.p1, w.fc2_w, self.z2, self.p2, "gelu", bias=w.fc2_b)
+        plan += self.lin.forward(sc, self.p2, w.fc3_w, self.p3, EPI_BIAS, bias=w.fc3_b)
         if head:                                   # the embeddings share the projector's slot: gathered once it is released
-            assert self._u_slot("llm.embed") is self._u_slot("projector") and self._u_slot("llm.lm_head") is not self._u_slot("projector")
-            plan += [self._u_release("projector"), self._u_gather("llm.embed")]
+            assert self.pools.slot("llm.embed") is self.pools.slot("projector") and self.pools.slot("llm.lm_head") is not self.pools.slot("projector")
+            plan += [self.pools.release("projector"), self.pools.gather("llm.embed")]
         plan.append(T.map_rows(self.p3, self.x[0], rows=B * 256, group=256, stride=S, offset=1, scatter=True, run=False))
         if head:
-            plan.append(self._u_await("llm.embed"))
+            plan.append(self.pools.await_("llm.embed"))
         plan.append(ops.embed_splice(self.input_ids, w.embed, self.x[0].view(B, S, D), d.n_patches, run=False))
         if head:
-            plan.append(self._u_release("llm.embed"))
+            plan.append(self.pools.release("llm.embed"))
         lseq = [f"llm.layer{l:02d}" for l in range(d.llm_layers)]
         for l in range(d.llm_layers):      # sharded: the next layer's gather runs under this layer's compute
-            plan += self._u_seq(lseq, l, False, self._layer_forward(l))
+            plan += self._seq(lseq, l, False, self._layer_forward(l))
         if head:
-            plan.append(self._u_await("llm.lm_head"))
+            plan.append(self.pools.await_("llm.lm_head"))
         plan += [ops.rmsnorm(self.x[-1], w.norm, self.hn, d.rms_eps, run=False),
-                 g(self.hn, w.lm_head, self.logits, EPI_F32_BF16R)]
+                 self.lin.gemm(sc, self.hn, w.lm_head, self.logits, EPI_F32_BF16R)]
         if self.preference is not None:
             plan.append(T.preference_loss(self.logits, self.targets, self.pair,
                                           None if self.preference.reference_free else self.ref_logprob, self.row_stats,
@@ -1114,48 +364,46 @@ class TrainStep:
         plan replays them (without the down projection, whose output is x[l+1]) when activations are recomputed."""
         d, w, B, S = self.dims, self.w, self.B, self.S
         D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
-        lin, lw = self._lin, w.layers[l]
+        lw, sc = w.layers[l], self.scratch.main
         lq, lo = self.qkv[0].stride(0), self.ao[0].stride(0)
         st, so = (S * lq, hd, lq), (S * lo, hd, lo)
         x, xm, qkv = self.x[l], self.xm[l], self.qkv[l]
-        plan = [ops.rmsnorm(x, lw.ln1, self.h1[l], d.rms_eps, run=False)] + lin(self.h1[l], lw.qkv_w, qkv, EPI_NONE)
+        plan = [ops.rmsnorm(x, lw.ln1, self.h1[l], d.rms_eps, run=False)] + self.lin.forward(sc, self.h1[l], lw.qkv_w, qkv, EPI_NONE)
         plan += [T.rope(qkv, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, run=False),
                  T.attention_lse(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.lse[l], B=B, H=H, Sq=S, Skv=S,
                                  head_dim=hd, q_strides=st, k_strides=st, v_strides=st, o_strides=so,
                                  causal=True, key_mask=self.key_mask, run=False)]
-        plan += lin(self.ao[l], lw.o_w, xm, EPI_RES, res=x)
+        plan += self.lin.forward(sc, self.ao[l], lw.o_w, xm, EPI_RES, res=x)
         plan += [ops.rmsnorm(xm, lw.ln2, self.h2[l], d.rms_eps, run=False)]
-        plan += self._lin_act(self.h2[l], lw.gu_w, self.gu[l], self.act[l], "swiglu")
+        plan += self.lin.forward_act(sc, self.h2[l], lw.gu_w, self.gu[l], self.act[l], "swiglu")
         if with_down:
-            plan += lin(self.act[l], lw.down_w, self.x[l + 1], EPI_RES, res=xm)
+            plan += self.lin.forward(sc, self.act[l], lw.down_w, self.x[l + 1], EPI_RES, res=xm)
         return plan
 
     def _plan_backward(self) -> List[Op]:
-        d, w, B, S, st = self.dims, self.w, self.B, self.S, self.store
+        d, w, B, S, st, sc = self.dims, self.w, self.B, self.S, self.store, self.scratch.main
         D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
         lm = "language_model.model"
         plan: List[Op] = [T.cross_entropy_backward(self.logits, self.targets, self.mean_cnt, self.dlogits, IGNORE_INDEX, run=False)
                           if self._row_cfg is None else
                           T.policy_loss_backward(self.logits, self.targets, self.row_stats, self.stats, self.dlogits,
                                                  self.policy or self.preference.backward_config(), IGNORE_INDEX, run=False)]
-        head = "projector" in self._units
+        head = self.pools is not None and "projector" in self.pools.units
         if head:
-            plan.append(self._u_await_grad("llm.lm_head"))
-            self._cur_unit = "llm.lm_head"
-        plan += self._wgrad(self.dlogits, self.hn, w.lm_head)
-        self._ready.append((len(plan), "llm.lm_head"))
-        plan.append(self._dgrad(self.dlogits, w.lm_head, self.dh))
-        if self.value is not None:                 # + the value loss's gradient on the value rows of dh; dw, db of the head
+            plan.append(self.pools.await_grad("llm.lm_head"))
+        with self._planning("llm.lm_head"):
+            plan += self.lin.wgrad(sc, self.dlogits, self.hn, w.lm_head)
+            self._ready.append((len(plan), "llm.lm_head"))
+            plan.append(self.lin.dgrad(sc, self.dlogits, w.lm_head, self.dh))
+        if self.value is not None:                # + the value loss's gradient on the value rows of dh; dw, db of the head
             plan.append(T.value_head_backward(self.hn, self.value_head.weight, self.value_rows, self.value_index, self.value_count,
                                               st.grad_view("value_head.weight"), st.grad_view("value_head.bias")[:1],
                                               None if self.value.detach else self.dh, self.value, group_rows=S,
                                               inv_world=1.0 / self.world if self.comm.active else 1.0, run=False))
-        self._cur_unit = None
-        if head:                                   # the projector's dgrad layouts travel under the whole decoder backward
-            plan += [self._u_release("llm.lm_head"), self._u_flush("llm.lm_head"), self._u_gather("projector", backward=True)]
-        lb = self._lin_bwd
+        if head:                                  # the projector's dgrad layouts travel under the whole decoder backward
+            plan += [self.pools.release("llm.lm_head"), self.pools.flush("llm.lm_head"), self.pools.gather("projector", backward=True)]
         dx, dx2 = self.dxa, self.dxb
-        plan.append(T.rmsnorm_backward(self.x[-1], w.norm, self.dh, dx, self._gvec(f"{lm}.norm.weight", D), self.norm_ws,
+        plan.append(T.rmsnorm_backward(self.x[-1], w.norm, self.dh, dx, self._gvec(f"{lm}.norm.weight", D), sc.norm_ws,
                                        d.rms_eps, run=False))
         lq, lo = self.qkv[0].stride(0), self.ao[0].stride(0)
         assert self.dqkv.stride(0) == lq and self.dao.stride(0) == lo
@@ -1164,60 +412,57 @@ class TrainStep:
         lseq = [f"llm.layer{l:02d}" for l in range(d.llm_layers - 1, stop_layer - 1, -1)]
         for j, l in enumerate(range(d.llm_layers - 1, stop_layer - 1, -1)):
             lw, b = w.layers[l], f"{lm}.layers.{l}"
-            self._cur_unit = lseq[j] if lseq[j] in self._units else None
             body: List[Op] = []                # this layer's ops: one parameter-sharded unit
-            if self.recompute:         # incl. the top layer: the plan stays idempotent (graph capture runs it twice)
-                body += self._layer_forward(l, with_down=False)
-            body += self._lin_bwd_act(dx, self.act[l], lw.down_w, self.gu[l], self.dgu, self.dact, "swiglu")
-            body += lb(self.dgu, self.h2[l], lw.gu_w, self.dh)
-            body.append(T.rmsnorm_backward(self.xm[l], lw.ln2, self.dh, dx2, self._gvec(f"{b}.post_attention_layernorm.weight", D),
-                                           self.norm_ws, d.rms_eps, dres=dx, run=False))
-            body += lb(dx2, self.ao[l], lw.o_w, self.dao)
-            qkv, dq = self.qkv[l], self.dqkv
-            body.append(T.attention_backward(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.dao, self.lse[l], self.delta,
-                                             dq, dq[:, D:], dq[:, 2 * D:], B=B, H=H, Sq=S, Skv=S, head_dim=hd,
-                                             q_strides=strides, k_strides=strides, v_strides=strides,
-                                             o_strides=so, causal=True, key_mask=self.key_mask, run=False))
-            body.append(T.rope_backward(dq, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, run=False))
-            body += lb(dq, self.h1[l], lw.qkv_w, self.dh)
-            self._cur_unit = None
-            plan += self._u_seq(lseq, j, True, body)             # sharded: the flush reduce-scatters and frees the gradient slot
+            with self._planning(lseq[j]):
+                if self.recompute:     # incl. the top layer: the plan stays idempotent (graph capture runs it twice)
+                    body += self._layer_forward(l, with_down=False)
+                body += self.lin.backward_act(sc, dx, self.act[l], lw.down_w, self.gu[l], self.dgu, self.dact, "swiglu")
+                body += self.lin.backward(sc, self.dgu, self.h2[l], lw.gu_w, self.dh)
+                body.append(T.rmsnorm_backward(self.xm[l], lw.ln2, self.dh, dx2, self._gvec(f"{b}.post_attention_layernorm.weight", D),
+                                               sc.norm_ws, d.rms_eps, dres=dx, run=False))
+                body += self.lin.backward(sc, dx2, self.ao[l], lw.o_w, self.dao)
+                qkv, dq = self.qkv[l], self.dqkv
+                body.append(T.attention_backward(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.dao, self.lse[l], self.delta,
+                                                 dq, dq[:, D:], dq[:, 2 * D:], B=B, H=H, Sq=S, Skv=S, head_dim=hd,
+                                                 q_strides=strides, k_strides=strides, v_strides=strides,
+                                                 o_strides=so, causal=True, key_mask=self.key_mask, run=False))
+                body.append(T.rope_backward(dq, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, run=False))
+                body += self.lin.backward(sc, dq, self.h1[l], lw.qkv_w, self.dh)
+            plan += self._seq(lseq, j, True, body)             # sharded: the flush reduce-scatters and frees the gradient slot
             self._ready.append((len(plan), lseq[j]))
             plan.append(T.rmsnorm_backward(self.x[l], lw.ln1, self.dh, dx, self._gvec(f"{b}.input_layernorm.weight", D),
-                                           self.norm_ws, d.rms_eps, dres=dx2, run=False))
+                                           sc.norm_ws, d.rms_eps, dres=dx2, run=False))
         if stop_layer > 0:
             return plan
         # dx = gradient of inputs_embeds [B, S, D]
         if st.trainable(f"{lm}.embed_tokens.weight"):
             if head:
-                plan.append(self._u_await_grad("llm.embed"))
+                plan.append(self.pools.await_grad("llm.embed"))
             plan.append(T.fill_zero(st.grad_view(f"{lm}.embed_tokens.weight"), run=False))     # accumulated with atomics
             plan.append(T.embed_backward(self.input_ids, dx.view(B, S, D), st.grad_view(f"{lm}.embed_tokens.weight").view(d.vocab, D),
                                          d.n_patches, run=False))
             if head:
-                plan.append(self._u_flush("llm.embed"))
+                plan.append(self.pools.flush("llm.embed"))
         if head:
-            plan += [self._u_await("projector"), self._u_await_grad("projector")]
-            self._cur_unit = "projector"
+            plan += [self.pools.await_("projector"), self.pools.await_grad("projector")]
         if st.trainable("projector.fc3.weight") or self.lora is not None:
             plan.append(T.map_rows(dx, self.dp3, rows=B * 256, group=256, stride=S, offset=1, scatter=False, run=False))
-            plan += self._bias_grad(self.dp3, "projector.fc3.bias")
-            plan += self._lin_bwd_act(self.dp3, self.p2, w.fc3_w, self.z2, self.dz2, self.dp2, "gelu")
-            plan += self._bias_grad(self.dz2, "projector.fc2.bias")
-            plan += self._lin_bwd_act(self.dz2, self.p1, w.fc2_w, self.z1, self.dz1, self.dp1, "gelu")
-            plan += self._bias_grad(self.dz1, "projector.fc1.bias")
-            plan += lb(self.dz1, self.feats, w.fc1_w, self.dfeats if self.train_vision else None)
+            with self._planning("projector"):
+                plan += self._bias_grad(sc, self.dp3, "projector.fc3.bias")
+                plan += self.lin.backward_act(sc, self.dp3, self.p2, w.fc3_w, self.z2, self.dz2, self.dp2, "gelu")
+                plan += self._bias_grad(sc, self.dz2, "projector.fc2.bias")
+                plan += self.lin.backward_act(sc, self.dz2, self.p1, w.fc2_w, self.z1, self.dz1, self.dp1, "gelu")
+                plan += self._bias_grad(sc, self.dz1, "projector.fc1.bias")
+                plan += self.lin.backward(sc, self.dz1, self.feats, w.fc1_w, self.dfeats if self.train_vision else None)
             self._ready.append((len(plan), "projector"))
-            self._cur_unit = None
             if head:
-                plan += [self._u_release("projector"), self._u_flush("projector")]
+                plan += [self.pools.release("projector"), self.pools.flush("projector")]
             if self.train_vision:
                 self._bwd_tower_at = [len(plan)]                   # [start of tower 0, start of tower 1]: see _vis2
                 for ti, (tw, sv, col) in enumerate(zip((w.dino, w.siglip), self.vis, (0, d.dino.dim))):
                     if ti:
                         self._bwd_tower_at.append(len(plan))
-                    with self._side_scratch(ti == 1):
-                        plan += self._plan_tower_backward(tw, col, sv, len(plan))
+                    plan += self._plan_tower_backward(tw, col, sv, len(plan), self.scratch.side if ti else sc)
         return plan
 
     # ---- vision towers in training form (timm VisionTransformer blocks) ---------------------------
@@ -1239,50 +484,49 @@ class TrainStep:
             df=z(M, Hp), dz=za(M, Hp, R_(b0.fc1_w)),
             dpe=z(B * 256, Dm), tok=z(max(t.n_prefix, 1) * Dm, dtype=torch.float32))
 
-    def _plan_tower_forward(self, tw, feat_col: int, sv: dict) -> List[Op]:
+    def _plan_tower_forward(self, tw, feat_col: int, sv: dict, sc: ScratchSet) -> List[Op]:
         t, B, eps = tw.dims, self.B, self.dims.ln_eps
         Tk, Dm, hd = t.tokens, t.dim, t.head_dim
         col = self._vis.vbuf[1 if feat_col else 0]["col"]          # one im2col buffer per tower (kept for the patch wgrad)
-        g = self._g
         x0 = sv["x"][0]
         seq, j0 = self._vseq_fwd, self._vseq_fwd.index(self._vkey(tw, -1))
         whole: List[Op] = []                       # the tower's plan; `plan` below collects one unit's ops at a time
         plan = [ops.im2col_patch14(self.pixel_values, t.chan0, col, run=False)]
         if tw.prefix is not None:
             plan.append(ops.write_prefix_tokens(tw.prefix, x0, B, Tk, run=False))
-        plan.append(g(col, tw.patch_w, x0, ops.EPI_BIAS_RES, bias=tw.patch_b, res=tw.pos, res_row_mod=256,
+        plan.append(self.lin.gemm(sc, col, tw.patch_w, x0, ops.EPI_BIAS_RES, bias=tw.patch_b, res=tw.pos, res_row_mod=256,
                       out_map=(256, Tk, t.n_prefix)))
-        whole += self._u_seq(seq, j0, False, plan)
+        whole += self._seq(seq, j0, False, plan)
         lq, lo = sv["qkv"][0].stride(0), sv["ao"][0].stride(0)
         st, so = (Tk * lq, hd, lq), (Tk * lo, hd, lo)
         for i, b in enumerate(tw.blocks):
             if i:
-                whole += self._u_seq(seq, j0 + i, False, plan)
+                whole += self._seq(seq, j0 + i, False, plan)
             x, xm, qkv = sv["x"][i], sv["xm"][i], sv["qkv"][i]
             plan = [ops.layernorm(x, b.norm1_w, b.norm1_b, sv["h1"][i], eps, run=False)]
-            plan += self._lin(sv["h1"][i], b.qkv_w, qkv, EPI_BIAS, bias=b.qkv_b)
+            plan += self.lin.forward(sc, sv["h1"][i], b.qkv_w, qkv, EPI_BIAS, bias=b.qkv_b)
             plan += [T.attention_lse(qkv, qkv[:, Dm:], qkv[:, 2 * Dm:], sv["ao"][i], sv["lse"][i], B=B, H=t.heads, Sq=Tk,
                                      Skv=Tk, head_dim=hd, q_strides=st, k_strides=st, v_strides=st,
                                      o_strides=so, causal=False, run=False)]
             if b.ls1 is not None:
-                plan += self._lin(sv["ao"][i], b.proj_w, sv["u1"][i], EPI_BIAS, bias=b.proj_b)
+                plan += self.lin.forward(sc, sv["ao"][i], b.proj_w, sv["u1"][i], EPI_BIAS, bias=b.proj_b)
                 plan.append(T.scale_residual(sv["u1"][i], b.ls1, x, xm, run=False))
             else:
-                plan += self._lin(sv["ao"][i], b.proj_w, xm, ops.EPI_BIAS_RES, bias=b.proj_b, res=x)
+                plan += self.lin.forward(sc, sv["ao"][i], b.proj_w, xm, ops.EPI_BIAS_RES, bias=b.proj_b, res=x)
             plan.append(ops.layernorm(xm, b.norm2_w, b.norm2_b, sv["h2"][i], eps, run=False))
-            plan += self._lin_act(sv["h2"][i], b.fc1_w, sv["zz"][i], sv["f"][i], "gelu", bias=b.fc1_b)
+            plan += self.lin.forward_act(sc, sv["h2"][i], b.fc1_w, sv["zz"][i], sv["f"][i], "gelu", bias=b.fc1_b)
             if b.ls2 is not None:
-                plan += self._lin(sv["f"][i], b.fc2_w, sv["u2"][i], EPI_BIAS, bias=b.fc2_b)
+                plan += self.lin.forward(sc, sv["f"][i], b.fc2_w, sv["u2"][i], EPI_BIAS, bias=b.fc2_b)
                 plan.append(T.scale_residual(sv["u2"][i], b.ls2, xm, sv["x"][i + 1], run=False))
             else:
-                plan += self._lin(sv["f"][i], b.fc2_w, sv["x"][i + 1], ops.EPI_BIAS_RES, bias=b.fc2_b, res=xm)
-        whole += self._u_seq(seq, j0 + len(tw.blocks), False, plan)
+                plan += self.lin.forward(sc, sv["f"][i], b.fc2_w, sv["x"][i + 1], ops.EPI_BIAS_RES, bias=b.fc2_b, res=xm)
+        whole += self._seq(seq, j0 + len(tw.blocks), False, plan)
         # tap: patch rows of the last block output → this tower's channels of the fused feature map
         whole.append(T.map_rows(sv["x"][-1], self.feats[:, feat_col:feat_col + Dm], rows=B * 256, group=256, stride=Tk,
                                 offset=t.n_prefix, scatter=False, run=False))
         return whole
 
-    def _plan_tower_backward(self, tw, feat_col: int, sv: dict, base: int) -> List[Op]:
+    def _plan_tower_backward(self, tw, feat_col: int, sv: dict, base: int, sc: ScratchSet) -> List[Op]:
         """`base` = ops already in the backward plan (bucket-ready markers are absolute positions)."""
         t, B, eps, st = tw.dims, self.B, self.dims.ln_eps, self.store
         Tk, Dm, hd, M = t.tokens, t.dim, t.head_dim, B * t.tokens
@@ -1290,7 +534,6 @@ class TrainStep:
         tower_key = p.split(".")[1]
         gv = lambda name: self._gvec(name, Dm)
         gb = lambda name: st.grad_view(name) if st.trainable(name) else self._frozen_dw[Dm:2 * Dm]   # 2nd sink: LN dw + db
-        lb = self._lin_bwd
         dx, dx2 = sv["dxa"], sv["dxb"]
         seq, j0 = self._vseq_bwd, self._vseq_bwd.index(self._vkey(tw, t.n_run - 1))
         whole: List[Op] = [T.fill_zero(self._wide.get(dx.data_ptr(), dx), run=False),
@@ -1303,49 +546,47 @@ class TrainStep:
             b, bn = tw.blocks[i], f"{p}.blocks.{i}"
             dbr = dx
             plan: List[Op] = []                    # this block's ops: one parameter-sharded unit
-            self._cur_unit = self._vkey(tw, i) if self._vkey(tw, i) in self._units else None
-            if b.ls2 is not None:
-                plan.append(T.layerscale_backward(dx, sv["u2"][i], b.ls2, sv["du"], gv(f"{bn}.ls2.scale_factor"), self.col_ws, run=False))
-                dbr = sv["du"]
-            plan += self._bias_grad(dbr, f"{bn}.mlp.fc2.bias")
-            plan += self._lin_bwd_act(dbr, sv["f"][i], b.fc2_w, sv["zz"][i], sv["dz"], sv["df"], "gelu")
-            plan += self._bias_grad(sv["dz"][:, :t.mlp], f"{bn}.mlp.fc1.bias")
-            plan += lb(sv["dz"], sv["h2"][i], b.fc1_w, sv["dh"])
-            plan.append(T.layernorm_backward(sv["xm"][i], b.norm2_w, sv["dh"], dx2, gv(f"{bn}.norm2.weight"), gb(f"{bn}.norm2.bias"),
-                                             self.norm_ws, eps, dres=dx, run=False))
-            dbr = dx2
-            if b.ls1 is not None:
-                plan.append(T.layerscale_backward(dx2, sv["u1"][i], b.ls1, sv["du"], gv(f"{bn}.ls1.scale_factor"), self.col_ws, run=False))
-                dbr = sv["du"]
-            plan += self._bias_grad(dbr, f"{bn}.attn.proj.bias")
-            plan += lb(dbr, sv["ao"][i], b.proj_w, sv["dao"])
-            qkv, dq = sv["qkv"][i], sv["dqkv"]
-            plan.append(T.attention_backward(qkv, qkv[:, Dm:], qkv[:, 2 * Dm:], sv["ao"][i], sv["dao"], sv["lse"][i], sv["delta"],
-                                             dq, dq[:, Dm:], dq[:, 2 * Dm:], B=B, H=t.heads, Sq=Tk, Skv=Tk, head_dim=hd,
-                                             q_strides=strides, k_strides=strides, v_strides=strides,
-                                             o_strides=so, causal=False, run=False))
-            plan += self._bias_grad(dq, f"{bn}.attn.qkv.bias")
-            plan += lb(dq, sv["h1"][i], b.qkv_w, sv["dh"])
-            self._cur_unit = None
-            whole += self._u_seq(seq, j0 + (t.n_run - 1 - i), True, plan)
+            with self._planning(self._vkey(tw, i)):
+                if b.ls2 is not None:
+                    plan.append(T.layerscale_backward(dx, sv["u2"][i], b.ls2, sv["du"], gv(f"{bn}.ls2.scale_factor"), sc.col_ws, run=False))
+                    dbr = sv["du"]
+                plan += self._bias_grad(sc, dbr, f"{bn}.mlp.fc2.bias")
+                plan += self.lin.backward_act(sc, dbr, sv["f"][i], b.fc2_w, sv["zz"][i], sv["dz"], sv["df"], "gelu")
+                plan += self._bias_grad(sc, sv["dz"][:, :t.mlp], f"{bn}.mlp.fc1.bias")
+                plan += self.lin.backward(sc, sv["dz"], sv["h2"][i], b.fc1_w, sv["dh"])
+                plan.append(T.layernorm_backward(sv["xm"][i], b.norm2_w, sv["dh"], dx2, gv(f"{bn}.norm2.weight"), gb(f"{bn}.norm2.bias"),
+                                                 sc.norm_ws, eps, dres=dx, run=False))
+                dbr = dx2
+                if b.ls1 is not None:
+                    plan.append(T.layerscale_backward(dx2, sv["u1"][i], b.ls1, sv["du"], gv(f"{bn}.ls1.scale_factor"), sc.col_ws, run=False))
+                    dbr = sv["du"]
+                plan += self._bias_grad(sc, dbr, f"{bn}.attn.proj.bias")
+                plan += self.lin.backward(sc, dbr, sv["ao"][i], b.proj_w, sv["dao"])
+                qkv, dq = sv["qkv"][i], sv["dqkv"]
+                plan.append(T.attention_backward(qkv, qkv[:, Dm:], qkv[:, 2 * Dm:], sv["ao"][i], sv["dao"], sv["lse"][i], sv["delta"],
+                                                 dq, dq[:, Dm:], dq[:, 2 * Dm:], B=B, H=t.heads, Sq=Tk, Skv=Tk, head_dim=hd,
+                                                 q_strides=strides, k_strides=strides, v_strides=strides,
+                                                 o_strides=so, causal=False, run=False))
+                plan += self._bias_grad(sc, dq, f"{bn}.attn.qkv.bias")
+                plan += self.lin.backward(sc, dq, sv["h1"][i], b.qkv_w, sv["dh"])
+            whole += self._seq(seq, j0 + (t.n_run - 1 - i), True, plan)
             self._ready.append((base + len(whole), f"vision.{tower_key}.block{i:02d}"))
             whole.append(T.layernorm_backward(sv["x"][i], b.norm1_w, sv["dh"], dx, gv(f"{bn}.norm1.weight"), gb(f"{bn}.norm1.bias"),
-                                              self.norm_ws, eps, dres=dx2, run=False))
+                                              sc.norm_ws, eps, dres=dx2, run=False))
         # stem: dx = gradient of [prefix tokens | patch embeddings + pos]
         plan = []
-        self._cur_unit = self._vkey(tw, -1) if self._vkey(tw, -1) in self._units else None
         if st.trainable(f"{p}.pos_embed"):
             dxv = dx.view(B, Tk * Dm)
-            plan.append(T.colsum(dxv[:, t.n_prefix * Dm:], st.grad_view(f"{p}.pos_embed"), self.col_ws, run=False))
+            plan.append(T.colsum(dxv[:, t.n_prefix * Dm:], st.grad_view(f"{p}.pos_embed"), sc.col_ws, run=False))
             if t.n_prefix:
-                plan.append(T.colsum(dxv[:, :t.n_prefix * Dm], sv["tok"], self.col_ws, run=False))
+                plan.append(T.colsum(dxv[:, :t.n_prefix * Dm], sv["tok"], sc.col_ws, run=False))
                 plan.append(T.copy_f32(sv["tok"][:Dm], st.grad_view(f"{p}.cls_token"), run=False))
                 plan.append(T.copy_f32(sv["tok"][Dm:t.n_prefix * Dm], st.grad_view(f"{p}.reg_token"), run=False))
             plan.append(T.map_rows(dx, sv["dpe"], rows=B * 256, group=256, stride=Tk, offset=t.n_prefix, scatter=False, run=False))
-            plan += self._bias_grad(sv["dpe"], f"{p}.patch_embed.proj.bias")
-            plan += self._wgrad(sv["dpe"], self._vis.vbuf[1 if feat_col else 0]["col"], tw.patch_w)
-        self._cur_unit = None
-        whole += self._u_seq(seq, j0 + t.n_run, True, plan)
+            plan += self._bias_grad(sc, sv["dpe"], f"{p}.patch_embed.proj.bias")
+            with self._planning(self._vkey(tw, -1)):
+                plan += self.lin.wgrad(sc, sv["dpe"], self._vis.vbuf[1 if feat_col else 0]["col"], tw.patch_w)
+        whole += self._seq(seq, j0 + t.n_run, True, plan)
         self._ready.append((base + len(whole), f"vision.{tower_key}.stem"))
         return whole
 
@@ -1364,8 +605,6 @@ class TrainStep:
         """After AdamW wrote the bf16 copy of every group's logical matrix: refresh the forward and the dgrad layouts."""
         plan: List[Op] = []
         st = self.store
-        nmax = max((u.numel for u in st.units), default=8)
-        self._tW = torch.zeros(nmax, dtype=torch.bfloat16, device=self.device)
         # plain tensors (norm scales, biases, embeddings, LoRA adapters): updated bf16 values → the live tensors, as prepared
         # byte copies inside the plan (hundreds of them under LoRA: replayed with the graph instead of launched one by one)
         # ONE bl_batched_ops launch for the write-backs of the plain tensors and the re-packs of the GEMM weights (independent of
@@ -1380,18 +619,11 @@ class TrainStep:
                 continue                                          # parameter-sharded units are packed when gathered
             n, k = u.group.n, u.group.k
             rm = st.stage_view(u.offset, u.numel).view(n, k)
-            key = u.group.packed.data_ptr()
             entries.append(T.be_pack(rm, u.group.packed))
-            if key in self._wT:                                   # only weights that a dgrad GEMM actually reads
-                if k % 64 == 0 and n % 32 == 0:
-                    entries.append(T.be_transpose_pack(rm, self._wT[key], n))
-                else:
-                    plan.append(T.transpose_pack(rm, self._wT[key], n, run=False))
-            if key in self._w8:                                   # e4m3 copies follow the updated weight
-                plan += self._fp8_weight_ops(rm, self._w8[key])
+            plan += self.lin.repack_ops(rm, u.group.packed, entries)
         if entries:
             plan.insert(0, T.batched(entries, self.device, run=False))
-        plan += self._adapter_ops                                 # LoRA: adapter columns of the K-concatenated weights
+        plan += self.lin.adapter_ops                           # LoRA: adapter columns of the K-concatenated weights
         return plan
 
     # ---- running ------------------------------------------------------------------------------------------------
@@ -1477,23 +709,13 @@ class TrainStep:
             raise RuntimeError("set_policy_batch needs TrainStep(loss='policy')")
         if (ref_logprobs is None) != (self.policy.kl_coef == 0.0):
             raise ValueError("ref_logprobs goes together with a non-zero kl_coef")
-        dev, B, L, P, l = self.device, self.B, self.L, self.dims.n_patches, self._batch_len
-        valid = (self.targets != IGNORE_INDEX).view(B, self.S)
+        valid = (self.targets != IGNORE_INDEX).view(self.B, self.S)
         for name, src, dst in (("advantages", advantages, self.advantages), ("old_logprobs", old_logprobs, self.old_logprob),
                                ("ref_logprobs", ref_logprobs, self.ref_logprob)):
-            if src is None:
-                continue
-            src = torch.as_tensor(src)
-            if tuple(src.shape) != (B, l):
-                raise ValueError(f"{name}: shape {tuple(src.shape)}, expected {(B, l)} (aligned with the labels of set_batch)")
-            pad = torch.zeros(B, L, dtype=torch.float32, device=dev)
-            pad[:, :l] = src.to(dev, dtype=torch.float32)
-            rows = shift_to_rows(pad, P, 0.0)
-            bad = valid & ~torch.isfinite(rows)
-            if bool(bad.any()):
-                raise ValueError(f"{name}: {int(bad.sum())} non-finite value(s) on labelled positions — a token outside the "
-                                 "rollout's top-k / top-p support scores -inf; draw training rollouts with temperature only")
-            dst.copy_(torch.where(valid, rows, torch.zeros_like(rows)).view(-1))
+            if src is not None:
+                tokens_to_rows(name, src, dst, self._batch_len, self.dims.n_patches, valid,
+                               "on labelled positions — a token outside the rollout's top-k / top-p support scores -inf; draw "
+                               "training rollouts with temperature only")
 
     def set_value_batch(self, returns: torch.Tensor, old_values: Optional[torch.Tensor] = None) -> None:
         """The critic's targets for the batch of the preceding `set_batch`: the return R of each value position and the
@@ -1505,27 +727,21 @@ class TrainStep:
             raise RuntimeError("set_value_batch needs TrainStep(loss='policy', value=ValueLossConfig(...))")
         if (old_values is None) != (self.value.clip is None):
             raise ValueError("old_values goes together with value.clip (None only for the unclipped loss)")
-        dev, B, L, P, l = self.device, self.B, self.L, self.dims.n_patches, self._batch_len
+        B = self.B
         valid = (self.targets != IGNORE_INDEX).view(B, self.S)
-        by_action = self.value.level == "action"
         for name, src, dst in (("returns", returns, self.returns), ("old_values", old_values, self.old_values)):
             if src is None:
                 continue
-            src = torch.as_tensor(src)
-            want = (B,) if by_action else (B, l)
-            if tuple(src.shape) != want:
-                raise ValueError(f"{name}: shape {tuple(src.shape)}, expected {want}"
-                                 + ("" if by_action else " (aligned with the labels of set_batch)"))
-            if by_action:                       # one value row per sequence, found on the device: every row carries the sequence's
-                rows = src.to(dev, dtype=torch.float32)[:, None].expand(B, self.S)
-            else:
-                pad = torch.zeros(B, L, dtype=torch.float32, device=dev)
-                pad[:, :l] = src.to(dev, dtype=torch.float32)
-                rows = shift_to_rows(pad, P, 0.0)
+            if self.value.level == "token":
+                tokens_to_rows(name, src, dst, self._batch_len, self.dims.n_patches, valid, "on labelled positions")
+                continue
+            src = torch.as_tensor(src)          # one value row per sequence, found on the device: every row carries the sequence's
+            if tuple(src.shape) != (B,):
+                raise ValueError(f"{name}: shape {tuple(src.shape)}, expected {(B,)}")
+            rows = src.to(self.device, dtype=torch.float32)[:, None].expand(B, self.S)
             bad = valid & ~torch.isfinite(rows)
             if bool(bad.any()):
-                raise ValueError(f"{name}: {int(bad.any(dim=1).sum() if by_action else bad.sum())} non-finite value(s) "
-                                 f"on {'sequences with a label' if by_action else 'labelled positions'}")
+                raise ValueError(f"{name}: {int(bad.any(dim=1).sum())} non-finite value(s) on sequences with a label")
             dst.copy_(torch.where(valid, rows, torch.zeros_like(rows)).reshape(-1))
 
     def values(self) -> torch.Tensor:
@@ -1538,25 +754,6 @@ class TrainStep:
         if self.value.level == "action":        # at most one non-zero per sequence: the sum is that value, exactly
             return v.sum(dim=1)
         return shift_from_rows(v, self.dims.n_patches)[:, :self._batch_len]
-
-    def value_stats(self) -> Dict[str, torch.Tensor]:
-        """The 8 statistics of the value loss of the last forward (value_loss.VALUE_STAT_NAMES) as device scalars."""
-        if self.value is None:
-            raise RuntimeError("value_stats needs TrainStep(loss='policy', value=ValueLossConfig(...))")
-        return {name: self.vstats[i] for i, name in enumerate(VALUE_STAT_NAMES)}
-
-    def policy_stats(self) -> Dict[str, torch.Tensor]:
-        """The 8 step statistics of the last forward (policy_loss.STAT_NAMES) as device scalars."""
-        if self.policy is None:
-            raise RuntimeError("policy_stats needs TrainStep(loss='policy')")
-        return {name: self.stats[i] for i, name in enumerate(STAT_NAMES)}
-
-    def action_stats(self) -> Dict[str, torch.Tensor]:
-        """The per-sequence statistics of the last forward under policy.ratio_level="action" (policy_loss.GROUP_STAT_NAMES)
-        as device tensors [B]: the action's log-ratio, its ratio, its number of labelled tokens and its log π."""
-        if self.policy is None or self.policy.ratio_level != "action":
-            raise RuntimeError("action_stats needs TrainStep(loss='policy') with policy.ratio_level='action'")
-        return {name: self.group_stats[:, i] for i, name in enumerate(GROUP_STAT_NAMES)}
 
     def set_preference_batch(self, pair, ref_logprobs: Optional[torch.Tensor] = None) -> None:
         """The pair assignment of loss="preference" for the batch of the preceding `set_batch`: `pair` int [B] holds +k for
@@ -1571,46 +768,54 @@ class TrainStep:
             raise RuntimeError("set_preference_batch needs TrainStep(loss='preference')")
         if (ref_logprobs is None) != self.preference.reference_free:
             raise ValueError("ref_logprobs is given unless preference.reference_free")
-        dev, B, L, P_, l = self.device, self.B, self.L, self.dims.n_patches, self._batch_len
+        B = self.B
         pr = torch.as_tensor(pair).detach().cpu()
         if pr.dim() != 1 or pr.shape[0] != B or pr.dtype.is_floating_point or pr.dtype == torch.bool:
             raise ValueError(f"pair: an integer vector [{B}], got {pr.dtype} {tuple(pr.shape)}")
         valid = (self.targets != IGNORE_INDEX).view(B, self.S)
         n_pairs = check_pairs(pr.to(torch.int64).numpy(), valid.sum(dim=1).cpu().numpy())
         if ref_logprobs is not None:
-            src = torch.as_tensor(ref_logprobs)
-            if tuple(src.shape) != (B, l):
-                raise ValueError(f"ref_logprobs: shape {tuple(src.shape)}, expected {(B, l)} (aligned with the labels of set_batch)")
-            pad = torch.zeros(B, L, dtype=torch.float32, device=dev)
-            pad[:, :l] = src.to(dev, dtype=torch.float32)
-            rows = shift_to_rows(pad, P_, 0.0)
-            bad = valid & (pr != 0).to(dev)[:, None] & ~torch.isfinite(rows)
-            if bool(bad.any()):
-                raise ValueError(f"ref_logprobs: {int(bad.sum())} non-finite value(s) on labelled positions of paired sequences — a "
-                                 "token outside a top-k / top-p support scores -inf; score the reference with temperature only")
-            self.ref_logprob.copy_(torch.where(valid, rows, torch.zeros_like(rows)).view(-1))
+            tokens_to_rows("ref_logprobs", ref_logprobs, self.ref_logprob, self._batch_len, self.dims.n_patches, valid,
+                           "on labelled positions of paired sequences — a token outside a top-k / top-p support scores -inf; "
+                           "score the reference with temperature only", refuse=valid & (pr != 0).to(self.device)[:, None])
         self.pair.copy_(pr.to(torch.int32))
         self.n_pairs.fill_(n_pairs)
         self._pairs_set = True
 
+    def _stats(self, reader: str, have: bool, needs: str, names, buf: str) -> Dict[str, torch.Tensor]:
+        """{name: entry i along the last dimension of buffer `buf`} — device scalars for a vector of step statistics, device
+        vectors for a per-sequence / per-pair table; RuntimeError when the step was built without what the reader `needs`."""
+        if not have:
+            raise RuntimeError(f"{reader} needs {needs}")
+        return {name: getattr(self, buf).select(-1, i) for i, name in enumerate(names)}
+
+    def value_stats(self) -> Dict[str, torch.Tensor]:
+        """The 8 statistics of the value loss of the last forward (value_loss.VALUE_STAT_NAMES) as device scalars."""
+        return self._stats("value_stats", self.value is not None, "TrainStep(loss='policy', value=ValueLossConfig(...))",
+                           VALUE_STAT_NAMES, "vstats")
+
+    def policy_stats(self) -> Dict[str, torch.Tensor]:
+        """The 8 step statistics of the last forward (policy_loss.STAT_NAMES) as device scalars."""
+        return self._stats("policy_stats", self.policy is not None, "TrainStep(loss='policy')", STAT_NAMES, "stats")
+
+    def action_stats(self) -> Dict[str, torch.Tensor]:
+        """The per-sequence statistics of the last forward under policy.ratio_level="action" (policy_loss.GROUP_STAT_NAMES)
+        as device tensors [B]: the action's log-ratio, its ratio, its number of labelled tokens and its log π."""
+        return self._stats("action_stats", self.policy is not None and self.policy.ratio_level == "action",
+                           "TrainStep(loss='policy') with policy.ratio_level='action'", GROUP_STAT_NAMES, "group_stats")
+
     def preference_stats(self) -> Dict[str, torch.Tensor]:
         """The 8 step statistics of the last forward (preference_loss.PREF_STAT_NAMES) as device scalars."""
-        if self.preference is None:
-            raise RuntimeError("preference_stats needs TrainStep(loss='preference')")
-        return {name: self.stats[i] for i, name in enumerate(PREF_STAT_NAMES)}
+        return self._stats("preference_stats", self.preference is not None, "TrainStep(loss='preference')", PREF_STAT_NAMES, "stats")
 
     def pair_stats(self) -> Dict[str, torch.Tensor]:
         """The per-pair statistics of the last forward (preference_loss.PAIR_STAT_NAMES) as device tensors [B // 2]; the
         entries from the batch's number of pairs on are 0."""
-        if self.preference is None:
-            raise RuntimeError("pair_stats needs TrainStep(loss='preference')")
-        return {name: self.pair_stats_buf[:, i] for i, name in enumerate(PAIR_STAT_NAMES)}
+        return self._stats("pair_stats", self.preference is not None, "TrainStep(loss='preference')", PAIR_STAT_NAMES, "pair_stats_buf")
 
     def sequence_stats(self) -> Dict[str, torch.Tensor]:
         """The per-sequence statistics of the last forward (preference_loss.SEQ_STAT_NAMES) as device tensors [B]."""
-        if self.preference is None:
-            raise RuntimeError("sequence_stats needs TrainStep(loss='preference')")
-        return {name: self.seq_stats_buf[:, i] for i, name in enumerate(SEQ_STAT_NAMES)}
+        return self._stats("sequence_stats", self.preference is not None, "TrainStep(loss='preference')", SEQ_STAT_NAMES, "seq_stats_buf")
 
     def token_logprobs(self) -> torch.Tensor:
         """log π(token) of the last forward at the labelled positions, [B, l] aligned with `labels` (0 elsewhere): the row
@@ -1619,21 +824,6 @@ class TrainStep:
         if self._row_cfg is None:
             raise RuntimeError("token_logprobs needs TrainStep(loss='policy') or TrainStep(loss='preference')")
         return shift_from_rows(self.row_stats[:, 0].view(self.B, self.S), self.dims.n_patches)[:, :self._batch_len]
-
-    @contextlib.contextmanager
-    def _side_scratch(self, on: bool):
-        """While the SECOND tower's plans are built: the scratch buffers its ops bind are the side stream's own."""
-        if not (on and self._vis2):
-            yield
-            return
-        keep = {k: getattr(self, k) for k in self._scratch2}
-        for k, v in self._scratch2.items():
-            setattr(self, k, v)
-        try:
-            yield
-        finally:
-            for k, v in keep.items():
-                setattr(self, k, v)
 
     def _run_forked(self, main_ops: List[Op], side_ops: List[Op]) -> None:
         """main_ops on the current stream, side_ops on the vision side stream, joined at the end (fork / join with stream
@@ -1646,7 +836,7 @@ class TrainStep:
         main.wait_stream(self._vis_stream)
 
     def _replay(self, key: str, plan, graph: bool) -> None:
-        if self._materialized:
+        if self.pools is not None and self.pools.materialized:
             raise RuntimeError("materialize_params() ended this step object's training (its plans address the gather slots)")
         run = plan if callable(plan) else (lambda: ops.run_all(plan))      # a callable issues its own (forked) launches
         if not graph or (self.shard_params and key in ("vfwd", "fwd", "bwd")):      # per-unit collectives stay out of HIP graphs
@@ -1666,7 +856,7 @@ class TrainStep:
         """Vision towers (frozen) → projector → decoder → loss. Returns the device scalar loss (with a critic: policy loss +
         value.coef · value loss, `value_stats()["total"]`)."""
         if self.lora is not None and self.lora.dropout > 0.0:
-            self._drop_seed.add_(1)            # a fresh mask per forward pass; the backward pass recomputes it from the same value
+            self.lin.drop_seed.add_(1)            # a fresh mask per forward pass; the backward pass recomputes it from the same value
         if self.train_vision and self._vis2:
             self._replay("vfwd", lambda: self._run_forked(self._vfwd_tower[0], self._vfwd_tower[1]), graph)
         elif self.train_vision:
@@ -1701,9 +891,7 @@ class TrainStep:
             reduced.add(b.key)
             if b.key in st.sharded_keys:                           # reduced by the flush step inside the plan
                 return
-            ev = torch.cuda.Event()
-            ev.record(main)
-            self._comm_stream.wait_event(ev)
+            self._comm_stream.wait_stream(main)
             with torch.cuda.stream(self._comm_stream):
                 self.comm.reduce_scatter_bucket(st.grad_range(b.offset, b.numel), b, st.stage_view(b.offset, b.numel))
         for upto, key in self._ready:
@@ -1763,15 +951,14 @@ class TrainStep:
                     weight_decay=self.weight_decay if b.decay else 0.0, norm_coef=st.norm_coef,
                     p_bf16=st.own_slice(b) if sharded else st.stage_view(lo, hi - lo))
             if self.comm.active and not sharded:                   # gather bucket i while AdamW runs on bucket i+1
-                ev = torch.cuda.Event()
-                ev.record(main)
-                self._comm_stream.wait_event(ev)
+                self._comm_stream.wait_stream(main)
                 with torch.cuda.stream(self._comm_stream):
                     self.comm.all_gather_params(st.stage_view(b.offset, b.numel), b)
         if self.comm.active:
             main.wait_stream(self._comm_stream)
         self._replay("repack", self.repack_ops, graph)
-        self._params_updated.record(main)
+        if self.pools is not None:
+            self.pools.params_updated.record(main)
 
     def step(self, lr: float, graph: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """forward → backward → clip → AdamW. Returns (loss, grad norm) as device scalars (no host sync here)."""
@@ -1794,6 +981,25 @@ def shift_to_rows(values: torch.Tensor, n_patches: int, fill) -> torch.Tensor:
     out = torch.full_like(full, fill)
     out[:, :-1] = full[:, 1:]
     return out
+
+
+def tokens_to_rows(name: str, src, dst: torch.Tensor, l: int, n_patches: int, select: torch.Tensor, where: str,
+                   refuse: Optional[torch.Tensor] = None) -> None:
+    """Per-token values `src` [B, l], aligned with the labels of a batch of l ≤ L tokens → `dst` [B·S] fp32, aligned with the
+    logits rows (S = L + n_patches): padded to L with zeros, through `shift_to_rows`, zeroed outside the rows that `select`
+    [B, S] marks, copied. A non-finite value on a row of `refuse` (default: `select`) is a ValueError that names the input and
+    says `where`; the rows outside `select` are never read by a kernel, so what they hold does not matter."""
+    B, S = select.shape
+    src = torch.as_tensor(src)
+    if tuple(src.shape) != (B, l):
+        raise ValueError(f"{name}: shape {tuple(src.shape)}, expected {(B, l)} (aligned with the labels of set_batch)")
+    pad = torch.zeros(B, S - n_patches, dtype=torch.float32, device=dst.device)
+    pad[:, :l] = src.to(dst.device, dtype=torch.float32)
+    rows = shift_to_rows(pad, n_patches, 0.0)
+    bad = (select if refuse is None else refuse) & ~torch.isfinite(rows)
+    if bool(bad.any()):
+        raise ValueError(f"{name}: {int(bad.sum())} non-finite value(s) {where}")
+    dst.copy_(torch.where(select, rows, torch.zeros_like(rows)).view(-1))
 
 
 def shift_from_rows(rows: torch.Tensor, n_patches: int) -> torch.Tensor:

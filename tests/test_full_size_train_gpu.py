@@ -59,7 +59,7 @@ def test_lora_directional_derivative_full_size(dev, model, B):
         eps = target / nB
         for i, ad in enumerate(lora.adapters):
             ad.B.copy_((-(eps / nB) * st.grad_view(f"lora.{i}.B").view(ad.B.shape)).to(torch.bfloat16))
-        ops.run_all(ts._adapter_ops)
+        ops.run_all(ts.lin.adapter_ops)
         d = ts.forward().item() - loss0
         print(f"directional derivative: predicted {-target:.4f}, measured {d:.4f}")
         assert abs(d + target) <= 0.08 * target + 0.004, (target, d)
@@ -278,7 +278,7 @@ def test_cfg5_full_depth_13b_full_shard_fp8_recompute(dev):
     from bridgelang_amd import ops
     got = ops.unpack_weight(lw.o_w).float()
     u = ts.store.by_name["language_model.model.layers.39.self_attn.o_proj.weight"]     # world 1: the rank's master slice is the whole flat space
-    assert u in ts._units["llm.layer39"]["by_ptr"].values()
+    assert u in ts.pools.units["llm.layer39"]["by_ptr"].values()
     want = ts.store.master[u.offset:u.offset + u.numel].view(u.group.n, u.group.k).to(torch.bfloat16).float()
     assert torch.equal(got, want), "materialised layer weights must be the bf16 rounding of the fp32 masters"
     del ts, w

@@ -176,7 +176,7 @@ def test_building_the_step_runs_the_whole_refresh(base, dev):
         for ad in lora.adapters:
             ad.B.neg_()                                          # still dyadic: the merge stays exact; no refresh() here
         ts = TrainStep(model.weights, "lora", B, L + 8, lora=lora, max_grad_norm=float("inf"), refresh_adapted=True)
-        assert [op.name for op in ts._adapter_ops[-2:]] == ["bl_lora_merge_batched_bf16", "bl_quantize_weight_fp8_packed_batched"]
+        assert [op.name for op in ts.lin.adapter_ops[-2:]] == ["bl_lora_merge_batched_bf16", "bl_quantize_weight_fp8_packed_batched"]
         after = check_copies(lora, model, "reference", "after building the step")
         assert all(not torch.equal(i16(a), i16(b)) for a, b in zip(before, after)), "the e4m3 copies are those of the old adapters"
         index = {id(g): i for i, g in enumerate(model.weights.groups)}
@@ -211,7 +211,7 @@ def test_learner_step_requantises(base, dev):
         batch = policy_batch(ids.repeat_interleave(K, 0), None, tokens.reshape(B * K, n), lp.reshape(B * K, n), adv.reshape(-1))
         ts = TrainStep(model.weights, "lora", B * K, batch["input_ids"].shape[1], lora=lora, loss="policy",
                        policy=PolicyLossConfig(temperature=temp), max_grad_norm=float("inf"), refresh_adapted=True)
-        assert [op.name for op in ts._adapter_ops[-2:]] == ["bl_lora_merge_batched_bf16", "bl_quantize_weight_fp8_packed_batched"]
+        assert [op.name for op in ts.lin.adapter_ops[-2:]] == ["bl_lora_merge_batched_bf16", "bl_quantize_weight_fp8_packed_batched"]
         ts.set_batch(batch["input_ids"], batch["attention_mask"], pv_rep, batch["labels"])
         ts.set_policy_batch(batch["advantages"], batch["old_logprobs"])
         before = check_copies(lora, model, "device", "(f) before the step")

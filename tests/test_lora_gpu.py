@@ -224,7 +224,7 @@ def test_lora_dropout_step_is_consistent(dev):
     l2 = ts.forward().item()                                       # the seed moved on: another mask
     assert l1 != base_loss and l2 != l1 and abs(l1 - base_loss) < 0.2 * base_loss
     # hold the mask: every forward below runs at device seed 5
-    ts._drop_seed.fill_(4)
+    ts.lin.drop_seed.fill_(4)
     loss0 = ts.forward().item()
     ts.backward()
     st = ts.store
@@ -238,8 +238,8 @@ def test_lora_dropout_step_is_consistent(dev):
         for i, ad in enumerate(lora.adapters):
             ad.A.copy_((A0[i].float() - eps * g[i][0].view(ad.A.shape)).to(torch.bfloat16))
             ad.B.copy_((B0[i].float() - eps * g[i][1].view(ad.B.shape)).to(torch.bfloat16))
-        ops.run_all(ts._adapter_ops)
-        ts._drop_seed.fill_(4)
+        ops.run_all(ts.lin.adapter_ops)
+        ts.lin.drop_seed.fill_(4)
         d = ts.forward().item() - loss0
         deltas.append((target * loss0, d))
         print(f"lora dropout directional derivative: predicted {-target * loss0:.4f}, measured {d:.4f}")
@@ -251,8 +251,8 @@ def test_lora_dropout_step_is_consistent(dev):
     from oracle.synth import dropout_keep
     for i, ad in enumerate(lora.adapters):
         ad.A.copy_(A0[i]); ad.B.copy_(B0[i])
-    ops.run_all(ts._adapter_ops)
-    ts._drop_seed.fill_(4)
+    ops.run_all(ts.lin.adapter_ops)
+    ts.lin.drop_seed.fill_(4)
     ts.forward()                                                   # seed 5; fills ao / t of every adapted linear
     l = dims.llm_layers - 1
     packed = w.layers[l].o_w
@@ -261,7 +261,7 @@ def test_lora_dropout_step_is_consistent(dev):
     g_ = torch.Generator().manual_seed(11)
     dy = (torch.randn(Tn, D, generator=g_) * 0.5).to(torch.bfloat16)
     ts.dxb[:, :D].copy_(dy.to(dev))
-    ops.run_all(ts._lin_bwd(ts.dxb, ts.ao[l], packed, ts.dao))
+    ops.run_all(ts.lin.backward(ts.scratch.main, ts.dxb, ts.ao[l], packed, ts.dao))
     x = ts.ao[l][:, :D].float().cpu()
     Wm = ops.unpack_weight(packed).float().cpu()                   # [D, D]
     A, Bm = ad.A.float().cpu()[:, :D], ad.B.float().cpu()          # [R, D], [D, R]

@@ -182,3 +182,42 @@ def test_shift_helper_places_values_where_the_labels_go():
     back = shift_from_rows(rows, P)
     values[:, 0] = 0
     assert torch.equal(back, values)
+
+
+def test_tokens_to_rows_is_the_one_path_of_the_per_token_inputs():
+    """`tokens_to_rows` (what set_policy_batch / set_value_batch / set_preference_batch call): [B, l] values of a batch shorter
+    than the planned L → the rows `shift_to_rows` gives for the input padded to L, zero outside the selected rows; a
+    non-finite value is refused where a selected row reads it (the error names the input) and ignored elsewhere; a shape
+    that is not [B, l] is refused."""
+    from bridgelang_amd.training.step import tokens_to_rows
+    B, l, L, P = 2, 3, 5, 4
+    S = L + P
+    src = torch.tensor([[1.5, -2.0, 3.25], [0.5, 7.0, -1.0]])
+    select = torch.zeros(B, S, dtype=torch.bool)
+    select[0, P], select[0, P + 1], select[1, P + 1] = True, True, True      # rows that predict tokens 1, 2 of sequence 0 and 2 of 1
+    pad = torch.zeros(B, L)
+    pad[:, :l] = src
+    want = shift_to_rows(pad, P, 0.0)
+    assert want[0, P] == -2.0 and want[0, P + 1] == 3.25 and want[1, P] == 7.0      # the test's own reading of the layout
+    want = torch.where(select, want, torch.zeros(B, S))
+    dst = torch.full((B * S,), 9.0)
+    tokens_to_rows("advantages", src, dst, l, P, select, "on labelled positions")
+    assert torch.equal(dst, want.view(-1)) and int((dst != 0).sum()) == 3
+    dst.fill_(9.0)
+    tokens_to_rows("advantages", src.numpy(), dst, l, P, select, "on labelled positions")      # array-likes, as the setters take them
+    assert torch.equal(dst, want.view(-1))
+    bad = src.clone()
+    bad[0, 2] = float("-inf")                                        # read by selected row (0, P + 1)
+    with pytest.raises(ValueError, match="old_logprobs: 1 non-finite value.*on labelled positions"):
+        tokens_to_rows("old_logprobs", bad, dst, l, P, select, "on labelled positions")
+    ok = src.clone()
+    ok[1, 1], ok[0, 0] = float("nan"), float("inf")                  # row (1, P) is not selected; token 0 is predicted by no row
+    tokens_to_rows("old_logprobs", ok, dst, l, P, select, "on labelled positions")
+    assert torch.equal(dst, want.view(-1))
+    narrower = select.clone()
+    narrower[0] = False                                              # refusal on fewer rows than are kept (preference: paired sequences)
+    tokens_to_rows("ref_logprobs", bad, dst, l, P, select, "on labelled positions of paired sequences", refuse=narrower)
+    assert dst[P + 1] == float("-inf") and torch.equal(dst[S:], want.view(-1)[S:])
+    for shape in ((B, l + 1), (B, L), (B + 1, l), (B * l,)):
+        with pytest.raises(ValueError, match="returns: shape"):
+            tokens_to_rows("returns", torch.zeros(shape), dst, l, P, select, "on labelled positions")

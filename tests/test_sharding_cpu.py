@@ -173,3 +173,14 @@ def test_full_shard_covers_every_fsdp_unit_of_the_reference():
             for pool in {pool_of(k) for k in sharded}:
                 par = [st.grad_slot_of[k][1] for k in keys if k in st.sharded_keys and pool_of(k) == pool and pool != "layers"]
                 assert par == [i % 2 for i in range(len(par))]
+
+
+def test_param_store_module_does_not_import_the_engine():
+    """training/param_store.py is host-side bookkeeping: importing it in a fresh interpreter pulls in neither the inference
+    engine nor the training step (which imports the engine)."""
+    code = ("import sys, bridgelang_amd.training.param_store as ps; "
+            "assert ps.ParamStore and ps.STAGES and ps.pool_of('llm.layer00') == 'layers'; "
+            "bad = [m for m in ('bridgelang_amd.engine', 'bridgelang_amd.training.step') if m in sys.modules]; "
+            "assert not bad, bad")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr

@@ -214,7 +214,7 @@ def test_parameter_sharding_equals_replicated_weights(dev, stage, recompute):
             loss, norm = ts.step(1e-3, graph=(step == 2))
             log.append((loss.item(), norm.item()))
         if sp:
-            slots = ts._pool_slots["layers"]              # qkv_w is the first view carved from the slot's forward layouts
+            slots = ts.pools.slots["layers"]              # qkv_w is the first view carved from the slot's forward layouts
             assert all(w.layers[l].qkv_w.data_ptr() == slots[l % 2]["fwd"].data_ptr() for l in range(dims.llm_layers))
             from bridgelang_amd.engine import OpenVLAEngine
             with pytest.raises(RuntimeError):               # no inference over a model whose layers are sharded out
@@ -334,14 +334,14 @@ def test_fp8_wgrad_close_to_bf16_wgrad(dev):
         losses = [ts.step(2e-3)[0].item() for _ in range(8)]
         res[wg] = (loss0, norm0, grads, losses)
         if wg:   # the LAST weight gradient the backward computed on the fp8 path is layer 0's qkv: its operands are still in scratch
-            N, K, Tq = 3 * dims.llm_dim, dims.llm_dim, ts._Tq
+            N, K, Tq = 3 * dims.llm_dim, dims.llm_dim, ts.lin._Tq
             ts.forward(); ts.backward()                           # scratch + gradient of the same (post-update) step
-            qa = ts._wg_qA[:N * Tq].view(N, Tq).view(torch.float8_e4m3fn).double().cpu()
+            qa = ts.lin._wg_qA[:N * Tq].view(N, Tq).view(torch.float8_e4m3fn).double().cpu()
             from bridgelang_amd import ops
-            pb = ts._wg_pB[:K * Tq].view(torch.bfloat16).view(K // 16, Tq // 64, 64, 8)        # fragment-major packed codes of xᵀ
+            pb = ts.lin._wg_pB[:K * Tq].view(torch.bfloat16).view(K // 16, Tq // 64, 64, 8)        # fragment-major packed codes of xᵀ
             qb = ops.unpack_weight(pb).contiguous().view(torch.uint8).view(K, Tq).view(torch.float8_e4m3fn).double().cpu()
-            want = (ts._wg_sA[:N].double().cpu()[:, None] * ts._wg_sB[:K].double().cpu()[None, :]) * (qa @ qb.t())
-            u = ts._unit_of(w.layers[0].qkv_w)
+            want = (ts.lin._wg_sA[:N].double().cpu()[:, None] * ts.lin._wg_sB[:K].double().cpu()[None, :]) * (qa @ qb.t())
+            u = ts.lin.unit_of(w.layers[0].qkv_w)
             got = ts.store.grad_view(u).double().cpu()
             err = ((got - want).abs().max() / want.abs().max()).item()
             print(f"fp8 wgrad of layer 0 qkv vs fp64 on its quantised operands: max rel err {err:.2e}")

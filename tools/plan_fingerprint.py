@@ -1,8 +1,12 @@
-"""What do the op plans launch? One JSON line per op of the inference engines, the staggered pipelines and the fp8 training
-step on synthetic reduced-width weights: the kernel's name, every scalar argument and every field of its descriptors
-(device tables included), each device pointer as (owner, byte offset into the owner's allocation) — the owner being the
-attribute path under which the engine / pipeline / step / weights hold that allocation. A pointer nothing holds is an
-error. Two runs print the same lines exactly when the plans are the same launches on the same buffers:
+"""What do the op plans launch? One JSON line per op of the inference engines, the staggered pipelines and the training
+step (every stage, loss and option that changes a plan) on synthetic reduced-width weights: the kernel's name, every scalar
+argument and every field of its descriptors (device tables included), each device pointer as (owner, byte offset into the
+owner's allocation). An owner is named "a<ordinal>:<bytes>": the ordinal of the allocation's first appearance while a
+configuration's lists are walked in order, and its size — so the names do not depend on which object or attribute holds the
+allocation, only on which launches share it. A pointer that nothing reachable from the engine / pipeline / step holds is an
+error. For the training step the (position, bucket) list of the per-bucket reduce-scatter is written too, and for sharded
+parameters each unit's gather-time layout ops (the glue ops of the plans carry no tensors).
+Two runs print the same lines exactly when the plans are the same launches on the same buffers:
    python tools/plan_fingerprint.py --out before.jsonl      (at one commit)
    python tools/plan_fingerprint.py --out after.jsonl       (at another; then diff the two files)
 Run it before and after any change that is meant to leave the plans alone. Needs a GPU (tensors only; no plan is run)."""
@@ -41,27 +45,35 @@ def held_tensors(obj, path, seen):
 
 
 class Owners:
-    """Allocation intervals [base, end) → the first path that reaches each."""
+    """Allocation intervals [base, end). `find` names one "a<ordinal of first use>:<bytes>" (or, with `named`, by the
+    first path that reaches it: an op's own tensors)."""
 
-    def __init__(self, pairs):
+    def __init__(self, pairs, named=False):
         spans = {}
         for path, t in pairs:
             st = t.untyped_storage()
             if st.nbytes():
-                spans.setdefault(st.data_ptr(), (st.data_ptr() + st.nbytes(), path))
+                spans.setdefault(st.data_ptr(), (st.data_ptr() + st.nbytes(), path if named else None))
         self.bases = sorted(spans)
         self.spans = spans
+        self.n_used = 0
 
     def find(self, p):
         i = bisect.bisect_right(self.bases, p) - 1
         if i >= 0 and p < self.spans[self.bases[i]][0]:
-            return [self.spans[self.bases[i]][1], p - self.bases[i]]
+            base = self.bases[i]
+            end, name = self.spans[base]
+            if name is None:
+                name = f"a{self.n_used}:{end - base}"
+                self.spans[base] = (end, name)
+                self.n_used += 1
+            return [name, p - base]
         return None
 
 
 def describe(op, owners):
     """The JSON record of one op."""
-    own = Owners((f"keep[{i}]", t) for i, k in enumerate(op.keep) for _, t in held_tensors(k, "", set()))
+    own = Owners(((f"keep[{i}]", t) for i, k in enumerate(op.keep) for _, t in held_tensors(k, "", set())), named=True)
 
     def ptr(p):
         if not p:
@@ -129,9 +141,37 @@ def configurations(dev):
         yield pipeline(f"pipeline {name}", w, **kw)
     yield pipeline("pipeline head_dim 64", w64)
     from bridgelang_amd.training.step import TrainStep
-    for name, kw in (("fp8", {}), ("fp8 fp8_wgrad", dict(fp8_wgrad=True))):
-        ts = TrainStep(new(), "vla-train", 2, 8, fp8=True, **kw)
-        yield f"train step {name}", ts, {"forward_ops": ts.forward_ops, "backward_ops": ts.backward_ops, "repack_ops": ts.repack_ops}, None
+    from bridgelang_amd.training.policy_loss import PolicyLossConfig
+    from bridgelang_amd.training.value_loss import ValueLossConfig
+
+    def step(name, stage, w=None, **kw):
+        """Fresh weights per step: a parameter-sharded step frees the model's own allocations."""
+        ts = TrainStep(w or new(), stage, 2, 8, **kw)
+        lists = {"vision_forward_ops": ts.vision_forward_ops, "forward_ops": ts.forward_ops, "backward_ops": ts.backward_ops,
+                 "repack_ops": ts.repack_ops}
+        units = ts.pools.units if ts.pools is not None else {}      # parameter-sharded units: {bucket key: its gather-time layout ops}
+        for key, info in units.items():
+            lists[f"unit[{key}].fwd_ops"], lists[f"unit[{key}].bwd_ops"] = info["fwd_ops"], info["bwd_ops"]
+        towers = {"vfwd_tower": [len(p) for p in ts._vfwd_tower], "bwd_tower_at": getattr(ts, "_bwd_tower_at", None)}
+        return f"train step {name}", ts, lists, {"ready": ts._ready, **towers}
+
+    yield step("fp8", "vla-train", fp8=True)
+    yield step("fp8 fp8_wgrad", "vla-train", fp8=True, fp8_wgrad=True)
+    yield step("vla-train", "vla-train")
+    yield step("vla-full-train", "vla-full-train")
+    yield step("vla-full-train recompute", "vla-full-train", recompute=True)
+    yield step("vla-full-train shard_params", "vla-full-train", shard_params=True)
+    yield step("vla-train fp8 shard_params", "vla-train", fp8=True, shard_params=True)
+    yield step("vla-last-layer-train", "vla-last-layer-train")
+    yield step("align", "align")
+    for name, kw in (("lora r=8", {}), ("lora r=8 dropout=0.1", dict(dropout=0.1))):
+        ad = LoraAdapters(new(), r=8, **kw)
+        yield step(name, "lora", w=ad.w, lora=ad)
+    ad = LoraAdapters(new(), r=8).enable_fp8()
+    yield step("lora refresh_adapted fp8", "lora", w=ad.w, lora=ad, refresh_adapted=True)
+    yield step("vla-train loss=policy", "vla-train", loss="policy", value=ValueLossConfig(),
+               policy=PolicyLossConfig(token_range=(31744, 256), ratio_level="action"))
+    yield step("vla-train loss=preference", "vla-train", loss="preference")
 
 
 def main():
@@ -140,10 +180,10 @@ def main():
     a = ap.parse_args()
     n_ops = 0
     with open(a.out, "w") as f:
-        for cfg, owner, lists, layer_ends in configurations(torch.device("cuda:0")):
+        for cfg, owner, lists, marks in configurations(torch.device("cuda:0")):
             owners = Owners(held_tensors(owner, "", set()))
-            if layer_ends is not None:
-                f.write(json.dumps({"cfg": cfg, "layer_ends": layer_ends}) + "\n")
+            if marks is not None:               # positions inside the lists: layer ends / bucket-ready markers / tower splits
+                f.write(json.dumps({"cfg": cfg, **(marks if isinstance(marks, dict) else {"layer_ends": marks})}) + "\n")
             for lname, plan in lists.items():
                 for i, op in enumerate(plan):
                     f.write(json.dumps({"cfg": cfg, "list": lname, "i": i, **describe(op, owners)}) + "\n")
