@@ -787,13 +787,27 @@ __global__ __launch_bounds__(256) void gemm_mid2_kernel(GemmArgs p) {
 // K-tile: 5 activation — 36 real ones over 8 waves, the 4 surplus ones hit a zero-size descriptor: no traffic — and 4
 // weight. K order per output = every other kernel's (K-tile by K-tile, two 32-steps each): bit-identical results.
 // Staggered wave groups (the structure of gemm256s_kernel on the 288-row tile): the two 4-wave groups that
-// share each SIMD alternate roles segment by segment — one runs a 12-MFMA block while the other issues its LDS-DMA pieces
-// and reads the fragments of its next block — with one raw s_barrier per segment. A single X register set suffices (a
-// group's fragment reads happen while its MFMAs are not running): 9 × 4 accumulator tiles (144 VGPRs) + 6 + 4 + 4 fragments.
-// K-tile T+1's nine pieces per wave are issued over the six slots p6(T-1), p1 … p5(T) (2, 1, 2, 1, 2, 1); slot p6(T) issues
-// the first two pieces of T+2 and waits `vmcnt(2)`: everything older — all of T+1 — has landed, two barriers before its
-// first read (slot p1 of T+1), and the DMA stream never drains. Stage T is re-filled from slot p6(T) on; its last reads
-// are in slot p5(T) of either group, one barrier earlier.
+// share each SIMD alternate roles segment by segment — one runs a 24-MFMA phase while the other reads the fragments of its
+// next phase and issues LDS-DMA pieces — with one raw s_barrier per segment. Three phases per K-tile: phase q runs
+// activation third q (48 of the wave's 144 rows) against all four weight column tiles, both k-steps. A single X register
+// set suffices (a group's fragment reads happen while its MFMAs are not running) and the K-tile's 8 weight fragments are
+// read once: 9 × 4 accumulator tiles (144 VGPRs) + 6 + 4 + 4 fragments.
+// Slot q of K-tile T (before phase q; reads first, pieces second):
+//   slot 0: reads X third 0 + Ya + Yb (14), issues activation pieces 0, 1 of T+1
+//   slot 1: reads X third 1 (6),            issues activation pieces 2, 3, 4 of T+1
+//   slot 2: reads X third 2 (6),            issues the four weight pieces of T+2, waits `vmcnt(4)`
+// Segments (one barrier after each): group A runs slot q of T in segment 6T + 2q - 1, group B in segment 6T + 2q.
+// LDS reuse rule, held by construction: a piece is issued into a stage only after a barrier that follows the last
+// fragment read of the rows it overwrites by BOTH groups (reads are complete at the slot's lgkmcnt(0), before its barrier).
+//   - slots 0 and 1 of T (segments ≥ 6T - 1) write stage T+1 = the stage of T-1, whose last read is group B's slot 2 of
+//     T-1 in segment 6T - 2.
+//   - slot 2 of T (segments 6T + 3 / 6T + 4) writes stage T while third 2 of it is still being read (B's slot 2 runs in
+//     6T + 4, beside other waves' issues). It therefore issues only the weight pieces: the weight area of stage T is last
+//     read in slot 0 (segment 6T by B). No activation piece but piece 0 lies wholly inside thirds 0 and 1.
+// Landing: at slot 2 of T the wave's queue holds, oldest first, the nine pieces of T+1 (4 from slot 2 of T-1, 2 + 3 from
+// slots 0, 1 of T) and the four of T+2 just issued; `vmcnt(4)` leaves only those four outstanding, so all of T+1 has
+// landed when B's slot 2 ends (segment 6T + 4) and A's first read of T+1 is in segment 6T + 5, one barrier on. The DMA
+// stream never drains and there is no `vmcnt(0)` in the loop. Nothing else orders a ds_read behind a pending LDS-DMA.
 // ======================================================================================================================
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm288s_kernel(GemmArgs p) {
@@ -853,13 +867,17 @@ __global__ __launch_bounds__(512) void gemm288s_kernel(GemmArgs p) {
     DST[j * 2 + 1] = *(const bf16x8_t*)((SB) + offY + (2 * (NH) + j) * 2048 + 1024);                      \
   }
 #define MMA(YR, T3, NH)                                                                                   \
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                        \
+    _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                         \
+      _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                       \
+        acc[2 * (NH) + j][3 * (T3) + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                        \
+            YR[j * 2 + ks], X[i * 2 + ks], acc[2 * (NH) + j][3 * (T3) + i], 0, 0, 0);
+  // phase T3: activation third T3 against all four weight column tiles, both k-steps — 24 MFMAs
+#define PHASE(T3)                                                                                         \
   do {                                                                                                    \
     __builtin_amdgcn_s_setprio(1);                                                                        \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                      \
-      _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                       \
-        _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                     \
-          acc[2 * (NH) + j][3 * (T3) + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                      \
-              YR[j * 2 + ks], X[i * 2 + ks], acc[2 * (NH) + j][3 * (T3) + i], 0, 0, 0);                   \
+    MMA(Ya, T3, 0)                                                                                        \
+    MMA(Yb, T3, 1)                                                                                        \
     __builtin_amdgcn_s_setprio(0);                                                                        \
   } while (0)
 #define BAR()                                                                                             \
@@ -868,14 +886,11 @@ __global__ __launch_bounds__(512) void gemm288s_kernel(GemmArgs p) {
     __builtin_amdgcn_sched_barrier(0);                                                                    \
   } while (0)
 #define WAIT_LGKM() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define WAIT_VM2_LGKM() asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory")
-  // the six slots of K-tile T (stage SC; SN = the other stage): fragment reads first, then the LDS-DMA issue
-#define SLOT1(SC, T) do { READ_X(0, SC); READ_Y(Ya, 0, SC); __builtin_amdgcn_sched_barrier(0); ISSUE_A(2, (T) + 1); WAIT_LGKM(); } while (0)
-#define SLOT2(SC, T) do { READ_Y(Yb, 1, SC); __builtin_amdgcn_sched_barrier(0); ISSUE_A(3, (T) + 1); ISSUE_A(4, (T) + 1); WAIT_LGKM(); } while (0)
-#define SLOT3(SC, T) do { READ_X(1, SC); __builtin_amdgcn_sched_barrier(0); ISSUE_W(0, 0, (T) + 1); WAIT_LGKM(); } while (0)
-#define SLOT4(SC, T) do { ISSUE_W(0, 1, (T) + 1); ISSUE_W(1, 0, (T) + 1); } while (0)
-#define SLOT5(SC, T) do { READ_X(2, SC); __builtin_amdgcn_sched_barrier(0); ISSUE_W(1, 1, (T) + 1); WAIT_LGKM(); } while (0)
-#define SLOT6(SC, T) do { ISSUE_A(0, (T) + 2); ISSUE_A(1, (T) + 2); WAIT_VM2_LGKM(); } while (0)
+#define WAIT_VM4_LGKM() asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory")
+  // the three slots of K-tile T (stage SC): fragment reads first, then the LDS-DMA issue
+#define SLOT0(SC, T) do { READ_X(0, SC); READ_Y(Ya, 0, SC); READ_Y(Yb, 1, SC); __builtin_amdgcn_sched_barrier(0); ISSUE_A(0, (T) + 1); ISSUE_A(1, (T) + 1); WAIT_LGKM(); } while (0)
+#define SLOT1(SC, T) do { READ_X(1, SC); __builtin_amdgcn_sched_barrier(0); ISSUE_A(2, (T) + 1); ISSUE_A(3, (T) + 1); ISSUE_A(4, (T) + 1); WAIT_LGKM(); } while (0)
+#define SLOT2(SC, T) do { READ_X(2, SC); __builtin_amdgcn_sched_barrier(0); ISSUE_W(0, 0, (T) + 2); ISSUE_W(0, 1, (T) + 2); ISSUE_W(1, 0, (T) + 2); ISSUE_W(1, 1, (T) + 2); WAIT_VM4_LGKM(); } while (0)
 #define BL_EPILOGUE()                                                                                     \
   do {                                                                                                    \
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                      \
@@ -893,48 +908,36 @@ __global__ __launch_bounds__(512) void gemm288s_kernel(GemmArgs p) {
   char* const S0 = smem;
   char* const S1 = smem + STAGE;
 
-  // prologue: all nine pieces of K-tile 0, then what slot p6 of "K-tile -1" issues (the first two pieces of K-tile 1)
+  // prologue: all nine pieces of K-tile 0, then what slot 2 of "K-tile -1" issues (the four weight pieces of K-tile 1)
   ISSUE_A(0, 0); ISSUE_A(1, 0); ISSUE_A(2, 0); ISSUE_A(3, 0); ISSUE_A(4, 0);
   ISSUE_W(0, 0, 0); ISSUE_W(0, 1, 0); ISSUE_W(1, 0, 0); ISSUE_W(1, 1, 0);
-  ISSUE_A(0, 1); ISSUE_A(1, 1);
-  asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+  ISSUE_W(0, 0, 1); ISSUE_W(0, 1, 1); ISSUE_W(1, 0, 1); ISSUE_W(1, 1, 1);
+  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   BAR();
   if (wm == 0) {
-    // ======================= group A: MFMA block first, then the slot of the NEXT block =======================
-    SLOT1(S0, 0);
+    // ======================= group A: MFMA phase first, then the slot of the NEXT phase =======================
+    SLOT0(S0, 0);
     BAR();
     for (int t = 0; t < nk; t += 2) {        // nk is even (launcher: K % 128 == 0)
-      MMA(Ya, 0, 0); BAR();   SLOT2(S0, t); BAR();
-      MMA(Yb, 0, 1); BAR();   SLOT3(S0, t); BAR();
-      MMA(Yb, 1, 1); BAR();   SLOT4(S0, t); BAR();
-      MMA(Ya, 1, 0); BAR();   SLOT5(S0, t); BAR();
-      MMA(Ya, 2, 0); BAR();   SLOT6(S0, t); BAR();
-      MMA(Yb, 2, 1); BAR();   SLOT1(S1, t + 1); BAR();
-      MMA(Ya, 0, 0); BAR();   SLOT2(S1, t + 1); BAR();
-      MMA(Yb, 0, 1); BAR();   SLOT3(S1, t + 1); BAR();
-      MMA(Yb, 1, 1); BAR();   SLOT4(S1, t + 1); BAR();
-      MMA(Ya, 1, 0); BAR();   SLOT5(S1, t + 1); BAR();
-      MMA(Ya, 2, 0); BAR();   SLOT6(S1, t + 1); BAR();
-      MMA(Yb, 2, 1); BAR();   SLOT1(S0, t + 2); BAR();
+      PHASE(0); BAR();   SLOT1(S0, t); BAR();
+      PHASE(1); BAR();   SLOT2(S0, t); BAR();
+      PHASE(2); BAR();   SLOT0(S1, t + 1); BAR();
+      PHASE(0); BAR();   SLOT1(S1, t + 1); BAR();
+      PHASE(1); BAR();   SLOT2(S1, t + 1); BAR();
+      PHASE(2); BAR();   SLOT0(S0, t + 2); BAR();
     }
     BL_EPILOGUE();
     return;
   }
-  // ========================= group B: the slot of THIS block first, then its MFMA block =========================
+  // ========================= group B: the slot of THIS phase first, then its MFMA phase =========================
   BAR();
   for (int t = 0; t < nk; t += 2) {
-    SLOT1(S0, t); BAR();       MMA(Ya, 0, 0); BAR();
-    SLOT2(S0, t); BAR();       MMA(Yb, 0, 1); BAR();
-    SLOT3(S0, t); BAR();       MMA(Yb, 1, 1); BAR();
-    SLOT4(S0, t); BAR();       MMA(Ya, 1, 0); BAR();
-    SLOT5(S0, t); BAR();       MMA(Ya, 2, 0); BAR();
-    SLOT6(S0, t); BAR();       MMA(Yb, 2, 1); BAR();
-    SLOT1(S1, t + 1); BAR();   MMA(Ya, 0, 0); BAR();
-    SLOT2(S1, t + 1); BAR();   MMA(Yb, 0, 1); BAR();
-    SLOT3(S1, t + 1); BAR();   MMA(Yb, 1, 1); BAR();
-    SLOT4(S1, t + 1); BAR();   MMA(Ya, 1, 0); BAR();
-    SLOT5(S1, t + 1); BAR();   MMA(Ya, 2, 0); BAR();
-    SLOT6(S1, t + 1); BAR();   MMA(Yb, 2, 1); BAR();
+    SLOT0(S0, t); BAR();       PHASE(0); BAR();
+    SLOT1(S0, t); BAR();       PHASE(1); BAR();
+    SLOT2(S0, t); BAR();       PHASE(2); BAR();
+    SLOT0(S1, t + 1); BAR();   PHASE(0); BAR();
+    SLOT1(S1, t + 1); BAR();   PHASE(1); BAR();
+    SLOT2(S1, t + 1); BAR();   PHASE(2); BAR();
   }
   BL_EPILOGUE();
 #undef BL_RS
@@ -943,15 +946,13 @@ __global__ __launch_bounds__(512) void gemm288s_kernel(GemmArgs p) {
 #undef READ_X
 #undef READ_Y
 #undef MMA
+#undef PHASE
 #undef BAR
 #undef WAIT_LGKM
-#undef WAIT_VM2_LGKM
+#undef WAIT_VM4_LGKM
+#undef SLOT0
 #undef SLOT1
 #undef SLOT2
-#undef SLOT3
-#undef SLOT4
-#undef SLOT5
-#undef SLOT6
 #undef BL_EPILOGUE
 #endif
 }

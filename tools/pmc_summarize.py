@@ -41,8 +41,9 @@ def per_call(counter):
     """kernels of one bl_gemm_bf16 call (main launch + tail launch) summed; median over the 3 calls per shape"""
     rs = [r for r in rows[counter] if "gemm" in r[1] and "pack" not in r[1]]
     calls, cur = [], []
-    for r in rs:                                  # a tail kernel belongs to the preceding main kernel
-        if "tail" in r[1] and cur:
+    for r in rs:                                  # a tail kernel belongs to the preceding main kernel: gemm_ring8_kernel in
+        # tail mode follows the gemm256s launch of its call (the driver makes no ring8-only call after a 256 one)
+        if cur and ("tail" in r[1] or ("gemm_ring8_kernel" in r[1] and "gemm256s_kernel" in cur[0][1])):
             cur.append(r)
         else:
             if cur:
