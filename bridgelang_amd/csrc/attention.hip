@@ -685,21 +685,21 @@ int fill_args(const bl_attn_desc* d, AttnArgs& a) {
 }  // namespace bl_attention_impl
 using namespace bl_attention_impl;
 
-template <int HD, bool CAUSAL>
+template <int HD, bool CAUSAL, bool ROPE = false>
 int launch_seq(const AttnArgs& a, const bl_attn_desc* d, hipStream_t s) {
   constexpr int ROWB = (HD <= 64) ? 128 : 256;
   const int s_pad = (d->Skv + 31) / 32 * 32;
   const int lds = 2 * s_pad * ROWB;
   static bool attr_set = false;
   if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_seq_kernel<HD, CAUSAL>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_seq_kernel<HD, CAUSAL, ROPE>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
       return BL_E_LAUNCH;
     attr_set = true;
   }
   const int heads = d->B * d->H;
   const int nsp = heads >= 128 ? 1 : (heads >= 64 ? 2 : 4);
-  hipLaunchKernelGGL((attn_seq_kernel<HD, CAUSAL>), dim3(heads, nsp), dim3(512), lds, s, a, s_pad);
+  hipLaunchKernelGGL((attn_seq_kernel<HD, CAUSAL, ROPE>), dim3(heads, nsp), dim3(512), lds, s, a, s_pad);
   return BL_OK;
 }
 
@@ -746,17 +746,8 @@ extern "C" int bl_attention_rope_bf16(const bl_attn_desc* d, const bl_bf16* cos_
   if (d->head_dim != 128 || !d->causal || d->Skv != d->Sq || d->Sq > 320 || pos0 < 0 || pos0 + d->Skv > cache_len) return BL_E_SHAPE;
   if (!bl_aligned16(cos_tab) || !bl_aligned16(sin_tab) || !bl_aligned16(k_cache) || !bl_aligned16(v_cache)) return BL_E_ALIGN;
   a.cos_tab = cos_tab; a.sin_tab = sin_tab; a.k_cache = k_cache; a.v_cache = v_cache; a.cache_len = cache_len; a.pos0 = pos0;
-  const int s_pad = (d->Skv + 31) / 32 * 32, lds = 2 * s_pad * 256;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_seq_kernel<128, true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return BL_E_LAUNCH;
-    attr_set = true;
-  }
-  const int heads = d->B * d->H;
-  const int nsp = heads >= 128 ? 1 : (heads >= 64 ? 2 : 4);
-  hipLaunchKernelGGL((attn_seq_kernel<128, true, true>), dim3(heads, nsp), dim3(512), lds, (hipStream_t)stream, a, s_pad);
+  const int r = launch_seq<128, true, true>(a, d, (hipStream_t)stream);
+  if (r != BL_OK) return r;
   BL_CHECK_LAUNCH();
   return BL_OK;
 }
@@ -766,102 +757,97 @@ extern "C" int bl_attention_lse_bf16(const bl_attn_desc* d, float* lse, void* st
   return attention_launch(d, lse, stream);
 }
 
+// ---- decode: every entry point checks its own arguments, then ends in launch_decode ----
+// The checks all five forms share, after the form's own and in the order they have always run, and the launch. The
+// RoPE forms read the step's new k / v from the second and third thirds of the fused qkv row behind d->q.
+template <bool ROPE, bool GROUPED = false, bool GPOS = false>
+static int launch_decode(const bl_attn_desc* d, const AttnArgs& a, const bl_bf16* cos_tab, const bl_bf16* sin_tab, int pos,
+                         int n_groups, const std::conditional_t<GPOS, DecodeGroupsPos, DecodeGroups>& gr, void* stream) {
+  if (d->head_dim != 128 || d->Sq != 1) return BL_E_SHAPE;
+  if ((((uintptr_t)d->o) & 15) || (ROPE && (!bl_aligned16(cos_tab) || !bl_aligned16(sin_tab)))) return BL_E_ALIGN;
+  const long D = (long)d->H * d->head_dim;
+  hipLaunchKernelGGL((attn_decode_kernel<ROPE, GROUPED, GPOS>), dim3(n_groups * d->B * d->H), dim3(256), 0, (hipStream_t)stream, a,
+                     ROPE ? d->q + D : nullptr, ROPE ? d->q + 2 * D : nullptr, cos_tab, sin_tab, pos, gr);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
 extern "C" int bl_attention_decode_bf16(const bl_attn_desc* d, void* stream) {
   AttnArgs a;
   const int rc = fill_args(d, a);
   if (rc != BL_OK) return rc;
-  if (d->head_dim != 128 || d->Sq != 1 || d->Skv > 2048) return BL_E_SHAPE;
-  if (((uintptr_t)d->o) & 15) return BL_E_ALIGN;
-  hipLaunchKernelGGL((attn_decode_kernel<false>), dim3(d->B * d->H), dim3(256), 0, (hipStream_t)stream, a,
-                     (const uint16_t*)nullptr, (const uint16_t*)nullptr, (const uint16_t*)nullptr, (const uint16_t*)nullptr, 0,
-                     DecodeGroups{});
-  BL_CHECK_LAUNCH();
-  return BL_OK;
+  if (d->Skv > 2048) return BL_E_SHAPE;
+  return launch_decode<false>(d, a, nullptr, nullptr, 0, 1, DecodeGroups{}, stream);
+}
+
+// One batch at cache row `pos`; with `per_seq`, rope_pos[b] is each sequence's own rotation position (right-padded prompts).
+static int decode_rope(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab, int32_t pos, bool per_seq,
+                       const int32_t* rope_pos, void* stream) {
+  AttnArgs a;
+  const int rc = fill_args(d, a);
+  if (rc != BL_OK) return rc;
+  if (!cos_tab || !sin_tab || (per_seq && !rope_pos)) return BL_E_ARG;
+  if (d->Skv > 2048 || pos < 0 || d->Skv != pos + 1) return BL_E_SHAPE;
+  a.rope_pos = rope_pos;
+  return launch_decode<true>(d, a, cos_tab, sin_tab, pos, 1, DecodeGroups{}, stream);
 }
 
 extern "C" int bl_attention_decode_rope_bf16(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab,
                                              int32_t pos, void* stream) {
-  AttnArgs a;
-  const int rc = fill_args(d, a);
-  if (rc != BL_OK) return rc;
-  if (!cos_tab || !sin_tab) return BL_E_ARG;
-  if (d->head_dim != 128 || d->Sq != 1 || d->Skv > 2048 || pos < 0 || d->Skv != pos + 1) return BL_E_SHAPE;
-  if ((((uintptr_t)d->o) & 15) || !bl_aligned16(cos_tab) || !bl_aligned16(sin_tab)) return BL_E_ALIGN;
-  const long D = (long)d->H * d->head_dim;   // q / k_new / v_new are the three thirds of the fused qkv row
-  hipLaunchKernelGGL((attn_decode_kernel<true>), dim3(d->B * d->H), dim3(256), 0, (hipStream_t)stream, a, d->q + D,
-                     d->q + 2 * D, cos_tab, sin_tab, pos, DecodeGroups{});
-  BL_CHECK_LAUNCH();
-  return BL_OK;
+  return decode_rope(d, cos_tab, sin_tab, pos, false, nullptr, stream);
 }
 
 extern "C" int bl_attention_decode_rope_pos_bf16(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab,
                                                  int32_t pos, const int32_t* rope_pos, void* stream) {
+  return decode_rope(d, cos_tab, sin_tab, pos, true, rope_pos, stream);
+}
+
+// n_groups batches in one launch. Pos is int32_t: pos[g] is group g's cache row, a host int (cache_len unused); or
+// const int32_t* (GPOS): pos[g][b] is every sequence's own position on the device, inside caches of cache_len rows.
+template <bool GPOS, class Pos>
+static int decode_rope_grouped(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab, int32_t n_groups,
+                               bl_bf16* const* k_caches, bl_bf16* const* v_caches, const Pos* pos, int32_t cache_len,
+                               void* stream) {
+  if (!d || !d->q || !d->o || !cos_tab || !sin_tab || !k_caches || !v_caches || !pos) return BL_E_ARG;
+  if (GPOS && d->key_mask) return BL_E_ARG;   // every sequence attends to its own rows 0..pos: no key mask in this form
+  if (n_groups < 1 || n_groups > 8 || (GPOS && (cache_len < 1 || cache_len > 2048))) return BL_E_SHAPE;
+  bl_attn_desc d0 = *d;                       // validate strides / alignment with group 0's caches in place of k / v
+  d0.k = k_caches[0]; d0.v = v_caches[0];
+  if constexpr (GPOS) d0.Skv = cache_len; else d0.Skv = pos[0] + 1;
   AttnArgs a;
-  const int rc = fill_args(d, a);
+  const int rc = fill_args(&d0, a);
   if (rc != BL_OK) return rc;
-  if (!cos_tab || !sin_tab || !rope_pos) return BL_E_ARG;
-  if (d->head_dim != 128 || d->Sq != 1 || d->Skv > 2048 || pos < 0 || d->Skv != pos + 1) return BL_E_SHAPE;
-  if ((((uintptr_t)d->o) & 15) || !bl_aligned16(cos_tab) || !bl_aligned16(sin_tab)) return BL_E_ALIGN;
-  a.rope_pos = rope_pos;
-  const long D = (long)d->H * d->head_dim;
-  hipLaunchKernelGGL((attn_decode_kernel<true>), dim3(d->B * d->H), dim3(256), 0, (hipStream_t)stream, a, d->q + D,
-                     d->q + 2 * D, cos_tab, sin_tab, pos, DecodeGroups{});
-  BL_CHECK_LAUNCH();
-  return BL_OK;
+  std::conditional_t<GPOS, DecodeGroupsPos, DecodeGroups> gr{};
+  for (int g = 0; g < n_groups; ++g) {
+    if (!k_caches[g] || !v_caches[g]) return BL_E_ARG;
+    if constexpr (GPOS) {
+      if (!pos[g]) return BL_E_ARG;
+      if (((uintptr_t)pos[g]) & 3) return BL_E_ALIGN;
+      gr.rope_pos[g] = pos[g];
+    } else {
+      if (pos[g] < 0 || pos[g] + 1 > 2048) return BL_E_SHAPE;
+      gr.pos[g] = pos[g];
+    }
+    if (!bl_aligned16(k_caches[g]) || !bl_aligned16(v_caches[g])) return BL_E_ALIGN;
+    gr.k[g] = k_caches[g]; gr.v[g] = v_caches[g];
+  }
+  if constexpr (GPOS) {
+    gr.cache_len = cache_len;
+    // the guard keeps a position inside [0, cache_len): the cache row stride must hold that many rows per head
+    if (d->k_hs < (int64_t)cache_len * d->k_rs || d->v_hs < (int64_t)cache_len * d->v_rs || d->k_rs < 128 || d->v_rs < 128)
+      return BL_E_SHAPE;
+  }
+  return launch_decode<true, true, GPOS>(d, a, cos_tab, sin_tab, 0, n_groups, gr, stream);
 }
 
 extern "C" int bl_attention_decode_rope_grouped_bf16(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab,
                                                      int32_t n_groups, bl_bf16* const* k_caches, bl_bf16* const* v_caches,
                                                      const int32_t* pos, void* stream) {
-  if (!d || !d->q || !d->o || !cos_tab || !sin_tab || !k_caches || !v_caches || !pos) return BL_E_ARG;
-  if (n_groups < 1 || n_groups > 8) return BL_E_SHAPE;
-  bl_attn_desc d0 = *d;                       // validate strides / alignment with group 0's caches in place of k / v
-  d0.k = k_caches[0]; d0.v = v_caches[0]; d0.Skv = pos[0] + 1;
-  AttnArgs a;
-  const int rc = fill_args(&d0, a);
-  if (rc != BL_OK) return rc;
-  DecodeGroups gr{};
-  for (int g = 0; g < n_groups; ++g) {
-    if (!k_caches[g] || !v_caches[g]) return BL_E_ARG;
-    if (pos[g] < 0 || pos[g] + 1 > 2048) return BL_E_SHAPE;
-    if (!bl_aligned16(k_caches[g]) || !bl_aligned16(v_caches[g])) return BL_E_ALIGN;
-    gr.k[g] = k_caches[g]; gr.v[g] = v_caches[g]; gr.pos[g] = pos[g];
-  }
-  if (d->head_dim != 128 || d->Sq != 1) return BL_E_SHAPE;
-  if ((((uintptr_t)d->o) & 15) || !bl_aligned16(cos_tab) || !bl_aligned16(sin_tab)) return BL_E_ALIGN;
-  const long D = (long)d->H * d->head_dim;
-  hipLaunchKernelGGL((attn_decode_kernel<true, true>), dim3(n_groups * d->B * d->H), dim3(256), 0, (hipStream_t)stream, a,
-                     d->q + D, d->q + 2 * D, cos_tab, sin_tab, 0, gr);
-  BL_CHECK_LAUNCH();
-  return BL_OK;
+  return decode_rope_grouped<false>(d, cos_tab, sin_tab, n_groups, k_caches, v_caches, pos, 0, stream);
 }
 
 extern "C" int bl_attention_decode_rope_pos_grouped_bf16(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab,
                                                          int32_t n_groups, bl_bf16* const* k_caches, bl_bf16* const* v_caches,
                                                          const int32_t* const* rope_pos, int32_t cache_len, void* stream) {
-  if (!d || !d->q || !d->o || !cos_tab || !sin_tab || !k_caches || !v_caches || !rope_pos) return BL_E_ARG;
-  if (d->key_mask) return BL_E_ARG;           // every sequence attends to its own rows 0..pos: no key mask in this form
-  if (n_groups < 1 || n_groups > 8 || cache_len < 1 || cache_len > 2048) return BL_E_SHAPE;
-  bl_attn_desc d0 = *d;                       // validate strides / alignment with group 0's caches in place of k / v
-  d0.k = k_caches[0]; d0.v = v_caches[0]; d0.Skv = cache_len;
-  AttnArgs a;
-  const int rc = fill_args(&d0, a);
-  if (rc != BL_OK) return rc;
-  DecodeGroupsPos gr{};
-  for (int g = 0; g < n_groups; ++g) {
-    if (!k_caches[g] || !v_caches[g] || !rope_pos[g]) return BL_E_ARG;
-    if (!bl_aligned16(k_caches[g]) || !bl_aligned16(v_caches[g]) || (((uintptr_t)rope_pos[g]) & 3)) return BL_E_ALIGN;
-    gr.k[g] = k_caches[g]; gr.v[g] = v_caches[g]; gr.rope_pos[g] = rope_pos[g];
-  }
-  gr.cache_len = cache_len;
-  if (d->head_dim != 128 || d->Sq != 1) return BL_E_SHAPE;
-  // the guard keeps a position inside [0, cache_len): the cache row stride must hold that many rows per head
-  if (d->k_hs < (int64_t)cache_len * d->k_rs || d->v_hs < (int64_t)cache_len * d->v_rs || d->k_rs < 128 || d->v_rs < 128)
-    return BL_E_SHAPE;
-  if ((((uintptr_t)d->o) & 15) || !bl_aligned16(cos_tab) || !bl_aligned16(sin_tab)) return BL_E_ALIGN;
-  const long D = (long)d->H * d->head_dim;
-  hipLaunchKernelGGL((attn_decode_kernel<true, true, true>), dim3(n_groups * d->B * d->H), dim3(256), 0, (hipStream_t)stream, a,
-                     d->q + D, d->q + 2 * D, cos_tab, sin_tab, 0, gr);
-  BL_CHECK_LAUNCH();
-  return BL_OK;
+  return decode_rope_grouped<true>(d, cos_tab, sin_tab, n_groups, k_caches, v_caches, rope_pos, cache_len, stream);
 }

@@ -36,6 +36,31 @@ def _bf16(t: torch.Tensor, what: str) -> torch.Tensor:
     return t
 
 
+def _f32(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype != torch.float32 or not t.is_cuda:
+        raise TypeError(f"{what}: expected a CUDA/HIP float32 tensor, got {t.dtype} on {t.device}")
+    return t
+
+
+def _contig_bf16(fn: str, *pairs) -> None:
+    """Every (tensor, name) pair is a contiguous bf16 device tensor."""
+    for t, n in pairs:
+        if not _bf16(t, n).is_contiguous():
+            raise ValueError(f"{fn}: {n} must be contiguous")
+
+
+def _dev(t, dtype: torch.dtype, shape, what: str) -> torch.Tensor:
+    """`t` is a contiguous device tensor of `dtype` and `shape`: a tuple (None = any extent) or an element count."""
+    ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_cuda and t.is_contiguous()
+    if ok and isinstance(shape, int):
+        ok = t.numel() == shape
+    elif ok:
+        ok = t.dim() == len(shape) and all(w is None or w == s for s, w in zip(t.shape, shape))
+    if not ok:
+        raise TypeError(f"{what} must be a contiguous CUDA/HIP {dtype} tensor {list(shape) if isinstance(shape, tuple) else [shape]}")
+    return t
+
+
 def _rows(t: torch.Tensor, what: str) -> int:
     """Leading dimension (elements) of a 2-D view whose last dim is contiguous."""
     if t.dim() != 2 or t.stride(1) != 1:
@@ -56,6 +81,13 @@ class Op:
         rc = self.fn(*self.args, stream if stream is not None else _stream())
         if rc != 0:
             _lib.check(rc, self.name)
+
+
+def _op(name: str, args: tuple, keep: tuple, run: bool, nbytes: float = 0.0, flops: float = 0.0) -> Op:
+    op = Op(name, getattr(_lib.load(), name), args, keep, flops=flops, nbytes=nbytes)
+    if run:
+        op.run()
+    return op
 
 
 def glue(name: str, fn, keep: tuple = ()) -> Op:
@@ -79,13 +111,11 @@ def run_all(ops: Sequence[Op]) -> None:
 def pack_weight(w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """nn.Linear-layout weight [N, K] (last dim contiguous) → fragment-major [N/16, K/32, 64, 8] (bl_pack_weight_bf16).
     N % 16 == 0 and K % 32 == 0 (zero-pad first). Done once at load time."""
-    lib = _lib.load()
     _bf16(w, "w")
     N, K = w.shape
     if out is None:
         out = torch.empty(N // 16, K // 32, 64, 8, dtype=torch.bfloat16, device=w.device)
-    _lib.check(lib.bl_pack_weight_bf16(w.data_ptr(), _rows(w, "w"), N, K, _bf16(out, "out").data_ptr(), _stream()),
-               "bl_pack_weight_bf16")
+    _op("bl_pack_weight_bf16", (w.data_ptr(), _rows(w, "w"), N, K, _bf16(out, "out").data_ptr()), (w, out), True)
     return out
 
 
@@ -107,6 +137,25 @@ def skinny_supported(M: int, K: int, epilogue: int) -> bool:
 def skinny_rows_supported(M: int, K: int, epilogue: int) -> bool:
     """Shapes bl_gemm_skinny_rows_bf16 takes: up to 128 stacked rows in the skinny kernel's summation order."""
     return M <= 128 and K in SKINNY_K and epilogue in _SKINNY_EPI
+
+
+def _gemm_desc(A, lda, W, out, M, N, K, epilogue, bias, scale, res, res_row_mod, out_map, keep):
+    """The bl_gemm_desc of gemm / gemm_fp8 and the tensors it points to, after those already in `keep`."""
+    d = GemmDesc()
+    d.A, d.lda = A.data_ptr(), lda
+    d.W, d.ldw = W.data_ptr(), K
+    d.C, d.ldc = out.data_ptr(), _rows(out, "out")
+    d.M, d.N, d.K, d.epilogue = M, N, K, epilogue
+    if bias is not None:
+        d.bias = _bf16(bias, "bias").data_ptr(); keep.append(bias)
+    if scale is not None:
+        d.scale = _bf16(scale, "scale").data_ptr(); keep.append(scale)
+    if res is not None:
+        d.res, d.ldres = _bf16(res, "res").data_ptr(), _rows(res, "res"); keep.append(res)
+    d.res_row_mod = res_row_mod
+    if out_map is not None:
+        d.out_group, d.out_stride, d.out_offset = out_map
+    return d, keep
 
 
 def gemm(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue: int = EPI_NONE, *,
@@ -131,7 +180,6 @@ def gemm(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue: int = EP
     `skinny_rows=True`: bl_gemm_skinny_rows_bf16 — up to 128 rows in the skinny kernel's arithmetic (row results
     bit-identical to the M <= 16 kernel; the merged decode iteration of StaggeredDecodePipeline).
     """
-    lib = _lib.load()
     _bf16(A, "A"); _bf16(W, "W")
     if W.dim() != 4 or W.shape[2:] != (64, 8) or not W.is_contiguous():
         raise ValueError(f"gemm: W must be a packed weight [N/16, K/32, 64, 8] (ops.pack_weight), got {tuple(W.shape)}")
@@ -142,19 +190,7 @@ def gemm(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue: int = EP
     want = torch.float32 if epilogue in (EPI_F32, EPI_F32_BF16R) else torch.bfloat16
     if out.dtype != want or not out.is_cuda:
         raise TypeError(f"gemm: out must be {want} on device")
-    d = GemmDesc()
-    d.A, d.lda = A.data_ptr(), _rows(A, "A")
-    d.W, d.ldw = W.data_ptr(), K
-    d.C, d.ldc = out.data_ptr(), _rows(out, "out")
-    d.M, d.N, d.K, d.epilogue = M, N, K, epilogue
-    keep = [A, W, out]
-    if bias is not None:
-        d.bias = _bf16(bias, "bias").data_ptr(); keep.append(bias)
-    if scale is not None:
-        d.scale = _bf16(scale, "scale").data_ptr(); keep.append(scale)
-    if res is not None:
-        d.res, d.ldres = _bf16(res, "res").data_ptr(), _rows(res, "res"); keep.append(res)
-    d.res_row_mod = res_row_mod
+    d, keep = _gemm_desc(A, _rows(A, "A"), W, out, M, N, K, epilogue, bias, scale, res, res_row_mod, out_map, [A, W, out])
     if epilogue in (EPI_SWIGLU_KEEP, EPI_BIAS_GELU_KEEP):
         if out2 is None:
             raise ValueError("gemm: the *_KEEP epilogues need out2")
@@ -167,8 +203,6 @@ def gemm(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue: int = EP
     if epilogue in (EPI_SWIGLU_BWD, EPI_GELU_BWD) and (res is None or res.shape[0] < M or
                                                        res.shape[1] < (2 * N if epilogue == EPI_SWIGLU_BWD else N)):
         raise ValueError("gemm: the *_BWD epilogues read the saved pre-activation through res")
-    if out_map is not None:
-        d.out_group, d.out_stride, d.out_offset = out_map
     if workspace is not None:
         d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
         keep.append(workspace)
@@ -191,15 +225,11 @@ def gemm(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue: int = EP
         name = "bl_gemm_skinny_rows_bf16"
     else:
         name = "bl_gemm_skinny_bf16" if use_skinny else "bl_gemm_bf16"
-    fn = getattr(lib, name)
     # algorithmic work: logical FLOPs; bytes = each operand once + the output once
     esz = 4 if epilogue in (EPI_F32, EPI_F32_BF16R) else 2
-    op = Op(name, fn, (C.byref(d),), (d, *keep),
-            flops=2.0 * M * (algo_nk[0] if algo_nk else N) * (algo_nk[1] if algo_nk else K),
-            nbytes=2.0 * (M * K + N * K) + esz * M * n_out)
-    if run:
-        op.run()
-    return op
+    return _op(name, (C.byref(d),), (d, *keep), run,
+               flops=2.0 * M * (algo_nk[0] if algo_nk else N) * (algo_nk[1] if algo_nk else K),
+               nbytes=2.0 * (M * K + N * K) + esz * M * n_out)
 
 
 _GF_TAIL = {0: "", 1: "+tail64x64", 2: "+tail128x64", 3: "+tail128x128"}
@@ -258,7 +288,6 @@ def quantize_packed_weight_fp8(wp: torch.Tensor, w8: Optional[torch.Tensor] = No
     fl32(448 / amax) where quantize_weight_fp8 divides by the scale, so a few codes per 10^5 differ between the two; the
     scales are equal. Writes every byte of w8 / scale in place (replayable; captured graphs that read them stay valid).
     Returns (w8, scale, op)."""
-    lib = _lib.load()
     _bf16(wp, "wp")
     if wp.dim() != 4 or wp.shape[2:] != (64, 8) or not wp.is_contiguous():
         raise ValueError("quantize_packed_weight_fp8: wp must come from pack_weight")
@@ -273,30 +302,22 @@ def quantize_packed_weight_fp8(wp: torch.Tensor, w8: Optional[torch.Tensor] = No
         raise ValueError(f"quantize_packed_weight_fp8: w8 must hold the {N * K} bytes of [N/16, K/64, 64, 16]")
     if scale.dtype != torch.float32 or scale.numel() != N or not scale.is_contiguous() or not scale.is_cuda:
         raise ValueError(f"quantize_packed_weight_fp8: scale fp32 [{N}]")
-    op = Op("bl_quantize_weight_fp8_packed", lib.bl_quantize_weight_fp8_packed,
-            (wp.data_ptr(), N, K, w8.data_ptr(), scale.data_ptr()), (wp, w8, scale), nbytes=3.0 * N * K)
-    if run:
-        op.run()
-    return w8, scale, op
+    return w8, scale, _op("bl_quantize_weight_fp8_packed", (wp.data_ptr(), N, K, w8.data_ptr(), scale.data_ptr()),
+                          (wp, w8, scale), run, nbytes=3.0 * N * K)
 
 
 def quantize_rows_fp8(x: torch.Tensor, q: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
                       run: bool = True):
     """Activations bf16 [rows, cols] → (e4m3 codes uint8 [rows, cols], fp32 scale per row = amax / 448)
     (bl_quantize_rows_fp8). Returns (q, scales, op)."""
-    lib = _lib.load()
     _bf16(x, "x")
     rows, cols = x.shape
     if q is None:
         q = torch.empty(rows, cols, dtype=torch.uint8, device=x.device)
     if scales is None:
         scales = torch.empty(rows, dtype=torch.float32, device=x.device)
-    op = Op("bl_quantize_rows_fp8", lib.bl_quantize_rows_fp8,
-            (x.data_ptr(), _rows(x, "x"), rows, cols, q.data_ptr(), q.stride(0), scales.data_ptr()), (x, q, scales),
-            nbytes=3.0 * rows * cols)
-    if run:
-        op.run()
-    return q, scales, op
+    return q, scales, _op("bl_quantize_rows_fp8", (x.data_ptr(), _rows(x, "x"), rows, cols, q.data_ptr(), q.stride(0),
+                                                   scales.data_ptr()), (x, q, scales), run, nbytes=3.0 * rows * cols)
 
 
 def gemm_fp8(A8: torch.Tensor, scale_a: torch.Tensor, W8: torch.Tensor, scale_w: torch.Tensor, out: torch.Tensor,
@@ -305,7 +326,6 @@ def gemm_fp8(A8: torch.Tensor, scale_a: torch.Tensor, W8: torch.Tensor, scale_w:
              run: bool = True) -> Op:
     """out = epilogue(scale_a[m] · scale_w[n] · (A8 @ W8.T)) on the fp8 MFMA path (bl_gemm_fp8). A8 uint8 e4m3 codes
     [M, K]; W8 = quantize_weight_fp8(...)[0]. `scale` (LayerScale, EPI_BIAS_RES), `res_row_mod` and `out_map` as in gemm."""
-    lib = _lib.load()
     if A8.dtype != torch.uint8 or not A8.is_cuda or A8.stride(1) != 1:
         raise TypeError("gemm_fp8: A8 must be a CUDA/HIP uint8 matrix of e4m3 codes")
     if W8.dim() != 4 or W8.shape[2:] != (64, 8) or not W8.is_contiguous():
@@ -319,28 +339,12 @@ def gemm_fp8(A8: torch.Tensor, scale_a: torch.Tensor, W8: torch.Tensor, scale_w:
         raise TypeError("gemm_fp8: out dtype / fp32 scales")
     if scale_a.numel() < M or scale_w.numel() != N:
         raise ValueError("gemm_fp8: scale_a [M], scale_w [N]")
-    d = GemmDesc()
-    d.A, d.lda = A8.data_ptr(), A8.stride(0)
-    d.W, d.ldw = W8.data_ptr(), K
-    d.C, d.ldc = out.data_ptr(), _rows(out, "out")
-    d.M, d.N, d.K, d.epilogue = M, N, K, epilogue
-    keep = [A8, W8, out, scale_a, scale_w]
-    if bias is not None:
-        d.bias = _bf16(bias, "bias").data_ptr(); keep.append(bias)
-    if scale is not None:
-        d.scale = _bf16(scale, "scale").data_ptr(); keep.append(scale)
-    if res is not None:
-        d.res, d.ldres = _bf16(res, "res").data_ptr(), _rows(res, "res"); keep.append(res)
-    d.res_row_mod = res_row_mod
-    if out_map is not None:
-        d.out_group, d.out_stride, d.out_offset = out_map
+    d, keep = _gemm_desc(A8, A8.stride(0), W8, out, M, N, K, epilogue, bias, scale, res, res_row_mod, out_map,
+                         [A8, W8, out, scale_a, scale_w])
     n_out = N // 2 if epilogue == EPI_SWIGLU else N
     esz = 4 if epilogue in (EPI_F32, EPI_F32_BF16R) else 2
-    op = Op("bl_gemm_fp8", lib.bl_gemm_fp8, (C.byref(d), scale_a.data_ptr(), scale_w.data_ptr()), (d, *keep),
-            flops=2.0 * M * N * K, nbytes=1.0 * (M * K + N * K) + esz * M * n_out)
-    if run:
-        op.run()
-    return op
+    return _op("bl_gemm_fp8", (C.byref(d), scale_a.data_ptr(), scale_w.data_ptr()), (d, *keep), run,
+               flops=2.0 * M * N * K, nbytes=1.0 * (M * K + N * K) + esz * M * n_out)
 
 
 class Fp8Weight(NamedTuple):
@@ -358,48 +362,35 @@ def linear_fp8(x: torch.Tensor, q: torch.Tensor, sx: torch.Tensor, w8: torch.Ten
 
 def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor, eps: float = 1e-6,
               run: bool = True) -> Op:
-    lib = _lib.load()
     _bf16(x, "x"); _bf16(out, "out")
     rows, dim = x.shape
-    op = Op("bl_layernorm_bf16", lib.bl_layernorm_bf16,
-            (x.data_ptr(), _rows(x, "x"), _bf16(w, "w").data_ptr(), _bf16(b, "b").data_ptr(), out.data_ptr(),
-             _rows(out, "out"), rows, dim, float(eps)), (x, w, b, out))
-    if run:
-        op.run()
-    return op
+    return _op("bl_layernorm_bf16", (x.data_ptr(), _rows(x, "x"), _bf16(w, "w").data_ptr(), _bf16(b, "b").data_ptr(),
+                                     out.data_ptr(), _rows(out, "out"), rows, dim, float(eps)), (x, w, b, out), run)
+
+
+def _rmsnorm(name: str, x, w, out, eps, run, nbytes_per_elem: float) -> Op:
+    _bf16(x, "x"); _bf16(out, "out")
+    rows, dim = x.shape
+    return _op(name, (x.data_ptr(), _rows(x, "x"), _bf16(w, "w").data_ptr(), out.data_ptr(), _rows(out, "out"), rows, dim,
+                      float(eps)), (x, w, out), run, nbytes=nbytes_per_elem * rows * dim)
 
 
 def rmsnorm(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, eps: float = 1e-6, run: bool = True) -> Op:
-    lib = _lib.load()
-    _bf16(x, "x"); _bf16(out, "out")
-    rows, dim = x.shape
-    op = Op("bl_rmsnorm_bf16", lib.bl_rmsnorm_bf16,
-            (x.data_ptr(), _rows(x, "x"), _bf16(w, "w").data_ptr(), out.data_ptr(), _rows(out, "out"), rows, dim,
-             float(eps)), (x, w, out))
-    if run:
-        op.run()
-    return op
+    return _rmsnorm("bl_rmsnorm_bf16", x, w, out, eps, run, 0.0)
 
 
 def rmsnorm_skinny(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, eps: float = 1e-6, run: bool = True) -> Op:
     """HF LlamaRMSNorm in the arithmetic of the skinny GEMM's fused a_norm (bl_rmsnorm_skinny_bf16); dim in SKINNY_K."""
-    lib = _lib.load()
-    _bf16(x, "x"); _bf16(out, "out")
-    rows, dim = x.shape
-    op = Op("bl_rmsnorm_skinny_bf16", lib.bl_rmsnorm_skinny_bf16,
-            (x.data_ptr(), _rows(x, "x"), _bf16(w, "w").data_ptr(), out.data_ptr(), _rows(out, "out"), rows, dim,
-             float(eps)), (x, w, out), nbytes=4.0 * rows * dim)
-    if run:
-        op.run()
-    return op
+    return _rmsnorm("bl_rmsnorm_skinny_bf16", x, w, out, eps, run, 4.0)
 
 
 def _attn_desc(q, k, v, o, B, H, Sq, Skv, hd, q_str, k_str, v_str, o_str, causal, scale, key_mask):
     d = AttnDesc()
     d.q, (d.q_bs, d.q_hs, d.q_rs) = _bf16(q, "q").data_ptr(), q_str
     d.k, (d.k_bs, d.k_hs, d.k_rs) = _bf16(k, "k").data_ptr(), k_str
-    d.v, (d.v_bs, d.v_hs, d.v_rs) = _bf16(v, "v").data_ptr(), v_str
-    d.o, (d.o_bs, d.o_hs, d.o_rs) = _bf16(o, "o").data_ptr(), o_str
+    if v is not None:            # attention_probs reads q and k alone: v and o stay null
+        d.v, (d.v_bs, d.v_hs, d.v_rs) = _bf16(v, "v").data_ptr(), v_str
+        d.o, (d.o_bs, d.o_hs, d.o_rs) = _bf16(o, "o").data_ptr(), o_str
     if key_mask is not None:
         if key_mask.dtype != torch.uint8 or key_mask.dim() != 2 or key_mask.stride(1) != 1:
             raise TypeError("key_mask must be a [B, Skv] uint8 tensor")
@@ -412,14 +403,10 @@ def attention(q, k, v, o, *, B: int, H: int, Sq: int, Skv: int, head_dim: int, q
               o_strides, causal: bool, scale: Optional[float] = None, key_mask: Optional[torch.Tensor] = None,
               run: bool = True) -> Op:
     """Flash attention over strided [batch, head, row, head_dim] views; strides are (batch, head, row) in elements."""
-    lib = _lib.load()
     scale = head_dim ** -0.5 if scale is None else scale
     d = _attn_desc(q, k, v, o, B, H, Sq, Skv, head_dim, q_strides, k_strides, v_strides, o_strides, causal, scale,
                    key_mask)
-    op = Op("bl_attention_bf16", lib.bl_attention_bf16, (C.byref(d),), (d, q, k, v, o, key_mask))
-    if run:
-        op.run()
-    return op
+    return _op("bl_attention_bf16", (C.byref(d),), (d, q, k, v, o, key_mask), run)
 
 
 def attention_rope(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, o: torch.Tensor, cos: torch.Tensor,
@@ -427,35 +414,24 @@ def attention_rope(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
                    key_mask: Optional[torch.Tensor] = None, run: bool = True) -> Op:
     """Prefill attention over fused, un-rotated qkv rows [B*S, 3*H*hd] with RoPE and the KV-cache write fused in
     (bl_attention_rope_bf16): caches [B, H, cache_len, hd] receive rotated k and v at positions pos0.., o [B*S, H*hd]."""
-    lib = _lib.load()
     D = H * head_dim
-    for t, n in ((qkv, "qkv"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cos, "cos"), (sin, "sin")):
-        _bf16(t, n)
-        if not t.is_contiguous():
-            raise ValueError(f"attention_rope: {n} must be contiguous")
+    _contig_bf16("attention_rope", (qkv, "qkv"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cos, "cos"), (sin, "sin"))
     cache_len = k_cache.shape[2]
     scale = head_dim ** -0.5 if scale is None else scale
     st = (S * 3 * D, head_dim, 3 * D)
     d = _attn_desc(qkv, qkv[:, D:], qkv[:, 2 * D:], o, B, H, S, S, head_dim, st, st, st, (S * D, head_dim, D), True, scale, key_mask)
-    op = Op("bl_attention_rope_bf16", lib.bl_attention_rope_bf16,
-            (C.byref(d), cos.data_ptr(), sin.data_ptr(), pos0, k_cache.data_ptr(), v_cache.data_ptr(), cache_len),
-            (d, qkv, k_cache, v_cache, o, cos, sin, key_mask))
-    if run:
-        op.run()
-    return op
+    return _op("bl_attention_rope_bf16",
+               (C.byref(d), cos.data_ptr(), sin.data_ptr(), pos0, k_cache.data_ptr(), v_cache.data_ptr(), cache_len),
+               (d, qkv, k_cache, v_cache, o, cos, sin, key_mask), run)
 
 
 def attention_decode(q, k, v, o, *, B: int, H: int, Skv: int, head_dim: int, q_strides, k_strides, v_strides,
                      o_strides, scale: Optional[float] = None, key_mask: Optional[torch.Tensor] = None,
                      run: bool = True) -> Op:
-    lib = _lib.load()
     scale = head_dim ** -0.5 if scale is None else scale
     d = _attn_desc(q, k, v, o, B, H, 1, Skv, head_dim, q_strides, k_strides, v_strides, o_strides, False, scale,
                    key_mask)
-    op = Op("bl_attention_decode_bf16", lib.bl_attention_decode_bf16, (C.byref(d),), (d, q, k, v, o, key_mask))
-    if run:
-        op.run()
-    return op
+    return _op("bl_attention_decode_bf16", (C.byref(d),), (d, q, k, v, o, key_mask), run)
 
 
 def attention_decode_rope(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, o: torch.Tensor,
@@ -465,12 +441,8 @@ def attention_decode_rope(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
     """One decode step's attention with RoPE and the KV-cache append fused: qkv [B, 3*H*hd] is the step's fused
     projection (q | k | v), caches [B, H, cache_len, hd]; rotates q and k at `pos`, writes k', v to cache row `pos`,
     attends over keys 0..pos, writes o [B, H*hd]."""
-    lib = _lib.load()
     D = H * head_dim
-    for t, n in ((qkv, "qkv"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cos, "cos"), (sin, "sin")):
-        _bf16(t, n)
-        if not t.is_contiguous():
-            raise ValueError(f"attention_decode_rope: {n} must be contiguous")
+    _contig_bf16("attention_decode_rope", (qkv, "qkv"), (k_cache, "k_cache"), (v_cache, "v_cache"), (cos, "cos"), (sin, "sin"))
     cache_len = k_cache.shape[2]
     if pos >= cache_len or pos >= cos.shape[0]:
         raise ValueError("attention_decode_rope: position outside the cache / rope table")
@@ -478,20 +450,12 @@ def attention_decode_rope(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
     cs = (H * cache_len * head_dim, cache_len * head_dim, head_dim)
     d = _attn_desc(qkv, k_cache, v_cache, o, B, H, 1, pos + 1, head_dim, (3 * D, head_dim, 3 * D), cs, cs,
                    (D, head_dim, D), False, scale, key_mask)
+    name, args, keep = "bl_attention_decode_rope_bf16", (C.byref(d), cos.data_ptr(), sin.data_ptr(), pos), \
+        (d, qkv, k_cache, v_cache, o, cos, sin, key_mask)
     if rope_pos is not None:     # right-padded prompts: per-sequence rotation position (int32 [B]), shared cache row
-        if rope_pos.dtype != torch.int32 or not rope_pos.is_cuda or rope_pos.numel() != B or not rope_pos.is_contiguous():
-            raise TypeError("attention_decode_rope: rope_pos must be a contiguous CUDA/HIP int32 tensor [B]")
-        op = Op("bl_attention_decode_rope_pos_bf16", lib.bl_attention_decode_rope_pos_bf16,
-                (C.byref(d), cos.data_ptr(), sin.data_ptr(), pos, rope_pos.data_ptr()),
-                (d, qkv, k_cache, v_cache, o, cos, sin, key_mask, rope_pos))
-        if run:
-            op.run()
-        return op
-    op = Op("bl_attention_decode_rope_bf16", lib.bl_attention_decode_rope_bf16,
-            (C.byref(d), cos.data_ptr(), sin.data_ptr(), pos), (d, qkv, k_cache, v_cache, o, cos, sin, key_mask))
-    if run:
-        op.run()
-    return op
+        _dev(rope_pos, torch.int32, B, "attention_decode_rope: rope_pos")
+        name, args, keep = "bl_attention_decode_rope_pos_bf16", args + (rope_pos.data_ptr(),), keep + (rope_pos,)
+    return _op(name, args, keep, run)
 
 
 def attention_probs(q: torch.Tensor, k: torch.Tensor, *, B: int, H: int, Sq: int, Skv: int, head_dim: int, q_strides, k_strides,
@@ -504,16 +468,8 @@ def attention_probs(q: torch.Tensor, k: torch.Tensor, *, B: int, H: int, Sq: int
     un-rotated and is rotated on load at pos0 + row (rope_pos[b] + row with an int32 [B] device tensor); without, q is
     rotated in memory. probs: fp32 [B, H, Sq, p_cols >= Skv] view with a contiguous last dim — columns past Skv are zeroed;
     seg: contiguous fp32 [B, H, Sq, n_seg] with seg_bounds int32 [B, n_seg + 1]. Either output may be None."""
-    lib = _lib.load()
     scale = head_dim ** -0.5 if scale is None else scale
-    d = AttnDesc()
-    d.q, (d.q_bs, d.q_hs, d.q_rs) = _bf16(q, "q").data_ptr(), q_strides
-    d.k, (d.k_bs, d.k_hs, d.k_rs) = _bf16(k, "k").data_ptr(), k_strides
-    if key_mask is not None:
-        if key_mask.dtype != torch.uint8 or key_mask.dim() != 2 or key_mask.stride(1) != 1:
-            raise TypeError("key_mask must be a [B, Skv] uint8 tensor")
-        d.key_mask, d.mask_bs = key_mask.data_ptr(), key_mask.stride(0)
-    d.B, d.H, d.Sq, d.Skv, d.head_dim, d.causal, d.scale = B, H, Sq, Skv, head_dim, int(causal), float(scale)
+    d = _attn_desc(q, k, None, None, B, H, Sq, Skv, head_dim, q_strides, k_strides, None, None, causal, scale, key_mask)
     if (cos is None) != (sin is None):
         raise ValueError("attention_probs: cos and sin come together")
     rope_rows = 0
@@ -523,9 +479,8 @@ def attention_probs(q: torch.Tensor, k: torch.Tensor, *, B: int, H: int, Sq: int
             if not t.is_contiguous() or t.dim() != 2 or t.shape[1] != head_dim // 2:
                 raise ValueError(f"attention_probs: {n} must be a contiguous [positions, head_dim/2] table")
         rope_rows = min(cos.shape[0], sin.shape[0])
-    if rope_pos is not None and (rope_pos.dtype != torch.int32 or not rope_pos.is_cuda or rope_pos.numel() != B
-                                 or not rope_pos.is_contiguous()):
-        raise TypeError("attention_probs: rope_pos must be a contiguous CUDA/HIP int32 tensor [B]")
+    if rope_pos is not None:
+        _dev(rope_pos, torch.int32, B, "attention_probs: rope_pos")
     p_ptr, p_str, p_cols = None, (0, 0, 0), 0
     if probs is not None:
         if probs.dtype != torch.float32 or not probs.is_cuda or probs.dim() != 4 or probs.stride(3) != 1 \
@@ -534,71 +489,55 @@ def attention_probs(q: torch.Tensor, k: torch.Tensor, *, B: int, H: int, Sq: int
         p_ptr, p_str, p_cols = probs.data_ptr(), probs.stride()[:3], probs.shape[3]
     s_ptr, b_ptr, n_seg = None, None, 0
     if seg is not None:
-        if seg.dtype != torch.float32 or not seg.is_cuda or not seg.is_contiguous() or seg.dim() != 4 \
-                or tuple(seg.shape[:3]) != (B, H, Sq):
-            raise TypeError("attention_probs: seg must be a contiguous CUDA/HIP fp32 [B, H, Sq, n_seg] tensor")
-        n_seg = seg.shape[3]
-        if seg_bounds is None or seg_bounds.dtype != torch.int32 or not seg_bounds.is_cuda or not seg_bounds.is_contiguous() \
-                or tuple(seg_bounds.shape) != (B, n_seg + 1):
-            raise TypeError("attention_probs: seg_bounds must be a contiguous CUDA/HIP int32 [B, n_seg + 1] tensor")
-        s_ptr, b_ptr = seg.data_ptr(), seg_bounds.data_ptr()
-    op = Op("bl_attention_probs_f32", lib.bl_attention_probs_f32,
-            (C.byref(d), None if cos is None else cos.data_ptr(), None if sin is None else sin.data_ptr(), rope_rows, pos0,
-             None if rope_pos is None else rope_pos.data_ptr(), p_ptr, p_str[0], p_str[1], p_str[2], p_cols, s_ptr, b_ptr, n_seg),
-            (d, q, k, key_mask, cos, sin, rope_pos, probs, seg, seg_bounds),
-            flops=2.0 * B * H * Sq * Skv * head_dim,
-            nbytes=2.0 * B * H * (Sq + Skv) * head_dim + 4.0 * B * H * Sq * (p_cols + n_seg))
-    if run:
-        op.run()
-    return op
+        n_seg = _dev(seg, torch.float32, (B, H, Sq, None), "attention_probs: seg").shape[3]
+        s_ptr, b_ptr = seg.data_ptr(), _dev(seg_bounds, torch.int32, (B, n_seg + 1), "attention_probs: seg_bounds").data_ptr()
+    return _op("bl_attention_probs_f32",
+               (C.byref(d), None if cos is None else cos.data_ptr(), None if sin is None else sin.data_ptr(), rope_rows, pos0,
+                None if rope_pos is None else rope_pos.data_ptr(), p_ptr, p_str[0], p_str[1], p_str[2], p_cols, s_ptr, b_ptr, n_seg),
+               (d, q, k, key_mask, cos, sin, rope_pos, probs, seg, seg_bounds), run,
+               flops=2.0 * B * H * Sq * Skv * head_dim,
+               nbytes=2.0 * B * H * (Sq + Skv) * head_dim + 4.0 * B * H * Sq * (p_cols + n_seg))
 
 
 def rope_kvcache(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
                  v_cache: torch.Tensor, *, B: int, S: int, H: int, head_dim: int, pos0: int, run: bool = True) -> Op:
     """qkv [B*S, 3*H*hd] (q rotated in place); caches [B, H, cache_len, hd]; cos/sin [max_pos, hd/2] bf16."""
-    lib = _lib.load()
-    for t, n in ((qkv, "qkv"), (cos, "cos"), (sin, "sin"), (k_cache, "k_cache"), (v_cache, "v_cache")):
-        _bf16(t, n)
-        if not t.is_contiguous():
-            raise ValueError(f"rope_kvcache: {n} must be contiguous")
+    _contig_bf16("rope_kvcache", (qkv, "qkv"), (cos, "cos"), (sin, "sin"), (k_cache, "k_cache"), (v_cache, "v_cache"))
     cache_len = k_cache.shape[2]
     if pos0 + S > cos.shape[0]:
         raise ValueError("rope_kvcache: position exceeds the cos/sin table")
-    op = Op("bl_rope_kvcache_bf16", lib.bl_rope_kvcache_bf16,
-            (qkv.data_ptr(), B, S, H, head_dim, cos.data_ptr(), sin.data_ptr(), pos0, k_cache.data_ptr(),
-             v_cache.data_ptr(), cache_len), (qkv, cos, sin, k_cache, v_cache))
-    if run:
-        op.run()
-    return op
+    return _op("bl_rope_kvcache_bf16", (qkv.data_ptr(), B, S, H, head_dim, cos.data_ptr(), sin.data_ptr(), pos0,
+                                        k_cache.data_ptr(), v_cache.data_ptr(), cache_len), (qkv, cos, sin, k_cache, v_cache), run)
 
 
 def embed_splice(ids: torch.Tensor, table: torch.Tensor, dst: torch.Tensor, n_patches: int, run: bool = True) -> Op:
     """dst[b,0] = table[ids[b,0]]; dst[b, 1+n_patches+j] = table[ids[b,1+j]].  ids int64 [B,L]; dst [B, L+n_patches, D]."""
-    lib = _lib.load()
     if ids.dtype != torch.int64 or not ids.is_contiguous():
         raise TypeError("ids must be a contiguous int64 tensor")
     B, L = ids.shape
     dim = table.shape[1]
     if tuple(dst.shape) != (B, L + n_patches, dim) or not dst.is_contiguous():
         raise ValueError(f"embed_splice: dst must be contiguous [{B}, {L + n_patches}, {dim}]")
-    op = Op("bl_embed_splice_bf16", lib.bl_embed_splice_bf16,
-            (ids.data_ptr(), B, L, _bf16(table, "table").data_ptr(), dim, n_patches, _bf16(dst, "dst").data_ptr()),
-            (ids, table, dst))
-    if run:
-        op.run()
-    return op
+    return _op("bl_embed_splice_bf16", (ids.data_ptr(), B, L, _bf16(table, "table").data_ptr(), dim, n_patches,
+                                        _bf16(dst, "dst").data_ptr()), (ids, table, dst), run)
 
 
 def argmax(logits: torch.Tensor, out: torch.Tensor, run: bool = True) -> Op:
-    lib = _lib.load()
     if logits.dtype != torch.float32 or out.dtype != torch.int64:
         raise TypeError("argmax: logits fp32 [rows, n], out int64 [rows]")
     rows, n = logits.shape
-    op = Op("bl_argmax_f32", lib.bl_argmax_f32, (logits.data_ptr(), _rows(logits, "logits"), rows, n, out.data_ptr()),
-            (logits, out))
-    if run:
-        op.run()
-    return op
+    return _op("bl_argmax_f32", (logits.data_ptr(), _rows(logits, "logits"), rows, n, out.data_ptr()), (logits, out), run)
+
+
+def _warp_head(fn: str, logits, temperature, top_k, top_p, *own) -> tuple:
+    """What sample and score share: fp32 logits [rows, n] (any row stride) and the per-row device settings are checked, then
+    the caller's `own` tensors as (tensor, dtype, extents after [rows], name); returns the leading arguments of the call."""
+    rows, n = logits.shape
+    _f32(logits, f"{fn}: logits")
+    for t, dtype, tail, name in ((temperature, torch.float32, (), "temperature"), (top_k, torch.int32, (), "top_k"),
+                                 (top_p, torch.float32, (), "top_p")) + own:
+        _dev(t, dtype, (rows,) + tail, f"{fn}: {name}")
+    return (logits.data_ptr(), _rows(logits, "logits"), rows, n, temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr())
 
 
 def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
@@ -607,26 +546,11 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
     DEVICE settings: temperature fp32 (0 = greedy), top_k int32 (0 = off), top_p fp32 (>= 1 = off), seed int64; `step` is
     the Philox counter. Writes ids int64 [rows] and wt int64 [rows, 2] = (weight of the token, kept total).
     vocab=(first, count) restricts the policy to that token range (bl_sample_range_f32)."""
-    lib = _lib.load()
-    rows, n = logits.shape
-    want = ((logits, torch.float32, (rows, n)), (temperature, torch.float32, (rows,)), (top_k, torch.int32, (rows,)),
-            (top_p, torch.float32, (rows,)), (seed, torch.int64, (rows,)), (ids, torch.int64, (rows,)), (wt, torch.int64, (rows, 2)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_cuda or (t.dim() == 1 and rows > 1 and t.stride(0) != 1):
-            raise TypeError("sample: logits fp32 [rows, n]; temperature fp32, top_k int32, top_p fp32, seed int64, ids int64 "
-                            "[rows] (contiguous); wt int64 [rows, 2]; all on the device")
-    if not wt.is_contiguous():
-        raise TypeError("sample: wt must be contiguous")
-    args = (logits.data_ptr(), _rows(logits, "logits"), rows, n, temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
-            seed.data_ptr(), int(step), ids.data_ptr(), wt.data_ptr())
-    keep = (logits, temperature, top_k, top_p, seed, ids, wt)
-    if vocab is None:
-        op = Op("bl_sample_f32", lib.bl_sample_f32, args, keep)
-    else:
-        op = Op("bl_sample_range_f32", lib.bl_sample_range_f32, args + (int(vocab[0]), int(vocab[1])), keep)
-    if run:
-        op.run()
-    return op
+    head = _warp_head("sample", logits, temperature, top_k, top_p,
+                      (seed, torch.int64, (), "seed"), (ids, torch.int64, (), "ids"), (wt, torch.int64, (2,), "wt"))
+    return _op("bl_sample_f32" if vocab is None else "bl_sample_range_f32",
+               head + (seed.data_ptr(), int(step), ids.data_ptr(), wt.data_ptr()) + (() if vocab is None else (int(vocab[0]), int(vocab[1]))),
+               (logits, temperature, top_k, top_p, seed, ids, wt), run)
 
 
 def score(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, tokens: torch.Tensor,
@@ -638,71 +562,41 @@ def score(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, 
     token, kept total) and, given range_wt int32 [rows, count], the kept weights of tokens range_first … range_first +
     count - 1. vocab=(first, count) restricts the policy to that token range (bl_score_range_f32); range_first keeps its
     full-vocabulary numbering and the report range must lie inside `vocab`."""
-    lib = _lib.load()
-    rows, n = logits.shape
-    want = ((logits, torch.float32, (rows, n)), (temperature, torch.float32, (rows,)), (top_k, torch.int32, (rows,)),
-            (top_p, torch.float32, (rows,)), (tokens, torch.int64, (rows,)), (wt, torch.int64, (rows, 2)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_cuda or (t.dim() == 1 and rows > 1 and t.stride(0) != 1):
-            raise TypeError("score: logits fp32 [rows, n]; temperature fp32, top_k int32, top_p fp32, tokens int64 [rows] "
-                            "(contiguous); wt int64 [rows, 2]; all on the device")
-    if not wt.is_contiguous():
-        raise TypeError("score: wt must be contiguous")
-    count = 0
+    own = [(tokens, torch.int64, (), "tokens"), (wt, torch.int64, (2,), "wt")]
     if range_wt is not None:
-        if range_wt.dtype != torch.int32 or range_wt.dim() != 2 or range_wt.shape[0] != rows or not range_wt.is_cuda or \
-                not range_wt.is_contiguous():
-            raise TypeError("score: range_wt int32 [rows, count], contiguous, on the device")
-        count = range_wt.shape[1]
-    keep = (logits, temperature, top_k, top_p, tokens, wt) + ((range_wt,) if count else ())
-    args = (logits.data_ptr(), _rows(logits, "logits"), rows, n, temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
-            tokens.data_ptr(), wt.data_ptr(), int(range_first), count, range_wt.data_ptr() if count else None)
-    if vocab is None:
-        op = Op("bl_score_f32", lib.bl_score_f32, args, keep)
-    else:
-        op = Op("bl_score_range_f32", lib.bl_score_range_f32, args + (int(vocab[0]), int(vocab[1])), keep)
-    if run:
-        op.run()
-    return op
+        own.append((range_wt, torch.int32, (None,), "range_wt"))
+    head = _warp_head("score", logits, temperature, top_k, top_p, *own)
+    count = 0 if range_wt is None else range_wt.shape[1]
+    return _op("bl_score_f32" if vocab is None else "bl_score_range_f32",
+               head + (tokens.data_ptr(), wt.data_ptr(), int(range_first), count, range_wt.data_ptr() if count else None)
+               + (() if vocab is None else (int(vocab[0]), int(vocab[1]))),
+               (logits, temperature, top_k, top_p, tokens, wt) + ((range_wt,) if count else ()), run)
 
 
 def cross_entropy(logits: torch.Tensor, targets: torch.Tensor, row_loss: torch.Tensor, mean_and_count: torch.Tensor,
                   ignore_index: int = -100, run: bool = True) -> Op:
     """Per-row CE over fp32 logits [rows, n] against int64 targets [rows] (already shifted); mean over valid rows."""
-    lib = _lib.load()
     if logits.dtype != torch.float32 or targets.dtype != torch.int64 or row_loss.dtype != torch.float32:
         raise TypeError("cross_entropy: logits/row_loss fp32, targets int64")
     rows, n = logits.shape
-    op = Op("bl_cross_entropy_f32", lib.bl_cross_entropy_f32,
-            (logits.data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
-             row_loss.data_ptr(), mean_and_count.data_ptr()), (logits, targets, row_loss, mean_and_count))
-    if run:
-        op.run()
-    return op
+    return _op("bl_cross_entropy_f32", (logits.data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
+                                        row_loss.data_ptr(), mean_and_count.data_ptr()), (logits, targets, row_loss, mean_and_count), run)
 
 
 def im2col_patch14(pixel_values: torch.Tensor, chan0: int, out: torch.Tensor, run: bool = True) -> Op:
     """pixel_values [B,6,224,224] bf16 → out [B*256, ld>=588] patch rows of channels chan0..chan0+2."""
-    lib = _lib.load()
     _bf16(pixel_values, "pixel_values"); _bf16(out, "out")
     if tuple(pixel_values.shape[1:]) != (6, 224, 224) or not pixel_values.is_contiguous():
         raise ValueError("im2col_patch14: pixel_values must be contiguous [B, 6, 224, 224]")
     B = pixel_values.shape[0]
-    op = Op("bl_im2col_patch14_bf16", lib.bl_im2col_patch14_bf16,
-            (pixel_values.data_ptr(), B, chan0, out.data_ptr(), _rows(out, "out")), (pixel_values, out))
-    if run:
-        op.run()
-    return op
+    return _op("bl_im2col_patch14_bf16", (pixel_values.data_ptr(), B, chan0, out.data_ptr(), _rows(out, "out")),
+               (pixel_values, out), run)
 
 
 def write_prefix_tokens(prefix: torch.Tensor, x: torch.Tensor, B: int, T: int, run: bool = True) -> Op:
-    lib = _lib.load()
     n_prefix, dim = prefix.shape
-    op = Op("bl_write_prefix_tokens_bf16", lib.bl_write_prefix_tokens_bf16,
-            (_bf16(prefix, "prefix").data_ptr(), n_prefix, dim, _bf16(x, "x").data_ptr(), B, T), (prefix, x))
-    if run:
-        op.run()
-    return op
+    return _op("bl_write_prefix_tokens_bf16", (_bf16(prefix, "prefix").data_ptr(), n_prefix, dim, _bf16(x, "x").data_ptr(), B, T),
+               (prefix, x), run)
 
 
 def attention_decode_rope_grouped(qkv: torch.Tensor, k_caches: Sequence[torch.Tensor], v_caches: Sequence[torch.Tensor],
@@ -713,83 +607,65 @@ def attention_decode_rope_grouped(qkv: torch.Tensor, k_caches: Sequence[torch.Te
     caches k_caches[g] / v_caches[g]. Exactly one of `pos` / `rope_pos` gives the positions: `pos[g]`, one host int for
     the whole group (bl_attention_decode_rope_grouped_bf16), or `rope_pos[g]`, a contiguous int32 device tensor [B] with
     every sequence's own position (right-padded batches, bl_attention_decode_rope_pos_grouped_bf16)."""
-    lib = _lib.load()
+    fn = "attention_decode_rope_grouped"
     if (pos is None) == (rope_pos is None):
-        raise ValueError("attention_decode_rope_grouped: give exactly one of pos / rope_pos")
+        raise ValueError(f"{fn}: give exactly one of pos / rope_pos")
     G, D = len(pos if rope_pos is None else rope_pos), H * head_dim
     if not (1 <= G <= 8) or len(k_caches) != G or len(v_caches) != G:
-        raise ValueError("attention_decode_rope_grouped: 1..8 groups, one cache pair and position each")
-    for t, n in [(qkv, "qkv"), (cos, "cos"), (sin, "sin")] + [(t, "cache") for t in list(k_caches) + list(v_caches)]:
-        _bf16(t, n)
-        if not t.is_contiguous():
-            raise ValueError(f"attention_decode_rope_grouped: {n} must be contiguous")
+        raise ValueError(f"{fn}: 1..8 groups, one cache pair and position each")
+    _contig_bf16(fn, (qkv, "qkv"), (cos, "cos"), (sin, "sin"), *[(t, "cache") for t in list(k_caches) + list(v_caches)])
     cache_len = k_caches[0].shape[2]
     if any(tuple(t.shape) != tuple(k_caches[0].shape) for t in list(k_caches) + list(v_caches)):
-        raise ValueError("attention_decode_rope_grouped: all caches must share one shape")
+        raise ValueError(f"{fn}: all caches must share one shape")
     if qkv.shape[0] != G * B or o.shape[0] != G * B:
-        raise ValueError("attention_decode_rope_grouped: row count != G*B")
+        raise ValueError(f"{fn}: row count != G*B")
     cs = (H * cache_len * head_dim, cache_len * head_dim, head_dim)
     kp = (C.c_void_p * G)(*[t.data_ptr() for t in k_caches])
     vp = (C.c_void_p * G)(*[t.data_ptr() for t in v_caches])
-    if rope_pos is not None:
+    if rope_pos is not None:     # the positions: a table of device pointers and the key count cache_len ...
         for t in rope_pos:
-            if t.dtype != torch.int32 or not t.is_cuda or t.numel() != B or not t.is_contiguous():
-                raise TypeError("attention_decode_rope_grouped: each rope_pos[g] must be a contiguous CUDA/HIP int32 tensor [B]")
+            _dev(t, torch.int32, B, f"{fn}: each rope_pos[g]")
         if tuple(k_caches[0].shape[:2]) != (B, H) or cache_len > cos.shape[0]:
-            raise ValueError("attention_decode_rope_grouped: caches must be [B, H, cache_len, hd] with cache_len inside the rope table")
-        d = _attn_desc(qkv, k_caches[0], v_caches[0], o, B, H, 1, cache_len, head_dim, (3 * D, head_dim, 3 * D), cs, cs,
-                       (D, head_dim, D), False, head_dim ** -0.5, None)
-        rp = (C.c_void_p * G)(*[t.data_ptr() for t in rope_pos])
-        op = Op("bl_attention_decode_rope_pos_grouped_bf16", lib.bl_attention_decode_rope_pos_grouped_bf16,
-                (C.byref(d), cos.data_ptr(), sin.data_ptr(), G, kp, vp, rp, cache_len),
-                (d, qkv, o, cos, sin, kp, vp, rp, list(k_caches), list(v_caches), list(rope_pos)))
-        if run:
-            op.run()
-        return op
-    if max(pos) >= cache_len or max(pos) >= cos.shape[0]:
-        raise ValueError("attention_decode_rope_grouped: position outside the cache / rope table")
-    d = _attn_desc(qkv, k_caches[0], v_caches[0], o, B, H, 1, pos[0] + 1, head_dim, (3 * D, head_dim, 3 * D), cs, cs,
+            raise ValueError(f"{fn}: caches must be [B, H, cache_len, hd] with cache_len inside the rope table")
+        name, Skv = "bl_attention_decode_rope_pos_grouped_bf16", cache_len
+        tab = (C.c_void_p * G)(*[t.data_ptr() for t in rope_pos])
+        tail, held = (tab, cache_len), (list(rope_pos),)
+    else:                        # ... or a table of host ints
+        if max(pos) >= cache_len or max(pos) >= cos.shape[0]:
+            raise ValueError(f"{fn}: position outside the cache / rope table")
+        name, Skv = "bl_attention_decode_rope_grouped_bf16", pos[0] + 1
+        tab = (C.c_int32 * G)(*[int(x) for x in pos])
+        tail, held = (tab,), ()
+    d = _attn_desc(qkv, k_caches[0], v_caches[0], o, B, H, 1, Skv, head_dim, (3 * D, head_dim, 3 * D), cs, cs,
                    (D, head_dim, D), False, head_dim ** -0.5, None)
-    pp = (C.c_int32 * G)(*[int(x) for x in pos])
-    op = Op("bl_attention_decode_rope_grouped_bf16", lib.bl_attention_decode_rope_grouped_bf16,
-            (C.byref(d), cos.data_ptr(), sin.data_ptr(), G, kp, vp, pp), (d, qkv, o, cos, sin, kp, vp, pp, list(k_caches), list(v_caches)))
-    if run:
-        op.run()
-    return op
+    return _op(name, (C.byref(d), cos.data_ptr(), sin.data_ptr(), G, kp, vp) + tail,
+               (d, qkv, o, cos, sin, kp, vp, tab, list(k_caches), list(v_caches)) + held, run)
 
 
 def gather_rows(src: torch.Tensor, row_index: torch.Tensor, dst: torch.Tensor, run: bool = True) -> Op:
     """dst[b] = src[b, row_index[b]] (bl_gather_rows_bf16): src [B, R, W] with contiguous rows (any row stride), row_index
     int64 device [B], dst contiguous [B, W]. A pure 16-byte copy, no allocation: usable inside a captured graph."""
-    lib = _lib.load()
     _bf16(src, "src"); _bf16(dst, "dst")
     if src.dim() != 3 or src.stride(2) != 1 or src.stride(0) != src.shape[1] * src.stride(1):
         raise ValueError(f"gather_rows: src must be [B, R, W] with contiguous rows and batch stride R * row stride, got stride {src.stride()}")
     B, R, Wd = src.shape
     if tuple(dst.shape) != (B, Wd) or not dst.is_contiguous():
         raise ValueError(f"gather_rows: dst must be contiguous [{B}, {Wd}]")
-    if row_index.dtype != torch.int64 or not row_index.is_cuda or row_index.numel() != B or not row_index.is_contiguous():
-        raise TypeError("gather_rows: row_index must be a contiguous CUDA/HIP int64 tensor [B]")
-    op = Op("bl_gather_rows_bf16", lib.bl_gather_rows_bf16,
-            (src.data_ptr(), row_index.data_ptr(), R, src.stride(1), Wd, dst.data_ptr(), B), (src, row_index, dst))
-    if run:
-        op.run()
-    return op
+    _dev(row_index, torch.int64, B, "gather_rows: row_index")
+    return _op("bl_gather_rows_bf16", (src.data_ptr(), row_index.data_ptr(), R, src.stride(1), Wd, dst.data_ptr(), B),
+               (src, row_index, dst), run)
+
+
+_FRAMES = (None, None, None, 3)      # uint8 frames [B, H, W, 3]
 
 
 def preprocess_u8(frames: torch.Tensor, mean_std: torch.Tensor, out: torch.Tensor, run: bool = True) -> Op:
     """uint8 frames [B, H, W, 3] already at the model resolution → pixel_values [B, 6, H, W] bf16 (bl_preprocess_u8_bf16)."""
-    lib = _lib.load()
-    if frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous() or frames.dim() != 4 or frames.shape[-1] != 3:
-        raise TypeError("preprocess_u8: frames must be a contiguous CUDA/HIP uint8 tensor [B, H, W, 3]")
-    B, H, W, _ = frames.shape
+    B, H, W, _ = _dev(frames, torch.uint8, _FRAMES, "preprocess_u8: frames").shape
     if tuple(out.shape) != (B, 6, H, W) or not out.is_contiguous() or mean_std.dtype != torch.float32 or mean_std.numel() != 12:
         raise ValueError("preprocess_u8: out must be contiguous [B, 6, H, W] bf16, mean_std 12 floats")
-    op = Op("bl_preprocess_u8_bf16", lib.bl_preprocess_u8_bf16, (frames.data_ptr(), B, H, W, mean_std.data_ptr(), _bf16(out, "out").data_ptr()),
-            (frames, mean_std, out), nbytes=B * H * W * (3 + 12.0))
-    if run:
-        op.run()
-    return op
+    return _op("bl_preprocess_u8_bf16", (frames.data_ptr(), B, H, W, mean_std.data_ptr(), _bf16(out, "out").data_ptr()),
+               (frames, mean_std, out), run, nbytes=B * H * W * (3 + 12.0))
 
 
 def _bicubic(x: float) -> float:
@@ -853,10 +729,7 @@ def resize_u8(frames: torch.Tensor, out_h: int, out_w: int, filter: str = "bicub
     """uint8 frames [B, H, W, 3] on the GPU → [B, out_h, out_w, 3], bit-identical to PIL `Image.resize((out_w, out_h),
     BICUBIC | LANCZOS)` per frame: horizontal pass, uint8 intermediate, vertical pass (a pass whose size does not change
     is skipped, as in Pillow)."""
-    lib = _lib.load()
-    if frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous() or frames.dim() != 4 or frames.shape[-1] != 3:
-        raise TypeError("resize_u8: frames must be a contiguous CUDA/HIP uint8 tensor [B, H, W, 3]")
-    B, H, W, _ = frames.shape
+    B, H, W, _ = _dev(frames, torch.uint8, _FRAMES, "resize_u8: frames").shape
     cur = frames
 
     def tables(n_in, n_out):
@@ -869,14 +742,14 @@ def resize_u8(frames: torch.Tensor, out_h: int, out_w: int, filter: str = "bicub
     if W != out_w:
         b, c, ks = tables(W, out_w)
         dst = torch.empty(B, H, out_w, 3, dtype=torch.uint8, device=frames.device)
-        Op("bl_resample_pass_u8", lib.bl_resample_pass_u8, (cur.data_ptr(), dst.data_ptr(), B, H, W, out_w, 1, b.data_ptr(),
-                                                             c.data_ptr(), ks), (cur, dst, b, c)).run()
+        _op("bl_resample_pass_u8", (cur.data_ptr(), dst.data_ptr(), B, H, W, out_w, 1, b.data_ptr(), c.data_ptr(), ks),
+            (cur, dst, b, c), True)
         cur = dst
     if H != out_h:
         b, c, ks = tables(H, out_h)
         dst = torch.empty(B, out_h, out_w, 3, dtype=torch.uint8, device=frames.device)
-        Op("bl_resample_pass_u8", lib.bl_resample_pass_u8, (cur.data_ptr(), dst.data_ptr(), B, out_w, H, out_h, 0, b.data_ptr(),
-                                                             c.data_ptr(), ks), (cur, dst, b, c)).run()
+        _op("bl_resample_pass_u8", (cur.data_ptr(), dst.data_ptr(), B, out_w, H, out_h, 0, b.data_ptr(), c.data_ptr(), ks),
+            (cur, dst, b, c), True)
         cur = dst
     return cur
 
@@ -890,21 +763,15 @@ def crop_resize_bilinear_u8(frames: torch.Tensor, y_base: float, y_step: float, 
     """tf.image.crop_and_resize (+ the uint8 ↔ float32 conversions around it) of the eval-time centre crop
     (experiments/robot/openvla_utils.py:81-155) on uint8 frames [B, H, W, 3] in HBM; the four fp32 sampling constants
     come from the caller (vla/eval_preprocess.py computes them exactly as its host restatement does)."""
-    lib = _lib.load()
-    if frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous() or frames.dim() != 4 or frames.shape[-1] != 3:
-        raise TypeError("crop_resize_bilinear_u8: frames must be a contiguous CUDA/HIP uint8 tensor [B, H, W, 3]")
-    B, H, W, _ = frames.shape
+    B, H, W, _ = _dev(frames, torch.uint8, _FRAMES, "crop_resize_bilinear_u8: frames").shape
     if out is None:
         out = torch.empty(B, out_h, out_w, 3, dtype=torch.uint8, device=frames.device)
     elif tuple(out.shape) != (B, out_h, out_w, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
         raise ValueError(f"crop_resize_bilinear_u8: out must be contiguous uint8 [{B}, {out_h}, {out_w}, 3]")
-    op = Op("bl_crop_resize_bilinear_u8", lib.bl_crop_resize_bilinear_u8,
-            (frames.data_ptr(), out.data_ptr(), B, H, W, out_h, out_w, float(y_base), float(y_step), float(x_base), float(x_step)),
-            (frames, out), nbytes=B * (H * W + out_h * out_w) * 3.0)
-    if run:
-        op.run()
-        return out
-    return op
+    op = _op("bl_crop_resize_bilinear_u8",
+             (frames.data_ptr(), out.data_ptr(), B, H, W, out_h, out_w, float(y_base), float(y_step), float(x_base), float(x_step)),
+             (frames, out), run, nbytes=B * (H * W + out_h * out_w) * 3.0)
+    return out if run else op
 
 
 def augment_frames_u8(frames: torch.Tensor, params: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -914,10 +781,7 @@ def augment_frames_u8(frames: torch.Tensor, params: torch.Tensor, out: Optional[
     [B, H, W, 3] in HBM with the host-drawn parameter table params [B, 8] fp32 on the device (bl_augment_frames_u8).
     Writes `out` (uint8 [B, H, W, 3]) and / or, fused, `pixel_values` ([B, 6, H, W] bf16 with the 12-float `mean_std` of
     preprocess_u8: equal to preprocess_u8 of `out`). `workspace`: int64 [B, 3], zeroed inside the call."""
-    lib = _lib.load()
-    if frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous() or frames.dim() != 4 or frames.shape[-1] != 3:
-        raise TypeError("augment_frames_u8: frames must be a contiguous CUDA/HIP uint8 tensor [B, H, W, 3]")
-    B, H, W, _ = frames.shape
+    B, H, W, _ = _dev(frames, torch.uint8, _FRAMES, "augment_frames_u8: frames").shape
     if H < 2 or W < 2:
         raise ValueError("augment_frames_u8: H and W must be at least 2")
     if (params.dtype != torch.float32 or params.device != frames.device or tuple(params.shape) != (B, 8)
@@ -938,25 +802,17 @@ def augment_frames_u8(frames: torch.Tensor, params: torch.Tensor, out: Optional[
     elif (workspace.dtype != torch.int64 or workspace.numel() < B * 3 or not workspace.is_contiguous()
           or workspace.device != frames.device):
         raise ValueError(f"augment_frames_u8: workspace must be a contiguous int64 tensor of at least {B * 3} elements")
-    op = Op("bl_augment_frames_u8", lib.bl_augment_frames_u8,
-            (frames.data_ptr(), B, H, W, params.data_ptr(), workspace.data_ptr(), out.data_ptr() if out is not None else None,
-             pixel_values.data_ptr() if pixel_values is not None else None, mean_std.data_ptr() if pixel_values is not None else None),
-            (frames, params, workspace, out, pixel_values, mean_std),
-            nbytes=B * H * W * (3.0 + (3 if out is not None else 0) + (12 if pixel_values is not None else 0)))
-    if run:
-        op.run()
-    return op
+    return _op("bl_augment_frames_u8",
+               (frames.data_ptr(), B, H, W, params.data_ptr(), workspace.data_ptr(), out.data_ptr() if out is not None else None,
+                pixel_values.data_ptr() if pixel_values is not None else None, mean_std.data_ptr() if pixel_values is not None else None),
+               (frames, params, workspace, out, pixel_values, mean_std), run,
+               nbytes=B * H * W * (3.0 + (3 if out is not None else 0) + (12 if pixel_values is not None else 0)))
 
 
 def fill_synth(dst: torch.Tensor, seed: int, mean: float, scale: float, *, rows: Optional[int] = None,
                cols: Optional[int] = None, ld: Optional[int] = None, run: bool = True) -> Op:
     """Deterministic synthetic fill (see oracle/synth.py for the CPU restatement of the same generator)."""
-    lib = _lib.load()
     _bf16(dst, "dst")
     if rows is None:
         rows, cols, ld = 1, dst.numel(), dst.numel()
-    op = Op("bl_fill_synth_bf16_2d", lib.bl_fill_synth_bf16_2d,
-            (dst.data_ptr(), rows, cols, ld, seed & 0xFFFFFFFF, float(mean), float(scale)), (dst,))
-    if run:
-        op.run()
-    return op
+    return _op("bl_fill_synth_bf16_2d", (dst.data_ptr(), rows, cols, ld, seed & 0xFFFFFFFF, float(mean), float(scale)), (dst,), run)

@@ -7,21 +7,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
-from .ops import Op, _attn_desc, _bf16, _rows
-
-
-def _op(name: str, args: tuple, keep: tuple, run: bool, nbytes: float = 0.0, flops: float = 0.0) -> Op:
-    op = Op(name, getattr(_lib.load(), name), args, keep, flops=flops, nbytes=nbytes)
-    if run:
-        op.run()
-    return op
-
-
-def _f32(t: torch.Tensor, what: str) -> torch.Tensor:
-    if t.dtype != torch.float32 or not t.is_cuda:
-        raise TypeError(f"{what}: expected a CUDA/HIP float32 tensor, got {t.dtype} on {t.device}")
-    return t
+from .ops import Op, _attn_desc, _bf16, _dev, _f32, _op, _rows
 
 
 def cross_entropy_backward(logits, targets, mean_and_count, dlogits, ignore_index: int = -100, run: bool = True) -> Op:
@@ -101,8 +87,7 @@ def preference_loss(logits, targets, pair, ref_logprob, row_stats, stats, pair_s
     if int(group_rows) != group_rows or group_rows < 1 or rows % int(group_rows):
         raise ValueError(f"preference_loss: needs group_rows >= 1 dividing the {rows} rows, got {group_rows!r}")
     groups = rows // int(group_rows)
-    if pair.dtype != torch.int32 or not pair.is_cuda or pair.numel() != groups or not pair.is_contiguous():
-        raise TypeError(f"preference_loss: pair int32 [{groups}] contiguous on the device")
+    _dev(pair, torch.int32, groups, "preference_loss: pair")
     if (ref_logprob is None) != bool(cfg.reference_free):
         raise ValueError("preference_loss: ref_logprob is given unless cfg.reference_free")
     if ref_logprob is not None and (_f32(ref_logprob, "ref_logprob").numel() != rows or not ref_logprob.is_contiguous()):
@@ -111,8 +96,8 @@ def preference_loss(logits, targets, pair, ref_logprob, row_stats, stats, pair_s
         raise ValueError("preference_loss: pair_stats fp32 [cap >= 1, 4] contiguous")
     if tuple(_f32(seq_stats, "seq_stats").shape) != (groups, 4) or not seq_stats.is_contiguous():
         raise ValueError(f"preference_loss: seq_stats fp32 [{groups}, 4] contiguous")
-    if n_pairs is not None and (n_pairs.dtype != torch.int32 or not n_pairs.is_cuda or n_pairs.numel() != 1):
-        raise TypeError("preference_loss: n_pairs is an int32 device scalar")
+    if n_pairs is not None:
+        _dev(n_pairs, torch.int32, 1, "preference_loss: n_pairs")
     rng = cfg.token_range
     first, count = (0, n) if rng is None else (int(rng[0]), int(rng[1]))
     return _op("bl_preference_loss_f32",
@@ -144,9 +129,8 @@ def _value_common(hn, w, value_rows, index, count, cfg, group_rows, what: str):
         raise ValueError(f"{what}: w bf16 [{dim}] contiguous")
     if tuple(_f32(value_rows, "value_rows").shape) != (rows, 4) or not value_rows.is_contiguous():
         raise ValueError(f"{what}: value_rows fp32 [{rows}, 4] contiguous")
-    for t, n, name in ((index, cap, "index"), (count, 1, "count")):
-        if t.dtype != torch.int32 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
-            raise TypeError(f"{what}: {name} int32 [{n}] contiguous on the device")
+    _dev(index, torch.int32, cap, f"{what}: index")
+    _dev(count, torch.int32, 1, f"{what}: count")
     return rows, dim, cap, (int(group_rows) if cfg.level == "action" else 0), (1 if cfg.level == "action" else 0)
 
 

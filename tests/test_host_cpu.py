@@ -24,6 +24,38 @@ def test_library_exports_every_declared_symbol():
     assert lib.bl_abi_version() >= 1 and lib.bl_build_arch() == b"gfx950"
 
 
+def test_signatures_match_header_types():
+    """_lib.SIGNATURES mirrors every prototype of the header type for type: a swapped int32_t / int64_t pair would pass the
+    name check above and corrupt a call silently. No prototype may go unparsed (86 of them when this was written)."""
+    import ctypes as C
+    from bridgelang_amd import _lib
+    header = (ROOT / "include" / "bridgelang_hip.h").read_text()
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header, flags=re.S)
+    code = re.sub(r"\{[^{}]*\}", " ", code)                      # struct bodies: their members are no prototypes
+    scalar = {"int64_t": C.c_int64, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "float": C.c_float, "int": C.c_int}
+    desc = {"bl_gemm_desc": C.POINTER(_lib.GemmDesc), "bl_attn_desc": C.POINTER(_lib.AttnDesc)}
+
+    def ctype(param):
+        words = param.replace("*", " * ").split()
+        words = [w for w in words[:-1] if w != "const"]          # drop the parameter's name and the qualifiers
+        if "*" in words:
+            return desc.get(words[0], C.c_void_p) if words[1:] == ["*"] else C.c_void_p
+        (word,) = words
+        return scalar[word]                                      # KeyError: a type this test does not know yet
+
+    protos = {}
+    for res, name, params in re.findall(r"\b(int|const\s+char\s*\*)\s*(bl_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code):
+        params = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+        assert name not in protos, name
+        protos[name] = (C.c_int if res == "int" else C.c_char_p, [ctype(p) for p in params])
+    assert set(protos) == set(re.findall(r"\b(bl_[a-z0-9_]+)\s*\(", code)), "a prototype went unparsed"
+    assert len(protos) >= 86 and set(protos) == set(_lib.SIGNATURES), set(protos) ^ set(_lib.SIGNATURES)
+    assert protos["bl_build_arch"][0] is C.c_char_p and all(r is C.c_int for n, (r, _) in protos.items() if n != "bl_build_arch")
+    wrong = {n: (protos[n], tuple(_lib.SIGNATURES[n])) for n in protos
+             if (protos[n][0], list(protos[n][1])) != (_lib.SIGNATURES[n][0], list(_lib.SIGNATURES[n][1]))}
+    assert not wrong, wrong
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     from bridgelang_amd import _lib
     monkeypatch.setenv("BRIDGELANG_HIP_LIB", str(tmp_path / "nope.so"))
