@@ -133,6 +133,7 @@ SIGNATURES = {
     "bl_value_head_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp,
                                     _vp, _vp]),
     "bl_value_head_backward_f32": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _vp]),
+    "bl_value_predict_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _f32, _vp, _vp, _vp, _i64, _vp]),
     "bl_rmsnorm_backward_bf16": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),
     "bl_layernorm_backward_bf16": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),
     "bl_colsum_bf16": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),

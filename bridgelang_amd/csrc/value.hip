@@ -25,6 +25,10 @@
 //   value_wgrad_kernel    a thread owns 8 columns and walks the list in ascending order: dw[k] = fma(dv_r, hn[r,k], dw[k]);
 //                         one more workgroup sums db (lane L takes entries L, L + 64, … ascending, then wave_sum).
 //   value_dgrad_kernel    one wave per list entry: dh[r,k] = bf16(float(dh[r,k]) + dv_r·w[k]); skipped when dh is NULL.
+//
+// Inference, one launch (bl_value_predict_f32):
+//   value_predict_kernel  one wave per residual row: the final RMSNorm of norm.hip and value_rows_kernel's v, the row held in
+//                         registers in between — the bits of the two ops in sequence, one fp32 per row out.
 #include "bl_common.h"
 #include <limits.h>
 #include <math.h>
@@ -234,6 +238,58 @@ __global__ __launch_bounds__(256) void value_dgrad_kernel(const uint16_t* w, int
   }
 }
 
+// Inference: V(s) straight from the residual rows — the final RMSNorm and the head in one launch (bl_value_predict_f32).
+// Defined by composition: the bits of bl_rmsnorm_bf16 (norm.hip, norm_rows_kernel<NCH, true>) followed by
+// value_rows_kernel's v. Both give lane L the columns [512·c + 8·L, + 8) of chunk c, so the row never leaves the
+// registers: the sum of squares in norm_rows_kernel's expression and order, hn = bf16(norm_w · bf16(x · rstd)) through the
+// same rbf / pack2bf, then value_rows_kernel's one fmaf chain per lane in ascending k, wave_sum, + b on lane 0.
+// One wave per row, four per workgroup, no LDS, no barrier; a row at or beyond `rows` and a column at or beyond `dim` are
+// never loaded; the only store is out[row · out_stride].
+template <int NCH>
+__global__ __launch_bounds__(256) void value_predict_kernel(const uint16_t* __restrict__ x, long ldx, int rows, int dim,
+                                                            const uint16_t* __restrict__ nw, float eps,
+                                                            const uint16_t* __restrict__ w, const uint16_t* __restrict__ b,
+                                                            float* __restrict__ out, long out_stride) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;   // whole wave exits together
+  const int nchunk = dim >> 3;
+  const uint16_t* xr = x + (long)row * ldx;
+  float v[NCH][8];
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int ch = c * 64 + lane;
+    u32x4_t q = {0u, 0u, 0u, 0u};
+    if (ch < nchunk) q = *(const u32x4_t*)(xr + ch * 8);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { v[c][2 * i] = bflo(q[i]); v[c][2 * i + 1] = bfhi(q[i]); }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s += v[c][i] * v[c][i];
+  }
+  s = wave_sum(s);
+  const float inv_n = 1.0f / (float)dim;
+  const float rstd = 1.0f / sqrtf(s * inv_n + eps);
+  float acc = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int ch = c * 64 + lane;
+    if (ch >= nchunk) continue;
+    const u32x4_t nq = *(const u32x4_t*)(nw + ch * 8);
+    u32x4_t hq;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      hq[i] = pack2bf(bflo(nq[i]) * rbf(v[c][2 * i] * rstd), bfhi(nq[i]) * rbf(v[c][2 * i + 1] * rstd));
+    float h[8], ww[8];
+    unpack8(hq, h);
+    unpack8(*(const u32x4_t*)(w + ch * 8), ww);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc = fmaf(h[e], ww[e], acc);
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) out[(long)row * out_stride] = acc + bf2f(b[0]);
+}
+
 }  // namespace bl_value_impl
 using namespace bl_value_impl;
 
@@ -285,6 +341,28 @@ extern "C" int bl_value_head_backward_f32(const bl_bf16* hn, int64_t ld, int32_t
   if (dh)
     hipLaunchKernelGGL(value_dgrad_kernel, dim3((int)((cap + 3) / 4)), dim3(256), 0, s, (const uint16_t*)w, dim, value_rows, index,
                        count, (int)cap, rows, inv_world, (uint16_t*)dh, (long)lddh);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
+extern "C" int bl_value_predict_f32(const bl_bf16* x, int64_t ldx, int32_t rows, int32_t dim, const bl_bf16* norm_w, float eps,
+                                    const bl_bf16* w, const bl_bf16* b, float* out, int64_t out_stride, void* stream) {
+  if (!x || !norm_w || !w || !b || !out) return BL_E_ARG;
+  if (rows <= 0 || dim <= 0 || (dim % 8) || dim > 64 * 8 * 10 || out_stride < 1) return BL_E_SHAPE;
+  if ((ldx % 8) || !bl_aligned16(x) || !bl_aligned16(norm_w) || !bl_aligned16(w)) return BL_E_ALIGN;
+  const dim3 grid((rows + 3) / 4), block(256);
+  hipStream_t s = (hipStream_t)stream;
+#define BL_VP_CASE(N)                                                                                                  \
+  case N:                                                                                                              \
+    hipLaunchKernelGGL((value_predict_kernel<N>), grid, block, 0, s, (const uint16_t*)x, (long)ldx, rows, dim,         \
+                       (const uint16_t*)norm_w, eps, (const uint16_t*)w, (const uint16_t*)b, out, (long)out_stride);   \
+    break;
+  switch ((dim / 8 + 63) / 64) {
+    BL_VP_CASE(1) BL_VP_CASE(2) BL_VP_CASE(3) BL_VP_CASE(4) BL_VP_CASE(5)
+    BL_VP_CASE(6) BL_VP_CASE(7) BL_VP_CASE(8) BL_VP_CASE(9) BL_VP_CASE(10)
+    default: return BL_E_SHAPE;
+  }
+#undef BL_VP_CASE
   BL_CHECK_LAUNCH();
   return BL_OK;
 }

@@ -15,7 +15,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import ops, train_ops
 from .attention_taps import MAX_SEGMENTS, ActionAttention, AttnTaps, pad_bounds, prompt_segments
 from .llm_plan import decode_fused, decode_layer, head, head_fused, prefill_layer
 from .ops import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_F32_BF16R, EPI_NONE, EPI_RES, EPI_SWIGLU, Fp8Weight, Op
@@ -47,7 +47,7 @@ class OpenVLAEngine:
                  use_mask: bool = False, splitk: bool = False, fp8: bool = False, padded: bool = False,
                  vision_only: bool = False, text_only: bool = False, sample: bool = False, score: bool = False,
                  score_range: Optional[Tuple[int, int]] = None, vocab_range: Optional[Tuple[int, int]] = None,
-                 attn_taps: Optional[AttnTaps] = None):
+                 attn_taps: Optional[AttnTaps] = None, value: Optional[str] = None, value_head=None):
         """all_rows=True builds the training/eval-style forward instead of generation: logits for every position
         (`logits_all` [B*S, vocab] fp32) and no decode steps. use_mask=True threads a [B, S] uint8 key-padding mask
         (`key_mask`, 1 = attend) through the Llama attention (modeling_prismatic.py:387-390). splitk=True lets
@@ -85,7 +85,15 @@ class OpenVLAEngine:
         tensor `seg_bounds`, filled by `set_segments`); in an all_rows plan on all S rows, into one [B, H, S, S] buffer
         per tapped layer (`attention_maps()`). The taps read qkv and the KV cache and write nothing the plan reads: every
         id, logit and weight is what the engine without them gives, and with attn_taps=None every plan is op for op the
-        one it was."""
+        one it was.
+        value="action" | "token" with value_head=<training.value_head.ValueHead> adds the critic to a generation plan: one
+        bl_value_predict_f32 beside the pick of the prefill's head (and, at "token", of every decode step's), over the
+        residual rows the lm_head reads — final RMSNorm and head in one launch, since the norm's output is normally never
+        written at inference. `values` fp32 [1 | n_new, B]: values[0] is V(s) of the state the action is taken in (the row
+        that predicts the first action token, the learner's level="action" value row), values[t] the row that predicts
+        action token t + 1 (level="token"). The op reads the head's live weight / bias tensors in place: a learner's
+        write-back shows on the next replay of the same captured graph. It writes nothing the plan reads, and with
+        value=None every plan is op for op the one it was."""
         self.w, self.dims = weights, weights.dims
         self.vision_only, self.text_only = vision_only, text_only
         if text_only and (vision_only or padded or fp8):
@@ -188,6 +196,20 @@ class OpenVLAEngine:
             self.w8 = _fp8_layers(weights)
             self.h8, self.act8 = z(B * S, D, dtype=torch.uint8), z(B * S, I, dtype=torch.uint8)
             self.sq = z(B * S, dtype=torch.float32)
+        self.value, self.value_head, self.values = value, value_head, None
+        if value is not None:
+            if value not in ("action", "token"):
+                raise ValueError(f"value is None, 'action' or 'token', got {value!r}")
+            if all_rows or vision_only:
+                raise ValueError("value= belongs to a generation plan")
+            if value_head is None or value_head.dim != D:
+                raise ValueError(f"value={value!r} needs a value_head of dim {D}, got "
+                                 f"{None if value_head is None else value_head.dim}")
+            if value_head.weight.device != dev:
+                raise ValueError(f"value_head lives on {value_head.weight.device}, the weights on {dev}")
+            self.values = z(n_new if value == "token" else 1, B, dtype=torch.float32)
+        elif value_head is not None:
+            raise ValueError("value_head goes with value='action' or 'token'")
         self.attn_taps, self.tap_slot = attn_taps, {}
         if attn_taps is not None:
             if vision_only:
@@ -391,7 +413,15 @@ class OpenVLAEngine:
         """final RMSNorm → lm_head (bf16-rounded fp32 logits) → the token of generation step t."""
         logits = self.logits[t][b0:b1]
         norm_lin = functools.partial(self._norm_lin, fused=head_fused(logits.shape[0], self.dims), b0=b0, b1=b1)
-        return head(self.w, x_rows, logits, norm_lin, [self._pick(logits, t, b0, b1)])
+        return head(self.w, x_rows, logits, norm_lin, [self._pick(logits, t, b0, b1)] + self._value(x_rows, t, b0, b1))
+
+    def _value(self, x_rows: torch.Tensor, t: int, b0: int = 0, b1: Optional[int] = None) -> List[Op]:
+        """The critic over the residual rows generation step t's lm_head reads, into values[t] (nothing without a head, and
+        nothing past step 0 at level "action"). The pipeline calls it with its own rows for this engine's batch."""
+        if self.value is None or (t > 0 and self.value != "token"):
+            return []
+        vh = self.value_head
+        return [train_ops.value_predict(x_rows, self.w.norm, self.dims.rms_eps, vh.weight, vh.bias, self.values[t][b0:b1], run=False)]
 
     def _pick(self, logits: torch.Tensor, t: int, b0: int = 0, b1: Optional[int] = None) -> Op:
         """Generation step t's token from its logits: greedy argmax (sample=True: the seeded draw; score=True: the score
@@ -555,6 +585,13 @@ class OpenVLAEngine:
         if self.attn_taps is None or not self.all_rows:
             raise ValueError("engine was not built with attn_taps on an all_rows plan")
         return tuple(self.tap_maps[self.tap_slot[l]] if l in self.tap_slot else None for l in range(self.dims.llm_layers))
+
+    def value_result(self) -> torch.Tensor:
+        """The critic's values of the last run, as a view of the static buffer (device tensor; no host sync): fp32 [B] at
+        value="action", [B, n_new] at "token"."""
+        if self.values is None:
+            raise ValueError("engine was not built with value=")
+        return self.values[0] if self.value == "action" else self.values.t()
 
     def set_sampling(self, params) -> None:
         """Fill the per-sequence settings buffers from a `sampling.SamplingParams` (scalars or one value per sequence;

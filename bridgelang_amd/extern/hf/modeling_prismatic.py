@@ -212,8 +212,10 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
     def engine(self, batch: int, prompt_len: int, n_new: int = 7, padded: bool = False, cached: bool = False,
                sample: bool = False, score: bool = False, score_range: Optional[Tuple[int, int]] = None,
                vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None,
-               attn_taps: Optional[AttnTaps] = None) -> OpenVLAEngine:
-        """`attn_taps` (attention_taps.AttnTaps): an engine whose plan records where the action tokens attend; part of the
+               attn_taps: Optional[AttnTaps] = None, value: Optional[str] = None) -> OpenVLAEngine:
+        """`value` ("action" | "token", see `attach_value_head`): an engine whose plan also evaluates the attached value
+        head; the level and the head's identity join the cache key only when given.
+        `attn_taps` (attention_taps.AttnTaps): an engine whose plan records where the action tokens attend; part of the
         cache key only when given, so the engines of every other call are the ones they were.
         `use_adapters` (see `attach_adapters`): None = the adapted weights if adapters are attached, False = the base
         model, True = the adapted weights or an error. Part of the cache key; adapted engines are built over
@@ -234,11 +236,13 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         weights = self._adapters.adapted_weights() if adapted else self.weights
         key = (batch, prompt_len, n_new, fp8, padded, cached, sample) + (("score", score_range) if score else ()) + \
             (("vocab", vocab_range) if vocab_range is not None else ()) + (("adapted",) if adapted else ()) + \
-            ((("taps", attn_taps.key(self.dims.llm_layers)),) if attn_taps is not None else ())
+            ((("taps", attn_taps.key(self.dims.llm_layers)),) if attn_taps is not None else ()) + \
+            ((("value", value, id(self._value_head)),) if value is not None else ())
         return self._lru(self._engines, key,
                          lambda: OpenVLAEngine(weights, batch, prompt_len, n_new=n_new, fp8=fp8 and not padded, padded=padded,
                                                sample=sample, score=score, score_range=score_range, vocab_range=vocab_range,
-                                               attn_taps=attn_taps))
+                                               attn_taps=attn_taps, value=value,
+                                               value_head=self._value_head if value is not None else None))
 
     # ---- where the action tokens attend (attention_taps.py) ----
     @staticmethod
@@ -342,6 +346,45 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         lora.load_state_dict(sd)
         return self.attach_adapters(lora, fp8=fp8)
 
+    # ---- the critic at inference: V(s) from the rollout's own prefill (training/value_head.py, csrc/value.hip) ----
+    _value_head = None         # the attached training.value_head.ValueHead (the object itself, not a copy)
+
+    def attach_value_head(self, vh) -> "PrismaticForConditionalGeneration":
+        """Let `generate` / `predict_action` / `sample_actions` / `score_actions` return the critic's V(s) (`return_values=`):
+        `vh` is a training.value_head.ValueHead of dim `dims.llm_dim` on this model's device. The model keeps the object,
+        and its engines read `vh.weight` / `vh.bias` in place: a learner that trains this head (TrainStep(value_head=vh)) is
+        seen by the next call, with no rebuild. `use_adapters=` on those calls selects the trunk the value is computed over,
+        as it does for the policy."""
+        if vh.dim != self.dims.llm_dim:
+            raise ValueError(f"attach_value_head: the head's dim {vh.dim} is not the model's llm_dim {self.dims.llm_dim}")
+        if vh.weight.device != self.weights.embed.device:
+            raise ValueError(f"attach_value_head: the head lives on {vh.weight.device}, the model on {self.weights.embed.device}")
+        if self._value_head is not None and self._value_head is not vh:
+            self.detach_value_head()
+        self._value_head = vh
+        return self
+
+    def load_value_head(self, directory) -> "PrismaticForConditionalGeneration":
+        """Attach the head that `ValueHead.save` wrote into `directory` (`value_head.safetensors`)."""
+        from ...training.value_head import ValueHead
+        return self.attach_value_head(ValueHead.load(directory, self.weights.embed.device))
+
+    def detach_value_head(self) -> "PrismaticForConditionalGeneration":
+        """Drop the head and the engines built over it."""
+        self._value_head = None
+        for key in [k for k in self._engines if any(isinstance(p, tuple) and p[:1] == ("value",) for p in k)]:
+            del self._engines[key]
+        return self
+
+    def _value_level(self, return_values: Optional[str]) -> Optional[str]:
+        if return_values is None:
+            return None
+        if return_values not in ("action", "token"):
+            raise ValueError(f'return_values must be None, "action" or "token", got {return_values!r}')
+        if self._value_head is None:
+            raise ValueError("return_values= needs a value head (attach_value_head / load_value_head)")
+        return return_values
+
     # ---- forward: the reference's three branches (modeling_prismatic.py:322-415) ----
     cache_new_tokens = 7       # tokens a `forward(..., use_cache=True)` KV cache is sized for (prefill token + 6 cached steps)
 
@@ -426,8 +469,15 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
                  sampling: Optional[SamplingParams] = None, return_weights: bool = False,
                  forced_ids: Optional[torch.Tensor] = None, score_range: Optional[Tuple[int, int]] = None,
                  vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None,
-                 return_attention: Optional[str] = None, attention_layers=None, text_splits=None, **_: Any):
+                 return_attention: Optional[str] = None, attention_layers=None, text_splits=None,
+                 return_values: Optional[str] = None, **_: Any):
         """`use_adapters`: see `engine` (None: the attached adapters if any; False: the base model).
+        `return_values="action" | "token"` (a value head attached, `attach_value_head`) appends the critic's values, fp32 on
+        the device: [B] = V(s) of the state the action is taken in (the row that predicts the first new token, the
+        learner's level="action" value row), or [B, max_new_tokens] = the rows that predict every new token
+        (level="token"). Order of the returned elements: ids, then wt (`return_weights` / `forced_ids`), then range_wt
+        (`score_range`), then the values, then the `ActionAttention` (`return_attention`). The value op only reads the
+        residual rows: ids, logits and weights are those of the call without it.
         `return_attention="segments" | "full" | "both"` appends an `attention_taps.ActionAttention` to whatever the call
         returns: for every new token, tapped layer (`attention_layers`, None = all) and head, the attention of the query that
         produced it — summed over bos | image | text | generated ("segments"), over every cache row ("full"), or both.
@@ -462,11 +512,12 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         taps = self._attn_taps(return_attention, attention_layers)
         if taps is None and text_splits is not None:
             raise ValueError("text_splits goes with return_attention=")
+        value = self._value_level(return_values)
         if forced_ids is not None:
             forced = torch.as_tensor(forced_ids).to(self.device, torch.int64)
             padded = attention_mask is not None and not bool(attention_mask.bool().all())
             eng = self.engine(B, L, max_new_tokens, padded=padded, score=True, score_range=score_range, vocab_range=vocab_range,
-                              use_adapters=use_adapters, attn_taps=taps)
+                              use_adapters=use_adapters, attn_taps=taps, value=value)
             eng.set_sampling(sampling if sampling is not None else SamplingParams())
             if padded:
                 eng.set_forced_ids(forced)
@@ -480,6 +531,7 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
                 eng.score(ids, pv, forced)
             out = (torch.cat([ids, forced], dim=1), eng.gen_wt.permute(1, 0, 2).clone())
             out = out if score_range is None else out + (eng.gen_range_wt.permute(1, 0, 2).clone(),)
+            out = out if value is None else out + (eng.value_result().clone(),)
             return out if taps is None else out + (self._action_attention(eng),)
         if score_range is not None:
             raise ValueError("score_range goes with forced_ids=")
@@ -488,7 +540,7 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         sample = sampling is not None
         if attention_mask is not None and not bool(attention_mask.bool().all()):
             eng = self.engine(B, L, max_new_tokens, padded=True, sample=sample, vocab_range=vocab_range, use_adapters=use_adapters,
-                              attn_taps=taps)
+                              attn_taps=taps, value=value)
             if sample:
                 eng.set_sampling(sampling)
             eng.set_padded_inputs(ids, pv, attention_mask)
@@ -498,12 +550,14 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             new = eng.gen_ids.t()
         else:
             eng = self.engine(B, L, max_new_tokens, sample=sample, vocab_range=vocab_range, use_adapters=use_adapters,
-                              attn_taps=taps)
+                              attn_taps=taps, value=value)
             if taps is not None:
                 self._set_attention_segments(eng, None, text_splits)
             new = eng.generate(ids, pv, sampling)
         out = torch.cat([ids, new], dim=1)
         out = (out, eng.gen_wt.permute(1, 0, 2).clone()) if return_weights else out
+        if value is not None:
+            out = (out if isinstance(out, tuple) else (out,)) + (eng.value_result().clone(),)
         if taps is None:
             return out
         return (out if isinstance(out, tuple) else (out,)) + (self._action_attention(eng),)
@@ -536,7 +590,10 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         `action_token_range()`: with `sampling=` every draw is an action token, without it the call is constrained greedy
         decoding (the argmax over the action tokens). `return_attention=` / `attention_layers=` / `text_splits=` (see
         `generate`) return the `ActionAttention` of the action tokens as an extra last element; `text_splits` index the
-        input_ids as given (the empty token this call appends joins the last text piece)."""
+        input_ids as given (the empty token this call appends joins the last text piece).
+        `return_values="action" | "token"` (see `generate`, `attach_value_head`) returns the critic's values as one more
+        element, fp32 ndarray [B] or [B, n]. Order: the action, then (tokens, wt) with `return_weights`, then the values, then
+        the `ActionAttention`."""
         input_ids = input_ids.to(self.device)
         kwargs["use_adapters"] = use_adapters
         if action_tokens_only:
@@ -551,20 +608,26 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             kwargs["attention_mask"] = m
         n = self.get_action_dim(unnorm_key)
         generated = self.generate(input_ids, max_new_tokens=n, **kwargs)
-        wt = att = None
-        if kwargs.get("return_attention") is not None:   # the ActionAttention rides last
-            generated, att = (generated[0] if len(generated) == 2 else generated[:-1]), generated[-1]
-        if isinstance(generated, tuple):                 # sampling= with return_weights=True
-            generated, wt = generated
+        wt = att = vals = None
+        if isinstance(generated, tuple):
+            parts = list(generated)
+            if kwargs.get("return_attention") is not None:   # the ActionAttention rides last,
+                att = parts.pop()
+            if kwargs.get("return_values") is not None:      # the values before it
+                vals = parts.pop().cpu().numpy()
+            generated = parts[0]
+            if len(parts) > 1:                               # sampling= with return_weights=True
+                wt = parts[1]
         tokens = generated[:, -n:].cpu().numpy()
         if keys is not None:
             actions = np.stack([np.asarray(self.actions_from_token_ids(tokens[i:i + 1], k)).reshape(-1) for i, k in enumerate(keys)])
         else:
             actions = self.actions_from_token_ids(tokens, unnorm_key)
         out = actions if wt is None else (actions, tokens, wt.cpu().numpy())
-        if att is None:
-            return out
-        return (out if isinstance(out, tuple) else (out,)) + (att,)
+        for extra in (vals, att):
+            if extra is not None:
+                out = (out if isinstance(out, tuple) else (out,)) + (extra,)
+        return out
 
     @staticmethod
     def _stack_attention(parts: Sequence[ActionAttention], B: int) -> ActionAttention:
@@ -601,8 +664,11 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
                        num_samples: int = 1, attention_mask: Optional[torch.Tensor] = None,
                        action_tokens_only: bool = False,
                        use_adapters: Optional[bool] = None, return_attention: Optional[str] = None, attention_layers=None,
-                       text_splits=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                       text_splits=None, return_values: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """`use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy).
+        `return_values="action"` appends V(s) fp32 [B] — every copy of a sequence is in the same state, so one value per
+        sequence, taken from copy 0; `"token"` appends [B, num_samples, n], the values along every copy's own tokens. The
+        values come fourth, before the `ActionAttention`.
         `num_samples` sampled actions per sequence with their log-probabilities (RL rollouts, best-of-N, uncertainty):
         → (actions [B, num_samples, n], token_ids int64 [B, num_samples, n], logprobs fp64 [B, num_samples, n]). The batch
         is repeated `num_samples` times (several copies per engine run while the run stays within 16 sequences); copy j of a sequence with seed s draws with
@@ -621,10 +687,11 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         T, k, p, seed = sampling.resolve(B)
         keys = list(unnorm_key) if isinstance(unnorm_key, (list, tuple)) else None
         per_call = max(1, 16 // B)          # copies per engine run: batches up to 16 keep "a sequence's result is its batch-1 result"
-        acts, toks, lps, atts = [], [], [], []
+        acts, toks, lps, atts, vals = [], [], [], [], []
         att_kw = {}
         if return_attention is not None:
             att_kw = dict(return_attention=return_attention, attention_layers=attention_layers)
+        val_kw = {} if self._value_level(return_values) is None else dict(return_values=return_values)
         for j0 in range(0, num_samples, per_call):
             c = min(per_call, num_samples - j0)
             sp = SamplingParams(temperature=np.tile(T, c), top_k=np.tile(k, c), top_p=np.tile(p, c),
@@ -635,22 +702,30 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
                                       pixel_values=pixel_values.repeat(c, 1, 1, 1),
                                       attention_mask=None if attention_mask is None else attention_mask.repeat(c, 1),
                                       sampling=sp, return_weights=True, action_tokens_only=action_tokens_only,
-                                      use_adapters=use_adapters, **att_kw)
+                                      use_adapters=use_adapters, **val_kw, **att_kw)
             a, tok, wt = res[:3]
+            if val_kw:
+                vals.append(res[3].reshape((c, B) + res[3].shape[1:]))
             if att_kw:
-                atts.append(res[3])
+                atts.append(res[-1])
             acts.append(np.asarray(a).reshape(c, B, -1))
             toks.append(tok.reshape(c, B, -1))
             lps.append(logprob(wt).reshape(c, B, -1))
         out = tuple(np.concatenate(x, axis=0).transpose(1, 0, 2) for x in (acts, toks, lps))
+        if val_kw:      # [copies, B] / [copies, B, n] → copy 0's [B] / [B, copies, n]
+            out += (vals[0][0].copy() if return_values == "action" else np.concatenate(vals, axis=0).transpose(1, 0, 2),)
         return out + (self._stack_attention(atts, B),) if att_kw else out
 
     def score_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor, token_ids=None, actions=None,
                       unnorm_key: Optional[str] = None, sampling: Optional[SamplingParams] = None,
                       attention_mask: Optional[torch.Tensor] = None, return_bins: bool = False,
                       action_tokens_only: bool = False, use_adapters: Optional[bool] = None,
-                      return_attention: Optional[str] = None, attention_layers=None, text_splits=None):
-        """`return_attention=` (with `attention_layers=`, `text_splits=` [B, k]; see `generate`) appends the `ActionAttention`
+                      return_attention: Optional[str] = None, attention_layers=None, text_splits=None,
+                      return_values: Optional[str] = None):
+        """`return_values="action"` appends V(s) fp32 [B] (the state is the same for every candidate: candidate 0's);
+        `"token"` appends [B, K, n], the values along the given tokens. They ride after the log-probabilities (and the wt /
+        bin_wt of `return_bins`) and before the `ActionAttention`.
+        `return_attention=` (with `attention_layers=`, `text_splits=` [B, k]; see `generate`) appends the `ActionAttention`
         under the GIVEN actions, tensors [B, K, n, layers, H, ·], as an extra last element.
         `use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy — with adapters
         attached, an RL learner's reference policy).
@@ -687,10 +762,11 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         rng = (self.vocab_size - n_bins, n_bins) if return_bins else None
         ids, m = self._action_prompt(input_ids.to(self.device), attention_mask)      # the prompt as predict_action prepares it
         per_call = max(1, 16 // B)          # candidates per engine run, as sample_actions batches its copies
-        wts, bins, atts = [], [], []
+        wts, bins, atts, vals = [], [], [], []
         att_kw = {}
         if return_attention is not None:
             att_kw = dict(return_attention=return_attention, attention_layers=attention_layers)
+        val_kw = {} if self._value_level(return_values) is None else dict(return_values=return_values)
         for j0 in range(0, K, per_call):
             c = min(per_call, K - j0)
             sp = SamplingParams(temperature=np.tile(T, c), top_k=np.tile(k, c), top_p=np.tile(p, c), seed=0)
@@ -698,17 +774,23 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             out = self.generate(ids.repeat(c, 1), n, pixel_values=pixel_values.repeat(c, 1, 1, 1),
                                 attention_mask=None if m is None else m.repeat(c, 1), sampling=sp, forced_ids=forced,
                                 score_range=rng, vocab_range=self.action_token_range() if action_tokens_only else None,
-                                use_adapters=use_adapters, **att_kw,
+                                use_adapters=use_adapters, **val_kw, **att_kw,
                                 **(dict(text_splits=torch.as_tensor(text_splits).reshape(B, -1).repeat(c, 1))
                                    if att_kw and text_splits is not None else {}))
             if att_kw:
                 atts.append(out[-1])
+            if val_kw:
+                v = out[-1 - bool(att_kw)].cpu().numpy()
+                vals.append(v.reshape((c, B) + v.shape[1:]))
             wts.append(out[1].cpu().numpy().reshape(c, B, n, 2))
             if return_bins:
                 bins.append(out[2].cpu().numpy().reshape(c, B, n, n_bins))
         wt = np.concatenate(wts, axis=0).transpose(1, 0, 2, 3)
         lp = logprob(wt)
         res = (lp, wt, np.concatenate(bins, axis=0).transpose(1, 0, 2, 3)) if return_bins else lp
+        if val_kw:
+            res = (res if isinstance(res, tuple) else (res,)) + \
+                (vals[0][0].copy() if return_values == "action" else np.concatenate(vals, axis=0).transpose(1, 0, 2),)
         if not att_kw:
             return res
         return (res if isinstance(res, tuple) else (res,)) + (self._stack_attention(atts, B),)

@@ -109,6 +109,20 @@ class PrismaticVLM:
     def generate(self, input_ids: torch.LongTensor, pixel_values, max_new_tokens: int = 7, **kwargs: Any) -> torch.LongTensor:
         return self.hf.generate(input_ids, max_new_tokens=max_new_tokens, pixel_values=self._stack(pixel_values), **kwargs)
 
+    def attach_value_head(self, vh) -> "PrismaticVLM":
+        """The critic at inference (PrismaticForConditionalGeneration.attach_value_head): `return_values=` on `generate` /
+        `predict_action` then returns V(s) from the same prefill."""
+        self.hf.attach_value_head(vh)
+        return self
+
+    def load_value_head(self, directory) -> "PrismaticVLM":
+        self.hf.load_value_head(directory)
+        return self
+
+    def detach_value_head(self) -> "PrismaticVLM":
+        self.hf.detach_value_head()
+        return self
+
     def attention_maps(self, input_ids: torch.LongTensor, pixel_values=None, attention_mask=None, layers=None) -> tuple:
         """HF's `attentions` of the all-position forward (PrismaticForConditionalGeneration.attention_maps)."""
         return self.hf.attention_maps(input_ids, None if pixel_values is None else self._stack(pixel_values), attention_mask, layers)
@@ -123,7 +137,8 @@ class OpenVLA(PrismaticVLM):
 
     def predict_action(self, image, instruction: str, unnorm_key: Optional[str] = None, **kwargs: str) -> np.ndarray:
         """openvla.py:35-103: PIL image + instruction → un-normalised continuous action. `return_attention=` (with
-        `attention_layers=`, `text_splits=`; see the HF model's `generate`) returns (action, ActionAttention)."""
+        `attention_layers=`, `text_splits=`; see the HF model's `generate`) returns (action, ActionAttention);
+        `return_values="action" | "token"` (a value head attached) puts the critic's values, fp32 [1] / [1, n], between the two."""
         image_transform, tokenizer = self.vision_backbone.image_transform, self.llm_backbone.tokenizer
         prompt_builder = self.get_prompt_builder()
         prompt_builder.add_turn(role="human", message=f"What action should the robot take to {instruction.lower()}?")
@@ -140,16 +155,21 @@ class OpenVLA(PrismaticVLM):
             raise ValueError(f"Unsupported `pixel_values` type = {type(pixel_values)}")
         n = self.get_action_dim(unnorm_key)
         generated_ids = self.generate(input_ids, pixel_values, max_new_tokens=n, **kwargs)
-        attention = None
+        attention = values = None
         if kwargs.get("return_attention") is not None:
-            generated_ids, attention = generated_ids[0], generated_ids[-1]
+            generated_ids, attention = generated_ids[:-1], generated_ids[-1]
+        if kwargs.get("return_values") is not None:
+            values = generated_ids[-1].cpu().numpy()
+        if isinstance(generated_ids, tuple):
+            generated_ids = generated_ids[0]
         predicted_action_token_ids = generated_ids[0, -n:]
         normalized_actions = self.action_tokenizer.decode_token_ids_to_actions(predicted_action_token_ids.cpu().numpy())
         action_norm_stats = self.get_action_stats(unnorm_key)
         mask = action_norm_stats.get("mask", np.ones_like(action_norm_stats["q01"], dtype=bool))
         action_high, action_low = np.array(action_norm_stats["q99"]), np.array(action_norm_stats["q01"])
         action = np.where(mask, 0.5 * (normalized_actions + 1) * (action_high - action_low) + action_low, normalized_actions)
-        return action if attention is None else (action, attention)
+        out = tuple(x for x in (action, values, attention) if x is not None)
+        return out[0] if len(out) == 1 else out
 
     @staticmethod
     def _check_unnorm_key(norm_stats: Dict, unnorm_key: str) -> str:

@@ -101,13 +101,16 @@ class StaggeredDecodePipeline:
     def __init__(self, weights: VLAWeights, batch: int, prompt_len: int, n_new: int = 7, split_vision: bool = False,
                  fp8: bool = False, padded: bool = False, sample: bool = False, score: bool = False,
                  score_range: Optional[Tuple[int, int]] = None, vocab_range: Optional[Tuple[int, int]] = None,
-                 attn_taps=None):
+                 attn_taps=None, value: Optional[str] = None, value_head=None):
         """split_vision=True adds a third stage: the vision towers + projector of the batch submitted NOW run beside the
         Llama prefill of the batch submitted one step earlier (n_new + 1 slots, latency n_new + 1 steps).
         score=True (with score_range, as OpenVLAEngine's) scores given tokens instead of producing them: every slot is an
         `OpenVLAEngine(score=True)`, `step(..., forced_ids=, sampling=)` fills the slot's forced ids and settings, and the
         merged iteration ends in bl_score_f32 per group where a sampling pipeline draws. vocab_range=(first, count), with
-        sample=True or score=True, is OpenVLAEngine's: every draw and score is under the policy restricted to that range."""
+        sample=True or score=True, is OpenVLAEngine's: every draw and score is under the policy restricted to that range.
+        value="action" | "token" with value_head= is OpenVLAEngine's critic: every slot engine's prefill carries its
+        bl_value_predict_f32, at "token" the merged iteration adds one per group beside that group's pick, over the group's
+        rows of the stacked residual; step() / flush() append the finished batch's values ([B] / [B, n_new])."""
         if attn_taps is not None:
             raise ValueError("StaggeredDecodePipeline has no attention taps: its merged decode iteration runs several batches' "
                              "rows in one launch; use OpenVLAEngine(attn_taps=...)")
@@ -121,7 +124,9 @@ class StaggeredDecodePipeline:
         self.lag = 1 if split_vision else 0         # steps between a batch's submission and its prefill
         self.slots = n_new + self.lag
         self.engines = [OpenVLAEngine(weights, batch, prompt_len, n_new, fp8=fp8, padded=padded, sample=sample, score=score,
-                                      score_range=score_range, vocab_range=vocab_range) for _ in range(self.slots)]
+                                      score_range=score_range, vocab_range=vocab_range, value=value, value_head=value_head)
+                        for _ in range(self.slots)]
+        self.value = value
         self.vocab_range = self.engines[0].vocab_range
         self.device = dev = weights.embed.device
         d = self.dims
@@ -184,7 +189,8 @@ class StaggeredDecodePipeline:
         # iteration g of a batch draws with ITS slot's settings at Philox counter g, as its engine would — or scores ITS
         # slot's forced token g, which the next iteration's embedding consumes unchanged
         return plan + head(w, self.xd, self.logits, functools.partial(norm_lin, fused=head_fused(B, d)),
-                           [e._pick(self.logits[r], g) for g, e, r in groups])
+                           [e._pick(self.logits[r], g) for g, e, r in groups]
+                           + [op for g, e, r in groups for op in e._value(self.xd[r], g)])
 
     def _run_tick(self, k: int) -> None:
         """stage 1 of slot k ‖ the merged decode iteration over the other slots."""
@@ -237,7 +243,9 @@ class StaggeredDecodePipeline:
         A score=True pipeline takes the submitted batch's `forced_ids` [B, n_new] (required with input_ids; checked
         against the vocabulary unless `ids_checked=True`, a host synchronisation for ids on the device) and `sampling`
         into the slot, and returns the completed batch's wt [B, n_new, 2] — with score_range the pair (wt, range_wt
-        [B, n_new, count]) — again views."""
+        [B, n_new, count]) — again views.
+        A pipeline built with value= appends the completed batch's values (fp32 [B] at "action", [B, n_new] at "token") as
+        the last element of whatever it returns otherwise, a view like the others."""
         k = self._tick % self.slots
         if sampling is not None and (not (self.sample or self.score) or input_ids is None):
             raise ValueError("sampling goes with the input_ids of a pipeline built with sample=True or score=True")
@@ -267,8 +275,12 @@ class StaggeredDecodePipeline:
         """What step() / flush() hand out for a slot's finished batch (`own`: identity for views, clone for copies)."""
         if self.score:
             wt = own(e.gen_wt.permute(1, 0, 2))
-            return wt if e.gen_range_wt is None else (wt, own(e.gen_range_wt.permute(1, 0, 2)))
-        return (own(e.gen_ids.t()), own(e.gen_wt.permute(1, 0, 2))) if self.sample else own(e.gen_ids.t())
+            out = wt if e.gen_range_wt is None else (wt, own(e.gen_range_wt.permute(1, 0, 2)))
+        else:
+            out = (own(e.gen_ids.t()), own(e.gen_wt.permute(1, 0, 2))) if self.sample else own(e.gen_ids.t())
+        if self.value is None:
+            return out
+        return (*out, own(e.value_result())) if isinstance(out, tuple) else (out, own(e.value_result()))
 
     def flush(self, ticks: Optional[Sequence[int]] = None) -> List[Optional[torch.Tensor]]:
         """Drain: finish the batches still in flight with each slot's own per-batch plans; returns their ids oldest

@@ -35,6 +35,11 @@ bridgelang_amd/sampling.py; no seed: one is drawn from torch's default generator
 distribution. The settings are per-sequence device arrays, so requests with different settings (and requests with none:
 greedy rows, temperature 0, the greedy server's action bit for bit) share batches and pipelines. Any other payload key is
 answered with "error"; so is a sampling key sent to a server without `sample=True`.
+
+The critic (`value_head=`, opt-in): a payload may carry `"return_value": true`; the answer is then
+{"action": ndarray[7], "value": float} (plus "logprob" when that was asked for too): V(s) of the state the action was taken
+in, from the same prefill (engine.py, `value="action"`). Requests with and without it share batches. Sent to a server
+without a value head it is answered with "error".
 """
 from __future__ import annotations
 
@@ -107,7 +112,7 @@ def decode_tree(obj: Any) -> Any:
 
 # ---- server ----------------------------------------------------------------------------------------------------------
 class _Request:
-    __slots__ = ("input_ids", "pixel_values", "unnorm_key", "future", "mask", "group", "sampling", "want_logprob")
+    __slots__ = ("input_ids", "pixel_values", "unnorm_key", "future", "mask", "group", "sampling", "want_logprob", "want_value")
 
     def __init__(self, input_ids, pixel_values, unnorm_key):
         self.input_ids, self.pixel_values, self.unnorm_key = input_ids, pixel_values, unnorm_key
@@ -116,6 +121,7 @@ class _Request:
         self.group: Optional[tuple] = None            # requests with equal group keys may share a GPU batch
         self.sampling: Tuple[float, int, float, int] = (0.0, 0, 1.0, 0)    # sample=True: temperature (0 = greedy), top_k, top_p, seed
         self.want_logprob = False
+        self.want_value = False
 
 
 class OpenVLAServer:
@@ -130,15 +136,21 @@ class OpenVLAServer:
     `adapter=` (a directory written by `training.finetune.save_checkpoint`, or a training.lora.LoraAdapters over `vla`'s
     weights) serves the model under those LoRA adapters: they are attached (`vla.load_adapter` / `vla.attach_adapters`)
     before any pipeline is built, and the pipelines read the adapted weights. A learner that refreshes the adapted weights
-    while the server runs must let the pipelines drain first (`LoraAdapters.refresh`, ordering contract)."""
+    while the server runs must let the pipelines drain first (`LoraAdapters.refresh`, ordering contract).
+    `value_head=` (a training.value_head.ValueHead, or a directory `ValueHead.save` wrote) attaches the critic
+    (`vla.attach_value_head` / `vla.load_value_head`): every batch then also evaluates V(s) of its states (one more launch per
+    prefill), `predict_action(..., return_values="action")` on the plain route, and a request with `"return_value": true`
+    is answered with it."""
 
     _BASE_KEYS = ("image", "instruction", "unnorm_key")
     _SAMPLING_KEYS = ("temperature", "top_k", "top_p", "seed", "return_logprob")
+    _VALUE_KEYS = ("return_value",)
 
     def __init__(self, vla: Any, processor: Any, openvla_path: Union[str, Path] = "openvla/openvla-7b",
                  max_batch: int = 16, max_wait_ms: float = 2.0, norm_stats_path: Optional[Union[str, Path]] = None,
                  pipeline_batch: Optional[int] = None, max_pipelines: int = 2, pad_to: Optional[int] = None,
-                 sample: bool = False, action_tokens_only: bool = False, adapter: Any = None, attn_taps: Any = None):
+                 sample: bool = False, action_tokens_only: bool = False, adapter: Any = None, attn_taps: Any = None,
+                 value_head: Any = None):
         if attn_taps is not None:
             raise ValueError("OpenVLAServer does not return attention: call the model's generate / predict_action with "
                              "return_attention=...")
@@ -148,6 +160,13 @@ class OpenVLAServer:
                 vla.load_adapter(adapter)
             else:
                 vla.attach_adapters(adapter)
+        self.value = None                         # "action" when a value head is attached: what the pipelines / calls are built with
+        if value_head is not None:
+            if isinstance(value_head, (str, Path)):
+                vla.load_value_head(value_head)
+            else:
+                vla.attach_value_head(value_head)
+            self.value = "action"
         self.sample = bool(sample)
         if action_tokens_only and not sample:
             raise ValueError("action_tokens_only goes with sample=True")
@@ -183,7 +202,9 @@ class OpenVLAServer:
         sampling_keys = [k for k in self._SAMPLING_KEYS if k in payload]
         if sampling_keys and not self.sample:
             raise ValueError(f"{sampling_keys}: this server was started without sample=True")
-        unknown = [k for k in payload if k not in self._BASE_KEYS + self._SAMPLING_KEYS] if self.sample else []
+        if "return_value" in payload and self.value is None:
+            raise ValueError("return_value: this server was started without a value_head")
+        unknown = [k for k in payload if k not in self._BASE_KEYS + self._SAMPLING_KEYS + self._VALUE_KEYS] if self.sample else []
         if unknown:
             raise ValueError(f"unknown payload keys {unknown}")
         prompt = get_openvla_prompt(instruction, self.openvla_path)
@@ -195,6 +216,7 @@ class OpenVLAServer:
                                            payload.get("seed", None)).resolve(1)        # validates; draws a missing seed
             req.sampling = (float(T[0]), int(k[0]), float(p[0]), int(seed[0]))
         req.want_logprob = bool(payload.get("return_logprob", False))
+        req.want_value = bool(payload.get("return_value", False))
         return req
 
     def _sampling_of(self, rows: List[_Request]):
@@ -217,8 +239,9 @@ class OpenVLAServer:
             else:
                 payload = decode_tree(payload)
             action = self._submit(payload)
-            if isinstance(action, dict):      # return_logprob
-                return dumps(action) if double_encode else {k: encode_ndarray(v) for k, v in action.items()}
+            if isinstance(action, dict):      # return_logprob / return_value (a plain float)
+                return dumps(action) if double_encode else {k: encode_ndarray(v) if isinstance(v, np.ndarray) else v
+                                                            for k, v in action.items()}
             return dumps(action) if double_encode else encode_ndarray(action)
         except Exception:   # noqa: BLE001 — the reference answers every failure with "error"
             logging.error(traceback.format_exc())
@@ -289,11 +312,14 @@ class OpenVLAServer:
         lora = getattr(self.vla, "_adapters", None)
         return lora.adapted_weights() if lora is not None else self.vla.weights
 
+    def _value_kw(self) -> Dict[str, Any]:
+        return {} if self.value is None else dict(value=self.value, value_head=self.vla._value_head)
+
     def _padded_pipe(self):
         from .pipeline import StaggeredDecodePipeline
         if self._pad_pipe is None:
             pipe = StaggeredDecodePipeline(self._weights(), self.pipeline_batch, self.pad_to, padded=True, sample=self.sample,
-                                           vocab_range=self.vocab_range)
+                                           vocab_range=self.vocab_range, **self._value_kw())
             pipe.capture()
             self.pipelines_built += 1
             self._pad_pipe = (pipe, {})
@@ -310,28 +336,37 @@ class OpenVLAServer:
             del self._pipes[old_len]
             del old
             torch.cuda.empty_cache()
-        pipe = StaggeredDecodePipeline(self._weights(), self.pipeline_batch, L, sample=self.sample, vocab_range=self.vocab_range)
+        pipe = StaggeredDecodePipeline(self._weights(), self.pipeline_batch, L, sample=self.sample, vocab_range=self.vocab_range,
+                                       **self._value_kw())
         pipe.capture()
         self.pipelines_built += 1
         self._pipes[L] = (pipe, {})
         return self._pipes[L]
 
     @staticmethod
-    def _answer(r: _Request, action: np.ndarray, wt: Optional[np.ndarray]) -> Any:
-        if not r.want_logprob:
+    def _answer(r: _Request, action: np.ndarray, wt: Optional[np.ndarray], value: Optional[float] = None) -> Any:
+        if not (r.want_logprob or r.want_value):
             return action
-        from .sampling import logprob
-        return {"action": action, "logprob": logprob(wt)}
+        out = {"action": action}
+        if r.want_logprob:
+            from .sampling import logprob
+            out["logprob"] = logprob(wt)
+        if r.want_value:
+            out["value"] = float(value)
+        return out
 
     def _resolve(self, reqs: List[_Request], out) -> None:
-        """`out`: the pipeline's token ids [B, 7], or with sample=True the pair (ids, wt [B, 7, 2])."""
-        token_ids, wt = out if self.sample else (out, None)
+        """`out`: the pipeline's token ids [B, 7], or with sample=True the pair (ids, wt [B, 7, 2]); with a value head the
+        values [B] ride last."""
+        out = tuple(out) if isinstance(out, (tuple, list)) else (out,)
+        vals = out[-1].cpu().numpy() if self.value is not None else None
+        token_ids, wt = out[0], (out[1] if self.sample else None)
         ids = token_ids.cpu().numpy()
         wt = wt.cpu().numpy() if wt is not None else None
         for i, r in enumerate(reqs):
             try:
                 action = np.asarray(self.vla.actions_from_token_ids(ids[i:i + 1], r.unnorm_key)).reshape(-1)
-                r.future.set_result(self._answer(r, action, None if wt is None else wt[i]))
+                r.future.set_result(self._answer(r, action, None if wt is None else wt[i], None if vals is None else vals[i]))
             except Exception as e:   # noqa: BLE001 — e.g. an unknown unnorm_key: that request alone fails
                 r.future.set_exception(e)
 
@@ -385,7 +420,7 @@ class OpenVLAServer:
                 self._record(batch)
                 done = tick - (pipe.slots - 1)
                 if done in inflight:
-                    self._resolve(inflight.pop(done), tuple(o.clone() for o in out) if self.sample else out.clone())
+                    self._resolve(inflight.pop(done), tuple(o.clone() for o in out) if isinstance(out, tuple) else out.clone())
             except Exception as e:   # noqa: BLE001
                 for r in batch:
                     if not r.future.done():
@@ -416,25 +451,28 @@ class OpenVLAServer:
             rows = batch + [batch[-1]] * (size - n)
             ids = torch.cat([r.input_ids for r in rows], dim=0)
             pv = torch.cat([r.pixel_values for r in rows], dim=0)
-            wt = None
+            wt = vals = None
+            vkw = {} if self.value is None else dict(return_values=self.value)
             if self.sample:                   # per-row settings: mixed requests (greedy ones included) ride one call
                 kw = dict(unnorm_key=[r.unnorm_key for r in rows], attention_mask=torch.cat([r.mask for r in rows], dim=0)) \
                     if batch[0].mask is not None else dict(unnorm_key=batch[0].unnorm_key)
-                actions, _, wt = self.vla.predict_action(input_ids=ids, pixel_values=pv, sampling=self._sampling_of(rows),
-                                                         return_weights=True, **kw,
-                                                         **(dict(action_tokens_only=True) if self.vocab_range is not None else {}))
-                actions, wt = np.asarray(actions), np.asarray(wt)[:n]
+                res = self.vla.predict_action(input_ids=ids, pixel_values=pv, sampling=self._sampling_of(rows),
+                                              return_weights=True, **kw, **vkw,
+                                              **(dict(action_tokens_only=True) if self.vocab_range is not None else {}))
+                actions, wt = np.asarray(res[0]), np.asarray(res[2])[:n]
+                vals = res[3] if vkw else None
             elif batch[0].mask is not None:     # pad_to: lengths and keys are mixed — every sequence un-normalised with its own key
-                actions = np.asarray(self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=[r.unnorm_key for r in rows],
-                                                             attention_mask=torch.cat([r.mask for r in rows], dim=0),
-                                                             do_sample=False))
+                actions = self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=[r.unnorm_key for r in rows],
+                                                  attention_mask=torch.cat([r.mask for r in rows], dim=0), do_sample=False, **vkw)
             else:
-                actions = np.asarray(self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=batch[0].unnorm_key,
-                                                             do_sample=False))
-            actions = actions.reshape(size, -1)[:n]
+                actions = self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=batch[0].unnorm_key,
+                                                  do_sample=False, **vkw)
+            if vkw and not self.sample:
+                actions, vals = actions
+            actions = np.asarray(actions).reshape(size, -1)[:n]
             self._record(batch)
             for i, (r, a) in enumerate(zip(batch, actions)):
-                r.future.set_result(self._answer(r, a, None if wt is None else wt[i]))
+                r.future.set_result(self._answer(r, a, None if wt is None else wt[i], None if vals is None else vals[i]))
         except Exception as e:   # noqa: BLE001 — delivered to every waiting request
             for r in batch:
                 if not r.future.done():

@@ -177,6 +177,24 @@ def value_head_backward(hn, w, value_rows, index, count, dw, db, dh, cfg, group_
                (hn, w, value_rows, index, count, dw, db, dh), run, nbytes=(2.0 if dh is None else 6.0) * cap * dim)
 
 
+def value_predict(x, norm_w, eps: float, w, b, out, run: bool = True) -> Op:
+    """V(s) of the residual rows x [rows, dim] (bf16, any row stride that is a multiple of 8) at inference: the final RMSNorm
+    (norm_w, eps) and the value head (w bf16 [dim], b bf16 [1]) in one launch, out fp32 [rows] (any stride) — bit for bit
+    `ops.rmsnorm` followed by `value_head`'s v, without writing the norm's output. w and b are read when the op runs."""
+    rows, dim = _bf16(x, "x").shape
+    for t, what in ((norm_w, "norm_w"), (w, "w")):
+        if _bf16(t, what).numel() != dim or not t.is_contiguous():
+            raise ValueError(f"value_predict: {what} bf16 [{dim}] contiguous")
+    if _bf16(b, "b").numel() != 1:
+        raise ValueError("value_predict: b bf16 [1]")
+    if _f32(out, "out").dim() != 1 or out.shape[0] != rows or (rows > 1 and out.stride(0) < 1):
+        raise ValueError(f"value_predict: out fp32 [{rows}] with a positive stride")
+    return _op("bl_value_predict_f32",
+               (x.data_ptr(), _rows(x, "x"), rows, dim, norm_w.data_ptr(), float(eps), w.data_ptr(), b.data_ptr(), out.data_ptr(),
+                out.stride(0) if rows > 1 else 1),
+               (x, norm_w, w, b, out), run, nbytes=2.0 * rows * dim + 4.0 * dim + 4.0 * rows, flops=5.0 * rows * dim)
+
+
 def rmsnorm_backward(x, w, dy, dx, dw, ws, eps: float, dres: Optional[torch.Tensor] = None, run: bool = True) -> Op:
     rows, dim = x.shape
     return _op("bl_rmsnorm_backward_bf16",

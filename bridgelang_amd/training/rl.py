@@ -43,7 +43,9 @@ def group_advantages(rewards, eps: float = 1e-6) -> torch.Tensor:
 
 def gae(rewards, values, last_values=None, dones=None, gamma: float = 0.99, lam: float = 0.95) -> Tuple[torch.Tensor, torch.Tensor]:
     """Generalised advantage estimation over N trajectories of T steps: rewards and values [N, T] (V of the state each
-    action was taken in: the learner's `forward()` over the rollout batch, then `values()`), `last_values` [N] the value of
+    action was taken in: what the rollout itself returned — `predict_action` / `sample_actions(..., return_values="action")`
+    with the critic attached to the model (`attach_value_head`) — or, as before, the learner's `forward()` over the rollout
+    batch, then `values()`), `last_values` [N] the value of
     the state after the last step (None: 0, the trajectory ended there), `dones` [N, T] true where the episode ended WITH
     step t (None: nowhere), so nothing is bootstrapped or carried across it:
 
@@ -78,7 +80,7 @@ def gae(rewards, values, last_values=None, dones=None, gamma: float = 0.99, lam:
 
 
 def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pad_to: Optional[int] = None,
-                 token_range: Optional[Tuple[int, int]] = None) -> Dict[str, torch.Tensor]:
+                 token_range: Optional[Tuple[int, int]] = None, values=None, returns=None) -> Dict[str, torch.Tensor]:
     """The training batch of one sampled action per sequence. prompt_ids int64 [B, lp] right-padded with attention_mask
     [B, lp] (None: no padding); token_ids int64 [B, n] and logprobs [B, n] as `sample_actions` reports them (K samples per
     prompt: repeat the prompt rows and flatten to [B·K, n] first); advantages [B], one per sequence, broadcast over its n
@@ -92,7 +94,10 @@ def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pa
     A non-finite log-probability raises ValueError: a token outside a top-k / top-p support scores -inf, and the policy
     loss is defined for temperature-only rollouts. `token_range=(first, count)` is the learner's
     `PolicyLossConfig.token_range` (`model.action_token_range()`): an action token outside it raises ValueError — it has
-    probability 0 under the restricted policy, so the rollouts were not drawn from it."""
+    probability 0 under the restricted policy, so the rollouts were not drawn from it.
+    `values` [B] (the critic's V(s) the rollout returned, `return_values="action"`) and `returns` [B] (`gae`'s) are checked
+    (shape, finite) and passed through as fp32 `old_values` / `returns`, ready for `ts.set_value_batch(returns, old_values)`
+    at value level "action"; a key is added only for the one that is given."""
     ids, tok = _cpu(prompt_ids, torch.int64), _cpu(token_ids, torch.int64)
     lp, adv = _cpu(logprobs, torch.float64), _cpu(advantages, torch.float64)
     if ids.dim() != 2 or tok.dim() != 2 or tok.shape[0] != ids.shape[0] or tok.shape[1] < 1:
@@ -105,6 +110,16 @@ def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pa
                          "-inf; draw training rollouts with temperature only")
     if not bool(torch.isfinite(adv).all()):
         raise ValueError("policy_batch: advantages must be finite")
+    extra = {}
+    for key, name, x in (("old_values", "values", values), ("returns", "returns", returns)):
+        if x is None:
+            continue
+        x = _cpu(x, torch.float64)
+        if tuple(x.shape) != (B,):
+            raise ValueError(f"policy_batch: {name} [{B}], one per sequence, got {tuple(x.shape)}")
+        if not bool(torch.isfinite(x).all()):
+            raise ValueError(f"policy_batch: {name} must be finite")
+        extra[key] = x.to(torch.float32)
     if token_range is not None:
         first, count = int(token_range[0]), int(token_range[1])
         outside = (tok < first) | (tok >= first + count)
@@ -143,7 +158,7 @@ def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pa
         labels[b, s:s + n] = tok[b]
         out_adv[b, s:s + n] = float(adv[b])
         out_lp[b, s:s + n] = lp[b].to(torch.float32)
-    return {"input_ids": out_ids, "attention_mask": out_m, "labels": labels, "advantages": out_adv, "old_logprobs": out_lp}
+    return {"input_ids": out_ids, "attention_mask": out_m, "labels": labels, "advantages": out_adv, "old_logprobs": out_lp, **extra}
 
 
 def pairs_from_rewards(rewards, min_gap: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

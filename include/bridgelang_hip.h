@@ -441,6 +441,16 @@ int bl_value_head_f32(const bl_bf16* hn, int64_t ld, int32_t rows, int32_t dim, 
 int bl_value_head_backward_f32(const bl_bf16* hn, int64_t ld, int32_t rows, int32_t dim, int32_t group_rows, int32_t level,
                                const bl_bf16* w, const float* value_rows, const int32_t* index, const int32_t* count,
                                float inv_world, float* dw, float* db, bl_bf16* dh, int64_t lddh, void* stream);
+/* The critic at inference: V(s) of `rows` residual rows x [rows, dim] (leading dimension ldx), the final RMSNorm and the
+ * head in one launch: out[r * out_stride] = sum_k hn[r,k]*w[k] + b with hn[r,:] the bf16 row bl_rmsnorm_bf16(x, norm_w, eps)
+ * would write — bit for bit the v of bl_value_head_f32 over that row (the same lane ownership, the same sum of squares, the
+ * same roundings, the same fmaf chain and butterfly); hn is never written. One wave per row; rows at or beyond `rows` and
+ * columns in [dim, ldx) are not read; the one store per row is the fp32 at out[r * out_stride]. w, norm_w bf16 [dim], b bf16
+ * [1], read when the kernel runs (a captured graph sees their current contents). A NULL pointer: BL_E_ARG; rows <= 0,
+ * dim % 8 != 0, dim > 5120 or out_stride < 1: BL_E_SHAPE; x, norm_w or w not 16-byte aligned or ldx % 8 != 0: BL_E_ALIGN;
+ * nothing is launched on a rejection. */
+int bl_value_predict_f32(const bl_bf16* x, int64_t ldx, int32_t rows, int32_t dim, const bl_bf16* norm_w, float eps,
+                         const bl_bf16* w, const bl_bf16* b, float* out, int64_t out_stride, void* stream);
 /* LlamaRMSNorm backward: dx = rstd*(w*dy - xhat*mean(w*dy*xhat)) [+ dres: the residual stream's own gradient];
  * dw[j] = sum_rows dy*bf16(xhat). partial_ws >= ceil(rows/64)*dim floats. */
 int bl_rmsnorm_backward_bf16(const bl_bf16* x, int64_t ldx, const bl_bf16* w, const bl_bf16* dy, int64_t lddy,
