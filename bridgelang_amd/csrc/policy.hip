@@ -21,6 +21,12 @@
 // group-level values and writes group_stats), then the statistics with the log-ratio read from group_stats. m, log S, H
 // and g stay where the backward kernel reads them, so the backward entry points serve both levels.
 //
+// bl_policy_loss_is_f32 is either level with the rollout correction: a truncated importance weight w = min(exp(q − μ), cap),
+// 0 outside a trust band, between the proximal policy q (given, or this forward's own logp) and the behaviour policy μ that
+// drew the tokens, as a constant factor of the surrogate. The same kernels in their IS instantiation: is_terms is the one
+// definition of (λ, ρ, w), (λ, w) per row go to is_rows and six more means to is_stats. g still holds ∂row_loss/∂logp, so
+// the backward entry points serve it too.
+//
 // bl_preference_loss_f32 is the preference-pair loss (DPO family; training/preference_loss.py) on the same rows: the row
 // pass without the surrogate, then preference_seq_kernel, preference_pair_kernel and preference_apply_kernel (below, with
 // their own comment). It leaves g per row, and the number of pairs in stats[1], for the same backward entry points.
@@ -68,16 +74,57 @@ __device__ __forceinline__ RowTerms row_terms(float logp, float A, float q, cons
   kl_terms(logp, ref, row, P, t.kl, t.g);
   return t;
 }
+
+// ---- the rollout correction (bl_policy_loss_is_f32): a truncated importance weight between the proximal policy q and the
+// behaviour policy μ that drew the tokens. The kernels below are templates on IS: the IS = false instantiations are the
+// uncorrected loss and never look at an IsArgs (they are passed an empty one); the IS = true ones read and write through it.
+struct IsArgs {
+  const float* mu;      // behaviour log-probability per row
+  float* rows;          // fp32 [rows, 2] = (λ, w)
+  float cap, lo, hi;    // w = min(ρ, cap), 0 where ρ is outside [lo, hi] (no mask: lo = 0, hi = +inf)
+};
+// Everything that follows from λ = q − μ (a token's, or c·Σ over a group). ONE definition for the row kernels, the group
+// kernel and both reductions, as surrogate_terms is for the ratio.
+struct IsTerms {
+  float lambda, rho, w;
+  bool masked, truncated;
+};
+__device__ __forceinline__ IsTerms is_terms(float lambda, const IsArgs& I) {
+  IsTerms s;
+  s.lambda = lambda;
+  s.rho = expf(lambda);
+  s.masked = s.rho < I.lo || s.rho > I.hi;
+  s.truncated = !s.masked && s.rho > I.cap;
+  s.w = s.masked ? 0.f : fminf(s.rho, I.cap);
+  return s;
+}
+// w·x as a product of its own: the compiler may not contract it into the sum x goes on to, so with w = 1 every later
+// result has the bits of the uncorrected loss (the empty statement only hides the product from the optimiser)
+__device__ __forceinline__ float weighted(float w, float x) {
+  float y = w * x;
+  asm volatile("" : "+v"(y));
+  return y;
+}
+// the weight is a constant factor of the surrogate: on pg and on the surrogate's share of g, before the KL share is taken off
+__device__ __forceinline__ void weight_surrogate(RowTerms& t, float w) {
+  t.pg = weighted(w, t.pg);
+  t.g = weighted(w, t.g);
+}
+// a row's proximal log-probability: the given one, or (self-proximal) this forward's own logp as a constant
+__device__ __forceinline__ float proximal(const float* old_lp, long row, float logp) { return old_lp ? old_lp[row] : logp; }
+
 __device__ __forceinline__ float row_loss_of(const RowTerms& t, float H, const PolicyParams& P) {
   return t.pg - P.entropy_coef * H + P.kl_coef * t.kl;
 }
 
 // what thread 0 / lane 0 does once S and W of a row are known. lr points at column `first`; tgt is relative to it.
 // SURR = false is the row pass of the preference loss: the same logp, H, m and log S, no surrogate (adv, old_lp and ref_lp
-// are not read); ratio, row_loss, clipped and g are written as zeros for preference_apply_kernel to fill.
-template <bool SURR>
+// are not read); ratio, row_loss, clipped and g are written as zeros for preference_apply_kernel to fill. IS (with SURR)
+// is the rollout correction: q may be this row's own logp, the surrogate carries w, and (λ, w) go to I.rows.
+template <bool SURR, bool IS>
 __device__ __forceinline__ void finish_row(const float* lr, int n, long tgt, float m, float S, float W, const float* adv,
-                                           const float* old_lp, const float* ref_lp, int row, const PolicyParams& P, float* rs) {
+                                           const float* old_lp, const float* ref_lp, int row, const PolicyParams& P,
+                                           const IsArgs& I, float* rs) {
   const float logS = logf(S);
   const float H = logS - W / S;                                       // −Σ p·logp, logp = (z − m) − log S
   const float za = (tgt >= 0 && tgt < n) ? lr[tgt] * P.inv_t : NAN;    // a token outside the row: NaN, never a stray read
@@ -87,7 +134,18 @@ __device__ __forceinline__ void finish_row(const float* lr, int n, long tgt, flo
   rs[RS_M] = m;
   rs[RS_LOGS] = logS;
   if constexpr (SURR) {
-    const RowTerms t = row_terms(logp, adv[row], old_lp[row], ref_lp, row, P);
+    RowTerms t;
+    if constexpr (IS) {
+      const float q = proximal(old_lp, row, logp);
+      const IsTerms s = is_terms(q - I.mu[row], I);
+      t = surrogate_terms(logp - q, adv[row], P);
+      weight_surrogate(t, s.w);
+      kl_terms(logp, ref_lp, row, P, t.kl, t.g);
+      I.rows[2 * (long)row] = s.lambda;
+      I.rows[2 * (long)row + 1] = s.w;
+    } else {
+      t = row_terms(logp, adv[row], old_lp[row], ref_lp, row, P);
+    }
     rs[RS_RATIO] = t.ratio;
     rs[RS_LOSS] = row_loss_of(t, H, P);
     rs[RS_CLIPPED] = t.active ? 0.f : 1.f;
@@ -101,16 +159,17 @@ __device__ __forceinline__ void finish_row(const float* lr, int n, long tgt, flo
 }
 
 // one workgroup per row; the row is the n columns from column `first` on
-template <bool SURR>
+template <bool SURR, bool IS = false>
 __global__ __launch_bounds__(256) void policy_rows_kernel(const float* logits, long ld, int first, int n, const int64_t* targets,
                                                           long ignore_index, const float* adv, const float* old_lp,
-                                                          const float* ref_lp, PolicyParams P, float* row_stats) {
+                                                          const float* ref_lp, PolicyParams P, IsArgs I, float* row_stats) {
   __shared__ float red_m[4], red_s[4], red_w[4];
   const int row = blockIdx.x;
   const long tgt = targets[row];
   float* rs = row_stats + (long)row * 8;
   if (tgt == ignore_index) {          // uniform per workgroup
     if (threadIdx.x < 8) rs[threadIdx.x] = 0.f;
+    if (IS && threadIdx.x < 2) I.rows[2 * (long)row + threadIdx.x] = 0.f;
     return;
   }
   const float* lr = logits + (long)row * ld + first;
@@ -141,23 +200,24 @@ __global__ __launch_bounds__(256) void policy_rows_kernel(const float* logits, l
   if ((threadIdx.x & 63) == 0) { red_s[wave] = s; red_w[wave] = w; }
   __syncthreads();
   if (threadIdx.x == 0)
-    finish_row<SURR>(lr, n, tgt - first, m, red_s[0] + red_s[1] + red_s[2] + red_s[3], red_w[0] + red_w[1] + red_w[2] + red_w[3],
-               adv, old_lp, ref_lp, row, P, rs);
+    finish_row<SURR, IS>(lr, n, tgt - first, m, red_s[0] + red_s[1] + red_s[2] + red_s[3], red_w[0] + red_w[1] + red_w[2] + red_w[3],
+               adv, old_lp, ref_lp, row, P, I, rs);
 }
 
 // n <= 256: one wave per row, four rows per workgroup, the lane's float4 stays in registers between the two passes. The
 // order of every sum is the workgroup kernel's on such a row (there waves 1–3 hold no column and add zeros).
-template <bool SURR>
+template <bool SURR, bool IS = false>
 __global__ __launch_bounds__(256) void policy_rows_wave_kernel(const float* logits, long ld, int first, int n, int rows,
                                                                const int64_t* targets, long ignore_index, const float* adv,
                                                                const float* old_lp, const float* ref_lp, PolicyParams P,
-                                                               float* row_stats) {
+                                                               IsArgs I, float* row_stats) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;            // uniform per wave, and the kernel has no barrier
   const long tgt = targets[row];
   float* rs = row_stats + (long)row * 8;
   if (tgt == ignore_index) {
     if (lane < 8) rs[lane] = 0.f;
+    if (IS && lane < 2) I.rows[2 * (long)row + lane] = 0.f;
     return;
   }
   const float* lr = logits + (long)row * ld + first;
@@ -177,7 +237,7 @@ __global__ __launch_bounds__(256) void policy_rows_wave_kernel(const float* logi
   }
   s = wave_sum(s);
   w = wave_sum(w);
-  if (lane == 0) finish_row<SURR>(lr, n, tgt - first, m, s + 0.f + 0.f + 0.f, w + 0.f + 0.f + 0.f, adv, old_lp, ref_lp, row, P, rs);
+  if (lane == 0) finish_row<SURR, IS>(lr, n, tgt - first, m, s + 0.f + 0.f + 0.f, w + 0.f + 0.f + 0.f, adv, old_lp, ref_lp, row, P, I, rs);
 }
 
 // The action-level ratio. One wave per sequence (its group_rows consecutive rows), four sequences per workgroup, no barrier.
@@ -185,26 +245,35 @@ __global__ __launch_bounds__(256) void policy_rows_wave_kernel(const float* logi
 // of those lane partials (deterministic, no float atomics). Reads what the row pass left (logp, H) and overwrites ratio,
 // row_loss, clipped and g of the valid rows: ratio_G = exp(s_G), s_G = c·Σ (logp − q), and
 // g_r = c·Σ_j (−A_j·ratio_G·[active_j]) − kl_coef·expm1(ref_r − logp_r). group_stats[seq] = (s_G, ratio_G, n_G, Σ logp);
-// an empty group writes zeros there and touches no row.
+// an empty group writes zeros there and touches no row. IS is the rollout correction at this level: λ_G = c·Σ (q − μ)
+// over the same rows with the same c, the group's surrogate sum carries w_G, and every valid row gets (λ_G, w_G) in I.rows.
+template <bool IS>
 __global__ __launch_bounds__(256) void policy_group_kernel(float* row_stats, int group_rows, int groups, int by_mean,
                                                            const int64_t* targets, long ignore_index, const float* adv,
                                                            const float* old_lp, const float* ref_lp, PolicyParams P,
-                                                           float* group_stats) {
+                                                           IsArgs I, float* group_stats) {
   const int seq = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (seq >= groups) return;          // uniform per wave
   const long r0 = (long)seq * group_rows;
-  float sd = 0.f, sl = 0.f;           // Σ (logp − q), Σ logp
+  float sd = 0.f, sl = 0.f, sm = 0.f; // Σ (logp − q), Σ logp, Σ (q − μ)
   int c = 0;
   for (int k = lane; k < group_rows; k += 64) {
     const long r = r0 + k;
     if (targets[r] == ignore_index) continue;
     const float logp = row_stats[r * 8 + RS_LOGP];
-    sd += logp - old_lp[r];
+    if constexpr (IS) {
+      const float q = proximal(old_lp, r, logp);
+      sd += logp - q;
+      sm += q - I.mu[r];
+    } else {
+      sd += logp - old_lp[r];
+    }
     sl += logp;
     ++c;
   }
   sd = wave_sum(sd);
   sl = wave_sum(sl);
+  if constexpr (IS) sm = wave_sum(sm);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
   float* gs = group_stats + (long)seq * 4;
@@ -221,12 +290,22 @@ __global__ __launch_bounds__(256) void policy_group_kernel(float* row_stats, int
     gsum += surrogate_terms(s, adv[r], P).g;
   }
   gsum = wave_sum(gsum);
+  IsTerms is = {0.f, 1.f, 1.f, false, false};
+  if constexpr (IS) {                 // the weight is formed at the ratio's level, with its norm; w_G·Σ_j = Σ_j w_G·
+    is = is_terms(w * sm, I);
+    gsum = weighted(is.w, gsum);
+  }
   for (int k = lane; k < group_rows; k += 64) {
     const long r = r0 + k;
     if (targets[r] == ignore_index) continue;
     float* rs = row_stats + r * 8;
     RowTerms t = surrogate_terms(s, adv[r], P);
     t.g = w * gsum;
+    if constexpr (IS) {
+      t.pg = weighted(is.w, t.pg);
+      I.rows[2 * r] = is.lambda;
+      I.rows[2 * r + 1] = is.w;
+    }
     kl_terms(rs[RS_LOGP], ref_lp, (int)r, P, t.kl, t.g);
     rs[RS_RATIO] = t.ratio;
     rs[RS_LOSS] = row_loss_of(t, rs[RS_H], P);
@@ -242,13 +321,19 @@ __global__ __launch_bounds__(256) void policy_group_kernel(float* row_stats, int
 }
 
 // the 8 step statistics: means over valid rows (single workgroup, fixed summation order → deterministic). The log-ratio
-// of a row is its own (group_stats NULL) or its group's, as policy_group_kernel left it in group_stats.
+// of a row is its own (group_stats NULL) or its group's, as policy_group_kernel left it in group_stats. IS: λ of a row
+// (its own or its group's) is read back from I.rows, pg carries w, and six more means go to is_out (w, ρ, truncated,
+// masked, ρ − 1 − λ, −λ; then two zeros), summed in the same order as the other seven.
+template <bool IS>
 __device__ __forceinline__ void stats_body(const float* row_stats, const int64_t* targets, long ignore_index, const float* adv,
                                            const float* old_lp, const float* ref_lp, const PolicyParams& P, int rows,
-                                           const float* group_stats, int group_rows, float* out) {
-  __shared__ float rsum[4][7];
+                                           const float* group_stats, int group_rows, float* out, const IsArgs& I, float* is_out) {
+  constexpr int NS = IS ? 13 : 7;
+  __shared__ float rsum[4][NS];
   __shared__ int rc[4];
-  float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // row_loss, pg, H, kl, clipped, approx KL, ratio
+  float a[NS];                        // row_loss, pg, H, kl, clipped, approx KL, ratio; IS: then w, ρ, truncated, masked, ρ − 1 − λ, −λ
+#pragma unroll
+  for (int k = 0; k < NS; ++k) a[k] = 0.f;
   int c = 0;
   for (int i = threadIdx.x; i < rows; i += 256) {
     if (targets[i] == ignore_index) continue;
@@ -257,8 +342,20 @@ __device__ __forceinline__ void stats_body(const float* row_stats, const int64_t
     if (group_stats) {
       t = surrogate_terms(group_stats[(long)(i / group_rows) * 4], adv[i], P);
       kl_terms(rs[RS_LOGP], ref_lp, i, P, t.kl, t.g);
+    } else if constexpr (IS) {
+      t = row_terms(rs[RS_LOGP], adv[i], proximal(old_lp, i, rs[RS_LOGP]), ref_lp, i, P);
     } else {
       t = row_terms(rs[RS_LOGP], adv[i], old_lp[i], ref_lp, i, P);
+    }
+    if constexpr (IS) {
+      const IsTerms s = is_terms(I.rows[2 * (long)i], I);
+      t.pg = weighted(s.w, t.pg);
+      a[7] += s.w;
+      a[8] += s.rho;
+      a[9] += s.truncated ? 1.f : 0.f;
+      a[10] += s.masked ? 1.f : 0.f;
+      a[11] += expm1f(s.lambda) - s.lambda;              // (ρ − 1) − λ
+      a[12] += -s.lambda;
     }
     a[0] += rs[RS_LOSS];
     a[1] += t.pg;
@@ -270,33 +367,46 @@ __device__ __forceinline__ void stats_body(const float* row_stats, const int64_t
     ++c;
   }
 #pragma unroll
-  for (int k = 0; k < 7; ++k) a[k] = wave_sum(a[k]);
+  for (int k = 0; k < NS; ++k) a[k] = wave_sum(a[k]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-    for (int k = 0; k < 7; ++k) rsum[threadIdx.x >> 6][k] = a[k];
+    for (int k = 0; k < NS; ++k) rsum[threadIdx.x >> 6][k] = a[k];
     rc[threadIdx.x >> 6] = c;
   }
   __syncthreads();
-  if (threadIdx.x < 7) {
+  if (threadIdx.x < NS) {
     const int k = threadIdx.x;
     const int cnt = rc[0] + rc[1] + rc[2] + rc[3];
     const float mean = cnt > 0 ? (rsum[0][k] + rsum[1][k] + rsum[2][k] + rsum[3][k]) / (float)cnt : 0.f;
-    out[k == 0 ? 0 : k + 1] = mean;
-    if (k == 0) out[1] = (float)cnt;
+    if (k < 7) {
+      out[k == 0 ? 0 : k + 1] = mean;
+      if (k == 0) out[1] = (float)cnt;
+    } else {
+      is_out[k - 7] = mean;
+    }
+  } else if (IS && threadIdx.x < 15) {
+    is_out[threadIdx.x - 7] = 0.f;    // the two spare slots
   }
 }
 __global__ __launch_bounds__(256) void policy_stats_kernel(const float* row_stats, const int64_t* targets, long ignore_index,
                                                            const float* adv, const float* old_lp, const float* ref_lp,
                                                            PolicyParams P, int rows, float* out) {
-  stats_body(row_stats, targets, ignore_index, adv, old_lp, ref_lp, P, rows, nullptr, 1, out);
+  stats_body<false>(row_stats, targets, ignore_index, adv, old_lp, ref_lp, P, rows, nullptr, 1, out, IsArgs{}, nullptr);
 }
 __global__ __launch_bounds__(256) void policy_stats_grouped_kernel(const float* row_stats, const int64_t* targets,
                                                                    long ignore_index, const float* adv, const float* ref_lp,
                                                                    PolicyParams P, int rows, const float* group_stats,
                                                                    int group_rows, float* out) {
-  stats_body(row_stats, targets, ignore_index, adv, nullptr, ref_lp, P, rows, group_stats, group_rows, out);
+  stats_body<false>(row_stats, targets, ignore_index, adv, nullptr, ref_lp, P, rows, group_stats, group_rows, out, IsArgs{}, nullptr);
+}
+// both levels of the corrected loss: group_stats NULL is the token level (old_lp NULL: self-proximal)
+__global__ __launch_bounds__(256) void policy_stats_is_kernel(const float* row_stats, const int64_t* targets, long ignore_index,
+                                                              const float* adv, const float* old_lp, const float* ref_lp,
+                                                              PolicyParams P, int rows, const float* group_stats,
+                                                              int group_rows, float* out, IsArgs I, float* is_out) {
+  stats_body<true>(row_stats, targets, ignore_index, adv, old_lp, ref_lp, P, rows, group_stats, group_rows, out, I, is_out);
 }
 
 __device__ __forceinline__ u32x4_t pack8(const float* v) {
@@ -515,8 +625,8 @@ static bool bad_range(int32_t n, int32_t first, int32_t count) {
 static int policy_forward_check(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
                                 const float* advantages, const float* old_logprob, float temperature, float clip_low,
                                 float clip_high, const float* row_stats, const float* stats, int32_t vocab_first,
-                                int32_t vocab_count) {
-  if (!logits || !targets || !advantages || !old_logprob || !row_stats || !stats) return BL_E_ARG;
+                                int32_t vocab_count, bool need_old = true) {
+  if (!logits || !targets || !advantages || (need_old && !old_logprob) || !row_stats || !stats) return BL_E_ARG;
   if (!(temperature > 0.f) || !(clip_low >= 0.f) || !(clip_high >= 0.f)) return BL_E_ARG;
   if (rows <= 0 || bad_range(n, vocab_first, vocab_count) || (ld % 4) || ld < n) return BL_E_SHAPE;
   if (!bl_aligned16(logits)) return BL_E_ALIGN;
@@ -524,17 +634,18 @@ static int policy_forward_check(const float* logits, int64_t ld, int32_t rows, i
 }
 
 // by_wave: a range of at most 256 columns goes to the wave-per-row kernel. The unranged entry point never asks for it.
-template <bool SURR = true>
+template <bool SURR = true, bool IS = false>
 static void launch_rows(const float* logits, int64_t ld, int32_t rows, const int64_t* targets, int64_t ignore_index,
                         const float* advantages, const float* old_logprob, const float* ref_logprob, const PolicyParams& P,
-                        float* row_stats, int32_t vocab_first, int32_t vocab_count, bool by_wave, void* stream) {
+                        float* row_stats, int32_t vocab_first, int32_t vocab_count, bool by_wave, void* stream,
+                        const IsArgs& I = IsArgs{}) {
   if (by_wave && vocab_count <= 256)
-    hipLaunchKernelGGL(policy_rows_wave_kernel<SURR>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, (long)ld,
-                       vocab_first, vocab_count, rows, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P,
-                       row_stats);
+    hipLaunchKernelGGL((policy_rows_wave_kernel<SURR, IS>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits,
+                       (long)ld, vocab_first, vocab_count, rows, targets, (long)ignore_index, advantages, old_logprob, ref_logprob,
+                       P, I, row_stats);
   else
-    hipLaunchKernelGGL(policy_rows_kernel<SURR>, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, vocab_first,
-                       vocab_count, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P, row_stats);
+    hipLaunchKernelGGL((policy_rows_kernel<SURR, IS>), dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld,
+                       vocab_first, vocab_count, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P, I, row_stats);
 }
 
 static int policy_forward(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
@@ -568,10 +679,44 @@ extern "C" int bl_policy_loss_grouped_f32(const float* logits, int64_t ld, int32
   const int groups = rows / group_rows;
   launch_rows(logits, ld, rows, targets, ignore_index, advantages, old_logprob, ref_logprob, P, row_stats, vocab_first,
               vocab_count, true, stream);
-  hipLaunchKernelGGL(policy_group_kernel, dim3((groups + 3) / 4), dim3(256), 0, (hipStream_t)stream, row_stats, group_rows,
-                     groups, ratio_norm, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P, group_stats);
+  hipLaunchKernelGGL(policy_group_kernel<false>, dim3((groups + 3) / 4), dim3(256), 0, (hipStream_t)stream, row_stats, group_rows,
+                     groups, ratio_norm, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P, IsArgs{},
+                     group_stats);
   hipLaunchKernelGGL(policy_stats_grouped_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, row_stats, targets,
                      (long)ignore_index, advantages, ref_logprob, P, rows, group_stats, group_rows, stats);
+  BL_CHECK_LAUNCH();
+  return BL_OK;
+}
+
+// The corrected loss at either level: the launches of the uncorrected form of that level, each in its IS instantiation
+// (rows, [groups,] statistics) — no launch more. At action level the row pass's token-level (λ, w) of the valid rows are
+// overwritten by the group pass, as ratio, row_loss, clipped and g are.
+extern "C" int bl_policy_loss_is_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                     int64_t ignore_index, const float* advantages, const float* old_logprob,
+                                     const float* behaviour_logprob, const float* ref_logprob, float temperature, float clip_low,
+                                     float clip_high, float entropy_coef, float kl_coef, float* row_stats, float* stats,
+                                     int32_t vocab_first, int32_t vocab_count, int32_t group_rows, int32_t ratio_norm,
+                                     float* group_stats, float is_cap, float is_mask_low, float is_mask_high, float* is_rows,
+                                     float* is_stats, void* stream) {
+  const int bad = policy_forward_check(logits, ld, rows, n, targets, advantages, old_logprob, temperature, clip_low, clip_high,
+                                       row_stats, stats, vocab_first, vocab_count, false);
+  if (bad != BL_OK) return bad;
+  if (!behaviour_logprob || !is_rows || !is_stats) return BL_E_ARG;
+  if (group_rows >= 0 && (group_stats != nullptr) != (group_rows > 0)) return BL_E_ARG;
+  if (!(is_cap > 0.f) || !(is_mask_low >= 0.f) || !(is_mask_low < is_mask_high)) return BL_E_ARG;
+  if (group_rows < 0 || (group_rows > 0 && rows % group_rows) || (ratio_norm != 0 && ratio_norm != 1)) return BL_E_SHAPE;
+  const PolicyParams P = {1.0f / temperature, clip_low, clip_high, entropy_coef, ref_logprob ? kl_coef : 0.f};
+  const IsArgs I = {behaviour_logprob, is_rows, is_cap, is_mask_low, is_mask_high};
+  launch_rows<true, true>(logits, ld, rows, targets, ignore_index, advantages, old_logprob, ref_logprob, P, row_stats, vocab_first,
+                          vocab_count, true, stream, I);
+  if (group_rows > 0) {
+    const int groups = rows / group_rows;
+    hipLaunchKernelGGL(policy_group_kernel<true>, dim3((groups + 3) / 4), dim3(256), 0, (hipStream_t)stream, row_stats,
+                       group_rows, groups, ratio_norm, targets, (long)ignore_index, advantages, old_logprob, ref_logprob, P, I,
+                       group_stats);
+  }
+  hipLaunchKernelGGL(policy_stats_is_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, row_stats, targets, (long)ignore_index,
+                     advantages, old_logprob, ref_logprob, P, rows, group_stats, group_rows > 0 ? group_rows : 1, stats, I, is_stats);
   BL_CHECK_LAUNCH();
   return BL_OK;
 }

@@ -28,18 +28,31 @@ def _policy_rows(logits, targets, row_stats, stats, what: str):
 
 
 def policy_loss(logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats, cfg, ignore_index: int = -100,
-                run: bool = True, group_rows: Optional[int] = None, group_stats: Optional[torch.Tensor] = None) -> Op:
+                run: bool = True, group_rows: Optional[int] = None, group_stats: Optional[torch.Tensor] = None,
+                behaviour_logprob: Optional[torch.Tensor] = None, is_rows: Optional[torch.Tensor] = None,
+                is_stats: Optional[torch.Tensor] = None) -> Op:
     """Clipped-surrogate policy-gradient loss over fp32 logits [rows, n] (training/policy_loss.py is the definition; `cfg` a
     PolicyLossConfig). advantages / old_logprob / ref_logprob (None: no KL term) fp32 [rows]; row_stats fp32 [rows, 8] and
     stats fp32 [8] receive policy_loss.ROW_STAT_NAMES / STAT_NAMES. With cfg.token_range the policy is over that token
     range alone (bl_policy_loss_range_f32). With cfg.ratio_level == "action" the ratio is per sequence of `group_rows`
     consecutive rows (bl_policy_loss_grouped_f32) and group_stats fp32 [rows / group_rows, 4] receives
-    policy_loss.GROUP_STAT_NAMES; at token level both are ignored."""
+    policy_loss.GROUP_STAT_NAMES; at token level both are ignored. With cfg.rollout_is_cap set it is the rollout correction
+    (bl_policy_loss_is_f32, either level): behaviour_logprob fp32 [rows] is what the sampler reported, old_logprob the
+    proximal policy's or None (self-proximal: this forward's own logp), and is_rows fp32 [rows, 2] / is_stats fp32 [8]
+    receive (λ, w) per row / policy_loss.IS_STAT_NAMES; without it those three must be None and old_logprob given."""
     rows, n = _policy_rows(logits, targets, row_stats, stats, "policy_loss")
-    for t, what in ((advantages, "advantages"), (old_logprob, "old_logprob"), (ref_logprob, "ref_logprob")):
+    for t, what in ((advantages, "advantages"), (old_logprob, "old_logprob"), (ref_logprob, "ref_logprob"),
+                    (behaviour_logprob, "behaviour_logprob")):
         if t is not None and (_f32(t, what).numel() != rows or not t.is_contiguous()):
             raise ValueError(f"policy_loss: {what} fp32 [{rows}] contiguous")
     rng = getattr(cfg, "token_range", None)
+    if getattr(cfg, "rollout_is_cap", None) is not None:
+        return _policy_loss_is(logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats, cfg, ignore_index, run,
+                               group_rows, group_stats, behaviour_logprob, is_rows, is_stats, rows, n)
+    if behaviour_logprob is not None or is_rows is not None or is_stats is not None:
+        raise ValueError("policy_loss: behaviour_logprob, is_rows and is_stats go with cfg.rollout_is_cap")
+    if old_logprob is None:
+        raise ValueError("policy_loss: old_logprob=None (self-proximal) needs cfg.rollout_is_cap")
     head = (_f32(logits, "logits").data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
             advantages.data_ptr(), old_logprob.data_ptr(), ref_logprob.data_ptr() if ref_logprob is not None else None,
             float(cfg.temperature), float(cfg.clip_low), float(cfg.clip_high), float(cfg.entropy_coef), float(cfg.kl_coef),
@@ -47,19 +60,49 @@ def policy_loss(logits, targets, advantages, old_logprob, ref_logprob, row_stats
     keep = (logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats)
     nbytes = 8.0 * rows * (n if rng is None else rng[1])
     if getattr(cfg, "ratio_level", "token") == "action":
-        if group_rows is None or int(group_rows) != group_rows or group_rows < 1 or rows % int(group_rows):
-            raise ValueError(f"policy_loss: ratio_level='action' needs group_rows >= 1 dividing the {rows} rows, got {group_rows!r}")
-        groups = rows // int(group_rows)
-        if group_stats is None:
-            raise ValueError(f"policy_loss: ratio_level='action' needs group_stats fp32 [{groups}, 4]")
-        if tuple(_f32(group_stats, "group_stats").shape) != (groups, 4) or not group_stats.is_contiguous():
-            raise ValueError(f"policy_loss: group_stats fp32 [{groups}, 4] contiguous")
+        g_rows, norm, group_stats = _group_args(cfg, rows, group_rows, group_stats)
         first, count = (0, n) if rng is None else (int(rng[0]), int(rng[1]))
-        return _op("bl_policy_loss_grouped_f32",
-                   head + (first, count, int(group_rows), 1 if cfg.ratio_norm == "mean" else 0, group_stats.data_ptr()),
+        return _op("bl_policy_loss_grouped_f32", head + (first, count, g_rows, norm, group_stats.data_ptr()),
                    keep + (group_stats,), run, nbytes=nbytes + 64.0 * rows)
     return _op("bl_policy_loss_f32" if rng is None else "bl_policy_loss_range_f32",
                head + (() if rng is None else (int(rng[0]), int(rng[1]))), keep, run, nbytes=nbytes)
+
+
+def _group_args(cfg, rows: int, group_rows, group_stats):
+    """(group_rows, ratio_norm, group_stats) of an action-level call, checked."""
+    if group_rows is None or int(group_rows) != group_rows or group_rows < 1 or rows % int(group_rows):
+        raise ValueError(f"policy_loss: ratio_level='action' needs group_rows >= 1 dividing the {rows} rows, got {group_rows!r}")
+    groups = rows // int(group_rows)
+    if group_stats is None:
+        raise ValueError(f"policy_loss: ratio_level='action' needs group_stats fp32 [{groups}, 4]")
+    if tuple(_f32(group_stats, "group_stats").shape) != (groups, 4) or not group_stats.is_contiguous():
+        raise ValueError(f"policy_loss: group_stats fp32 [{groups}, 4] contiguous")
+    return int(group_rows), 1 if cfg.ratio_norm == "mean" else 0, group_stats
+
+
+def _policy_loss_is(logits, targets, advantages, old_logprob, ref_logprob, row_stats, stats, cfg, ignore_index, run, group_rows,
+                    group_stats, behaviour_logprob, is_rows, is_stats, rows: int, n: int) -> Op:
+    """`policy_loss` with the rollout correction: one symbol for both levels and both proximal modes."""
+    if behaviour_logprob is None or is_rows is None or is_stats is None:
+        raise ValueError(f"policy_loss: cfg.rollout_is_cap needs behaviour_logprob fp32 [{rows}], is_rows fp32 [{rows}, 2] and is_stats fp32 [8]")
+    if tuple(_f32(is_rows, "is_rows").shape) != (rows, 2) or not is_rows.is_contiguous() or _f32(is_stats, "is_stats").numel() != 8:
+        raise ValueError(f"policy_loss: is_rows fp32 [{rows}, 2] contiguous and is_stats fp32 [8]")
+    rng = cfg.token_range
+    first, count = (0, n) if rng is None else (int(rng[0]), int(rng[1]))
+    if cfg.ratio_level == "action":
+        g_rows, norm, gs = _group_args(cfg, rows, group_rows, group_stats)
+    else:
+        g_rows, norm, gs = 0, 0, None
+    low, high = cfg.rollout_is_mask or (0.0, float("inf"))
+    return _op("bl_policy_loss_is_f32",
+               (_f32(logits, "logits").data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
+                advantages.data_ptr(), old_logprob.data_ptr() if old_logprob is not None else None, behaviour_logprob.data_ptr(),
+                ref_logprob.data_ptr() if ref_logprob is not None else None,
+                float(cfg.temperature), float(cfg.clip_low), float(cfg.clip_high), float(cfg.entropy_coef), float(cfg.kl_coef),
+                row_stats.data_ptr(), stats.data_ptr(), first, count, g_rows, norm, gs.data_ptr() if gs is not None else None,
+                float(cfg.rollout_is_cap), float(low), float(high), is_rows.data_ptr(), is_stats.data_ptr()),
+               (logits, targets, advantages, old_logprob, behaviour_logprob, ref_logprob, row_stats, stats, gs, is_rows, is_stats),
+               run, nbytes=8.0 * rows * count + 80.0 * rows)
 
 
 def policy_loss_backward(logits, targets, row_stats, stats, dlogits, cfg, ignore_index: int = -100, run: bool = True) -> Op:

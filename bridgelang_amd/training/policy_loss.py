@@ -59,6 +59,29 @@ GROUP_STAT_NAMES per sequence (zeros for a sequence without a valid row, which c
 the token-level loss exactly. With `"sum"` and the token-mean loss a group's surrogate is counted n_G times: harmless when
 every action has the same number of tokens (OpenVLA: 7), but with ragged groups longer actions weigh more — `"mean"`, or
 advantages scaled by 1 / n_G, if that is not wanted.
+
+The ROLLOUT CORRECTION is part of it as well (`PolicyLossConfig.rollout_is_cap`, `bl_policy_loss_is_f32`): decoupled PPO with
+a truncated importance weight. The policy that DREW the tokens (the decode engine, perhaps through the e4m3 prefill) is not
+the policy the learner differentiates, so a row has two log-probabilities: the behaviour one μ_r (`behaviour_logprobs`, what
+the sampler reported) and the proximal one q_r the clip is centred on. q_r is `old_logprobs`, exactly as above, or with
+`old_logprobs=None` (self-proximal, allowed only with the correction on) the logp_r of THIS forward taken as a constant:
+the log ratio is then 0 exactly, the ratio 1 and every row active. With cap = `rollout_is_cap` (> 0, may be inf) and
+(low, high) = `rollout_is_mask` (0 ≤ low < high, high may be inf; None: no mask), at token level
+
+    λ_r = q_r − μ_r          ρ_r = exp(λ_r)
+    masked_r    = ρ_r < low or ρ_r > high
+    w_r         = 0 if masked_r else min(ρ_r, cap)
+    truncated_r = not masked_r and ρ_r > cap
+    pg_r = w_r · (−min(ratio·A, clip(ratio)·A))
+    g_r  = w_r · (−A·ratio·[active]) + the unchanged KL share
+
+and at action level the weight is formed at the level of the ratio, with its norm c: λ_G = c·Σ_{r∈G} (q_r − μ_r) in row
+order, ρ_G, w_G, masked_G and truncated_G from λ_G as above on every valid row of G, and
+g_r = c·Σ_{j∈G} w_G·(−A_j·ratio_G·[active_j]) + KL share. w is a CONSTANT in both modes (no gradient flows through it, nor
+through the self-proximal q); the entropy and KL terms are not weighted; a masked row still counts in n_valid, so masking
+shrinks the gradient instead of renormalising it. `stats` keeps its layout: `pg` and `loss` are the weighted ones, `ratio`,
+`clip_frac` and `approx_kl` stay about π_θ/π_prox. `is_stats` (IS_STAT_NAMES) are means over valid rows of w, ρ, truncated,
+masked, ρ − 1 − λ (the k3 estimate of KL(μ‖π_prox)) and −λ (k1), then two zero slots. μ must be finite on valid rows.
 """
 from __future__ import annotations
 
@@ -75,6 +98,8 @@ STAT_NAMES = ("loss", "n_valid", "pg", "entropy", "kl", "clip_frac", "approx_kl"
 ROW_STAT_NAMES = ("logp", "entropy", "ratio", "row_loss", "clipped", "m", "log_s", "g")
 # the per-sequence statistics of the action-level ratio (fp32 [groups, 4]): s_G, ratio_G, n_G, Σ_G logp
 GROUP_STAT_NAMES = ("log_ratio", "ratio", "n", "logp")
+# the step statistics of the rollout correction (fp32 [8]): means over valid rows; slots 6 and 7 are zero and have no name
+IS_STAT_NAMES = ("weight", "rho", "trunc_frac", "mask_frac", "rollout_kl", "rollout_k1")
 
 
 @dataclass(frozen=True)
@@ -87,8 +112,25 @@ class PolicyLossConfig:
     token_range: Optional[Tuple[int, int]] = None    # (first, count): the policy is over these tokens alone
     ratio_level: str = "token"                       # "token": one ratio per token; "action": one per sequence's labelled tokens
     ratio_norm: str = "sum"                          # action level: exp(Σ δ) ("sum") or exp(Σ δ / n_G) ("mean")
+    rollout_is_cap: Optional[float] = None           # set: the rollout correction is on, w = min(π_prox / μ, cap); may be inf
+    rollout_is_mask: Optional[Tuple[float, float]] = None    # (low, high): w = 0 where π_prox / μ leaves [low, high]
 
     def __post_init__(self):
+        if self.rollout_is_cap is not None:
+            cap = float(self.rollout_is_cap)
+            if not cap > 0:
+                raise ValueError(f"PolicyLossConfig: rollout_is_cap is None or > 0 (inf: no truncation), got {self.rollout_is_cap!r}")
+            object.__setattr__(self, "rollout_is_cap", cap)
+        if self.rollout_is_mask is not None:
+            if self.rollout_is_cap is None:
+                raise ValueError("PolicyLossConfig: rollout_is_mask needs rollout_is_cap (the correction it masks)")
+            try:
+                low, high = (float(v) for v in self.rollout_is_mask)
+            except (TypeError, ValueError):
+                low, high = 1.0, 0.0
+            if not 0 <= low < high:
+                raise ValueError("PolicyLossConfig: rollout_is_mask is None or (low, high) with 0 <= low < high (high may be inf)")
+            object.__setattr__(self, "rollout_is_mask", (low, high))
         if self.ratio_level not in ("token", "action"):
             raise ValueError(f"PolicyLossConfig: ratio_level is 'token' or 'action', got {self.ratio_level!r}")
         if self.ratio_norm not in ("sum", "mean"):
@@ -142,6 +184,11 @@ class PolicyLossResult:
     stats: np.ndarray         # [8] fp64, STAT_NAMES
     dlogits: np.ndarray       # [rows, n] fp64
     group_stats: Optional[np.ndarray] = None      # [groups, 4] fp64, GROUP_STAT_NAMES (action level only)
+    log_rho: Optional[np.ndarray] = None          # [rows]  λ = q − μ (the group's at action level); these five with the
+    weight: Optional[np.ndarray] = None           # [rows]  w                                        rollout correction only
+    masked: Optional[np.ndarray] = None           # [rows]  bool
+    truncated: Optional[np.ndarray] = None        # [rows]  bool
+    is_stats: Optional[np.ndarray] = None         # [8] fp64, IS_STAT_NAMES
 
 
 def _group_sums(v, valid, group_rows: int):
@@ -185,18 +232,25 @@ def slice_range(logits, targets, token_range, ignore_index: int, what: str):
 
 
 def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cfg: Optional[PolicyLossConfig] = None,
-                ignore_index: int = IGNORE_INDEX, group_rows: Optional[int] = None) -> PolicyLossResult:
+                ignore_index: int = IGNORE_INDEX, group_rows: Optional[int] = None, behaviour_logprobs=None) -> PolicyLossResult:
     """`group_rows`: rows per sequence, needed (and dividing the row count) with cfg.ratio_level == "action"; ignored at
-    token level."""
+    token level. `behaviour_logprobs`: μ of the rollout correction, given iff cfg.rollout_is_cap is set; `old_logprobs` may
+    then be None (self-proximal)."""
     cfg = cfg or PolicyLossConfig()
     by_action = cfg.ratio_level == "action"
+    corrected = cfg.rollout_is_cap is not None
+    if corrected != (behaviour_logprobs is not None):
+        raise ValueError("policy_loss: behaviour_logprobs goes together with cfg.rollout_is_cap")
+    if old_logprobs is None and not corrected:
+        raise ValueError("policy_loss: old_logprobs=None (self-proximal) needs the rollout correction (cfg.rollout_is_cap)")
     if by_action:
         rows = np.shape(logits)[0]
         if group_rows is None or int(group_rows) != group_rows or group_rows < 1 or rows % int(group_rows):
             raise ValueError(f"policy_loss: ratio_level='action' needs group_rows >= 1 dividing the {rows} rows, got {group_rows!r}")
         group_rows = int(group_rows)
     if cfg.token_range is not None:
-        return _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, cfg, ignore_index, group_rows)
+        return _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, cfg, ignore_index, group_rows,
+                                  behaviour_logprobs)
     l = np.asarray(logits, dtype=np.float64)
     tg = np.asarray(targets, dtype=np.int64)
     rows, n = l.shape
@@ -205,15 +259,17 @@ def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cf
         raise ValueError("policy_loss: logits must be finite")
     if valid.any() and (tg[valid].min() < 0 or tg[valid].max() >= n):
         raise ValueError(f"policy_loss: targets must lie in [0, {n}) or be {ignore_index}")
-    check_finite(valid, advantages=advantages, old_logprobs=old_logprobs, ref_logprobs=ref_logprobs)
+    check_finite(valid, advantages=advantages, old_logprobs=old_logprobs, ref_logprobs=ref_logprobs,
+                 behaviour_logprobs=behaviour_logprobs)
     A = np.where(valid, np.asarray(advantages, dtype=np.float64), 0.0)
-    q = np.where(valid, np.asarray(old_logprobs, dtype=np.float64), 0.0)
     ref = None if ref_logprobs is None else np.where(valid, np.asarray(ref_logprobs, dtype=np.float64), 0.0)
     T = float(cfg.temperature)
     logp_all, p, H = row_softmax(l, T)
     a = np.where(valid, tg, 0)
     logp = logp_all[np.arange(rows), a]
-    lr = logp - q
+    q = np.where(valid, logp if old_logprobs is None else np.asarray(old_logprobs, dtype=np.float64), 0.0)   # self-proximal: a constant
+    lr = np.where(valid, logp, 0.0) - q
+    lam = np.where(valid, q - np.asarray(behaviour_logprobs, dtype=np.float64), 0.0) if corrected else None
     group_stats = None
     if by_action:                                 # every valid row takes its group's log-ratio s_G = c·Σ δ
         sums, n_g = _group_sums(lr, valid, group_rows)
@@ -222,11 +278,22 @@ def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cf
         lr = np.where(valid, np.repeat(s_g, group_rows), 0.0)
         group_stats = np.stack([s_g, np.where(n_g > 0, np.exp(s_g), 0.0), n_g.astype(np.float64),
                                 _group_sums(logp, valid, group_rows)[0]], axis=1)
+        if corrected:                             # … and, with the correction, its group's λ_G = c·Σ (q − μ)
+            lam = np.where(valid, np.repeat(c_g * _group_sums(lam, valid, group_rows)[0], group_rows), 0.0)
+    w = np.ones(rows)
+    if corrected:
+        low, high = cfg.rollout_is_mask or (0.0, np.inf)
+        rho = np.exp(lam)
+        masked = valid & ((rho < low) | (rho > high))
+        truncated = valid & ~masked & (rho > cfg.rollout_is_cap)
+        w = np.where(masked, 0.0, np.minimum(rho, cfg.rollout_is_cap))
     ratio = np.exp(lr)
     lo, hi = 1.0 - cfg.clip_low, 1.0 + cfg.clip_high
     pg = -np.minimum(ratio * A, np.clip(ratio, lo, hi) * A)
     active = ((A >= 0) & (ratio <= hi)) | ((A < 0) & (ratio >= lo))
     g = np.where(active, -A * ratio, 0.0)
+    if corrected:                                 # w is a constant factor of the surrogate (a group's rows share w_G)
+        pg, g = w * pg, w * g
     if by_action:                                 # … and its group's surrogate gradient c·Σ_j −A_j·ratio_G·[active_j]
         g = np.repeat(c_g * _group_sums(g, valid, group_rows)[0], group_rows)
     kl = np.zeros(rows)
@@ -246,20 +313,25 @@ def policy_loss(logits, targets, advantages, old_logprobs, ref_logprobs=None, cf
     mean = lambda v: float(v[valid].sum() / nv) if nv else 0.0
     stats = np.array([mean(row_loss), nv, mean(pg), mean(H), mean(kl), mean((~active).astype(np.float64)),
                       mean(np.expm1(lr) - lr), mean(ratio)], dtype=np.float64)
-    return PolicyLossResult(logp=zero(logp), entropy=zero(H), ratio=zero(ratio), pg=zero(pg), kl=zero(kl), row_loss=zero(row_loss),
-                            clipped=valid & ~active, valid=valid, g=zero(g), loss=stats[0], stats=stats, dlogits=dl,
-                            group_stats=group_stats)
+    res = PolicyLossResult(logp=zero(logp), entropy=zero(H), ratio=zero(ratio), pg=zero(pg), kl=zero(kl), row_loss=zero(row_loss),
+                           clipped=valid & ~active, valid=valid, g=zero(g), loss=stats[0], stats=stats, dlogits=dl,
+                           group_stats=group_stats)
+    if corrected:
+        res.log_rho, res.weight, res.masked, res.truncated = zero(lam), zero(w), masked, truncated
+        res.is_stats = np.array([mean(w), mean(rho), mean(truncated.astype(np.float64)), mean(masked.astype(np.float64)),
+                                 mean(np.expm1(lam) - lam), mean(-lam), 0.0, 0.0], dtype=np.float64)
+    return res
 
 
 def _policy_loss_range(logits, targets, advantages, old_logprobs, ref_logprobs, cfg: PolicyLossConfig, ignore_index: int,
-                       group_rows: Optional[int] = None) -> PolicyLossResult:
+                       group_rows: Optional[int] = None, behaviour_logprobs=None) -> PolicyLossResult:
     """`policy_loss` on logits[:, first : first + count] with the targets shifted by `first`; dlogits widened with zeros."""
     import dataclasses
     first, count = cfg.token_range
     n = np.shape(logits)[1]
     sliced, shifted = slice_range(logits, targets, cfg.token_range, ignore_index, "policy_loss")     # only the range is looked at
     res = policy_loss(sliced, shifted, advantages, old_logprobs, ref_logprobs,
-                      dataclasses.replace(cfg, token_range=None), ignore_index, group_rows)
+                      dataclasses.replace(cfg, token_range=None), ignore_index, group_rows, behaviour_logprobs)
     dl = np.zeros((sliced.shape[0], n), dtype=np.float64)
     dl[:, first:first + count] = res.dlogits
     res.dlogits = dl

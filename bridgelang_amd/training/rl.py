@@ -5,7 +5,8 @@ Host-side tensor layout only; the loop that uses it is the caller's.
 `policy_batch` serves both ratio levels of the loss unchanged. It gives every sequence one advantage and labels on
 exactly its n action tokens, and those labelled tokens are what `PolicyLossConfig(ratio_level="action")` takes as the
 sequence's group: the action's ratio π(a)/π_old(a) is formed from the n `old_logprobs` of the row, and
-`TrainStep.action_stats()` reports it per sequence.
+`TrainStep.action_stats()` reports it per sequence. With `rollout_is=True` it is the batch of a learner with the rollout
+correction (`PolicyLossConfig.rollout_is_cap`): the sampler's log-probabilities are the behaviour policy's, not π_old.
 
 `gae` is PPO's estimator for trajectories with per-step rewards and a learned critic (`TrainStep(value=...)`): advantages
 for `set_policy_batch`, returns for `set_value_batch`.
@@ -80,7 +81,8 @@ def gae(rewards, values, last_values=None, dones=None, gamma: float = 0.99, lam:
 
 
 def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pad_to: Optional[int] = None,
-                 token_range: Optional[Tuple[int, int]] = None, values=None, returns=None) -> Dict[str, torch.Tensor]:
+                 token_range: Optional[Tuple[int, int]] = None, values=None, returns=None, rollout_is: bool = False,
+                 proximal_logprobs=None) -> Dict[str, torch.Tensor]:
     """The training batch of one sampled action per sequence. prompt_ids int64 [B, lp] right-padded with attention_mask
     [B, lp] (None: no padding); token_ids int64 [B, n] and logprobs [B, n] as `sample_actions` reports them (K samples per
     prompt: repeat the prompt rows and flatten to [B·K, n] first); advantages [B], one per sequence, broadcast over its n
@@ -97,7 +99,12 @@ def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pa
     probability 0 under the restricted policy, so the rollouts were not drawn from it.
     `values` [B] (the critic's V(s) the rollout returned, `return_values="action"`) and `returns` [B] (`gae`'s) are checked
     (shape, finite) and passed through as fp32 `old_values` / `returns`, ready for `ts.set_value_batch(returns, old_values)`
-    at value level "action"; a key is added only for the one that is given."""
+    at value level "action"; a key is added only for the one that is given.
+    `rollout_is=True` is the batch of a learner with the rollout correction (`PolicyLossConfig.rollout_is_cap`): the
+    sampler's `logprobs` go out as `behaviour_logprobs` instead, and `old_logprobs` is `proximal_logprobs` [B, n] (the
+    learner's own log-probabilities of the tokens before the update, finite) laid out the same way — or, when that is not
+    given, absent: `ts.set_policy_batch(b["advantages"], b.get("old_logprobs"), behaviour_logprobs=b["behaviour_logprobs"])`
+    is then the self-proximal step. `proximal_logprobs` without `rollout_is` raises ValueError."""
     ids, tok = _cpu(prompt_ids, torch.int64), _cpu(token_ids, torch.int64)
     lp, adv = _cpu(logprobs, torch.float64), _cpu(advantages, torch.float64)
     if ids.dim() != 2 or tok.dim() != 2 or tok.shape[0] != ids.shape[0] or tok.shape[1] < 1:
@@ -110,6 +117,13 @@ def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pa
                          "-inf; draw training rollouts with temperature only")
     if not bool(torch.isfinite(adv).all()):
         raise ValueError("policy_batch: advantages must be finite")
+    if proximal_logprobs is not None and not rollout_is:
+        raise ValueError("policy_batch: proximal_logprobs goes with rollout_is=True (without it logprobs ARE old_logprobs)")
+    prox = None
+    if proximal_logprobs is not None:
+        prox = _cpu(proximal_logprobs, torch.float64)
+        if tuple(prox.shape) != (B, n) or not bool(torch.isfinite(prox).all()):
+            raise ValueError(f"policy_batch: proximal_logprobs [{B}, {n}], finite, got shape {tuple(prox.shape)}")
     extra = {}
     for key, name, x in (("old_values", "values", values), ("returns", "returns", returns)):
         if x is None:
@@ -158,7 +172,17 @@ def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pa
         labels[b, s:s + n] = tok[b]
         out_adv[b, s:s + n] = float(adv[b])
         out_lp[b, s:s + n] = lp[b].to(torch.float32)
-    return {"input_ids": out_ids, "attention_mask": out_m, "labels": labels, "advantages": out_adv, "old_logprobs": out_lp, **extra}
+    out = {"input_ids": out_ids, "attention_mask": out_m, "labels": labels, "advantages": out_adv}
+    if not rollout_is:
+        out["old_logprobs"] = out_lp
+    elif prox is not None:
+        out["old_logprobs"] = torch.zeros(B, l, dtype=torch.float32)
+        for b, (p, s) in enumerate(seqs):
+            out["old_logprobs"][b, s:s + n] = prox[b].to(torch.float32)
+    out.update(extra)
+    if rollout_is:
+        out["behaviour_logprobs"] = out_lp
+    return out
 
 
 def pairs_from_rewards(rewards, min_gap: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -32,7 +32,7 @@ from ..ops import EPI_BIAS, EPI_F32_BF16R, EPI_NONE, EPI_RES, Op
 from ..weights import VLAWeights
 from .linears import Linears, Scratch, ScratchSet
 from .param_store import STAGES, ParamStore, no_decay, param_sharded_key, pool_of, trainable_names      # noqa: F401  (re-exported)
-from .policy_loss import GROUP_STAT_NAMES, STAT_NAMES, PolicyLossConfig
+from .policy_loss import GROUP_STAT_NAMES, IS_STAT_NAMES, STAT_NAMES, PolicyLossConfig
 from .preference_loss import PAIR_STAT_NAMES, PREF_STAT_NAMES, SEQ_STAT_NAMES, PreferenceLossConfig, check_pairs
 from .sharding import ShardComm, comm_order
 from .unit_pools import UnitPools
@@ -79,7 +79,10 @@ class TrainStep:
         entry points: the policy — and with it `token_logprobs()` and `policy_stats()` — is the softmax over that token range
         alone, as rollouts drawn with `action_tokens_only=True` need, and dlogits is 0 outside it. With
         `policy.ratio_level="action"` the forward's loss op is the grouped entry point: one importance ratio per sequence
-        (its labelled tokens are the action), reported by `action_stats()`; the backward plan is the same.
+        (its labelled tokens are the action), reported by `action_stats()`; the backward plan is the same. With
+        `policy.rollout_is_cap` the forward's loss op is bl_policy_loss_is_f32 (either level): the surrogate carries a
+        truncated importance weight between the proximal policy and the one that drew the tokens (`set_policy_batch`'s
+        `behaviour_logprobs`), reported by `rollout_stats()` and `token_weights()`; the backward plan is the same.
         `loss="preference"`: the preference-pair loss of training/preference_loss.py (DPO, IPO, hinge; cDPO, SimPO and RPO
         by its options) over the same rows, configured by `preference` (a PreferenceLossConfig; its defaults if None) and fed
         by `set_preference_batch` after `set_batch`: every sequence is the chosen or the rejected side of a pair, or in
@@ -231,6 +234,10 @@ class TrainStep:
             self.row_loss, self.mean_cnt = self.row_stats[:, 3], self.stats[:2]
             if self.policy.ratio_level == "action":      # one group per sequence: its S rows
                 self.group_stats = z(B, 4, dtype=torch.float32)
+            if self.policy.rollout_is_cap is not None:   # the rollout correction: μ per row in, (λ, w) per row and 8 means out
+                self.behaviour_logprob = z(Tn, dtype=torch.float32)
+                self.is_rows, self.is_stats = z(Tn, 2, dtype=torch.float32), z(8, dtype=torch.float32)
+                self._self_proximal = False
             self._batch_len = prompt_len
             if value is not None:               # the critic: per-row inputs, the device's list of value rows, per-row outputs
                 self.returns, self.old_values = z(Tn, dtype=torch.float32), z(Tn, dtype=torch.float32)
@@ -282,6 +289,11 @@ class TrainStep:
             self._vfwd_tower.append(self._plan_tower_forward(tw, col, sv, self.scratch.side if ti else main))
             self.vision_forward_ops += self._vfwd_tower[-1]
         self.forward_ops = self._plan_forward()
+        if self.policy is not None and self.policy.rollout_is_cap is not None:
+            # the self-proximal forward: the same ops with the loss op given no proximal input. Both plans are fixed here;
+            # `set_policy_batch` only says which one `forward()` runs, and each keeps its own captured graph
+            at = next(i for i, op in enumerate(self.forward_ops) if op.name == "bl_policy_loss_is_f32")
+            self.forward_ops_self = self.forward_ops[:at] + [self._policy_loss_op(self_proximal=True)] + self.forward_ops[at + 1:]
         self._ready: List[Tuple[int, str]] = []      # (number of backward ops enqueued, bucket key complete at that point)
         self.backward_ops = self._plan_backward()
         self.repack_ops = self._plan_repack()
@@ -347,10 +359,7 @@ class TrainStep:
         elif self.policy is None:
             plan.append(ops.cross_entropy(self.logits, self.targets, self.row_loss, self.mean_cnt, IGNORE_INDEX, run=False))
         else:
-            plan.append(T.policy_loss(self.logits, self.targets, self.advantages, self.old_logprob,
-                                      self.ref_logprob if self.policy.kl_coef != 0.0 else None, self.row_stats, self.stats,
-                                      self.policy, IGNORE_INDEX, run=False, group_rows=self.S,
-                                      group_stats=getattr(self, "group_stats", None)))
+            plan.append(self._policy_loss_op())
             if self.value is not None:
                 vh = self.value_head
                 plan.append(T.value_head(self.hn, self.targets, vh.weight, vh.bias, self.returns,
@@ -358,6 +367,16 @@ class TrainStep:
                                          self.value_count, self.value_rows, self.vstats, policy_stats=self.stats, group_rows=S,
                                          ignore_index=IGNORE_INDEX, run=False))
         return plan
+
+    def _policy_loss_op(self, self_proximal: bool = False) -> Op:
+        """The forward's policy-loss op. With the rollout correction it is bl_policy_loss_is_f32, given the proximal
+        log-probabilities or (`self_proximal`) none; otherwise the op of the level, as ever."""
+        corrected = self.policy.rollout_is_cap is not None
+        extra = dict(behaviour_logprob=self.behaviour_logprob, is_rows=self.is_rows, is_stats=self.is_stats) if corrected else {}
+        return T.policy_loss(self.logits, self.targets, self.advantages, None if self_proximal else self.old_logprob,
+                             self.ref_logprob if self.policy.kl_coef != 0.0 else None, self.row_stats, self.stats,
+                             self.policy, IGNORE_INDEX, run=False, group_rows=self.S,
+                             group_stats=getattr(self, "group_stats", None), **extra)
 
     def _layer_forward(self, l: int, with_down: bool = True) -> List[Op]:
         """Forward ops of decoder layer l from its saved input x[l] (modeling_llama.py LlamaDecoderLayer). The backward
@@ -699,23 +718,38 @@ class TrainStep:
             self.pair.zero_()
             self._pairs_set = False
 
-    def set_policy_batch(self, advantages: torch.Tensor, old_logprobs: torch.Tensor, ref_logprobs: Optional[torch.Tensor] = None) -> None:
+    def set_policy_batch(self, advantages: torch.Tensor, old_logprobs: Optional[torch.Tensor], ref_logprobs: Optional[torch.Tensor] = None,
+                         behaviour_logprobs: Optional[torch.Tensor] = None) -> None:
         """Per-token inputs of loss="policy", [B, l] aligned with the `labels` of the preceding `set_batch`: the advantage
         and the behaviour policy's log-probability of each labelled token, and a reference policy's (needed iff kl_coef is
         set). They get the padding, patch-column insertion and one-position shift the labels got; values on unlabelled
         positions are not read. Non-finite values on labelled positions raise ValueError (a -inf from `score_actions`
-        under top-k / top-p: rollouts for training are drawn with temperature only)."""
+        under top-k / top-p: rollouts for training are drawn with temperature only).
+        With the rollout correction (`policy.rollout_is_cap`) the sampler's log-probabilities go in as `behaviour_logprobs`
+        (required), and `old_logprobs` are the PROXIMAL policy's — the learner's own `token_logprobs()` before the update —
+        or None: self-proximal, the forward's own log-probabilities taken as constants, which needs no extra forward when
+        a rollout is used for one update. The two are two forward plans built with the step, equal up to the loss op, each
+        with its own captured graph; this call only selects which one `forward()` runs. Without the correction both of
+        these raise ValueError."""
         if self.policy is None:
             raise RuntimeError("set_policy_batch needs TrainStep(loss='policy')")
         if (ref_logprobs is None) != (self.policy.kl_coef == 0.0):
             raise ValueError("ref_logprobs goes together with a non-zero kl_coef")
+        corrected = self.policy.rollout_is_cap is not None
+        if corrected != (behaviour_logprobs is not None):
+            raise ValueError("behaviour_logprobs goes together with policy.rollout_is_cap (the rollout correction)")
+        if old_logprobs is None and not corrected:
+            raise ValueError("old_logprobs=None (self-proximal) needs policy.rollout_is_cap (the rollout correction)")
         valid = (self.targets != IGNORE_INDEX).view(self.B, self.S)
         for name, src, dst in (("advantages", advantages, self.advantages), ("old_logprobs", old_logprobs, self.old_logprob),
-                               ("ref_logprobs", ref_logprobs, self.ref_logprob)):
+                               ("ref_logprobs", ref_logprobs, self.ref_logprob),
+                               ("behaviour_logprobs", behaviour_logprobs, getattr(self, "behaviour_logprob", None))):
             if src is not None:
                 tokens_to_rows(name, src, dst, self._batch_len, self.dims.n_patches, valid,
                                "on labelled positions — a token outside the rollout's top-k / top-p support scores -inf; draw "
                                "training rollouts with temperature only")
+        if corrected:
+            self._self_proximal = old_logprobs is None
 
     def set_value_batch(self, returns: torch.Tensor, old_values: Optional[torch.Tensor] = None) -> None:
         """The critic's targets for the batch of the preceding `set_batch`: the return R of each value position and the
@@ -798,6 +832,20 @@ class TrainStep:
         """The 8 step statistics of the last forward (policy_loss.STAT_NAMES) as device scalars."""
         return self._stats("policy_stats", self.policy is not None, "TrainStep(loss='policy')", STAT_NAMES, "stats")
 
+    def rollout_stats(self) -> Dict[str, torch.Tensor]:
+        """The statistics of the rollout correction of the last forward (policy_loss.IS_STAT_NAMES) as device scalars: mean
+        weight and mean π_prox/μ, the truncated and masked fractions, and the k3 / k1 estimates of KL(μ‖π_prox). Per rank."""
+        return self._stats("rollout_stats", self.policy is not None and self.policy.rollout_is_cap is not None,
+                           "TrainStep(loss='policy') with policy.rollout_is_cap", IS_STAT_NAMES, "is_stats")
+
+    def token_weights(self) -> torch.Tensor:
+        """The importance weight w of the last forward at the labelled positions, [B, l] aligned with `labels` (0
+        elsewhere, and on masked tokens; the action's weight on each of its tokens at ratio_level="action"), shifted back
+        as `token_logprobs()` is."""
+        if self.policy is None or self.policy.rollout_is_cap is None:
+            raise RuntimeError("token_weights needs TrainStep(loss='policy') with policy.rollout_is_cap")
+        return shift_from_rows(self.is_rows[:, 1].view(self.B, self.S), self.dims.n_patches)[:, :self._batch_len]
+
     def action_stats(self) -> Dict[str, torch.Tensor]:
         """The per-sequence statistics of the last forward under policy.ratio_level="action" (policy_loss.GROUP_STAT_NAMES)
         as device tensors [B]: the action's log-ratio, its ratio, its number of labelled tokens and its log π."""
@@ -839,7 +887,7 @@ class TrainStep:
         if self.pools is not None and self.pools.materialized:
             raise RuntimeError("materialize_params() ended this step object's training (its plans address the gather slots)")
         run = plan if callable(plan) else (lambda: ops.run_all(plan))      # a callable issues its own (forked) launches
-        if not graph or (self.shard_params and key in ("vfwd", "fwd", "bwd")):      # per-unit collectives stay out of HIP graphs
+        if not graph or (self.shard_params and key in ("vfwd", "fwd", "fwd_self", "bwd")):      # per-unit collectives stay out of HIP graphs
             run()
             return
         gr = self._graphs.get(key)
@@ -863,7 +911,10 @@ class TrainStep:
             self._replay("vfwd", self.vision_forward_ops, graph)
         else:
             self._vis.run_vision()
-        self._replay("fwd", self.forward_ops, graph)
+        if getattr(self, "_self_proximal", False):
+            self._replay("fwd_self", self.forward_ops_self, graph)
+        else:
+            self._replay("fwd", self.forward_ops, graph)
         return self.mean_cnt[0] if self.value is None else self.vstats[7]
 
     def backward(self, graph: bool = False) -> None:

@@ -389,6 +389,33 @@ int bl_policy_loss_grouped_f32(const float* logits, int64_t ld, int32_t rows, in
                                float entropy_coef, float kl_coef, float* row_stats, float* stats, int32_t vocab_first,
                                int32_t vocab_count, int32_t group_rows, int32_t ratio_norm, float* group_stats,
                                void* stream);
+/* bl_policy_loss_range_f32 (group_rows = 0, group_stats NULL) or bl_policy_loss_grouped_f32 (group_rows > 0, group_stats
+ * given) with the ROLLOUT CORRECTION of decoupled PPO (training/policy_loss.py with PolicyLossConfig.rollout_is_cap): the
+ * tokens were drawn by a behaviour policy with log-probability behaviour_logprob (mu, fp32 [rows], what the sampler
+ * reported), the ratio is clipped around a proximal policy q, and the surrogate carries a truncated importance weight
+ * between the two. q is old_logprob, or with old_logprob NULL (self-proximal) the row's own logp of this call taken as a
+ * constant: log ratio = 0 exactly, ratio = 1, nothing is clipped. Per valid row, lambda = q - mu at token level, or
+ * lambda_G = c * sum_G (q - mu) with the group and the c of ratio_norm at action level (every valid row of G carries it):
+ *   rho = exp(lambda),  masked = rho < is_mask_low or rho > is_mask_high,  w = masked ? 0 : min(rho, is_cap),
+ *   pg = w * (-min(ratio*A, clip(ratio)*A)),  d row_loss / d logp = w * (surrogate share) + the unchanged KL share.
+ * w carries no gradient; entropy and KL are not weighted; a masked row still counts in n_valid. No mask is (0, +inf);
+ * is_cap may be +inf. stats keeps its layout (loss and mean pg are the weighted ones; ratio, clipped fraction and
+ * approximate KL stay about ratio). is_rows fp32 [rows, 2] = (lambda, w), zeros on ignored rows. is_stats fp32 [8] = means
+ * over valid rows, in the summation order of stats, of (w, rho, truncated = not masked and rho > is_cap, masked,
+ * rho - 1 - lambda, -lambda), then two zeros. With mu = q bit for bit, is_cap >= 1 and no mask, w = 1 and row_stats,
+ * stats and group_stats are bit for bit those of the uncorrected entry point. As many launches as the uncorrected form of
+ * the level (two / three), deterministic, no allocation. The gradient is bl_policy_loss_backward_f32 /
+ * bl_policy_loss_backward_range_f32, unchanged. Constraints as bl_policy_loss_grouped_f32 except that old_logprob may be
+ * NULL; NULL behaviour_logprob / is_rows / is_stats, group_stats given without group_rows > 0 or the reverse, is_cap <= 0,
+ * is_mask_low < 0 or is_mask_low >= is_mask_high (NaN included) is BL_E_ARG; group_rows < 0, rows % group_rows != 0 or
+ * ratio_norm outside {0, 1} is BL_E_SHAPE; nothing is launched on a rejection. */
+int bl_policy_loss_is_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                          int64_t ignore_index, const float* advantages, const float* old_logprob,
+                          const float* behaviour_logprob, const float* ref_logprob, float temperature, float clip_low,
+                          float clip_high, float entropy_coef, float kl_coef, float* row_stats, float* stats,
+                          int32_t vocab_first, int32_t vocab_count, int32_t group_rows, int32_t ratio_norm,
+                          float* group_stats, float is_cap, float is_mask_low, float is_mask_high, float* is_rows,
+                          float* is_stats, void* stream);
 /* The preference-pair loss (DPO family; training/preference_loss.py is the definition) over the same rows. Rows
  * [b*group_rows, (b+1)*group_rows) are sequence b; pair int32 [rows / group_rows] holds +k (chosen side of pair k), -k
  * (rejected side) or 0 (in no pair), k in 1..P; an id outside +-P counts as 0 on the device. With delta_b = c_b * sum over
