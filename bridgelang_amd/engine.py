@@ -11,7 +11,7 @@ only, modeling_prismatic.py:326,460-463); per-sample results equal independent b
 from __future__ import annotations
 
 import functools
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -40,6 +40,23 @@ def _fp8_layers(weights: VLAWeights) -> list:
                   for n in ("qkv_w", "o_w", "gu_w", "down_w")} for lw in weights.layers]
         weights.__dict__["_fp8_layers"] = cache
     return cache
+
+
+class EngineResult(NamedTuple):
+    """What one run of a generation plan offers, in the order every public call documents (`OpenVLAEngine.result`);
+    None: not part of this engine's plan."""
+    ids: torch.Tensor                                   # int64 [B, n_new]
+    wt: Optional[torch.Tensor] = None                   # int64 [B, n_new, 2]: sample=True / score=True
+    range_wt: Optional[torch.Tensor] = None             # int32 [B, n_new, count]: score_range
+    values: Optional[torch.Tensor] = None               # fp32 [B] / [B, n_new]: value=
+    attention: Optional[ActionAttention] = None         # attn_taps on a generation plan
+
+
+def present(*parts):
+    """The one formatter of every public return: `parts` in their documented order, the None ones dropped; the bare
+    element when one is left, else a tuple."""
+    out = tuple(p for p in parts if p is not None)
+    return out[0] if len(out) == 1 else out
 
 
 class OpenVLAEngine:
@@ -572,12 +589,13 @@ class OpenVLAEngine:
         if self.tap_seg is not None:
             self.seg_bounds.copy_(pad_bounds(bounds.cpu(), MAX_SEGMENTS))
 
-    def action_attention(self) -> ActionAttention:
-        """What the taps of the last run recorded, as views of the static buffers (device tensors; no host sync)."""
+    def action_attention(self, own=lambda x: x) -> ActionAttention:
+        """What the taps of the last run recorded, as views of the static buffers (device tensors; no host sync) — or, with
+        `own=torch.clone`, as copies."""
         if self.attn_taps is None or self.all_rows:
             raise ValueError("engine was not built with attn_taps on a generation plan")
-        probs = None if self.tap_probs is None else self.tap_probs.permute(2, 0, 1, 3, 4)
-        seg = None if self.tap_seg is None else self.tap_seg.permute(2, 0, 1, 3, 4)[..., :len(self.seg_names)]
+        probs = None if self.tap_probs is None else own(self.tap_probs.permute(2, 0, 1, 3, 4))
+        seg = None if self.tap_seg is None else own(self.tap_seg.permute(2, 0, 1, 3, 4)[..., :len(self.seg_names)])
         return ActionAttention(probs=probs, segments=seg, names=self.seg_names, layers=self.tap_layers)
 
     def attention_maps(self) -> tuple:
@@ -643,5 +661,14 @@ class OpenVLAEngine:
         self.set_forced_ids(forced_ids)
         self.set_inputs(input_ids, pixel_values)
         self.replay()
-        wt = self.gen_wt.permute(1, 0, 2)
-        return wt if self.gen_range_wt is None else (wt, self.gen_range_wt.permute(1, 0, 2))
+        r = self.result()
+        return present(r.wt, r.range_wt)
+
+    def result(self, own=lambda x: x) -> EngineResult:
+        """The last run as one record; `own` is applied to every tensor (identity: views of the static buffers, which the
+        next run overwrites; `torch.clone`: copies). Device tensors, no host sync."""
+        return EngineResult(ids=own(self.gen_ids.t()),
+                            wt=own(self.gen_wt.permute(1, 0, 2)) if self.sample or self.score_mode else None,
+                            range_wt=None if self.gen_range_wt is None else own(self.gen_range_wt.permute(1, 0, 2)),
+                            values=None if self.values is None else own(self.value_result()),
+                            attention=self.action_attention(own) if self.attn_taps is not None and not self.all_rows else None)

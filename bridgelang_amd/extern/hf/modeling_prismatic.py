@@ -34,14 +34,14 @@ from __future__ import annotations
 from collections import OrderedDict
 from dataclasses import dataclass, replace
 from types import SimpleNamespace
-from typing import Any, Dict, Optional, Sequence, Tuple, Union
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 from transformers import PreTrainedModel
 
 from ...attention_taps import ActionAttention, AttnTaps, prompt_segments
-from ...engine import OpenVLAEngine
+from ...engine import EngineResult, OpenVLAEngine, present
 from ...sampling import SamplingParams, derive_seed, logprob
 from ...weights import TowerDims, VLADims, VLAWeights, allocate
 from .configuration_prismatic import OpenVLAConfig, PrismaticConfig
@@ -256,18 +256,6 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         return AttnTaps(layers=None if attention_layers is None else tuple(int(l) for l in attention_layers),
                         full=return_attention != "segments", segments=return_attention != "full")
 
-    @staticmethod
-    def _set_attention_segments(eng: OpenVLAEngine, attention_mask: Optional[torch.Tensor], text_splits) -> None:
-        """The segments of THIS call's prompts (after set_padded_inputs, which resets them, and before the plan runs)."""
-        mask = torch.ones(eng.B, eng.L, dtype=torch.int64) if attention_mask is None else attention_mask
-        eng.set_segments(*prompt_segments(mask, eng.n_patches, eng.n_new, text_splits))
-
-    @staticmethod
-    def _action_attention(eng: OpenVLAEngine) -> ActionAttention:
-        a = eng.action_attention()       # views of the engine's static buffers: hand out copies
-        return ActionAttention(probs=None if a.probs is None else a.probs.clone(),
-                               segments=None if a.segments is None else a.segments.clone(), names=a.names, layers=a.layers)
-
     @torch.no_grad()
     def attention_maps(self, input_ids: torch.LongTensor, pixel_values: Optional[torch.Tensor] = None,
                        attention_mask: Optional[torch.Tensor] = None, layers=None) -> tuple:
@@ -465,19 +453,15 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
     # ---- generation: greedy, or seeded sampling ----
     @torch.no_grad()
     def generate(self, input_ids: torch.LongTensor, max_new_tokens: int = 7, pixel_values: Optional[torch.Tensor] = None,
-                 attention_mask: Optional[torch.Tensor] = None, do_sample: bool = False, use_cache: bool = True,
-                 sampling: Optional[SamplingParams] = None, return_weights: bool = False,
-                 forced_ids: Optional[torch.Tensor] = None, score_range: Optional[Tuple[int, int]] = None,
-                 vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None,
-                 return_attention: Optional[str] = None, attention_layers=None, text_splits=None,
-                 return_values: Optional[str] = None, **_: Any):
-        """`use_adapters`: see `engine` (None: the attached adapters if any; False: the base model).
+                 attention_mask: Optional[torch.Tensor] = None, **kwargs: Any):
+        """The keywords are those of `_generate`, which is this call before its return is formatted.
+        `use_adapters`: see `engine` (None: the attached adapters if any; False: the base model).
         `return_values="action" | "token"` (a value head attached, `attach_value_head`) appends the critic's values, fp32 on
         the device: [B] = V(s) of the state the action is taken in (the row that predicts the first new token, the
         learner's level="action" value row), or [B, max_new_tokens] = the rows that predict every new token
-        (level="token"). Order of the returned elements: ids, then wt (`return_weights` / `forced_ids`), then range_wt
-        (`score_range`), then the values, then the `ActionAttention` (`return_attention`). The value op only reads the
-        residual rows: ids, logits and weights are those of the call without it.
+        (level="token"). The returned elements are the fields of `EngineResult` that were asked for, in its order: ids, wt,
+        range_wt, values, attention. The value op only reads the residual rows: ids, logits and weights are those of the
+        call without it.
         `return_attention="segments" | "full" | "both"` appends an `attention_taps.ActionAttention` to whatever the call
         returns: for every new token, tapped layer (`attention_layers`, None = all) and head, the attention of the query that
         produced it — summed over bos | image | text | generated ("segments"), over every cache row ("full"), or both.
@@ -500,6 +484,18 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         `vocab_range=(first, count)` restricts the policy to that token range (`sampling.py`, `vocab=`): draws, scores and
         weights are under the softmax of those logits alone, a forced token outside it scores weight 0, and without
         `sampling=` the call is constrained greedy decoding (temperature 0 through the sampling engine)."""
+        return present(*self._generate(input_ids, max_new_tokens, pixel_values, attention_mask, **kwargs))
+
+    def _generate(self, input_ids: torch.LongTensor, max_new_tokens: int = 7, pixel_values: Optional[torch.Tensor] = None,
+                  attention_mask: Optional[torch.Tensor] = None, do_sample: bool = False,
+                  sampling: Optional[SamplingParams] = None, return_weights: bool = False,
+                  forced_ids: Optional[torch.Tensor] = None, score_range: Optional[Tuple[int, int]] = None,
+                  vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None,
+                  return_attention: Optional[str] = None, attention_layers=None, text_splits=None,
+                  return_values: Optional[str] = None, **_: Any) -> EngineResult:
+        """`generate` as a record: its argument checks, one engine run, and the run's `EngineResult` with `ids` = prompt ‖
+        new tokens and `wt` only where `generate` returns it. What `predict_action` / `score_actions` read by field.
+        Keywords it does not know (`use_cache`) are accepted and ignored."""
         if do_sample and sampling is None:
             raise NotImplementedError("do_sample=True draws from torch's global device RNG stream, which the HIP path does "
                                       "not reproduce: pass sampling=SamplingParams(temperature=, top_k=, top_p=, seed=) instead")
@@ -507,60 +503,99 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             raise ValueError("return_weights goes with sampling=")
         if pixel_values is None:
             raise ValueError("generate() needs pixel_values")
-        B, L = input_ids.shape
         ids, pv = input_ids.to(self.device), pixel_values.to(self.device)
         taps = self._attn_taps(return_attention, attention_layers)
         if taps is None and text_splits is not None:
             raise ValueError("text_splits goes with return_attention=")
         value = self._value_level(return_values)
-        if forced_ids is not None:
-            forced = torch.as_tensor(forced_ids).to(self.device, torch.int64)
-            padded = attention_mask is not None and not bool(attention_mask.bool().all())
-            eng = self.engine(B, L, max_new_tokens, padded=padded, score=True, score_range=score_range, vocab_range=vocab_range,
-                              use_adapters=use_adapters, attn_taps=taps, value=value)
-            eng.set_sampling(sampling if sampling is not None else SamplingParams())
-            if padded:
-                eng.set_forced_ids(forced)
-                eng.set_padded_inputs(ids, pv, attention_mask)
-                if taps is not None:
-                    self._set_attention_segments(eng, attention_mask, text_splits)
-                eng.run_eager()
-            else:
-                if taps is not None:
-                    self._set_attention_segments(eng, None, text_splits)
-                eng.score(ids, pv, forced)
-            out = (torch.cat([ids, forced], dim=1), eng.gen_wt.permute(1, 0, 2).clone())
-            out = out if score_range is None else out + (eng.gen_range_wt.permute(1, 0, 2).clone(),)
-            out = out if value is None else out + (eng.value_result().clone(),)
-            return out if taps is None else out + (self._action_attention(eng),)
-        if score_range is not None:
+        forced = None if forced_ids is None else torch.as_tensor(forced_ids).to(self.device, torch.int64)
+        if forced is None and score_range is not None:
             raise ValueError("score_range goes with forced_ids=")
-        if vocab_range is not None and sampling is None:
-            sampling = SamplingParams(temperature=0.0, seed=0)
-        sample = sampling is not None
-        if attention_mask is not None and not bool(attention_mask.bool().all()):
-            eng = self.engine(B, L, max_new_tokens, padded=True, sample=sample, vocab_range=vocab_range, use_adapters=use_adapters,
-                              attn_taps=taps, value=value)
-            if sample:
-                eng.set_sampling(sampling)
+        r = self._run_engine(ids, pv, max_new_tokens, attention_mask, sampling, forced, score_range, vocab_range, use_adapters,
+                             taps, text_splits, value)
+        return r._replace(ids=torch.cat([ids, r.ids], dim=1), wt=r.wt if return_weights or forced is not None else None)
+
+    @torch.no_grad()
+    def _run_engine(self, ids: torch.Tensor, pv: torch.Tensor, n_new: int, attention_mask: Optional[torch.Tensor],
+                    sampling: Optional[SamplingParams], forced: Optional[torch.Tensor], score_range, vocab_range,
+                    use_adapters: Optional[bool], taps: Optional[AttnTaps], text_splits, value: Optional[str]) -> EngineResult:
+        """The one path of every generation call through an engine: choose it, fill its settings, forced ids, inputs and
+        segments (after the inputs: `set_padded_inputs` resets them), run the plan. Returns copies: nothing handed out
+        aliases an engine buffer. The model's engines are not captured, so `replay()` launches the plan eagerly."""
+        score = forced is not None
+        padded = attention_mask is not None and not bool(attention_mask.bool().all())
+        if sampling is None and score:
+            sampling = SamplingParams()                              # the unwarped distribution (a score has no seed)
+        elif sampling is None and vocab_range is not None:
+            sampling = SamplingParams(temperature=0.0, seed=0)       # constrained greedy decoding
+        eng = self.engine(*ids.shape, n_new, padded=padded, sample=sampling is not None and not score, score=score,
+                          score_range=score_range, vocab_range=vocab_range, use_adapters=use_adapters, attn_taps=taps, value=value)
+        if sampling is not None:
+            eng.set_sampling(sampling)
+        if score:
+            eng.set_forced_ids(forced)
+        if padded:
             eng.set_padded_inputs(ids, pv, attention_mask)
-            if taps is not None:
-                self._set_attention_segments(eng, attention_mask, text_splits)
-            eng.run_eager()
-            new = eng.gen_ids.t()
         else:
-            eng = self.engine(B, L, max_new_tokens, sample=sample, vocab_range=vocab_range, use_adapters=use_adapters,
-                              attn_taps=taps, value=value)
-            if taps is not None:
-                self._set_attention_segments(eng, None, text_splits)
-            new = eng.generate(ids, pv, sampling)
-        out = torch.cat([ids, new], dim=1)
-        out = (out, eng.gen_wt.permute(1, 0, 2).clone()) if return_weights else out
-        if value is not None:
-            out = (out if isinstance(out, tuple) else (out,)) + (eng.value_result().clone(),)
-        if taps is None:
-            return out
-        return (out if isinstance(out, tuple) else (out,)) + (self._action_attention(eng),)
+            eng.set_inputs(ids, pv)
+        if taps is not None:                # the segments of THIS call's prompts
+            mask = attention_mask if padded else torch.ones(eng.B, eng.L, dtype=torch.int64)
+            eng.set_segments(*prompt_segments(mask, eng.n_patches, eng.n_new, text_splits))
+        eng.replay()
+        return eng.result(torch.clone)
+
+
+def _numpy(t: Optional[torch.Tensor]) -> Optional[np.ndarray]:
+    return None if t is None else t.cpu().numpy()
+
+
+# ---- copies / candidates of a batch, several per engine run (`sample_actions`, `score_actions`) ----
+def copy_runs(B: int, K: int) -> List[Tuple[int, int]]:
+    """(first copy j0, copies c) of the engine runs that cover K copies of a batch of B: max(1, 16 // B) per run — batches up
+    to 16 keep "a sequence's result is its batch-1 result"."""
+    per_run = max(1, 16 // B)
+    return [(j0, min(per_run, K - j0)) for j0 in range(0, K, per_run)]
+
+
+def tile_sampling(T, k, p, seed, j0: int, c: int) -> SamplingParams:
+    """The resolved per-sequence settings [B] for copies j0 … j0 + c - 1, copy-major [c·B]: copy j draws with
+    `derive_seed(seed, j)`; seed=None (a score has none): 0."""
+    return SamplingParams(temperature=np.tile(T, c), top_k=np.tile(k, c), top_p=np.tile(p, c),
+                          seed=0 if seed is None else np.concatenate([derive_seed(seed, j) for j in range(j0, j0 + c)]))
+
+
+def tap_kwargs(return_attention, attention_layers, text_splits, B: int, c: int) -> dict:
+    """The attention keywords of a run over c copies (`text_splits` [B, k] tiled copy-major); none without `return_attention`."""
+    if return_attention is None:
+        return {}
+    return dict(return_attention=return_attention, attention_layers=attention_layers,
+                text_splits=None if text_splits is None else torch.as_tensor(text_splits).reshape(B, -1).repeat(c, 1))
+
+
+def stack_runs(parts: Sequence, B: int):
+    """Per-run results [c·B, …] (copy-major; arrays or tensors, None: absent) → [B, copies, …]."""
+    if parts[0] is None:
+        return None
+    split = [x.reshape((x.shape[0] // B, B) + tuple(x.shape[1:])) for x in parts]
+    if isinstance(split[0], np.ndarray):
+        return np.concatenate(split, axis=0).swapaxes(0, 1)
+    return torch.cat(split, dim=0).transpose(0, 1).contiguous()
+
+
+def stack_values(parts: Sequence, B: int, level: Optional[str]):
+    """The critic's values of the runs: every copy of a sequence is in the same state, so level "action" is copy 0's [B];
+    level "token" is every copy's [B, copies, n]."""
+    if parts[0] is None:
+        return None
+    return parts[0][:B].copy() if level == "action" else stack_runs(parts, B)
+
+
+def stack_attention(parts: Sequence[Optional[ActionAttention]], B: int) -> Optional[ActionAttention]:
+    """The ActionAttention of the runs → one with tensors [B, copies, n_new, layers, H, ·]."""
+    if parts[0] is None:
+        return None
+    return ActionAttention(probs=stack_runs([a.probs for a in parts], B), segments=stack_runs([a.segments for a in parts], B),
+                           names=parts[0].names, layers=parts[0].layers)
 
 
 class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
@@ -594,10 +629,13 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         `return_values="action" | "token"` (see `generate`, `attach_value_head`) returns the critic's values as one more
         element, fp32 ndarray [B] or [B, n]. Order: the action, then (tokens, wt) with `return_weights`, then the values, then
         the `ActionAttention`."""
+        p = self._predict(input_ids, unnorm_key, action_tokens_only, use_adapters, **kwargs)
+        return present(p.actions, None if p.wt is None else p.tokens, p.wt, p.values, p.attention)
+
+    def _predict(self, input_ids: torch.LongTensor, unnorm_key, action_tokens_only: bool = False,
+                 use_adapters: Optional[bool] = None, **kwargs: Any) -> SimpleNamespace:
+        """`predict_action` as named parts: actions, tokens, wt, values (numpy) and attention; None: not asked for."""
         input_ids = input_ids.to(self.device)
-        kwargs["use_adapters"] = use_adapters
-        if action_tokens_only:
-            kwargs["vocab_range"] = self.action_token_range()
         keys = list(unnorm_key) if isinstance(unnorm_key, (list, tuple)) else None
         if keys is not None:
             if len(keys) != input_ids.shape[0] or len({self.get_action_dim(k) for k in keys}) != 1:
@@ -607,38 +645,15 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         if m is not None:
             kwargs["attention_mask"] = m
         n = self.get_action_dim(unnorm_key)
-        generated = self.generate(input_ids, max_new_tokens=n, **kwargs)
-        wt = att = vals = None
-        if isinstance(generated, tuple):
-            parts = list(generated)
-            if kwargs.get("return_attention") is not None:   # the ActionAttention rides last,
-                att = parts.pop()
-            if kwargs.get("return_values") is not None:      # the values before it
-                vals = parts.pop().cpu().numpy()
-            generated = parts[0]
-            if len(parts) > 1:                               # sampling= with return_weights=True
-                wt = parts[1]
-        tokens = generated[:, -n:].cpu().numpy()
+        if action_tokens_only:
+            kwargs["vocab_range"] = self.action_token_range()
+        r = self._generate(input_ids, max_new_tokens=n, use_adapters=use_adapters, **kwargs)
+        tokens = r.ids[:, -n:].cpu().numpy()
         if keys is not None:
             actions = np.stack([np.asarray(self.actions_from_token_ids(tokens[i:i + 1], k)).reshape(-1) for i, k in enumerate(keys)])
         else:
             actions = self.actions_from_token_ids(tokens, unnorm_key)
-        out = actions if wt is None else (actions, tokens, wt.cpu().numpy())
-        for extra in (vals, att):
-            if extra is not None:
-                out = (out if isinstance(out, tuple) else (out,)) + (extra,)
-        return out
-
-    @staticmethod
-    def _stack_attention(parts: Sequence[ActionAttention], B: int) -> ActionAttention:
-        """The ActionAttention of several engine runs over c·B rows each (copy-major, as sample_actions / score_actions batch
-        them) → one with tensors [B, copies, n_new, layers, H, ·]."""
-        def cat(ts):
-            if ts[0] is None:
-                return None
-            return torch.cat([t.reshape((t.shape[0] // B, B) + tuple(t.shape[1:])) for t in ts], dim=0).transpose(0, 1).contiguous()
-        return ActionAttention(probs=cat([a.probs for a in parts]), segments=cat([a.segments for a in parts]),
-                               names=parts[0].names, layers=parts[0].layers)
+        return SimpleNamespace(actions=actions, tokens=tokens, wt=_numpy(r.wt), values=_numpy(r.values), attention=r.attention)
 
     def _action_prompt(self, input_ids: torch.LongTensor, m: Optional[torch.Tensor]):
         """The prompt with the empty token 29871 behind each sequence's last token → (input_ids, attention_mask)."""
@@ -667,8 +682,8 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
                        text_splits=None, return_values: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """`use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy).
         `return_values="action"` appends V(s) fp32 [B] — every copy of a sequence is in the same state, so one value per
-        sequence, taken from copy 0; `"token"` appends [B, num_samples, n], the values along every copy's own tokens. The
-        values come fourth, before the `ActionAttention`.
+        sequence, taken from copy 0; `"token"` appends [B, num_samples, n], the values along every copy's own tokens. Order:
+        actions, tokens, logprobs, values, attention.
         `num_samples` sampled actions per sequence with their log-probabilities (RL rollouts, best-of-N, uncertainty):
         → (actions [B, num_samples, n], token_ids int64 [B, num_samples, n], logprobs fp64 [B, num_samples, n]). The batch
         is repeated `num_samples` times (several copies per engine run while the run stays within 16 sequences); copy j of a sequence with seed s draws with
@@ -686,35 +701,16 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         B = input_ids.shape[0]
         T, k, p, seed = sampling.resolve(B)
         keys = list(unnorm_key) if isinstance(unnorm_key, (list, tuple)) else None
-        per_call = max(1, 16 // B)          # copies per engine run: batches up to 16 keep "a sequence's result is its batch-1 result"
-        acts, toks, lps, atts, vals = [], [], [], [], []
-        att_kw = {}
-        if return_attention is not None:
-            att_kw = dict(return_attention=return_attention, attention_layers=attention_layers)
-        val_kw = {} if self._value_level(return_values) is None else dict(return_values=return_values)
-        for j0 in range(0, num_samples, per_call):
-            c = min(per_call, num_samples - j0)
-            sp = SamplingParams(temperature=np.tile(T, c), top_k=np.tile(k, c), top_p=np.tile(p, c),
-                                seed=np.concatenate([derive_seed(seed, j) for j in range(j0, j0 + c)]))
-            if att_kw and text_splits is not None:
-                att_kw["text_splits"] = torch.as_tensor(text_splits).reshape(B, -1).repeat(c, 1)
-            res = self.predict_action(input_ids.repeat(c, 1), keys * c if keys is not None else unnorm_key,
-                                      pixel_values=pixel_values.repeat(c, 1, 1, 1),
-                                      attention_mask=None if attention_mask is None else attention_mask.repeat(c, 1),
-                                      sampling=sp, return_weights=True, action_tokens_only=action_tokens_only,
-                                      use_adapters=use_adapters, **val_kw, **att_kw)
-            a, tok, wt = res[:3]
-            if val_kw:
-                vals.append(res[3].reshape((c, B) + res[3].shape[1:]))
-            if att_kw:
-                atts.append(res[-1])
-            acts.append(np.asarray(a).reshape(c, B, -1))
-            toks.append(tok.reshape(c, B, -1))
-            lps.append(logprob(wt).reshape(c, B, -1))
-        out = tuple(np.concatenate(x, axis=0).transpose(1, 0, 2) for x in (acts, toks, lps))
-        if val_kw:      # [copies, B] / [copies, B, n] → copy 0's [B] / [B, copies, n]
-            out += (vals[0][0].copy() if return_values == "action" else np.concatenate(vals, axis=0).transpose(1, 0, 2),)
-        return out + (self._stack_attention(atts, B),) if att_kw else out
+        level = self._value_level(return_values)
+        runs = [self._predict(input_ids.repeat(c, 1), keys * c if keys is not None else unnorm_key, action_tokens_only, use_adapters,
+                              pixel_values=pixel_values.repeat(c, 1, 1, 1),
+                              attention_mask=None if attention_mask is None else attention_mask.repeat(c, 1),
+                              sampling=tile_sampling(T, k, p, seed, j0, c), return_weights=True, return_values=level,
+                              **tap_kwargs(return_attention, attention_layers, text_splits, B, c))
+                for j0, c in copy_runs(B, num_samples)]
+        return present(stack_runs([np.asarray(r.actions).reshape(r.tokens.shape[0], -1) for r in runs], B),
+                       stack_runs([r.tokens for r in runs], B), stack_runs([logprob(r.wt) for r in runs], B),
+                       stack_values([r.values for r in runs], B, level), stack_attention([r.attention for r in runs], B))
 
     def score_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor, token_ids=None, actions=None,
                       unnorm_key: Optional[str] = None, sampling: Optional[SamplingParams] = None,
@@ -723,10 +719,9 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
                       return_attention: Optional[str] = None, attention_layers=None, text_splits=None,
                       return_values: Optional[str] = None):
         """`return_values="action"` appends V(s) fp32 [B] (the state is the same for every candidate: candidate 0's);
-        `"token"` appends [B, K, n], the values along the given tokens. They ride after the log-probabilities (and the wt /
-        bin_wt of `return_bins`) and before the `ActionAttention`.
-        `return_attention=` (with `attention_layers=`, `text_splits=` [B, k]; see `generate`) appends the `ActionAttention`
-        under the GIVEN actions, tensors [B, K, n, layers, H, ·], as an extra last element.
+        `"token"` appends [B, K, n], the values along the given tokens. `return_attention=` (with `attention_layers=`,
+        `text_splits=` [B, k]; see `generate`) appends the `ActionAttention` under the GIVEN actions, tensors [B, K, n, layers,
+        H, ·]. Order: logprobs, then (wt, bin_wt) with `return_bins`, then the values, then the `ActionAttention`.
         `use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy — with adapters
         attached, an RL learner's reference policy).
         Log-probabilities of GIVEN actions under the policy `sample_actions` draws from (a PPO / GRPO learner's
@@ -761,39 +756,19 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         n_bins = self.config.n_action_bins
         rng = (self.vocab_size - n_bins, n_bins) if return_bins else None
         ids, m = self._action_prompt(input_ids.to(self.device), attention_mask)      # the prompt as predict_action prepares it
-        per_call = max(1, 16 // B)          # candidates per engine run, as sample_actions batches its copies
-        wts, bins, atts, vals = [], [], [], []
-        att_kw = {}
-        if return_attention is not None:
-            att_kw = dict(return_attention=return_attention, attention_layers=attention_layers)
-        val_kw = {} if self._value_level(return_values) is None else dict(return_values=return_values)
-        for j0 in range(0, K, per_call):
-            c = min(per_call, K - j0)
-            sp = SamplingParams(temperature=np.tile(T, c), top_k=np.tile(k, c), top_p=np.tile(p, c), seed=0)
+        level = self._value_level(return_values)
+        runs = []
+        for j0, c in copy_runs(B, K):
             forced = torch.from_numpy(np.ascontiguousarray(tok[:, j0:j0 + c].transpose(1, 0, 2)).reshape(c * B, n))
-            out = self.generate(ids.repeat(c, 1), n, pixel_values=pixel_values.repeat(c, 1, 1, 1),
-                                attention_mask=None if m is None else m.repeat(c, 1), sampling=sp, forced_ids=forced,
-                                score_range=rng, vocab_range=self.action_token_range() if action_tokens_only else None,
-                                use_adapters=use_adapters, **val_kw, **att_kw,
-                                **(dict(text_splits=torch.as_tensor(text_splits).reshape(B, -1).repeat(c, 1))
-                                   if att_kw and text_splits is not None else {}))
-            if att_kw:
-                atts.append(out[-1])
-            if val_kw:
-                v = out[-1 - bool(att_kw)].cpu().numpy()
-                vals.append(v.reshape((c, B) + v.shape[1:]))
-            wts.append(out[1].cpu().numpy().reshape(c, B, n, 2))
-            if return_bins:
-                bins.append(out[2].cpu().numpy().reshape(c, B, n, n_bins))
-        wt = np.concatenate(wts, axis=0).transpose(1, 0, 2, 3)
-        lp = logprob(wt)
-        res = (lp, wt, np.concatenate(bins, axis=0).transpose(1, 0, 2, 3)) if return_bins else lp
-        if val_kw:
-            res = (res if isinstance(res, tuple) else (res,)) + \
-                (vals[0][0].copy() if return_values == "action" else np.concatenate(vals, axis=0).transpose(1, 0, 2),)
-        if not att_kw:
-            return res
-        return (res if isinstance(res, tuple) else (res,)) + (self._stack_attention(atts, B),)
+            runs.append(self._generate(ids.repeat(c, 1), n, pixel_values=pixel_values.repeat(c, 1, 1, 1),
+                                       attention_mask=None if m is None else m.repeat(c, 1), sampling=tile_sampling(T, k, p, None, j0, c),
+                                       forced_ids=forced, score_range=rng,
+                                       vocab_range=self.action_token_range() if action_tokens_only else None,
+                                       use_adapters=use_adapters, return_values=level,
+                                       **tap_kwargs(return_attention, attention_layers, text_splits, B, c)))
+        wt = stack_runs([_numpy(r.wt) for r in runs], B)
+        return present(logprob(wt), wt if return_bins else None, stack_runs([_numpy(r.range_wt) for r in runs], B),
+                       stack_values([_numpy(r.values) for r in runs], B, level), stack_attention([r.attention for r in runs], B))
 
     def token_ids_from_actions(self, actions: np.ndarray, unnorm_key: Optional[str] = None) -> np.ndarray:
         """Un-normalised actions [..., n] → action token ids int64 [..., n]: the inverse of `actions_from_token_ids`, i.e.

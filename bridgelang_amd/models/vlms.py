@@ -10,6 +10,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
+from ..engine import present
 from ..extern.hf.configuration_prismatic import OpenVLAConfig
 from ..extern.hf.modeling_prismatic import OpenVLAForActionPrediction
 from ..training.checkpoint import from_model_state_dicts, to_model_state_dicts
@@ -154,22 +155,14 @@ class OpenVLA(PrismaticVLM):
         else:
             raise ValueError(f"Unsupported `pixel_values` type = {type(pixel_values)}")
         n = self.get_action_dim(unnorm_key)
-        generated_ids = self.generate(input_ids, pixel_values, max_new_tokens=n, **kwargs)
-        attention = values = None
-        if kwargs.get("return_attention") is not None:
-            generated_ids, attention = generated_ids[:-1], generated_ids[-1]
-        if kwargs.get("return_values") is not None:
-            values = generated_ids[-1].cpu().numpy()
-        if isinstance(generated_ids, tuple):
-            generated_ids = generated_ids[0]
-        predicted_action_token_ids = generated_ids[0, -n:]
+        r = self.hf._generate(input_ids, max_new_tokens=n, pixel_values=self._stack(pixel_values), **kwargs)
+        predicted_action_token_ids = r.ids[0, -n:]
         normalized_actions = self.action_tokenizer.decode_token_ids_to_actions(predicted_action_token_ids.cpu().numpy())
         action_norm_stats = self.get_action_stats(unnorm_key)
         mask = action_norm_stats.get("mask", np.ones_like(action_norm_stats["q01"], dtype=bool))
         action_high, action_low = np.array(action_norm_stats["q99"]), np.array(action_norm_stats["q01"])
         action = np.where(mask, 0.5 * (normalized_actions + 1) * (action_high - action_low) + action_low, normalized_actions)
-        out = tuple(x for x in (action, values, attention) if x is not None)
-        return out[0] if len(out) == 1 else out
+        return present(action, None if r.values is None else r.values.cpu().numpy(), r.attention)
 
     @staticmethod
     def _check_unnorm_key(norm_stats: Dict, unnorm_key: str) -> str:

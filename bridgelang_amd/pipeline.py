@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .engine import OpenVLAEngine
+from .engine import OpenVLAEngine, present
 from .llm_plan import decode_fused, decode_layer, head, head_fused
 from .ops import Op
 from .weights import VLAWeights
@@ -273,14 +273,8 @@ class StaggeredDecodePipeline:
 
     def _result(self, e: OpenVLAEngine, own):
         """What step() / flush() hand out for a slot's finished batch (`own`: identity for views, clone for copies)."""
-        if self.score:
-            wt = own(e.gen_wt.permute(1, 0, 2))
-            out = wt if e.gen_range_wt is None else (wt, own(e.gen_range_wt.permute(1, 0, 2)))
-        else:
-            out = (own(e.gen_ids.t()), own(e.gen_wt.permute(1, 0, 2))) if self.sample else own(e.gen_ids.t())
-        if self.value is None:
-            return out
-        return (*out, own(e.value_result())) if isinstance(out, tuple) else (out, own(e.value_result()))
+        r = e.result(own)
+        return present(None if self.score else r.ids, r.wt, r.range_wt, r.values)
 
     def flush(self, ticks: Optional[Sequence[int]] = None) -> List[Optional[torch.Tensor]]:
         """Drain: finish the batches still in flight with each slot's own per-batch plans; returns their ids oldest

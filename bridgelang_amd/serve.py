@@ -451,24 +451,26 @@ class OpenVLAServer:
             rows = batch + [batch[-1]] * (size - n)
             ids = torch.cat([r.input_ids for r in rows], dim=0)
             pv = torch.cat([r.pixel_values for r in rows], dim=0)
-            wt = vals = None
-            vkw = {} if self.value is None else dict(return_values=self.value)
+            padded = batch[0].mask is not None      # pad_to: lengths and keys are mixed — every sequence un-normalised with its own key
+            kw = dict(input_ids=ids, pixel_values=pv, unnorm_key=[r.unnorm_key for r in rows] if padded else batch[0].unnorm_key)
+            if padded:
+                kw["attention_mask"] = torch.cat([r.mask for r in rows], dim=0)
             if self.sample:                   # per-row settings: mixed requests (greedy ones included) ride one call
-                kw = dict(unnorm_key=[r.unnorm_key for r in rows], attention_mask=torch.cat([r.mask for r in rows], dim=0)) \
-                    if batch[0].mask is not None else dict(unnorm_key=batch[0].unnorm_key)
-                res = self.vla.predict_action(input_ids=ids, pixel_values=pv, sampling=self._sampling_of(rows),
-                                              return_weights=True, **kw, **vkw,
-                                              **(dict(action_tokens_only=True) if self.vocab_range is not None else {}))
-                actions, wt = np.asarray(res[0]), np.asarray(res[2])[:n]
-                vals = res[3] if vkw else None
-            elif batch[0].mask is not None:     # pad_to: lengths and keys are mixed — every sequence un-normalised with its own key
-                actions = self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=[r.unnorm_key for r in rows],
-                                                  attention_mask=torch.cat([r.mask for r in rows], dim=0), do_sample=False, **vkw)
+                kw.update(sampling=self._sampling_of(rows), return_weights=True)
+                if self.vocab_range is not None:
+                    kw["action_tokens_only"] = True
             else:
-                actions = self.vla.predict_action(input_ids=ids, pixel_values=pv, unnorm_key=batch[0].unnorm_key,
-                                                  do_sample=False, **vkw)
-            if vkw and not self.sample:
-                actions, vals = actions
+                kw["do_sample"] = False
+            if self.value is not None:
+                kw["return_values"] = self.value
+            res = self.vla.predict_action(**kw)
+            wt = None
+            if self.sample:
+                actions, _, wt, *vals = res
+                wt = np.asarray(wt)[:n]
+            else:
+                actions, *vals = res if self.value is not None else (res,)
+            vals = vals[0] if vals else None
             actions = np.asarray(actions).reshape(size, -1)[:n]
             self._record(batch)
             for i, (r, a) in enumerate(zip(batch, actions)):

@@ -3,8 +3,9 @@
 line. A record, nothing is gated: the score plan is the sampling plan with bl_score_f32 where that has bl_sample_f32.
 
   `sample_actions` against `score_actions` (token_ids = the sampled tokens; with and without return_bins) on one model
-  object at B = 16, L = 32, T = 1, k = 50, p = 0.95: wall time per call, host work included, `--calls` calls after two
-  warm-up calls, the three timed alternately `--rounds` times.
+  object at B = 16 (`--batch`), L = 32, T = 1, k = 50, p = 0.95: wall time per call, host work included, `--calls` calls
+  after two warm-up calls, the legs timed alternately `--rounds` times. A greedy `predict_action` rides along: at --batch 1
+  it is the latency of one action, where the per-call host work of the front end shows most.
 
     python tools/bench_score.py > profiles/bench_score.json
 """
@@ -18,7 +19,7 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
-B, L = 16, 32
+L = 32
 
 
 def main():
@@ -26,7 +27,9 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--model", default="openvla-7b", choices=["openvla-7b", "openvla-tiny"])
+    ap.add_argument("--batch", type=int, default=16)
     args = ap.parse_args()
+    B = args.batch
     from bridgelang_amd import weights as W
     from bridgelang_amd.extern.hf.configuration_prismatic import OpenVLAConfig
     from bridgelang_amd.extern.hf.modeling_prismatic import OpenVLAForActionPrediction
@@ -41,7 +44,8 @@ def main():
     ids, pv = ids.to(dev), (torch.rand(B, 6, 224, 224, generator=g) * 2 - 1).to(torch.bfloat16).to(dev)
     sp = SamplingParams(1.0, 50, 0.95, seed=list(range(B)))
     tokens = model.sample_actions(ids, pv, "robot", sp)[1]
-    legs = {"sample_actions": lambda: model.sample_actions(ids, pv, "robot", sp),
+    legs = {"predict_action": lambda: model.predict_action(input_ids=ids, pixel_values=pv, unnorm_key="robot"),
+            "sample_actions": lambda: model.sample_actions(ids, pv, "robot", sp),
             "score_actions": lambda: model.score_actions(ids, pv, token_ids=tokens, sampling=sp),
             "score_actions_return_bins": lambda: model.score_actions(ids, pv, token_ids=tokens, sampling=sp, return_bins=True)}
     runs = {k: [] for k in legs}
