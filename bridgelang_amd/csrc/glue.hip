@@ -109,31 +109,26 @@ __global__ void gather_rows_kernel(const uint16_t* src, const int64_t* row_index
   }
 }
 
-// ---- argmax over fp32 rows; ties → lowest index (torch.argmax) ----
+// ---- argmax over fp32 rows: the first NaN of the row, else its first maximum (argmax_key in bl_common.h; what
+// torch.argmax returns). The result is always an index in [0, n): the engine feeds it to the next step's embedding gather. ----
 __global__ __launch_bounds__(256) void argmax_kernel(const float* logits, long ld, int n, int64_t* out) {
-  __shared__ float sv[4];
+  __shared__ int sv[4];
   __shared__ int si[4];
   const float* row = logits + (long)blockIdx.x * ld;
-  float best = -INFINITY;
+  int best = (int)0x80000000;
   int bi = 0x7fffffff;
   for (int i = threadIdx.x * 4; i < n; i += 256 * 4) {
     const f32x4_t q = *(const f32x4_t*)(row + i);     // n % 4 == 0 checked on the host
 #pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (q[e] > best || (q[e] == best && i + e < bi)) { best = q[e]; bi = i + e; }
+    for (int e = 0; e < 4; ++e) argmax_take_next(argmax_key(q[e]), i + e, best, bi);   // i + e only grows in a thread
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
+  for (int o = 32; o > 0; o >>= 1) argmax_take(__shfl_xor(best, o, 64), __shfl_xor(bi, o, 64), best, bi);
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { sv[wave] = best; si[wave] = bi; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+    for (int w = 1; w < 4; ++w) argmax_take(sv[w], si[w], best, bi);
     out[blockIdx.x] = (int64_t)bi;
   }
 }
@@ -169,6 +164,8 @@ __global__ void write_prefix_kernel(const uint16_t* prefix, int n_prefix, int di
 
 // ---- shifted cross-entropy over fp32 logits (HF CausalLM loss, ignore_index = -100) ----
 // One workgroup per row: loss[row] = logsumexp(logits[row]) - logits[row][target]; rows whose target is ignored get 0.
+// A target outside [0, n) that is not ignore_index indexes nothing: that row's loss is NaN and the row counts as valid, so
+// the mean is NaN too (the rule of the policy kernels, policy.hip: NaN in the row's statistics, never a stray read).
 __global__ __launch_bounds__(256) void cross_entropy_rows_kernel(const float* logits, long ld, int n,
                                                                  const int64_t* targets, long ignore_index,
                                                                  float* row_loss) {
@@ -199,7 +196,10 @@ __global__ __launch_bounds__(256) void cross_entropy_rows_kernel(const float* lo
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[wave] = s;
   __syncthreads();
-  if (threadIdx.x == 0) row_loss[row] = logf(red[0] + red[1] + red[2] + red[3]) + mx - lr[tgt];
+  if (threadIdx.x == 0) {
+    const float lt = (tgt >= 0 && tgt < n) ? lr[tgt] : NAN;
+    row_loss[row] = logf(red[0] + red[1] + red[2] + red[3]) + mx - lt;
+  }
 }
 
 // mean of row_loss over rows whose target is not ignored (single workgroup, fixed summation order → deterministic)
@@ -667,7 +667,7 @@ extern "C" int bl_gather_rows_bf16(const bl_bf16* src, const int64_t* row_index,
 
 extern "C" int bl_argmax_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, int64_t* out, void* stream) {
   if (!logits || !out) return BL_E_ARG;
-  if (rows <= 0 || n <= 0 || (n % 4) || (ld % 4)) return BL_E_SHAPE;
+  if (rows <= 0 || n <= 0 || (n % 4) || (ld % 4) || ld < n) return BL_E_SHAPE;   // ld < n: rows would overlap
   if (!bl_aligned16(logits)) return BL_E_ALIGN;
   hipLaunchKernelGGL(argmax_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, n, out);
   BL_CHECK_LAUNCH();
@@ -758,7 +758,7 @@ extern "C" int bl_write_prefix_tokens_bf16(const bl_bf16* prefix, int32_t n_pref
 extern "C" int bl_cross_entropy_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
                                     int64_t ignore_index, float* row_loss, float* mean_and_count, void* stream) {
   if (!logits || !targets || !row_loss || !mean_and_count) return BL_E_ARG;
-  if (rows <= 0 || n <= 0 || (n % 4) || (ld % 4)) return BL_E_SHAPE;
+  if (rows <= 0 || n <= 0 || (n % 4) || (ld % 4) || ld < n) return BL_E_SHAPE;   // ld < n: rows would overlap
   if (!bl_aligned16(logits)) return BL_E_ALIGN;
   hipLaunchKernelGGL(cross_entropy_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, n,
                      targets, (long)ignore_index, row_loss);

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, l
   uint32_t* img = (uint32_t*)(smem + kFixedBytes);                // n: keys, then weights
   __shared__ u64 red[kWaves];
   __shared__ u64 sel[2];
-  __shared__ float s_best[kWaves];
+  __shared__ int s_best[kWaves];
   __shared__ int s_arg[kWaves];
 
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -203,31 +203,27 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const float* logits, l
   const float P = top_p[row];
   const int K = top_k[row];
 
-  // 1. the row → keys in LDS; maximum and its lowest index, compared as bl_argmax_f32 compares
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
+  // 1. the row → keys in LDS; maximum and its lowest index in bl_argmax_f32's order (argmax_key: the first NaN, else the
+  // first maximum), so a greedy row's id is in [0, n) whatever the row holds; rows with T > 0 need NaN-free logits
+  int bk = (int)0x80000000, bi = 0x7fffffff;
   for (int i = tid * 4; i < n; i += kThreads * 4) {               // n % 4 == 0 (host check): never past column n
     const f32x4_t q = *(const f32x4_t*)(src + i);
     u32x4_t k;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      if (q[e] > best || (q[e] == best && i + e < bi)) { best = q[e]; bi = i + e; }
+      argmax_take_next(argmax_key(q[e]), i + e, bk, bi);          // i + e only grows in a thread
       k[e] = key_of(q[e]);
     }
     *(u32x4_t*)(img + i) = k;
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if (lane == 0) { s_best[wave] = best; s_arg[wave] = bi; }
+  for (int o = 32; o > 0; o >>= 1) argmax_take(__shfl_xor(bk, o, 64), __shfl_xor(bi, o, 64), bk, bi);
+  if (lane == 0) { s_best[wave] = bk; s_arg[wave] = bi; }
   __syncthreads();
-  best = s_best[0]; bi = s_arg[0];
+  bk = s_best[0]; bi = s_arg[0];
 #pragma unroll
-  for (int w = 1; w < kWaves; ++w)
-    if (s_best[w] > best || (s_best[w] == best && s_arg[w] < bi)) { best = s_best[w]; bi = s_arg[w]; }
+  for (int w = 1; w < kWaves; ++w) argmax_take(s_best[w], s_arg[w], bk, bi);
+  const float best = argmax_value(bk);                            // the row maximum (either zero as +0: l − best is the same)
 
   int64_t tok = -1;                                               // SCORE: the token to score, relative to base; outside [0, n) it owns no lane
   int32_t* rw = nullptr;                                          // SCORE: this row of range_wt

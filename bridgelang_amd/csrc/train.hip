@@ -26,6 +26,8 @@ __device__ __forceinline__ u32x4_t pack8(const float* v) {
 }
 
 // ---- cross-entropy backward: dlogits = (softmax(logits) - onehot(target)) / n_valid, 0 on ignored rows ----
+// A target outside [0, n) that is not ignore_index matches no column: the row is read like any other and nothing is indexed by
+// the target (the forward, cross_entropy_rows_kernel in glue.hip, gives that row a NaN loss and counts it as valid).
 __global__ __launch_bounds__(256) void ce_backward_kernel(const float* logits, long ld, int n, const int64_t* targets,
                                                           long ignore_index, const float* mean_and_count,
                                                           uint16_t* dlogits, long ldd) {

@@ -26,7 +26,9 @@ library transcendental and no floating-point sum whose order matters:
 Per row the outputs are the token id and the integer pair (w_token, total_kept); the log-probability of the drawn token
 under the warped distribution is log(w_token / total_kept), taken on the host in fp64 (`logprob`) — the device never
 computes a logarithm. The logits here are bf16-rounded fp32, so exact ties are common, also at the top-k and top-p
-boundaries: every rule above is defined on ties. Logits must be free of NaN.
+boundaries: every rule above is defined on ties. A greedy row (T == 0) is defined on NaN as well: np.argmax's answer,
+the first NaN of the row (else the first maximum), so its id is always a token of the row; rows with T > 0 still require
+logits free of NaN.
 
 Scoring is the opposite direction: `score_row` / `score_rows` (device twin: `bl_score_f32`) take a GIVEN token and return
 its pair (kept weight, total_kept) under the same warped distribution — no seed and no step, the score does not depend on

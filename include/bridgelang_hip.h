@@ -283,7 +283,8 @@ int bl_embed_splice_bf16(const int64_t* ids, int32_t B, int32_t L, const bl_bf16
  * width and row_stride multiples of 8. An index outside [0, rows_per_batch) copies nothing for that row. */
 int bl_gather_rows_bf16(const bl_bf16* src, const int64_t* row_index, int64_t rows_per_batch, int64_t row_stride,
                         int32_t width, bl_bf16* dst, int32_t B, void* stream);
-/* Row-wise argmax of fp32 logits [rows, n] (first maximal index, as torch.argmax); out int64 [rows]. */
+/* Row-wise argmax of fp32 logits [rows, n] (row stride ld >= n) as torch.argmax: the first NaN of the row, else the first
+ * maximal index, so always an index in [0, n); out int64 [rows]. */
 int bl_argmax_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, int64_t* out, void* stream);
 /* Seeded sampling of one token per row of fp32 logits [rows, n] (leading dimension ld; columns >= n are never read):
  * temperature → top-k → top-p → one Philox4x32-10 draw, bit-identical to bridgelang_amd/sampling.py::sample_rows. The
@@ -324,7 +325,9 @@ int bl_score_range_f32(const float* logits, int64_t ld, int32_t rows, int32_t n,
 
 /* Shifted causal-LM cross-entropy (HF LlamaForCausalLM loss; labels prepared by the caller as `targets[row]` =
  * label of the NEXT position, -100 = ignore; base_strategy.py:287-297 consumes `output.loss`). row_loss[rows] receives
- * the per-row loss (0 where ignored); mean_and_count[0] = mean over valid rows, [1] = number of valid rows. */
+ * the per-row loss (0 where ignored); mean_and_count[0] = mean over valid rows, [1] = number of valid rows. A target
+ * outside [0, n) other than ignore_index indexes nothing: its row_loss and the mean are NaN, and it counts as valid.
+ * Row stride ld >= n. */
 int bl_cross_entropy_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
                          int64_t ignore_index, float* row_loss, float* mean_and_count, void* stream);
 

@@ -346,7 +346,8 @@ def rope_backward(dqkv, cos, sin, B: int, S: int, H: int, hd: int, pos0: int):
 
 def cross_entropy(logits, targets, ignore_index: int = -100):
     """dlogits = (softmax − onehot)/n_valid (0 on ignored rows) with mag = (p + onehot)/n_valid, and the forward's mean
-    loss over the valid rows with its companion, and the count."""
+    loss over the valid rows with its companion, and the count; `loss` / `lmag` are the per-row terms that mean and
+    m_mean average (0 on ignored rows)."""
     lg, tg = f64(logits), targets.detach().cpu().long()
     rows, n = lg.shape
     valid = tg != ignore_index
@@ -368,7 +369,7 @@ def cross_entropy(logits, targets, ignore_index: int = -100):
         lt = l.gather(1, tc.view(-1, 1))
         loss[s] = (v.double() * (torch.log(sm) + mx - lt).squeeze(-1))
         lmag[s] = (v.double() * (1.0 + torch.log(sm).abs() + mx.abs() + lt.abs()).squeeze(-1))
-    return dict(dl=dl, mag=mag, mean=loss.sum() / max(nv, 1), m_mean=lmag.sum() / max(nv, 1), count=nv)
+    return dict(dl=dl, mag=mag, mean=loss.sum() / max(nv, 1), m_mean=lmag.sum() / max(nv, 1), count=nv, loss=loss, lmag=lmag)
 
 
 def gemm_tn(P, Q, alpha: float):
