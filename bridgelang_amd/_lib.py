@@ -132,6 +132,9 @@ SIGNATURES = {
                                         _i32, _i32, _i32, _i32, _vp, _f32, _f32, _f32, _vp, _vp, _vp]),
     "bl_preference_loss_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _f32, _f32,
                                          _f32, _f32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "bl_distill_loss_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _f32, _f32, _f32, _vp, _vp, _i32, _i32, _vp]),
+    "bl_distill_loss_backward_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f32, _f32, _f32, _vp, _i64,
+                                               _i32, _i32, _vp]),
     "bl_value_head_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp,
                                     _vp, _vp]),
     "bl_value_head_backward_f32": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _vp]),

@@ -154,6 +154,42 @@ def preference_loss(logits, targets, pair, ref_logprob, row_stats, stats, pair_s
                nbytes=8.0 * rows * count + 64.0 * rows)
 
 
+def _distill_args(logits, targets, teacher, row_stats, stats, cfg, ignore_index: int, what: str):
+    """The arguments both distillation entry points share up to the teacher's leading dimension, checked → (rows, n, count,
+    head tuple, tail tuple)."""
+    from .training.distill_loss import KINDS
+    rows, n = _policy_rows(logits, targets, row_stats, stats, what)
+    rng = getattr(cfg, "token_range", None)
+    first, count = (0, n) if rng is None else (int(rng[0]), int(rng[1]))
+    if _f32(teacher, "teacher").dim() != 2 or tuple(teacher.shape) != (rows, count) or teacher.stride(1) != 1:
+        raise ValueError(f"{what}: teacher fp32 [{rows}, {count}] (one row per logits row, over the range) with unit column stride")
+    head = (_f32(logits, "logits").data_ptr(), _rows(logits, "logits"), rows, n, targets.data_ptr(), ignore_index,
+            teacher.data_ptr(), _rows(teacher, "teacher"))
+    tail = (KINDS.index(cfg.kind), float(cfg.beta), float(cfg.sft_coef), float(cfg.temperature))
+    return rows, n, first, count, head, tail
+
+
+def distill_loss(logits, targets, teacher, row_stats, stats, cfg, ignore_index: int = -100, run: bool = True) -> Op:
+    """Distribution-matching loss over fp32 logits [rows, n] (training/distill_loss.py is the definition; `cfg` a
+    DistillLossConfig): teacher fp32 [rows, count] in row layout over cfg.token_range (count = n without one), read on valid
+    rows only; row_stats fp32 [rows, 8] and stats fp32 [8] receive distill_loss.DISTILL_ROW_STAT_NAMES / DISTILL_STAT_NAMES."""
+    rows, n, first, count, head, tail = _distill_args(logits, targets, teacher, row_stats, stats, cfg, ignore_index, "distill_loss")
+    return _op("bl_distill_loss_f32", head + tail + (row_stats.data_ptr(), stats.data_ptr(), first, count),
+               (logits, targets, teacher, row_stats, stats), run, nbytes=16.0 * rows * count + 64.0 * rows)
+
+
+def distill_loss_backward(logits, targets, teacher, row_stats, stats, dlogits, cfg, ignore_index: int = -100, run: bool = True) -> Op:
+    """bf16 dlogits of `distill_loss` from the logits, the teacher and the row statistics it saved (stats[1] = n_valid); zeros
+    outside cfg.token_range and on ignored rows."""
+    rows, n, first, count, head, tail = _distill_args(logits, targets, teacher, row_stats, stats, cfg, ignore_index,
+                                                      "distill_loss_backward")
+    if tuple(_bf16(dlogits, "dlogits").shape) != (rows, n):
+        raise ValueError(f"distill_loss_backward: dlogits bf16 [{rows}, {n}]")
+    return _op("bl_distill_loss_backward_f32",
+               head + (row_stats.data_ptr(), stats.data_ptr()) + tail + (dlogits.data_ptr(), _rows(dlogits, "dlogits"), first, count),
+               (logits, targets, teacher, row_stats, stats, dlogits), run, nbytes=(2.0 * n + 8.0 * count) * rows)
+
+
 def value_index_slots(rows: int, level: str, group_rows: Optional[int]) -> int:
     """Capacity of the value-row list: one slot per row at token level, one per sequence of `group_rows` rows at action level."""
     if level == "token":

@@ -12,7 +12,11 @@ correction (`PolicyLossConfig.rollout_is_cap`): the sampler's log-probabilities 
 for `set_policy_batch`, returns for `set_value_batch`.
 
 `pairs_from_rewards` and `preference_batch` are the same glue for `TrainStep(loss="preference")`: the best rollout of a
-prompt against the worst, laid out as consecutive chosen / rejected sequences by `policy_batch`."""
+prompt against the worst, laid out as consecutive chosen / rejected sequences by `policy_batch`.
+
+`distill_batch` and `gaussian_bin_targets` are the glue for `TrainStep(loss="distill")`: a teacher's exact bin distribution
+from `score_actions(return_bins=True)`, or a Gaussian round the demonstrated bin, as the [B, l, bins] teacher of
+`set_distill_batch`, on `policy_batch`'s layout."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
@@ -238,3 +242,56 @@ def preference_batch(prompt_ids, attention_mask, chosen_ids, rejected_ids, ref_c
                          torch.zeros(2 * B), pad_to=pad_to, token_range=token_range)
     return {"input_ids": batch["input_ids"], "attention_mask": batch["attention_mask"], "labels": batch["labels"],
             "pair": two(gid, -gid).to(torch.int32), "ref_logprobs": batch["old_logprobs"] if have_ref else None}
+
+
+def distill_batch(prompt_ids, attention_mask, token_ids, bin_wt, wt, smoothing: float = 0.0, pad_to: Optional[int] = None,
+                  token_range: Optional[Tuple[int, int]] = None) -> Dict[str, torch.Tensor]:
+    """The training batch of loss="distill" from one action per prompt and a teacher's bin distribution of each of its
+    tokens: prompt_ids [B, lp] with attention_mask as for `policy_batch`, token_ids int64 [B, n], and bin_wt [B, n, bins] /
+    wt [B, n, 2] as `score_actions(return_bins=True, action_tokens_only=True)` reports them for those tokens (integer
+    weights over a kept total; the teacher may be the base policy, `use_adapters=False`, a checkpoint or an average). The
+    teacher is q = bin_wt / wt[..., 1] in fp64, with `smoothing` = α mixed with the uniform distribution, (1 − α)·q +
+    α / bins — what makes kind="reverse_kl" legal when a bin's integer weight is 0 — and rounded to fp32 once. The sequences
+    are laid out by `policy_batch` (labels on exactly the n action tokens). → dict of CPU tensors `input_ids`,
+    `attention_mask`, `labels` (for `set_batch`) and `teacher_probs` fp32 [B, l, bins] aligned with the labels, zero off them
+    (for `set_distill_batch`). `token_range` is the learner's `DistillLossConfig.token_range`: its count must be `bins`."""
+    tok = _cpu(token_ids, torch.int64)
+    bw, w = _cpu(bin_wt, torch.float64), _cpu(wt, torch.float64)
+    if tok.dim() != 2 or bw.dim() != 3 or tuple(bw.shape[:2]) != tuple(tok.shape) or tuple(w.shape) != tuple(tok.shape) + (2,):
+        raise ValueError(f"distill_batch: token_ids [B, n], bin_wt [B, n, bins] and wt [B, n, 2], got {tuple(tok.shape)}, "
+                         f"{tuple(bw.shape)} and {tuple(w.shape)}")
+    B, n, bins = bw.shape
+    if token_range is not None and int(token_range[1]) != bins:
+        raise ValueError(f"distill_batch: token_range {tuple(token_range)} has not the {bins} bins of bin_wt")
+    if not (np.isfinite(smoothing) and 0.0 <= smoothing <= 1.0):
+        raise ValueError(f"distill_batch: 0 <= smoothing <= 1, got {smoothing!r}")
+    total = w[..., 1]
+    if not bool(torch.isfinite(bw).all()) or bool((bw < 0).any()) or not bool(torch.isfinite(total).all()) or bool((total <= 0).any()):
+        raise ValueError("distill_batch: bin_wt must be finite and >= 0 and the kept total wt[..., 1] finite and > 0")
+    q = (1.0 - smoothing) * (bw / total[..., None]) + smoothing / bins
+    batch = policy_batch(prompt_ids, attention_mask, tok, torch.zeros(B, n), torch.zeros(B), pad_to=pad_to, token_range=token_range)
+    labels = batch["labels"]
+    teacher = torch.zeros(B, labels.shape[1], bins, dtype=torch.float32)
+    teacher[labels != IGNORE_INDEX] = q.reshape(B * n, bins).to(torch.float32)      # row-major: sequence b's n tokens in order
+    return {"input_ids": batch["input_ids"], "attention_mask": batch["attention_mask"], "labels": labels, "teacher_probs": teacher}
+
+
+def gaussian_bin_targets(token_ids, sigma: float, token_range: Tuple[int, int]) -> torch.Tensor:
+    """Soft ordinal labels for loss="distill": token_ids int64 [B, n] inside token_range = (first, count) → fp32 [B, n,
+    count], a Gaussian over the bin index round each token's bin, exp(−(j − bin)² / (2σ²)), truncated at the range's ends
+    and normalised in fp64. Neighbouring bins are neighbouring actions, which a one-hot label cannot say; sigma → 0 gives
+    the one-hot (sigma = 0 is it exactly)."""
+    tok = _cpu(token_ids, torch.int64)
+    first, count = int(token_range[0]), int(token_range[1])
+    if tok.dim() != 2:
+        raise ValueError(f"gaussian_bin_targets: token_ids [B, n], got {tuple(tok.shape)}")
+    if not (np.isfinite(sigma) and sigma >= 0):
+        raise ValueError(f"gaussian_bin_targets: sigma must be >= 0, got {sigma!r}")
+    if bool(((tok < first) | (tok >= first + count)).any()):
+        raise ValueError(f"gaussian_bin_targets: token(s) outside token_range [{first}, {first + count})")
+    d = torch.arange(count, dtype=torch.float64) - (tok - first)[..., None].to(torch.float64)
+    if sigma == 0:
+        g = (d == 0).to(torch.float64)
+    else:
+        g = torch.exp(-0.5 * (d / sigma) ** 2)        # the token's own bin is exp(0) = 1: the sum never vanishes
+    return (g / g.sum(dim=-1, keepdim=True)).to(torch.float32)

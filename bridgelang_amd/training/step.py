@@ -30,6 +30,7 @@ from .. import ops, train_ops as T
 from ..engine import rope_tables
 from ..ops import EPI_BIAS, EPI_F32_BF16R, EPI_NONE, EPI_RES, Op
 from ..weights import VLAWeights
+from .distill_loss import DISTILL_STAT_NAMES, DistillLossConfig, check_teacher
 from .linears import Linears, Scratch, ScratchSet
 from .param_store import STAGES, ParamStore, no_decay, param_sharded_key, pool_of, trainable_names      # noqa: F401  (re-exported)
 from .policy_loss import GROUP_STAT_NAMES, IS_STAT_NAMES, STAT_NAMES, PolicyLossConfig
@@ -51,7 +52,8 @@ class TrainStep:
                  force_comm: bool = False, recompute: bool = False, shard_params: bool = False, fp8: bool = False,
                  fp8_wgrad: bool = False, loss: str = "ce", policy: Optional[PolicyLossConfig] = None,
                  refresh_adapted: bool = False, preference: Optional[PreferenceLossConfig] = None,
-                 value: Optional[ValueLossConfig] = None, value_head: Optional[ValueHead] = None):
+                 value: Optional[ValueLossConfig] = None, value_head: Optional[ValueHead] = None,
+                 distill: Optional[DistillLossConfig] = None):
         """`lora`: a training.lora.LoraAdapters → stage "lora": the base model is frozen and only the adapters train.
         `refresh_adapted` (with `lora`): the re-pack plan that follows every optimizer step ends with the ONE batched merge
         launch of `lora.refresh_ops()`, so `lora.adapted_weights()` — the weights an inference engine of the model the adapters
@@ -95,9 +97,19 @@ class TrainStep:
         policy loss op in the forward plan and bl_value_head_backward_f32 sits between lm_head's input-gradient GEMM and the
         final norm's backward, adding the value loss's gradient into `dh`; `forward()` then returns policy loss + coef ·
         value loss. Without `value` both plans are what they were. Critic warm-up needs no mode of its own: advantages of 0
-        with entropy_coef = kl_coef = 0 make dlogits exactly 0, so every trunk gradient is the value path's."""
-        if loss not in ("ce", "policy", "preference"):
-            raise ValueError(f"loss must be 'ce', 'policy' or 'preference', got {loss!r}")
+        with entropy_coef = kl_coef = 0 make dlogits exactly 0, so every trunk gradient is the value path's.
+        `loss="distill"`: the distribution-matching loss of training/distill_loss.py (forward KL, reverse KL or JSD against
+        a teacher's whole row over the token range, plus sft_coef · NLL), configured by `distill` (a DistillLossConfig; its
+        defaults if None) and fed by `set_distill_batch` after `set_batch`. The forward plan ends with bl_distill_loss_f32 in
+        place of the cross-entropy op and the backward plan starts with bl_distill_loss_backward_f32; the teacher lives in
+        a static fp32 buffer [B·S, count] in row layout, so a captured graph serves every batch. `token_range` as for the
+        policy loss; `distill_stats()` reports the step statistics. `policy`, `preference` and `value` do not go with it."""
+        if loss not in ("ce", "policy", "preference", "distill"):
+            raise ValueError(f"loss must be 'ce', 'policy', 'preference' or 'distill', got {loss!r}")
+        if distill is not None and loss != "distill":
+            raise ValueError("`distill` configures loss='distill'")
+        if loss == "distill" and (policy is not None or preference is not None or value is not None):
+            raise ValueError("loss='distill' takes `distill` alone: `policy`, `preference` and `value` configure other losses")
         if policy is not None and loss != "policy":
             raise ValueError("`policy` configures loss='policy'")
         if preference is not None and loss != "preference":
@@ -113,7 +125,8 @@ class TrainStep:
         self.loss_kind = loss
         self.policy = (policy or PolicyLossConfig()) if loss == "policy" else None
         self.preference = (preference or PreferenceLossConfig()) if loss == "preference" else None
-        self._row_cfg = self.policy or self.preference           # whichever loss keeps row_stats: its T and token range
+        self.distill = (distill or DistillLossConfig()) if loss == "distill" else None
+        self._row_cfg = self.policy or self.preference or self.distill      # whichever loss keeps row_stats: its T and token range
         if self._row_cfg is not None and self._row_cfg.token_range is not None:
             first, count = self._row_cfg.token_range
             if first % 8 or count % 8 or first + count > weights.dims.vocab:
@@ -226,6 +239,12 @@ class TrainStep:
             self.pair, self.n_pairs = z(B, dtype=torch.int32), torch.ones(1, dtype=torch.int32, device=dev)
             self.pair_stats_buf, self.seq_stats_buf = z(max(B // 2, 1), 4, dtype=torch.float32), z(B, 4, dtype=torch.float32)
             self._batch_len, self._pairs_set = prompt_len, False
+        elif self.distill is not None:          # the teacher in row layout over the range; mean_cnt = (loss, n_valid)
+            count = self.distill.token_range[1] if self.distill.token_range is not None else V
+            self.teacher = z(Tn, count, dtype=torch.float32)
+            self.row_stats, self.stats = z(Tn, 8, dtype=torch.float32), z(8, dtype=torch.float32)
+            self.row_loss, self.mean_cnt = self.row_stats[:, 3], self.stats[:2]
+            self._batch_len, self._teacher_set = prompt_len, False
         elif self.policy is None:
             self.row_loss, self.mean_cnt = z(Tn, dtype=torch.float32), z(2, dtype=torch.float32)
         else:                                   # per-row inputs and statistics of the policy loss; mean_cnt = (loss, n_valid)
@@ -356,6 +375,9 @@ class TrainStep:
                                           None if self.preference.reference_free else self.ref_logprob, self.row_stats,
                                           self.stats, self.pair_stats_buf, self.seq_stats_buf, self.preference, group_rows=self.S,
                                           n_pairs=self.n_pairs, ignore_index=IGNORE_INDEX, run=False))
+        elif self.distill is not None:
+            plan.append(T.distill_loss(self.logits, self.targets, self.teacher, self.row_stats, self.stats, self.distill,
+                                       IGNORE_INDEX, run=False))
         elif self.policy is None:
             plan.append(ops.cross_entropy(self.logits, self.targets, self.row_loss, self.mean_cnt, IGNORE_INDEX, run=False))
         else:
@@ -405,6 +427,9 @@ class TrainStep:
         lm = "language_model.model"
         plan: List[Op] = [T.cross_entropy_backward(self.logits, self.targets, self.mean_cnt, self.dlogits, IGNORE_INDEX, run=False)
                           if self._row_cfg is None else
+                          T.distill_loss_backward(self.logits, self.targets, self.teacher, self.row_stats, self.stats, self.dlogits,
+                                                  self.distill, IGNORE_INDEX, run=False)
+                          if self.distill is not None else
                           T.policy_loss_backward(self.logits, self.targets, self.row_stats, self.stats, self.dlogits,
                                                  self.policy or self.preference.backward_config(), IGNORE_INDEX, run=False)]
         head = self.pools is not None and "projector" in self.pools.units
@@ -717,6 +742,8 @@ class TrainStep:
         if self.preference is not None:         # the pair assignment belongs to a batch: the next one brings its own
             self.pair.zero_()
             self._pairs_set = False
+        if self.distill is not None:            # the teacher belongs to a batch too
+            self._teacher_set = False
 
     def set_policy_batch(self, advantages: torch.Tensor, old_logprobs: Optional[torch.Tensor], ref_logprobs: Optional[torch.Tensor] = None,
                          behaviour_logprobs: Optional[torch.Tensor] = None) -> None:
@@ -816,6 +843,26 @@ class TrainStep:
         self.n_pairs.fill_(n_pairs)
         self._pairs_set = True
 
+    def set_distill_batch(self, teacher_probs) -> None:
+        """The teacher of loss="distill" for the batch of the preceding `set_batch`: `teacher_probs` [B, l, count], one
+        distribution over the token range (the vocabulary without one) per token position, aligned with the `labels` as
+        `set_policy_batch`'s inputs are (`rl.distill_batch`, `rl.gaussian_bin_targets`). It takes the padding,
+        patch-column insertion and one-position shift the labels took; rows on unlabelled positions are not read by a
+        kernel and may hold anything. On labelled positions the teacher must be finite, >= 0, sum to 1 within 1e-3, and
+        be > 0 everywhere under kind="reverse_kl": ValueError otherwise."""
+        if self.distill is None:
+            raise RuntimeError("set_distill_batch needs TrainStep(loss='distill')")
+        valid = (self.targets != IGNORE_INDEX).view(self.B, self.S)
+        tokens_to_rows("teacher_probs", teacher_probs, self.teacher, self._batch_len, self.dims.n_patches, valid,
+                       "on labelled positions", check=lambda rows: check_teacher(rows[valid].double().cpu().numpy(),
+                                                                                 np.ones(int(valid.sum()), dtype=bool),
+                                                                                 self.distill.kind, "set_distill_batch"))
+        self._teacher_set = True
+
+    def distill_stats(self) -> Dict[str, torch.Tensor]:
+        """The 8 step statistics of the last forward (distill_loss.DISTILL_STAT_NAMES) as device scalars."""
+        return self._stats("distill_stats", self.distill is not None, "TrainStep(loss='distill')", DISTILL_STAT_NAMES, "stats")
+
     def _stats(self, reader: str, have: bool, needs: str, names, buf: str) -> Dict[str, torch.Tensor]:
         """{name: entry i along the last dimension of buffer `buf`} — device scalars for a vector of step statistics, device
         vectors for a per-sequence / per-pair table; RuntimeError when the step was built without what the reader `needs`."""
@@ -870,7 +917,7 @@ class TrainStep:
         statistics shifted back. This is how a learner gets on-policy `old_logprobs`, or a frozen model's `ref_logprobs`,
         from the training forward itself."""
         if self._row_cfg is None:
-            raise RuntimeError("token_logprobs needs TrainStep(loss='policy') or TrainStep(loss='preference')")
+            raise RuntimeError("token_logprobs needs TrainStep(loss='policy'), TrainStep(loss='preference') or TrainStep(loss='distill')")
         return shift_from_rows(self.row_stats[:, 0].view(self.B, self.S), self.dims.n_patches)[:, :self._batch_len]
 
     def _run_forked(self, main_ops: List[Op], side_ops: List[Op]) -> None:
@@ -911,6 +958,8 @@ class TrainStep:
             self._replay("vfwd", self.vision_forward_ops, graph)
         else:
             self._vis.run_vision()
+        if self.distill is not None and not self._teacher_set:
+            raise RuntimeError("loss='distill': set_distill_batch comes after set_batch and before the forward pass")
         if getattr(self, "_self_proximal", False):
             self._replay("fwd_self", self.forward_ops_self, graph)
         else:
@@ -923,6 +972,8 @@ class TrainStep:
         st, lay = self.store, self.store.layout
         if self.preference is not None and not self._pairs_set:
             raise RuntimeError("loss='preference': set_preference_batch comes after set_batch and before the backward pass")
+        if self.distill is not None and not self._teacher_set:
+            raise RuntimeError("loss='distill': set_distill_batch comes after set_batch and before the backward pass")
         if not self.comm.active:
             if self._vis2 and getattr(self, "_bwd_tower_at", None) and len(self._bwd_tower_at) == 2:
                 a, b = self._bwd_tower_at
@@ -1025,8 +1076,8 @@ def shift_to_rows(values: torch.Tensor, n_patches: int, fill) -> torch.Tensor:
     the patch columns are inserted behind the first token (filled with `fill`), and everything moves one position to the
     left, because position t predicts token t + 1 (the last row gets `fill`). The labels and the policy loss's per-token
     inputs all take this one path."""
-    B, L = values.shape
-    full = torch.full((B, L + n_patches), fill, dtype=values.dtype, device=values.device)
+    B, L = values.shape[:2]                   # a trailing dimension (a vector per token) rides along
+    full = torch.full((B, L + n_patches) + tuple(values.shape[2:]), fill, dtype=values.dtype, device=values.device)
     full[:, :1] = values[:, :1]
     full[:, 1 + n_patches:] = values[:, 1:]
     out = torch.full_like(full, fill)
@@ -1035,22 +1086,28 @@ def shift_to_rows(values: torch.Tensor, n_patches: int, fill) -> torch.Tensor:
 
 
 def tokens_to_rows(name: str, src, dst: torch.Tensor, l: int, n_patches: int, select: torch.Tensor, where: str,
-                   refuse: Optional[torch.Tensor] = None) -> None:
+                   refuse: Optional[torch.Tensor] = None, check=None) -> None:
     """Per-token values `src` [B, l], aligned with the labels of a batch of l ≤ L tokens → `dst` [B·S] fp32, aligned with the
     logits rows (S = L + n_patches): padded to L with zeros, through `shift_to_rows`, zeroed outside the rows that `select`
     [B, S] marks, copied. A non-finite value on a row of `refuse` (default: `select`) is a ValueError that names the input and
-    says `where`; the rows outside `select` are never read by a kernel, so what they hold does not matter."""
+    says `where`; the rows outside `select` are never read by a kernel, so what they hold does not matter.
+    A `dst` [B·S, C] takes `src` [B, l, C] — a vector per token (the distillation teacher) — along the same path; `check`
+    (optional) is called with the shifted rows [B, S, C] before anything is copied and raises what it has to."""
     B, S = select.shape
     src = torch.as_tensor(src)
-    if tuple(src.shape) != (B, l):
-        raise ValueError(f"{name}: shape {tuple(src.shape)}, expected {(B, l)} (aligned with the labels of set_batch)")
-    pad = torch.zeros(B, S - n_patches, dtype=torch.float32, device=dst.device)
+    tail = tuple(dst.shape[1:])
+    if tuple(src.shape) != (B, l) + tail:
+        raise ValueError(f"{name}: shape {tuple(src.shape)}, expected {(B, l) + tail} (aligned with the labels of set_batch)")
+    pad = torch.zeros((B, S - n_patches) + tail, dtype=torch.float32, device=dst.device)
     pad[:, :l] = src.to(dst.device, dtype=torch.float32)
     rows = shift_to_rows(pad, n_patches, 0.0)
-    bad = (select if refuse is None else refuse) & ~torch.isfinite(rows)
+    sel = lambda m: m.reshape(B, S, *([1] * len(tail)))
+    bad = sel(select if refuse is None else refuse) & ~torch.isfinite(rows)
     if bool(bad.any()):
         raise ValueError(f"{name}: {int(bad.sum())} non-finite value(s) {where}")
-    dst.copy_(torch.where(select, rows, torch.zeros_like(rows)).view(-1))
+    if check is not None:
+        check(rows)
+    dst.copy_(torch.where(sel(select), rows, torch.zeros_like(rows)).view(dst.shape))
 
 
 def shift_from_rows(rows: torch.Tensor, n_patches: int) -> torch.Tensor:

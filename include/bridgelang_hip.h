@@ -444,6 +444,42 @@ int bl_preference_loss_f32(const float* logits, int64_t ld, int32_t rows, int32_
                            float label_smoothing, float margin, float sft_coef, float temperature, float* row_stats,
                            float* stats, float* pair_stats, float* seq_stats, int32_t vocab_first, int32_t vocab_count,
                            void* stream);
+/* The distribution-matching (distillation) loss over the same rows and `targets` convention (training/distill_loss.py is
+ * the fp64 definition): the student is the softmax of logits / temperature over the token range [vocab_first, vocab_first +
+ * vocab_count) of every row, exactly as in bl_policy_loss_range_f32, and it is compared with a TEACHER row q >= 0. teacher
+ * is fp32 [rows, vocab_count] with leading dimension ldt, in ROW layout: row r is row r's teacher and column j is token
+ * vocab_first + j. With p, logp of the student, Q = sum q and
+ *   kind 0 (forward_kl): D = sum q (log q - logp),                                        c = Q
+ *   kind 1 (reverse_kl): D = sum p (logp - log q),                                        c = D
+ *   kind 2 (jsd): mi = beta q + (1 - beta) p,  D = beta sum q log(q / mi) + c,            c = (1 - beta) sum p log(p / mi)
+ * (a term whose weight q or p is 0 is 0), row_loss = D + sft_coef * (-logp[target]) and the loss is the mean over valid
+ * rows. beta is read by kind 2 only. There is no temperature^2 factor. Outputs, every element written: row_stats fp32
+ * [rows, 8] = (logp[target], H, D, row_loss, agree 0/1 = student and teacher share their first argmax, max z, log sum
+ * exp(z - max), c), zeros on ignored rows; stats fp32 [8] = (loss, n_valid, mean D, mean H, mean teacher entropy
+ * -sum q log q, agreement, mean -logp[target], mean |sum_j j (p_j - q_j)| with j counted from vocab_first) over valid rows
+ * in a fixed summation order, all exactly 0 when every row is ignored. Two launches on `stream` (rows: one workgroup per
+ * row, or one wave per row for vocab_count <= 256; statistics: one workgroup), deterministic, no float atomics. Logits are
+ * read inside the range of valid rows only and the teacher on valid rows only. A valid target outside the range gives NaN
+ * in that row's logp, a teacher zero under kind 1 inf or NaN in that row's outputs: caller errors, never a stray access.
+ * n % 8 == 0, vocab_first % 8 == 0, vocab_count % 8 == 0, the range inside [0, n), ld % 4 == 0, ld >= n, ldt % 4 == 0,
+ * ldt >= vocab_count, else BL_E_SHAPE; a NULL pointer, kind outside {0, 1, 2}, beta outside (0, 1) with kind 2,
+ * temperature <= 0 or sft_coef < 0 (NaN included) is BL_E_ARG; logits or teacher not 16-byte aligned is BL_E_ALIGN;
+ * nothing is launched on a rejection. */
+int bl_distill_loss_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                        int64_t ignore_index, const float* teacher, int64_t ldt, int32_t kind, float beta, float sft_coef,
+                        float temperature, float* row_stats, float* stats, int32_t vocab_first, int32_t vocab_count,
+                        void* stream);
+/* dlogits (bf16) = d loss / d logits of bl_distill_loss_f32 from the logits, the teacher and what the forward saved (max z,
+ * log sum and c in row_stats, n_valid in stats[1]; same kind, beta, sft_coef and temperature):
+ *   kind 0: dD/dz_i = p_i c - q_i;   kinds 1, 2: dD/dz_i = p_i (u_i - c), u_i = logp_i - log q_i or (1 - beta)(logp_i - log mi_i);
+ *   dlogits_i = (dD/dz_i + sft_coef (p_i - [i == target])) / (temperature * n_valid).
+ * Writes the whole [rows, n] dlogits: exact +0 outside the range and on ignored rows. One launch, one workgroup per row;
+ * a row's logits (inside the range) and teacher row are read once. Constraints and codes as the forward, and ldd % 8 == 0,
+ * ldd >= n (BL_E_SHAPE), dlogits 16-byte aligned (BL_E_ALIGN). */
+int bl_distill_loss_backward_f32(const float* logits, int64_t ld, int32_t rows, int32_t n, const int64_t* targets,
+                                 int64_t ignore_index, const float* teacher, int64_t ldt, const float* row_stats,
+                                 const float* stats, int32_t kind, float beta, float sft_coef, float temperature,
+                                 bl_bf16* dlogits, int64_t ldd, int32_t vocab_first, int32_t vocab_count, void* stream);
 /* The critic of the policy step (training/value_loss.py is the definition): a linear value head on the bf16 final-norm
  * rows hn [rows, dim] (leading dimension ld) and PPO's clipped value loss. The VALUE ROWS are found on the device from
  * `targets` (the convention of bl_cross_entropy_f32): level 0 (token) every valid row, level 1 (action) the first valid row
