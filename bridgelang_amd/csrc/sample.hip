@@ -24,6 +24,7 @@
 // vocab_first, ids are reported as vocab_first + i, the scored token and the report range are taken relative to the
 // base, and no column outside the range is loaded. The unranged entry points are the base-0, count-n case.
 #include "bl_common.h"
+#include "sample_spec.h"
 
 namespace {
 
@@ -33,6 +34,7 @@ constexpr int kHistSlots = kBins + kBins / 32;                    // one pad slo
 constexpr int kLdsBytes = 160 * 1024;
 constexpr int kFixedBytes = kHistSlots * 8;
 constexpr int kMaxN = (kLdsBytes - kFixedBytes - 1024) / 4;       // 1 KB left for the static reduction scratch below
+static_assert(kMaxN == kSpecMaxN, "sample_spec.h states this kernel's row limit");
 
 typedef unsigned long long u64;
 
@@ -48,30 +50,7 @@ __device__ __forceinline__ float logit_of(uint32_t k) {
   return __builtin_bit_cast(float, k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
 }
 
-// e^x for x <= 0: sampling.py::exp_spec operation for operation (contraction off: every multiply and add rounds alone)
-__device__ __forceinline__ float exp_spec(float x) {
-#pragma clang fp contract(off)
-  x = fmaxf(x, -87.0f);
-  const float n = rintf(x * 1.44269504f);
-  float r = x - n * 0.693359375f;
-  r = r - n * -2.12194440e-4f;
-  float p = (float)(1.0 / 720);
-  p = p * r; p = p + (float)(1.0 / 120);
-  p = p * r; p = p + (float)(1.0 / 24);
-  p = p * r; p = p + (float)(1.0 / 6);
-  p = p * r; p = p + 0.5f;
-  p = p * r; p = p + 1.0f;
-  p = p * r; p = p + 1.0f;
-  const float scale = __builtin_bit_cast(float, (uint32_t)((int)n + 127) << 23);
-  return p * scale;
-}
-__device__ __forceinline__ uint32_t weight_of(float l, float mx, float T) {
-#pragma clang fp contract(off)
-  const float d = l - mx;
-  const float z = d / T;
-  const float e = exp_spec(z);
-  return (uint32_t)rintf(e * 1073741824.0f);
-}
+// exp_spec and weight_of (sampling.py's exponential and integer weight) live in sample_spec.h: beam.hip shares them
 
 // Philox4x32-10, counter (t, 0, 0, 0), key = the seed's two words → x0 << 32 | x1
 __device__ __forceinline__ u64 philox_u64(u64 seed, uint32_t t) {

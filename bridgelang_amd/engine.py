@@ -17,6 +17,7 @@ import torch
 
 from . import ops, train_ops
 from .attention_taps import MAX_SEGMENTS, ActionAttention, AttnTaps, pad_bounds, prompt_segments
+from .beam import MAX_BEAMS, start_scores
 from .llm_plan import decode_fused, decode_layer, head, head_fused, prefill_layer
 from .ops import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_F32_BF16R, EPI_NONE, EPI_RES, EPI_SWIGLU, Fp8Weight, Op
 from .weights import TowerW, VLAWeights
@@ -52,6 +53,14 @@ class EngineResult(NamedTuple):
     attention: Optional[ActionAttention] = None         # attn_taps on a generation plan
 
 
+class BeamTrace(NamedTuple):
+    """A beams= engine's run step by step (`OpenVLAEngine.beam_trace`): slot k of prompt e is column e·W + k."""
+    tokens: torch.Tensor                                # int64 [n_new, B]: the survivors' tokens
+    parents: torch.Tensor                               # int32 [n_new, B]: the slot of the same prompt each descends from
+    wt: torch.Tensor                                    # int64 [n_new, B, 2]: the token's weight pair on its parent's row
+    scores: torch.Tensor                                # fp32 [n_new, B]: the joint log-probability so far
+
+
 def present(*parts):
     """The one formatter of every public return: `parts` in their documented order, the None ones dropped; the bare
     element when one is left, else a tuple."""
@@ -64,7 +73,8 @@ class OpenVLAEngine:
                  use_mask: bool = False, splitk: bool = False, fp8: bool = False, padded: bool = False,
                  vision_only: bool = False, text_only: bool = False, sample: bool = False, score: bool = False,
                  score_range: Optional[Tuple[int, int]] = None, vocab_range: Optional[Tuple[int, int]] = None,
-                 attn_taps: Optional[AttnTaps] = None, value: Optional[str] = None, value_head=None):
+                 attn_taps: Optional[AttnTaps] = None, value: Optional[str] = None, value_head=None,
+                 beams: Optional[int] = None):
         """all_rows=True builds the training/eval-style forward instead of generation: logits for every position
         (`logits_all` [B*S, vocab] fp32) and no decode steps. use_mask=True threads a [B, S] uint8 key-padding mask
         (`key_mask`, 1 = attend) through the Llama attention (modeling_prismatic.py:387-390). splitk=True lets
@@ -110,8 +120,39 @@ class OpenVLAEngine:
         that predicts the first action token, the learner's level="action" value row), values[t] the row that predicts
         action token t + 1 (level="token"). The op reads the head's live weight / bias tensors in place: a learner's
         write-back shows on the next replay of the same captured graph. It writes nothing the plan reads, and with
-        value=None every plan is op for op the one it was."""
+        value=None every plan is op for op the one it was.
+        beams=W turns the plain generation plan into beam search over the new tokens (beam.py is its specification).
+        `batch` stays the number of rows: batch % W == 0 and prompt e owns rows e·W … e·W + W - 1; `set_inputs` /
+        `set_padded_inputs` take the batch / W prompts and replicate each W times. The W rows of a prompt run the prefill
+        as identical rows — W copies are prefilled, as `sample_actions` prefills its copies — and get identical logits:
+        that rests on the project's batch-invariance rule (a sequence's bits do not depend on the rows around it), so the
+        static start scores [0, -inf, …] make every survivor of step 0 a child of beam 0. Every pick is one
+        bl_beam_step_f32 fed by `beam_scores[t - 1]`, writing `gen_ids[t]`, `beam_parent[t]`, `gen_wt[t]` and
+        `beam_scores[t]` (all [n_new, B, …], slot-major within a prompt, best first); after the head of decode step t,
+        1 <= t <= n_new - 2, ONE bl_beam_reorder_kv_bf16 moves the generated cache rows S … S + t - 1 (padded: from each
+        sequence's own `rope_pos[1]` on) of all 2 · layers caches by `beam_parent[t]`. Nothing else carries state from step
+        to step: decode step t + 1 starts from the embedding of `gen_ids[t]`. `result()` backtracks: `ids` / `wt` are the W
+        finished sequences of every prompt, best first; `beam_trace()` hands out the per-step tokens, parents, pairs and
+        scores. Static buffers and launches only, so the plan is capturable like the sampling plan. `vocab_range`
+        restricts the continuations to that token range. beams goes with the plain generation plan: not with sample,
+        score, all_rows, attn_taps (the taps would have to be reordered too) or value="token" (value="action" is one
+        state, so one V(s)). With beams=None every plan is op for op the one it was."""
         self.w, self.dims = weights, weights.dims
+        self.beams = None
+        if beams is not None:
+            if isinstance(beams, bool) or int(beams) != beams or not 1 <= int(beams) <= MAX_BEAMS:
+                raise ValueError(f"beams must be an integer in 1 … {MAX_BEAMS}, got {beams!r}")
+            for on, why in ((sample, "sample=True draws tokens, beam search ranks them"),
+                            (score, "score=True scores given tokens, beam search chooses its own"),
+                            (all_rows or vision_only, "beam search belongs to a generation plan"),
+                            (attn_taps is not None, "attn_taps would have to be reordered with the beams: not built"),
+                            (value == "token", 'value="token" follows one sequence per row; beams change rows every step '
+                                               '(value="action" is fine)')):
+                if on:
+                    raise ValueError(f"beams={beams}: {why}")
+            if batch % int(beams):
+                raise ValueError(f"beams={beams}: batch {batch} is the number of rows and must be a multiple of the beams")
+            self.beams = int(beams)
         self.vision_only, self.text_only = vision_only, text_only
         if text_only and (vision_only or padded or fp8):
             raise ValueError("text_only is the plain bf16 language-model plan")
@@ -128,12 +169,14 @@ class OpenVLAEngine:
             raise ValueError("score_range goes with score=True")
         self.vocab_range = None
         if vocab_range is not None:
-            if not (sample or score):
-                raise ValueError("vocab_range goes with sample=True or score=True")
+            if not (sample or score or self.beams):
+                raise ValueError("vocab_range goes with sample=True, score=True or beams=")
             first, count = int(vocab_range[0]), int(vocab_range[1])
             if first < 0 or count < 1 or first + count > self.dims.vocab or first % 4 or count % 4:
                 raise ValueError(f"vocab_range {vocab_range}: multiples of 4 inside the vocabulary [0, {self.dims.vocab})")
             self.vocab_range = (first, count)
+        if self.beams and self.beams > (self.dims.vocab if self.vocab_range is None else self.vocab_range[1]):
+            raise ValueError(f"beams={self.beams} exceeds the number of tokens a step chooses from")
         use_mask = use_mask or padded
         if padded and (all_rows or fp8):
             raise ValueError("padded generation is built for the bf16 generation plan")
@@ -160,6 +203,10 @@ class OpenVLAEngine:
             self.samp_temperature, self.samp_top_k = z(B, dtype=torch.float32), z(B, dtype=torch.int32)
             self.samp_top_p, self.samp_seed = torch.ones(B, dtype=torch.float32, device=dev), z(B, dtype=torch.int64)
             self.gen_wt = z(n_new, B, 2, dtype=torch.int64)
+        if self.beams:  # per step and row: the survivor's parent slot, weight pair and score; step 0 reads the static start row
+            self.beam_scores, self.beam_parent = z(n_new, B, dtype=torch.float32), z(n_new, B, dtype=torch.int32)
+            self.gen_wt = z(n_new, B, 2, dtype=torch.int64)
+            self.beam_start = torch.from_numpy(start_scores(self.beams)).repeat(B // self.beams).to(dev)
         self.score_range, self.gen_range_wt = None, None
         if score:       # the same settings without a seed; gen_ids holds the forced tokens
             self.samp_temperature, self.samp_top_k = z(B, dtype=torch.float32), z(B, dtype=torch.int32)
@@ -193,6 +240,8 @@ class OpenVLAEngine:
             self.v_cache = [z(B, d.llm_heads, self.cache_len, d.head_dim) for _ in range(d.llm_layers)]
             self.xd, self.hd, self.aod = z(B, D), z(B, D), z(B, D)
             self.qkvd, self.actd = z(B, 3 * D), z(B, I)
+            if self.beams and self.beams > 1:       # the base pointers of all 2 · layers caches: one reorder launch per step
+                self.kv_table = ops.cache_table(self.k_cache + self.v_cache)
         self.cos, self.sin = rope_tables(d.head_dim, d.max_pos, d.rope_theta, dev)
         self.ws = torch.empty(64 << 20, dtype=torch.uint8, device=dev) if splitk else None   # split-K scratch (opt-in)
         if padded:        # one mask over the whole cache: real prompt rows and every generated row are visible
@@ -444,6 +493,11 @@ class OpenVLAEngine:
         """Generation step t's token from its logits: greedy argmax (sample=True: the seeded draw; score=True: the score
         of the forced token). The pipeline calls it with its own logits rows for this engine's batch."""
         ids = self.gen_ids[t][b0:b1]
+        if self.beams:
+            if (b0, self.B if b1 is None else b1) != (0, self.B):
+                raise ValueError("beam search is built for the whole batch (no batch ranges: the staggered pipeline has no beams)")
+            return ops.beam_step(logits, self.beams, self.beam_start if t == 0 else self.beam_scores[t - 1], ids,
+                                 self.beam_parent[t], self.gen_wt[t], self.beam_scores[t], run=False, vocab=self.vocab_range)
         if self.sample:
             return ops.sample(logits, self.samp_temperature[b0:b1], self.samp_top_k[b0:b1], self.samp_top_p[b0:b1],
                               self.samp_seed[b0:b1], t, ids, self.gen_wt[t][b0:b1], run=False, vocab=self.vocab_range)
@@ -486,7 +540,24 @@ class OpenVLAEngine:
         plan = [ops.embed_splice(self.gen_ids[t - 1].view(B, 1), w.embed, self.xd.view(B, 1, D), 0, run=False)]
         for l, lw in enumerate(w.layers):
             plan += decode_layer(l, lw, self.xd, self.qkvd, self.aod, self.actd, norm_lin, lin, attn)
-        return plan + self._head(self.xd, t)
+        return plan + self._head(self.xd, t) + self._beam_reorder(t)
+
+    def _beam_reorder(self, t: int) -> List[Op]:
+        """Behind the head of decode step t: slot k of every prompt takes the t generated cache rows of slot
+        beam_parent[t][k], in all caches at once. Nothing without beams, for one beam (the identity) and behind the last
+        step (no step reads the caches any more)."""
+        if not self.beams or self.beams == 1 or not 1 <= t <= self.n_new - 2:
+            return []
+        return [ops.beam_reorder_kv(self.kv_table, self.k_cache + self.v_cache, self.beams, self.beam_parent[t],
+                                    self.rope_pos[1] if self.padded else self.S, t, run=False)]
+
+    def _per_beam(self, t: Optional[torch.Tensor], what: str) -> Optional[torch.Tensor]:
+        """A beam engine's inputs are given per prompt: [B / W, …] → every prompt's W rows."""
+        if not self.beams or t is None:
+            return t
+        if t.shape[0] != self.B // self.beams:
+            raise ValueError(f"engine built for {self.B // self.beams} prompts of {self.beams} beams, got {what} {tuple(t.shape)}")
+        return t.repeat_interleave(self.beams, dim=0)
 
     # ---- execution ------------------------------------------------------------------------------------------------
     def all_ops(self) -> List[Op]:
@@ -534,6 +605,10 @@ class OpenVLAEngine:
             self._graph.replay()
 
     def set_inputs(self, input_ids: torch.Tensor, pixel_values: torch.Tensor) -> None:
+        """The batch's prompts and images (beams=W: the B / W prompts, each replicated to its W rows)."""
+        self._fill_inputs(self._per_beam(input_ids, "input_ids"), self._per_beam(pixel_values, "pixel_values"))
+
+    def _fill_inputs(self, input_ids: torch.Tensor, pixel_values: torch.Tensor) -> None:
         if tuple(input_ids.shape) != (self.B, self.L):
             raise ValueError(f"engine built for input_ids {(self.B, self.L)}, got {tuple(input_ids.shape)}")
         if self.text_only:
@@ -556,13 +631,14 @@ class OpenVLAEngine:
         with at least one token itself; positions come from the mask's row sums (at most L), so they stay inside the cache either way."""
         if not self.padded:
             raise ValueError("engine was not built with padded=True")
-        m = attention_mask.to(self.device).bool()
+        input_ids, pixel_values = self._per_beam(input_ids, "input_ids"), self._per_beam(pixel_values, "pixel_values")
+        m = self._per_beam(attention_mask, "attention_mask").to(self.device).bool()
         if tuple(m.shape) != (self.B, self.L):
             raise ValueError(f"attention_mask must be {(self.B, self.L)}")
         n_real = m.sum(dim=1)
         if check and (bool((n_real < 1).any()) or not bool((m == (torch.arange(self.L, device=self.device)[None, :] < n_real[:, None])).all())):
             raise ValueError("generate(): prompts must be right-padded (attention_mask = 1…1 0…0) with at least one token")
-        self.set_inputs(input_ids, pixel_values)
+        self._fill_inputs(input_ids, pixel_values)
         P = self.dims.n_patches
         self.cache_mask.fill_(1)
         self.cache_mask[:, 1 + P:self.S] = m[:, 1:].to(torch.uint8)          # column 0 (BOS) and the 256 patch columns stay on
@@ -648,7 +724,7 @@ class OpenVLAEngine:
             self.set_sampling(sampling)
         self.set_inputs(input_ids, pixel_values)
         self.replay()
-        return self.gen_ids.t()
+        return self.result().ids if self.beams else self.gen_ids.t()
 
     @torch.no_grad()
     def score(self, input_ids: torch.Tensor, pixel_values: torch.Tensor, forced_ids: torch.Tensor, sampling=None):
@@ -664,11 +740,30 @@ class OpenVLAEngine:
         r = self.result()
         return present(r.wt, r.range_wt)
 
+    def beam_trace(self, own=lambda x: x) -> BeamTrace:
+        """The last run's survivors step by step, as views of the static buffers (`own=torch.clone`: copies): what
+        `beam.backtrack` takes, and the scores that rank the finished sequences (`scores[-1]`)."""
+        if not self.beams:
+            raise ValueError("engine was not built with beams=")
+        return BeamTrace(tokens=own(self.gen_ids), parents=own(self.beam_parent), wt=own(self.gen_wt), scores=own(self.beam_scores))
+
+    def _backtrack(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`beam.backtrack` on the device (index copies on the current stream, no host sync): ids int64 [B, n_new] and wt
+        int64 [B, n_new, 2] of every prompt's W finished sequences, best first."""
+        rows = torch.arange(self.B, device=self.device)
+        first, slot = rows // self.beams * self.beams, rows
+        ids, wt = torch.empty_like(self.gen_ids.t()), torch.empty_like(self.gen_wt.permute(1, 0, 2))
+        for t in range(self.n_new - 1, -1, -1):
+            ids[:, t], wt[:, t] = self.gen_ids[t][slot], self.gen_wt[t][slot]
+            slot = first + self.beam_parent[t][slot]
+        return ids, wt
+
     def result(self, own=lambda x: x) -> EngineResult:
         """The last run as one record; `own` is applied to every tensor (identity: views of the static buffers, which the
-        next run overwrites; `torch.clone`: copies). Device tensors, no host sync."""
-        return EngineResult(ids=own(self.gen_ids.t()),
-                            wt=own(self.gen_wt.permute(1, 0, 2)) if self.sample or self.score_mode else None,
+        next run overwrites; `torch.clone`: copies). Device tensors, no host sync. A beam engine's `ids` / `wt` are the
+        backtracked sequences (new tensors either way): row e·W + k is prompt e's k-th best."""
+        ids, wt = self._backtrack() if self.beams else (self.gen_ids.t(), self.gen_wt.permute(1, 0, 2) if self.sample or self.score_mode else None)
+        return EngineResult(ids=own(ids), wt=None if wt is None else own(wt),
                             range_wt=None if self.gen_range_wt is None else own(self.gen_range_wt.permute(1, 0, 2)),
                             values=None if self.values is None else own(self.value_result()),
                             attention=self.action_attention(own) if self.attn_taps is not None and not self.all_rows else None)

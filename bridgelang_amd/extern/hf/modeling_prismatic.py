@@ -41,6 +41,7 @@ import torch
 from transformers import PreTrainedModel
 
 from ...attention_taps import ActionAttention, AttnTaps, prompt_segments
+from ...beam import MAX_BEAMS
 from ...engine import EngineResult, OpenVLAEngine, present
 from ...sampling import SamplingParams, derive_seed, logprob
 from ...weights import TowerDims, VLADims, VLAWeights, allocate
@@ -212,8 +213,10 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
     def engine(self, batch: int, prompt_len: int, n_new: int = 7, padded: bool = False, cached: bool = False,
                sample: bool = False, score: bool = False, score_range: Optional[Tuple[int, int]] = None,
                vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None,
-               attn_taps: Optional[AttnTaps] = None, value: Optional[str] = None) -> OpenVLAEngine:
-        """`value` ("action" | "token", see `attach_value_head`): an engine whose plan also evaluates the attached value
+               attn_taps: Optional[AttnTaps] = None, value: Optional[str] = None, beams: Optional[int] = None) -> OpenVLAEngine:
+        """`beams` (W): the beam-search engine of `batch` / W prompts (`OpenVLAEngine(beams=)`); part of the cache key only
+        when given.
+        `value` ("action" | "token", see `attach_value_head`): an engine whose plan also evaluates the attached value
         head; the level and the head's identity join the cache key only when given.
         `attn_taps` (attention_taps.AttnTaps): an engine whose plan records where the action tokens attend; part of the
         cache key only when given, so the engines of every other call are the ones they were.
@@ -237,12 +240,13 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         key = (batch, prompt_len, n_new, fp8, padded, cached, sample) + (("score", score_range) if score else ()) + \
             (("vocab", vocab_range) if vocab_range is not None else ()) + (("adapted",) if adapted else ()) + \
             ((("taps", attn_taps.key(self.dims.llm_layers)),) if attn_taps is not None else ()) + \
-            ((("value", value, id(self._value_head)),) if value is not None else ())
+            ((("value", value, id(self._value_head)),) if value is not None else ()) + \
+            ((("beams", int(beams)),) if beams is not None else ())
         return self._lru(self._engines, key,
                          lambda: OpenVLAEngine(weights, batch, prompt_len, n_new=n_new, fp8=fp8 and not padded, padded=padded,
                                                sample=sample, score=score, score_range=score_range, vocab_range=vocab_range,
                                                attn_taps=attn_taps, value=value,
-                                               value_head=self._value_head if value is not None else None))
+                                               value_head=self._value_head if value is not None else None, beams=beams))
 
     # ---- where the action tokens attend (attention_taps.py) ----
     @staticmethod
@@ -483,7 +487,14 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         appends range_wt int32 [B, max_new_tokens, count]: the kept weights of that token range at every step.
         `vocab_range=(first, count)` restricts the policy to that token range (`sampling.py`, `vocab=`): draws, scores and
         weights are under the softmax of those logits alone, a forced token outside it scores weight 0, and without
-        `sampling=` the call is constrained greedy decoding (temperature 0 through the sampling engine)."""
+        `sampling=` the call is constrained greedy decoding (temperature 0 through the sampling engine).
+        `num_beams=W` (2 … 16, at most the policy's token count) with `num_return_sequences=R <= W` (default 1) is beam search
+        over the new tokens on the device (bridgelang_amd/beam.py defines it: fixed length, no early finish, so
+        `length_penalty` / `early_stopping` cannot change the order and are ignored): ids [B·R, L + max_new_tokens],
+        prompt-major and best first, as HF shapes them; `return_weights=True` adds wt [B·R, max_new_tokens, 2], every token's
+        weight pair under the unwarped policy given the tokens before it. `vocab_range`, `use_adapters` and
+        `return_values="action"` combine with it; `sampling=`, `do_sample`, `forced_ids`, `return_attention` and
+        `return_values="token"` raise ValueError. `num_beams=1` is the call without it."""
         return present(*self._generate(input_ids, max_new_tokens, pixel_values, attention_mask, **kwargs))
 
     def _generate(self, input_ids: torch.LongTensor, max_new_tokens: int = 7, pixel_values: Optional[torch.Tensor] = None,
@@ -492,15 +503,24 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
                   forced_ids: Optional[torch.Tensor] = None, score_range: Optional[Tuple[int, int]] = None,
                   vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None,
                   return_attention: Optional[str] = None, attention_layers=None, text_splits=None,
-                  return_values: Optional[str] = None, **_: Any) -> EngineResult:
+                  return_values: Optional[str] = None, num_beams: int = 1, num_return_sequences: Optional[int] = None,
+                  **_: Any) -> EngineResult:
         """`generate` as a record: its argument checks, one engine run, and the run's `EngineResult` with `ids` = prompt ‖
         new tokens and `wt` only where `generate` returns it. What `predict_action` / `score_actions` read by field.
-        Keywords it does not know (`use_cache`) are accepted and ignored."""
+        Keywords it does not know (`use_cache`, `length_penalty`, `early_stopping`) are accepted and ignored."""
+        W, R = self._beam_args(num_beams, num_return_sequences, vocab_range)
+        if W > 1:
+            for on, why in ((sampling is not None or do_sample, "sampling= / do_sample draw tokens, beam search ranks them"),
+                            (forced_ids is not None, "forced_ids scores given tokens, beam search chooses its own"),
+                            (return_attention is not None, "return_attention: the taps are not reordered with the beams"),
+                            (return_values == "token", 'return_values="token" follows one sequence per row ("action" is available)')):
+                if on:
+                    raise ValueError(f"num_beams={W}: {why}")
         if do_sample and sampling is None:
             raise NotImplementedError("do_sample=True draws from torch's global device RNG stream, which the HIP path does "
                                       "not reproduce: pass sampling=SamplingParams(temperature=, top_k=, top_p=, seed=) instead")
-        if return_weights and sampling is None:
-            raise ValueError("return_weights goes with sampling=")
+        if return_weights and sampling is None and W == 1:
+            raise ValueError("return_weights goes with sampling= or num_beams=")
         if pixel_values is None:
             raise ValueError("generate() needs pixel_values")
         ids, pv = input_ids.to(self.device), pixel_values.to(self.device)
@@ -511,6 +531,9 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         forced = None if forced_ids is None else torch.as_tensor(forced_ids).to(self.device, torch.int64)
         if forced is None and score_range is not None:
             raise ValueError("score_range goes with forced_ids=")
+        if W > 1:       # the best R of every prompt's W beams, prompt-major
+            r = self._run_beams(ids, pv, max_new_tokens, attention_mask, W, R, vocab_range, use_adapters, value)
+            return r._replace(ids=torch.cat([ids.repeat_interleave(R, dim=0), r.ids], dim=1), wt=r.wt if return_weights else None)
         r = self._run_engine(ids, pv, max_new_tokens, attention_mask, sampling, forced, score_range, vocab_range, use_adapters,
                              taps, text_splits, value)
         return r._replace(ids=torch.cat([ids, r.ids], dim=1), wt=r.wt if return_weights or forced is not None else None)
@@ -543,6 +566,42 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             eng.set_segments(*prompt_segments(mask, eng.n_patches, eng.n_new, text_splits))
         eng.replay()
         return eng.result(torch.clone)
+
+    def _beam_args(self, num_beams, num_return_sequences, vocab_range) -> Tuple[int, int]:
+        """(W, R) of `num_beams` / `num_return_sequences`, checked: W an integer in 1 … MAX_BEAMS and at most the number of
+        tokens the policy chooses from, 1 <= R <= W (None: 1)."""
+        n_tokens = self.dims.vocab if vocab_range is None else int(vocab_range[1])
+        if isinstance(num_beams, bool) or not isinstance(num_beams, (int, np.integer)) or not 1 <= num_beams <= min(MAX_BEAMS, n_tokens):
+            raise ValueError(f"num_beams must be an integer in 1 … {min(MAX_BEAMS, n_tokens)} (at most {MAX_BEAMS} beams, and no "
+                             f"more than the {n_tokens} tokens of the policy), got {num_beams!r}")
+        R = 1 if num_return_sequences is None else num_return_sequences
+        if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 1 <= R <= num_beams:
+            raise ValueError(f"num_return_sequences must be an integer in 1 … num_beams = {num_beams}, got {num_return_sequences!r}")
+        return int(num_beams), int(R)
+
+    @torch.no_grad()
+    def _run_beams(self, ids: torch.Tensor, pv: torch.Tensor, n_new: int, attention_mask: Optional[torch.Tensor], W: int, R: int,
+                   vocab_range, use_adapters: Optional[bool], value: Optional[str]) -> EngineResult:
+        """Beam search of W beams for every prompt, the best R of each returned prompt-major: ids [B·R, n_new], wt
+        [B·R, n_new, 2], values [B·R] (V(s) is the prompt's: the same for its R rows). The prompts are split over engine
+        runs of max(1, 16 // W) prompts — a prompt's beams are never split, and every run stays within the 16 rows where a
+        sequence's result is its batch-1 result — so a prompt's beams do not depend on the prompts around it."""
+        B = ids.shape[0]
+        padded = attention_mask is not None and not bool(attention_mask.bool().all())
+        per_run, parts = max(1, 16 // W), []
+        for e0 in range(0, B, per_run):
+            c = min(per_run, B - e0)
+            eng = self.engine(c * W, ids.shape[1], n_new, padded=padded, vocab_range=vocab_range, use_adapters=use_adapters,
+                              value=value, beams=W)
+            if padded:
+                eng.set_padded_inputs(ids[e0:e0 + c], pv[e0:e0 + c], attention_mask[e0:e0 + c])
+            else:
+                eng.set_inputs(ids[e0:e0 + c], pv[e0:e0 + c])
+            eng.replay()
+            parts.append(eng.result(torch.clone))
+        best = lambda x: x.reshape((-1, W) + tuple(x.shape[1:]))[:, :R].reshape((-1,) + tuple(x.shape[1:]))
+        return EngineResult(ids=torch.cat([best(p.ids) for p in parts]), wt=torch.cat([best(p.wt) for p in parts]),
+                            values=None if value is None else torch.cat([best(p.values) for p in parts]))
 
 
 def _numpy(t: Optional[torch.Tensor]) -> Optional[np.ndarray]:
@@ -628,7 +687,10 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         input_ids as given (the empty token this call appends joins the last text piece).
         `return_values="action" | "token"` (see `generate`, `attach_value_head`) returns the critic's values as one more
         element, fp32 ndarray [B] or [B, n]. Order: the action, then (tokens, wt) with `return_weights`, then the values, then
-        the `ActionAttention`."""
+        the `ActionAttention`.
+        `num_beams=W` (see `generate`) returns the action of the best of W beams — the most likely whole action beam search
+        finds, where the greedy chain is only the most likely token at a time — shaped as today; `num_return_sequences=R > 1`
+        returns the best R, [B, R, n] (`beam_actions` adds their tokens and log-probabilities)."""
         p = self._predict(input_ids, unnorm_key, action_tokens_only, use_adapters, **kwargs)
         return present(p.actions, None if p.wt is None else p.tokens, p.wt, p.values, p.attention)
 
@@ -649,11 +711,16 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             kwargs["vocab_range"] = self.action_token_range()
         r = self._generate(input_ids, max_new_tokens=n, use_adapters=use_adapters, **kwargs)
         tokens = r.ids[:, -n:].cpu().numpy()
+        B, R = input_ids.shape[0], tokens.shape[0] // input_ids.shape[0]     # R > 1: num_return_sequences rows per prompt
         if keys is not None:
-            actions = np.stack([np.asarray(self.actions_from_token_ids(tokens[i:i + 1], k)).reshape(-1) for i, k in enumerate(keys)])
+            actions = np.stack([np.asarray(self.actions_from_token_ids(tokens[i:i + 1], k)).reshape(-1) for i, k in enumerate(k for k in keys for _ in range(R))])
         else:
             actions = self.actions_from_token_ids(tokens, unnorm_key)
-        return SimpleNamespace(actions=actions, tokens=tokens, wt=_numpy(r.wt), values=_numpy(r.values), attention=r.attention)
+        wt, values = _numpy(r.wt), _numpy(r.values)
+        if R > 1:       # [B, R, …], best first; V(s) is the prompt's
+            actions, tokens = np.asarray(actions).reshape(B, R, n), tokens.reshape(B, R, n)
+            wt, values = None if wt is None else wt.reshape(B, R, n, 2), None if values is None else values[::R].copy()
+        return SimpleNamespace(actions=actions, tokens=tokens, wt=wt, values=values, attention=r.attention)
 
     def _action_prompt(self, input_ids: torch.LongTensor, m: Optional[torch.Tensor]):
         """The prompt with the empty token 29871 behind each sequence's last token → (input_ids, attention_mask)."""
@@ -711,6 +778,37 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         return present(stack_runs([np.asarray(r.actions).reshape(r.tokens.shape[0], -1) for r in runs], B),
                        stack_runs([r.tokens for r in runs], B), stack_runs([logprob(r.wt) for r in runs], B),
                        stack_values([r.values for r in runs], B, level), stack_attention([r.attention for r in runs], B))
+
+    def beam_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor,
+                     unnorm_key: Union[str, Sequence[Optional[str]], None] = None, num_beams: int = 4,
+                     num_return_sequences: Optional[int] = None, attention_mask: Optional[torch.Tensor] = None,
+                     action_tokens_only: bool = False, use_adapters: Optional[bool] = None,
+                     return_values: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The `num_return_sequences` (None: all `num_beams`) most likely whole actions that beam search of `num_beams` beams
+        finds for every prompt, best first, in the shapes of `sample_actions`: → (actions [B, R, n], token_ids int64
+        [B, R, n], logprobs fp64 [B, R, n]). logprobs = `sampling.logprob` of the per-token weight pairs: every token's
+        log-probability under the unwarped policy given the tokens before it (their sum is the action's joint
+        log-probability), bit for bit what `score_actions(token_ids=those tokens)` returns. bridgelang_amd/beam.py defines the
+        search: fixed length n, no early finish, HF's `num_beams=W, do_sample=False` search when `action_tokens_only=True`
+        keeps EOS out of it. `return_values="action"` appends V(s) fp32 [B]; `use_adapters`: see `engine`. One beam is the
+        greedy action with its log-probabilities."""
+        if return_values == "token":
+            raise ValueError('beam_actions: return_values="token" follows one sequence per row ("action" is available)')
+        vocab_range = self.action_token_range() if action_tokens_only else None
+        W, R = self._beam_args(num_beams, num_beams if num_return_sequences is None else num_return_sequences, vocab_range)
+        level = self._value_level(return_values)
+        keys = list(unnorm_key) if isinstance(unnorm_key, (list, tuple)) else None
+        B = input_ids.shape[0]
+        if keys is not None and (len(keys) != B or len({self.get_action_dim(k) for k in keys}) != 1):
+            raise ValueError("beam_actions: a list of unnorm_keys needs one key per sequence, all of one action dimension")
+        n = self.get_action_dim(keys[0] if keys is not None else unnorm_key)
+        ids, m = self._action_prompt(input_ids.to(self.device), attention_mask)
+        r = self._run_beams(ids, pixel_values.to(self.device), n, m, W, R, vocab_range, use_adapters, level)
+        tokens = r.ids.cpu().numpy()
+        row_keys = [unnorm_key] * (B * R) if keys is None else [k for k in keys for _ in range(R)]
+        actions = np.stack([np.asarray(self.actions_from_token_ids(tokens[i:i + 1], k)).reshape(-1) for i, k in enumerate(row_keys)])
+        return present(actions.reshape(B, R, n), tokens.reshape(B, R, n), logprob(_numpy(r.wt)).reshape(B, R, n),
+                       None if level is None else _numpy(r.values)[::R].copy())
 
     def score_actions(self, input_ids: torch.LongTensor, pixel_values: torch.Tensor, token_ids=None, actions=None,
                       unnorm_key: Optional[str] = None, sampling: Optional[SamplingParams] = None,

@@ -21,7 +21,7 @@ from ._lib import (AttnDesc, GemmDesc, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_KE
                    EPI_RES, EPI_SWIGLU)
 
 __all__ = ["Op", "gemm", "gemm_last_form", "gemm_form_name", "gemm_fp8", "linear_fp8", "Fp8Weight", "quantize_rows_fp8", "quantize_weight_fp8", "quantize_packed_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "attention_probs", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
-           "argmax", "sample", "score", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
+           "argmax", "sample", "score", "beam_step", "cache_table", "beam_reorder_kv", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
            "EPI_NONE", "EPI_BIAS", "EPI_BIAS_GELU", "EPI_BIAS_RES", "EPI_RES", "EPI_SWIGLU", "EPI_F32", "EPI_F32_BF16R",
            "EPI_SWIGLU_KEEP", "EPI_BIAS_GELU_KEEP", "EPI_SWIGLU_BWD", "EPI_GELU_BWD"]
 
@@ -571,6 +571,53 @@ def score(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, 
                head + (tokens.data_ptr(), wt.data_ptr(), int(range_first), count, range_wt.data_ptr() if count else None)
                + (() if vocab is None else (int(vocab[0]), int(vocab[1]))),
                (logits, temperature, top_k, top_p, tokens, wt) + ((range_wt,) if count else ()), run)
+
+
+def beam_step(logits: torch.Tensor, W: int, scores_in: torch.Tensor, tokens: torch.Tensor, parents: torch.Tensor,
+              wt: torch.Tensor, scores_out: torch.Tensor, run: bool = True, vocab: Optional[Tuple[int, int]] = None) -> Op:
+    """One beam-search step over fp32 logits [rows, n] (any row stride; bl_beam_step_f32, specification: beam.beam_step):
+    every W consecutive rows are the beams of one prompt, scores_in fp32 [rows] their scores so far. Writes, per prompt and
+    best first, tokens int64 [rows], parents int32 [rows] (in [0, W)), wt int64 [rows, 2] and scores_out fp32 [rows].
+    vocab=(first, count) ranks the continuations inside that token range only."""
+    rows, n = _f32(logits, "beam_step: logits").shape
+    if W < 1 or rows % W:
+        raise ValueError(f"beam_step: {rows} rows are no whole number of prompts of {W} beams")
+    for t, dtype, tail, name in ((scores_in, torch.float32, (), "scores_in"), (tokens, torch.int64, (), "tokens"),
+                                 (parents, torch.int32, (), "parents"), (wt, torch.int64, (2,), "wt"),
+                                 (scores_out, torch.float32, (), "scores_out")):
+        _dev(t, dtype, (rows,) + tail, f"beam_step: {name}")
+    first, count = (0, n) if vocab is None else (int(vocab[0]), int(vocab[1]))
+    return _op("bl_beam_step_f32", (logits.data_ptr(), _rows(logits, "logits"), rows // W, int(W), n, scores_in.data_ptr(),
+                                    tokens.data_ptr(), parents.data_ptr(), wt.data_ptr(), scores_out.data_ptr(), first, count),
+               (logits, scores_in, tokens, parents, wt, scores_out), run)
+
+
+def cache_table(caches: Sequence[torch.Tensor]) -> torch.Tensor:
+    """The device table of base pointers `beam_reorder_kv` takes: int64 [len(caches)], built once per engine. The caller
+    keeps the caches alive (the Op built over the table does)."""
+    return torch.tensor([c.data_ptr() for c in caches], dtype=torch.int64, device=caches[0].device)
+
+
+def beam_reorder_kv(table: torch.Tensor, caches: Sequence[torch.Tensor], W: int, parents: torch.Tensor, row0, n_rows: int,
+                    run: bool = True) -> Op:
+    """In every cache of `caches` (contiguous bf16 [rows, H, cache_len, hd], all of one shape; `table` = cache_table(caches)),
+    batch row g·W + k takes cache rows row0 … row0 + n_rows - 1 of batch row g·W + parents[g·W + k], in place
+    (bl_beam_reorder_kv_bf16: one launch for all caches). parents int32 [rows] on the device; row0: a host int, or an int32
+    device tensor [rows] with every batch row's own first row (right-padded prompts)."""
+    fn = "beam_reorder_kv"
+    _contig_bf16(fn, *[(c, "cache") for c in caches])
+    shape = tuple(caches[0].shape)
+    if len(shape) != 4 or any(tuple(c.shape) != shape for c in caches):
+        raise ValueError(f"{fn}: all caches must share one shape [rows, H, cache_len, hd]")
+    rows, H, cache_len, hd = shape
+    _dev(table, torch.int64, len(caches), f"{fn}: table")
+    _dev(parents, torch.int32, (rows,), f"{fn}: parents")
+    per_row = isinstance(row0, torch.Tensor)
+    if per_row:
+        _dev(row0, torch.int32, (rows,), f"{fn}: row0")
+    return _op("bl_beam_reorder_kv_bf16", (table.data_ptr(), len(caches), rows, int(W), H, cache_len, hd, parents.data_ptr(),
+                                           0 if per_row else int(row0), row0.data_ptr() if per_row else None, int(n_rows)),
+               (table, list(caches), parents, row0), run, nbytes=4.0 * len(caches) * rows * H * n_rows * hd)
 
 
 def cross_entropy(logits: torch.Tensor, targets: torch.Tensor, row_loss: torch.Tensor, mean_and_count: torch.Tensor,

@@ -322,6 +322,31 @@ int bl_score_range_f32(const float* logits, int64_t ld, int32_t rows, int32_t n,
                        const int32_t* top_k, const float* top_p, const int64_t* tokens, int64_t* wt,
                        int32_t range_first, int32_t range_count, int32_t* range_wt, int32_t vocab_first,
                        int32_t vocab_count, void* stream);
+/* One step of beam search, bit-identical to bridgelang_amd/beam.py::beam_step: logits [groups * W, n] (row stride ld); the W
+ * rows of a group are the beams of one prompt, scores_in fp32 [groups * W] their joint log-probabilities so far. Over the
+ * token range [vocab_first, vocab_first + vocab_count) of every row, candidate (j, i) scores
+ * c = ((scores_in[j] + (l_i - max_j)) - lz_j), each operation rounded alone, lz_j the log of the row's integer softmax total
+ * (bl_sample_f32's weights at temperature 1). The W survivors of a group, in the order c descending then j * vocab_count + i
+ * ascending, go to slot k = 0 … W-1 of the group: tokens int64 (full-row numbering), parents int32 (j, in [0, W)), wt int64
+ * [., 2] = (weight of the token on row j, that row's total: bl_score_range_f32's pair under the default settings) and
+ * scores_out fp32 (c). Step 0 passes scores_in = (0, -inf, …). Two launches on `stream`: one workgroup per row (maximum and
+ * total, kept in that row's wt pair in between), then one workgroup per group, which reads all of its inputs before it writes
+ * any output, so scores_out may be scores_in. W in 1 … 16 and W <= vocab_count, other shapes as bl_sample_range_f32, else
+ * BL_E_SHAPE; a NULL pointer: BL_E_ARG; nothing is launched on a rejection. */
+int bl_beam_step_f32(const float* logits, int64_t ld, int32_t groups, int32_t W, int32_t n, const float* scores_in,
+                     int64_t* tokens, int32_t* parents, int64_t* wt, float* scores_out, int32_t vocab_first,
+                     int32_t vocab_count, void* stream);
+/* The KV-cache half of a beam step, in place: in each of the n_caches bf16 caches [rows, H, cache_len, head_dim] whose base
+ * pointers are the DEVICE table `caches`, batch row g * W + k takes the cache rows r0 … r0 + n_rows - 1 of batch row
+ * g * W + parents[g * W + k] (parents DEVICE int32 [rows]; an entry outside [0, W) keeps the slot's own rows). r0 = row0, or
+ * with row0_dev (DEVICE int32 [rows], right-padded prompts) every batch row's own first generated row; a cache row outside
+ * [0, cache_len) moves nothing. A workgroup owns all W slots of one (cache, prompt, head, cache row): it loads them, barriers,
+ * then stores, so a parent may have several children or be overwritten; everything outside the moved rows is untouched.
+ * One launch for the whole table. rows % W == 0, W in 1 … 16, head_dim % 8 == 0, W * head_dim <= 4096, row0 + n_rows <=
+ * cache_len, else BL_E_SHAPE; NULL caches / parents: BL_E_ARG; nothing is launched on a rejection. */
+int bl_beam_reorder_kv_bf16(bl_bf16* const* caches, int32_t n_caches, int32_t rows, int32_t W, int32_t H, int32_t cache_len,
+                            int32_t head_dim, const int32_t* parents, int32_t row0, const int32_t* row0_dev, int32_t n_rows,
+                            void* stream);
 
 /* Shifted causal-LM cross-entropy (HF LlamaForCausalLM loss; labels prepared by the caller as `targets[row]` =
  * label of the NEXT position, -100 = ignore; base_strategy.py:287-297 consumes `output.loss`). row_loss[rows] receives
