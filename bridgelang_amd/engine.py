@@ -74,7 +74,7 @@ class OpenVLAEngine:
                  vision_only: bool = False, text_only: bool = False, sample: bool = False, score: bool = False,
                  score_range: Optional[Tuple[int, int]] = None, vocab_range: Optional[Tuple[int, int]] = None,
                  attn_taps: Optional[AttnTaps] = None, value: Optional[str] = None, value_head=None,
-                 beams: Optional[int] = None):
+                 beams: Optional[int] = None, group: Optional[int] = None):
         """all_rows=True builds the training/eval-style forward instead of generation: logits for every position
         (`logits_all` [B*S, vocab] fp32) and no decode steps. use_mask=True threads a [B, S] uint8 key-padding mask
         (`key_mask`, 1 = attend) through the Llama attention (modeling_prismatic.py:387-390). splitk=True lets
@@ -136,8 +136,37 @@ class OpenVLAEngine:
         scores. Static buffers and launches only, so the plan is capturable like the sampling plan. `vocab_range`
         restricts the continuations to that token range. beams goes with the plain generation plan: not with sample,
         score, all_rows, attn_taps (the taps would have to be reordered too) or value="token" (value="action" is one
-        state, so one V(s)). With beams=None every plan is op for op the one it was."""
+        state, so one V(s)). With beams=None every plan is op for op the one it was.
+        group=G shares one prefill among the G rows of a prompt: `batch` stays the number of decode rows, batch
+        % G == 0, prompt p owns rows p·G … p·G + G - 1, and `set_inputs` takes the P = batch / G prompts. The towers, the
+        projector and the prefill are planned on P rows and the prompt caches hold P sequences; the residual rows of step
+        0 are replicated G-fold (bl_repeat_rows_bf16) in front of the head, and every decode step is today's decode layer
+        on batch rows whose attention (bl_attention_decode_rope_shared_bf16) reads the prompt's cache rows in place and
+        keeps the row's own tokens in `k_gen` / `v_gen` [batch, H, n_new - 1, hd]. Seeds, settings, forced ids and beam
+        start scores stay per row. Every id, weight and logit is the one the engine without group= gives on
+        `repeat_interleave`d inputs, bit for bit: a prefilled row does not depend on the rows around it, and the shared
+        kernel restates the decode kernel per row. Goes with sample, score (score_range), greedy, vocab_range, beams == G (the
+        reorder then runs over the gen caches from row 0; the prompt caches are never reordered) and value="action" (the
+        critic on the P prompt rows: `values` [1, P]). Not with padded, fp8, attn_taps, value="token", all_rows,
+        vision_only, text_only, beams != G, or a batch past the fused decode forms (16 rows, head_dim 128). With group=None
+        every plan is op for op the one it was."""
         self.w, self.dims = weights, weights.dims
+        self.group, self.P = None, batch
+        if group is not None:
+            if isinstance(group, bool) or int(group) != group or not 1 <= int(group) <= 16:
+                raise ValueError(f"group must be an integer in 1 … 16, got {group!r}")
+            for on, why in ((padded, "padded prompts put every row at its own position; the shared kernel has one"),
+                            (fp8, "the e4m3 prefill is not bit-identical to the path group= is specified against"),
+                            (attn_taps is not None, "attn_taps read one cache per row; the prompt rows are shared here"),
+                            (value == "token", 'value="token" is not built for shared prefills (value="action" is)'),
+                            (all_rows or vision_only or text_only, "a shared prefill belongs to the multimodal generation plan"),
+                            (beams is not None and int(beams) != int(group), f"beams={beams}: the beams of a prompt are its group"),
+                            (batch % int(group) != 0, f"batch {batch} is the number of rows and must be a multiple of the group"),
+                            (not decode_fused(batch, weights.dims), f"the shared decode attention is the fused form only: "
+                                                                     f"head_dim 128 and at most 16 rows, got batch {batch}")):
+                if on:
+                    raise ValueError(f"group={group}: {why}")
+            self.group, self.P = int(group), batch // int(group)
         self.beams = None
         if beams is not None:
             if isinstance(beams, bool) or int(beams) != beams or not 1 <= int(beams) <= MAX_BEAMS:
@@ -193,10 +222,11 @@ class OpenVLAEngine:
         dev = weights.embed.device
         self.device = dev
         B, S, D, I = batch, self.S, d.llm_dim, d.llm_inter
+        Bp = self.P               # rows of the towers, the projector and the prefill (group=: the prompts; else the batch)
         z = lambda *shape, dtype=torch.bfloat16: torch.zeros(*shape, dtype=dtype, device=dev)
         # inputs / outputs (static addresses so a captured graph can be replayed)
-        self.pixel_values = z(B, 6, 224, 224)
-        self.input_ids = z(B, prompt_len, dtype=torch.int64)
+        self.pixel_values = z(Bp, 6, 224, 224)
+        self.input_ids = z(Bp, prompt_len, dtype=torch.int64)
         self.gen_ids = z(n_new, B, dtype=torch.int64)
         self.logits = z(n_new, B, d.vocab, dtype=torch.float32)
         if sample:      # settings of the sequences now in the buffers (zeros: temperature 0 = greedy) and the weight pairs
@@ -225,23 +255,28 @@ class OpenVLAEngine:
         dmax = max(d.dino.dim, d.siglip.dim)
         hmax = max(d.dino.mlp_pad, d.siglip.mlp_pad)
         # one private set per tower: the two towers run concurrently on two streams
-        self.vbuf = [dict(col=z(B * 256, (d.patch_k + 63) // 64 * 64), x=z(B * tmax * dmax), h=z(B * tmax * dmax),
-                          ao=z(B * tmax * dmax), qkv=z(B * tmax * 3 * dmax), mlp=z(B * tmax * hmax),
+        self.vbuf = [dict(col=z(Bp * 256, (d.patch_k + 63) // 64 * 64), x=z(Bp * tmax * dmax), h=z(Bp * tmax * dmax),
+                          ao=z(Bp * tmax * dmax), qkv=z(Bp * tmax * 3 * dmax), mlp=z(Bp * tmax * hmax),
                           ws=None) for _ in range(2)]   # ViT GEMMs never reach the split-K regime (K <= 4352)
-        self.feats = z(B * 256, d.vision_dim)
-        self.p1, self.p2 = z(B * 256, 4 * d.vision_dim), z(B * 256, D)
+        self.feats = z(Bp * 256, d.vision_dim)
+        self.p1, self.p2 = z(Bp * 256, 4 * d.vision_dim), z(Bp * 256, D)
         # llm buffers
         if not vision_only:
-            self.x = z(B, S, D)
-            self.h, self.ao = z(B * S, D), z(B * S, D)
-            self.qkv = z(B * S, 3 * D)
-            self.act = z(B * S, I)
-            self.k_cache = [z(B, d.llm_heads, self.cache_len, d.head_dim) for _ in range(d.llm_layers)]
-            self.v_cache = [z(B, d.llm_heads, self.cache_len, d.head_dim) for _ in range(d.llm_layers)]
+            self.x = z(Bp, S, D)
+            self.h, self.ao = z(Bp * S, D), z(Bp * S, D)
+            self.qkv = z(Bp * S, 3 * D)
+            self.act = z(Bp * S, I)
+            self.k_cache = [z(Bp, d.llm_heads, self.cache_len, d.head_dim) for _ in range(d.llm_layers)]
+            self.v_cache = [z(Bp, d.llm_heads, self.cache_len, d.head_dim) for _ in range(d.llm_layers)]
             self.xd, self.hd, self.aod = z(B, D), z(B, D), z(B, D)
             self.qkvd, self.actd = z(B, 3 * D), z(B, I)
+            if self.group:      # the rows' own tokens, and the P-row buffers of the prefill's last-row layer
+                gen_len = max(1, n_new - 1)
+                self.k_gen = [z(B, d.llm_heads, gen_len, d.head_dim) for _ in range(d.llm_layers)]
+                self.v_gen = [z(B, d.llm_heads, gen_len, d.head_dim) for _ in range(d.llm_layers)]
+                self.xp, self.aop, self.actp = z(Bp, D), z(Bp, D), z(Bp, I)
             if self.beams and self.beams > 1:       # the base pointers of all 2 · layers caches: one reorder launch per step
-                self.kv_table = ops.cache_table(self.k_cache + self.v_cache)
+                self.kv_table = ops.cache_table(self.k_gen + self.v_gen if self.group else self.k_cache + self.v_cache)
         self.cos, self.sin = rope_tables(d.head_dim, d.max_pos, d.rope_theta, dev)
         self.ws = torch.empty(64 << 20, dtype=torch.uint8, device=dev) if splitk else None   # split-K scratch (opt-in)
         if padded:        # one mask over the whole cache: real prompt rows and every generated row are visible
@@ -253,7 +288,7 @@ class OpenVLAEngine:
             self.rope_pos = torch.zeros(n_new, B, dtype=torch.int32, device=dev)        # rotation position of new token t
             self.q_last, self.x_last = z(B, D), z(B, D)
         else:
-            self.key_mask = torch.ones(B, S, dtype=torch.uint8, device=dev) if use_mask else None
+            self.key_mask = torch.ones(Bp, S, dtype=torch.uint8, device=dev) if use_mask else None
         self.logits_all = z(B * S, d.vocab, dtype=torch.float32) if all_rows else None
         self.fp8 = fp8
         if fp8:
@@ -273,7 +308,7 @@ class OpenVLAEngine:
                                  f"{None if value_head is None else value_head.dim}")
             if value_head.weight.device != dev:
                 raise ValueError(f"value_head lives on {value_head.weight.device}, the weights on {dev}")
-            self.values = z(n_new if value == "token" else 1, B, dtype=torch.float32)
+            self.values = z(n_new if value == "token" else 1, Bp, dtype=torch.float32)
         elif value_head is not None:
             raise ValueError("value_head goes with value='action' or 'token'")
         self.attn_taps, self.tap_slot = attn_taps, {}
@@ -318,7 +353,7 @@ class OpenVLAEngine:
     # ---- plans ----------------------------------------------------------------------------------------------------
     def _plan_tower(self, tw: TowerW, feat_col: int, vb: dict) -> List[Op]:
         """timm VisionTransformer up to the tap: K1-K9 of SURVEY §2.4."""
-        t, B = tw.dims, self.B
+        t, B = tw.dims, self.P
         T, Dm, Hp, hd = t.tokens, t.dim, t.mlp_pad, t.head_dim
         M = B * T
         x = vb["x"][:M * Dm].view(M, Dm)
@@ -354,7 +389,7 @@ class OpenVLAEngine:
 
     def _plan_projector(self) -> List[Op]:
         """PrismaticProjector (modeling_prismatic.py:151-156); fc3 writes straight into LLM embedding rows 1..256."""
-        w, B, S, D = self.w, self.B, self.S, self.dims.llm_dim
+        w, B, S, D = self.w, self.P, self.S, self.dims.llm_dim
         return [self._g(self.feats, w.fc1_w, self.p1, EPI_BIAS_GELU, bias=w.fc1_b, run=False),
                 self._g(self.p1, w.fc2_w, self.p2, EPI_BIAS_GELU, bias=w.fc2_b, run=False),
                 self._g(self.p2, w.fc3_w, self.x.view(B * S, D), EPI_BIAS, bias=w.fc3_b, out_map=(256, S, 1), run=False)]
@@ -381,7 +416,7 @@ class OpenVLAEngine:
         """Llama prefill + first token for batch rows [b0, b1) (default: the whole batch). Every buffer is batch-major, so
         a batch range is a contiguous slice of each; results do not depend on the range a sequence is run in."""
         d, w, S = self.dims, self.w, self.S
-        b1 = self.B if b1 is None else b1
+        b1 = self.P if b1 is None else b1
         B, D, H, hd = b1 - b0, d.llm_dim, d.llm_heads, d.head_dim
         rows, x3 = slice(b0 * S, b1 * S), self.x[b0:b1]
         x, h, qkv, ao, act = x3.view(B * S, D), self.h[rows], self.qkv[rows], self.ao[rows], self.act[rows]
@@ -437,7 +472,14 @@ class OpenVLAEngine:
             return plan + [ops.rmsnorm(x, w.norm, h, d.rms_eps, run=False),
                            self._g(h, w.lm_head, self.logits_all[rows], EPI_F32_BF16R, run=False)]
         # final norm + lm_head on the last position only (the reference materialises all S rows)
-        return plan + self._head(x3[:, S - 1, :], 0, b0, b1)
+        return plan + self._first_token(x3[:, S - 1, :], b0, b1)
+
+    def _first_token(self, x_rows: torch.Tensor, b0: int, b1: int) -> List[Op]:
+        """The head of step 0 over the prefill's last residual rows. group=: the P rows are replicated G-fold into `xd`
+        first (a copy), so the head, and every per-row pick behind it, runs on all rows; the critic reads the P rows."""
+        if not self.group:
+            return self._head(x_rows, 0, b0, b1)
+        return [ops.repeat_rows(x_rows, self.xd, self.group, run=False)] + self._head(self.xd, 0, value_rows=x_rows)
 
     def _plan_last_rows(self, b0: int, b1: int) -> List[Op]:
         """The last decoder layer of a generation prefill + the first token: it still projects K/V for every position (the
@@ -446,6 +488,8 @@ class OpenVLAEngine:
         d, S, B, lw = self.dims, self.S, b1 - b0, self.w.layers[-1]
         D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
         x3, xd, aod, actd = self.x[b0:b1], self.xd[b0:b1], self.aod[b0:b1], self.actd[b0:b1]
+        if self.group:      # P rows of their own: xd takes their G-fold copies in front of the head
+            xd, aod, actd = self.xp, self.aop, self.actp
         h, qkv = self.h[b0 * S:b1 * S], self.qkv[b0 * S:b1 * S]
         kc, vc = self.k_cache[-1][b0:b1], self.v_cache[-1][b0:b1]
         cs = (H * self.cache_len * hd, self.cache_len * hd, hd)
@@ -466,7 +510,7 @@ class OpenVLAEngine:
         plan += self._tap(d.llm_layers - 1, 0, q_last, q_strides, S, None, mask, b0, b1)      # q_last is rotated
         plan.append(self._g(aod, lw.o_w, xd, EPI_RES, res=x_last, run=False))
         plan += self._norm_lin(xd, lw.ln2, lw.gu_w, actd, EPI_SWIGLU, ops.skinny_supported(B, D, EPI_SWIGLU), b0, b1)
-        return plan + [self._g(actd, lw.down_w, xd, EPI_RES, res=xd, run=False)] + self._head(xd, 0, b0, b1)
+        return plan + [self._g(actd, lw.down_w, xd, EPI_RES, res=xd, run=False)] + self._first_token(xd, b0, b1)
 
     def _norm_lin(self, x, norm_w, W, out, epi, fused: bool, b0: int = 0, b1: Optional[int] = None) -> List[Op]:
         """A linear on B rows with an RMSNorm in front: fused into the weight-streaming GEMM (`a_norm`), or a launch of
@@ -475,11 +519,14 @@ class OpenVLAEngine:
             return [self._g(x, W, out, epi, a_norm=(norm_w, self.dims.rms_eps), run=False)]
         return [ops.rmsnorm(x, norm_w, self.hd[b0:b1], self.dims.rms_eps, run=False), self._g(self.hd[b0:b1], W, out, epi, run=False)]
 
-    def _head(self, x_rows: torch.Tensor, t: int, b0: int = 0, b1: Optional[int] = None) -> List[Op]:
-        """final RMSNorm → lm_head (bf16-rounded fp32 logits) → the token of generation step t."""
+    def _head(self, x_rows: torch.Tensor, t: int, b0: int = 0, b1: Optional[int] = None,
+              value_rows: Optional[torch.Tensor] = None) -> List[Op]:
+        """final RMSNorm → lm_head (bf16-rounded fp32 logits) → the token of generation step t. `value_rows`: the rows the
+        critic reads where they are not `x_rows` (group=: the P prompt rows)."""
         logits = self.logits[t][b0:b1]
         norm_lin = functools.partial(self._norm_lin, fused=head_fused(logits.shape[0], self.dims), b0=b0, b1=b1)
-        return head(self.w, x_rows, logits, norm_lin, [self._pick(logits, t, b0, b1)] + self._value(x_rows, t, b0, b1))
+        return head(self.w, x_rows, logits, norm_lin,
+                    [self._pick(logits, t, b0, b1)] + self._value(x_rows if value_rows is None else value_rows, t, b0, b1))
 
     def _value(self, x_rows: torch.Tensor, t: int, b0: int = 0, b1: Optional[int] = None) -> List[Op]:
         """The critic over the residual rows generation step t's lm_head reads, into values[t] (nothing without a head, and
@@ -513,6 +560,9 @@ class OpenVLAEngine:
         d, B, pos = self.dims, self.B, self.S + t - 1
         D, H, hd = d.llm_dim, d.llm_heads, d.head_dim
         (cos, sin), kc, vc = rope or (self.cos, self.sin), self.k_cache[l], self.v_cache[l]
+        if self.group:      # the prompt's rows in place, the row's own tokens in its gen cache (fused form only: checked at build)
+            return [ops.attention_decode_rope_shared(qkv, kc, vc, self.k_gen[l], self.v_gen[l], ao, cos, sin, group=self.group, H=H,
+                                                     head_dim=hd, prefix_len=self.S, pos=pos, run=False)]
         if fused:
             # padded: every sequence appends at its own position (over its pad rows): the cache layout, and with
             # it every sum, is the one of the sequence's un-padded run
@@ -548,12 +598,15 @@ class OpenVLAEngine:
         step (no step reads the caches any more)."""
         if not self.beams or self.beams == 1 or not 1 <= t <= self.n_new - 2:
             return []
+        if self.group:      # the generated rows live in the gen caches, from row 0; the prompt caches are never reordered
+            return [ops.beam_reorder_kv(self.kv_table, self.k_gen + self.v_gen, self.beams, self.beam_parent[t], 0, t, run=False)]
         return [ops.beam_reorder_kv(self.kv_table, self.k_cache + self.v_cache, self.beams, self.beam_parent[t],
                                     self.rope_pos[1] if self.padded else self.S, t, run=False)]
 
     def _per_beam(self, t: Optional[torch.Tensor], what: str) -> Optional[torch.Tensor]:
-        """A beam engine's inputs are given per prompt: [B / W, …] → every prompt's W rows."""
-        if not self.beams or t is None:
+        """A beam engine's inputs are given per prompt: [B / W, …] → every prompt's W rows (group=: the prompts stay as they
+        are, one prefill row each)."""
+        if not self.beams or t is None or self.group:
             return t
         if t.shape[0] != self.B // self.beams:
             raise ValueError(f"engine built for {self.B // self.beams} prompts of {self.beams} beams, got {what} {tuple(t.shape)}")
@@ -605,20 +658,21 @@ class OpenVLAEngine:
             self._graph.replay()
 
     def set_inputs(self, input_ids: torch.Tensor, pixel_values: torch.Tensor) -> None:
-        """The batch's prompts and images (beams=W: the B / W prompts, each replicated to its W rows)."""
+        """The batch's prompts and images (beams=W: the B / W prompts, each replicated to its W rows; group=G: the B / G
+        prompts as they are)."""
         self._fill_inputs(self._per_beam(input_ids, "input_ids"), self._per_beam(pixel_values, "pixel_values"))
 
     def _fill_inputs(self, input_ids: torch.Tensor, pixel_values: torch.Tensor) -> None:
-        if tuple(input_ids.shape) != (self.B, self.L):
-            raise ValueError(f"engine built for input_ids {(self.B, self.L)}, got {tuple(input_ids.shape)}")
+        if tuple(input_ids.shape) != (self.P, self.L):
+            raise ValueError(f"engine built for input_ids {(self.P, self.L)}, got {tuple(input_ids.shape)}")
         if self.text_only:
             if pixel_values is not None:
                 raise ValueError("a text_only engine takes no pixel_values")
             self.input_ids.copy_(input_ids)
             self.epoch += 1
             return
-        if tuple(pixel_values.shape) != (self.B, 6, 224, 224):
-            raise ValueError(f"pixel_values must be [{self.B}, 6, 224, 224]")
+        if tuple(pixel_values.shape) != (self.P, 6, 224, 224):
+            raise ValueError(f"pixel_values must be [{self.P}, 6, 224, 224]")
         self.input_ids.copy_(input_ids)
         self.pixel_values.copy_(pixel_values.to(torch.bfloat16))
         self.epoch += 1

@@ -213,8 +213,11 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
     def engine(self, batch: int, prompt_len: int, n_new: int = 7, padded: bool = False, cached: bool = False,
                sample: bool = False, score: bool = False, score_range: Optional[Tuple[int, int]] = None,
                vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None,
-               attn_taps: Optional[AttnTaps] = None, value: Optional[str] = None, beams: Optional[int] = None) -> OpenVLAEngine:
-        """`beams` (W): the beam-search engine of `batch` / W prompts (`OpenVLAEngine(beams=)`); part of the cache key only
+               attn_taps: Optional[AttnTaps] = None, value: Optional[str] = None, beams: Optional[int] = None,
+               group: Optional[int] = None) -> OpenVLAEngine:
+        """`group` (G): the engine whose `batch` rows are `batch` / G prompts with one shared prefill each
+        (`OpenVLAEngine(group=)`, behind `share_prefill=True`); part of the cache key only when given.
+        `beams` (W): the beam-search engine of `batch` / W prompts (`OpenVLAEngine(beams=)`); part of the cache key only
         when given.
         `value` ("action" | "token", see `attach_value_head`): an engine whose plan also evaluates the attached value
         head; the level and the head's identity join the cache key only when given.
@@ -241,12 +244,13 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
             (("vocab", vocab_range) if vocab_range is not None else ()) + (("adapted",) if adapted else ()) + \
             ((("taps", attn_taps.key(self.dims.llm_layers)),) if attn_taps is not None else ()) + \
             ((("value", value, id(self._value_head)),) if value is not None else ()) + \
-            ((("beams", int(beams)),) if beams is not None else ())
+            ((("beams", int(beams)),) if beams is not None else ()) + ((("group", int(group)),) if group is not None else ())
         return self._lru(self._engines, key,
                          lambda: OpenVLAEngine(weights, batch, prompt_len, n_new=n_new, fp8=fp8 and not padded, padded=padded,
                                                sample=sample, score=score, score_range=score_range, vocab_range=vocab_range,
                                                attn_taps=attn_taps, value=value,
-                                               value_head=self._value_head if value is not None else None, beams=beams))
+                                               value_head=self._value_head if value is not None else None, beams=beams,
+                                               **({} if group is None else dict(group=group))))
 
     # ---- where the action tokens attend (attention_taps.py) ----
     @staticmethod
@@ -494,7 +498,12 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         prompt-major and best first, as HF shapes them; `return_weights=True` adds wt [B·R, max_new_tokens, 2], every token's
         weight pair under the unwarped policy given the tokens before it. `vocab_range`, `use_adapters` and
         `return_values="action"` combine with it; `sampling=`, `do_sample`, `forced_ids`, `return_attention` and
-        `return_values="token"` raise ValueError. `num_beams=1` is the call without it."""
+        `return_values="token"` raise ValueError. `num_beams=1` is the call without it.
+        `share_prefill=True` prefills every prompt once where the call asks several things about it: with `num_beams=W` the W
+        beams, with `forced_ids` [B, K, n] the K candidates (rows come back prompt-major, [B·K, …]; `sampling` then holds one
+        entry per row; B·K <= 16). Results are those of the replicated call, bit for bit. Padded prompts, `return_attention`,
+        `return_values="token"` and `model.fp8` raise ValueError with it; a call with one row per prompt has nothing to share
+        and runs as without it."""
         return present(*self._generate(input_ids, max_new_tokens, pixel_values, attention_mask, **kwargs))
 
     def _generate(self, input_ids: torch.LongTensor, max_new_tokens: int = 7, pixel_values: Optional[torch.Tensor] = None,
@@ -504,11 +513,28 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
                   vocab_range: Optional[Tuple[int, int]] = None, use_adapters: Optional[bool] = None,
                   return_attention: Optional[str] = None, attention_layers=None, text_splits=None,
                   return_values: Optional[str] = None, num_beams: int = 1, num_return_sequences: Optional[int] = None,
-                  **_: Any) -> EngineResult:
+                  share_prefill: bool = False, group: Optional[int] = None, **_: Any) -> EngineResult:
         """`generate` as a record: its argument checks, one engine run, and the run's `EngineResult` with `ids` = prompt ‖
         new tokens and `wt` only where `generate` returns it. What `predict_action` / `score_actions` read by field.
-        Keywords it does not know (`use_cache`, `length_penalty`, `early_stopping`) are accepted and ignored."""
+        Keywords it does not know (`use_cache`, `length_penalty`, `early_stopping`) are accepted and ignored.
+        `group=G` (with share_prefill=True; what `sample_actions` passes): G rows per prompt, prompt-major, over one prefill
+        of each prompt — `sampling` and a 2-D `forced_ids` then hold one entry per ROW."""
         W, R = self._beam_args(num_beams, num_return_sequences, vocab_range)
+        if group is not None and not share_prefill:
+            raise ValueError("group= goes with share_prefill=True")
+        if forced_ids is not None and torch.as_tensor(forced_ids).dim() == 3:        # [B, K, n]: K candidates per prompt
+            if not share_prefill or group is not None:
+                raise ValueError("forced_ids [B, K, n] goes with share_prefill=True (it is the group: no group= beside it)")
+            forced_ids = torch.as_tensor(forced_ids)
+            group, forced_ids = int(forced_ids.shape[1]), forced_ids.reshape(-1, forced_ids.shape[2])
+        if share_prefill:       # whatever the group engine rejects is refused here with its reason: no silent fall-back
+            for on, why in ((attention_mask is not None and not bool(torch.as_tensor(attention_mask).bool().all()),
+                             "padded prompts put every row at its own position; the shared decode kernel has one"),
+                            (return_attention is not None, "return_attention: the taps read one cache per row"),
+                            (return_values == "token", 'return_values="token" is not built for shared prefills ("action" is)'),
+                            (bool(getattr(self, "fp8", False)), "model.fp8: the e4m3 prefill is not the path it is specified against")):
+                if on:
+                    raise ValueError(f"share_prefill=True: {why}")
         if W > 1:
             for on, why in ((sampling is not None or do_sample, "sampling= / do_sample draw tokens, beam search ranks them"),
                             (forced_ids is not None, "forced_ids scores given tokens, beam search chooses its own"),
@@ -532,27 +558,31 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
         if forced is None and score_range is not None:
             raise ValueError("score_range goes with forced_ids=")
         if W > 1:       # the best R of every prompt's W beams, prompt-major
-            r = self._run_beams(ids, pv, max_new_tokens, attention_mask, W, R, vocab_range, use_adapters, value)
+            r = self._run_beams(ids, pv, max_new_tokens, attention_mask, W, R, vocab_range, use_adapters, value, share_prefill)
             return r._replace(ids=torch.cat([ids.repeat_interleave(R, dim=0), r.ids], dim=1), wt=r.wt if return_weights else None)
         r = self._run_engine(ids, pv, max_new_tokens, attention_mask, sampling, forced, score_range, vocab_range, use_adapters,
-                             taps, text_splits, value)
-        return r._replace(ids=torch.cat([ids, r.ids], dim=1), wt=r.wt if return_weights or forced is not None else None)
+                             taps, text_splits, value, group)
+        rows = ids if group is None else ids.repeat_interleave(group, dim=0)
+        return r._replace(ids=torch.cat([rows, r.ids], dim=1), wt=r.wt if return_weights or forced is not None else None)
 
     @torch.no_grad()
     def _run_engine(self, ids: torch.Tensor, pv: torch.Tensor, n_new: int, attention_mask: Optional[torch.Tensor],
                     sampling: Optional[SamplingParams], forced: Optional[torch.Tensor], score_range, vocab_range,
-                    use_adapters: Optional[bool], taps: Optional[AttnTaps], text_splits, value: Optional[str]) -> EngineResult:
+                    use_adapters: Optional[bool], taps: Optional[AttnTaps], text_splits, value: Optional[str],
+                    group: Optional[int] = None) -> EngineResult:
         """The one path of every generation call through an engine: choose it, fill its settings, forced ids, inputs and
         segments (after the inputs: `set_padded_inputs` resets them), run the plan. Returns copies: nothing handed out
-        aliases an engine buffer. The model's engines are not captured, so `replay()` launches the plan eagerly."""
+        aliases an engine buffer. The model's engines are not captured, so `replay()` launches the plan eagerly.
+        `group=G`: the engine of ids.shape[0] · G rows over one prefill per prompt (`OpenVLAEngine(group=)`)."""
         score = forced is not None
         padded = attention_mask is not None and not bool(attention_mask.bool().all())
         if sampling is None and score:
             sampling = SamplingParams()                              # the unwarped distribution (a score has no seed)
         elif sampling is None and vocab_range is not None:
             sampling = SamplingParams(temperature=0.0, seed=0)       # constrained greedy decoding
-        eng = self.engine(*ids.shape, n_new, padded=padded, sample=sampling is not None and not score, score=score,
-                          score_range=score_range, vocab_range=vocab_range, use_adapters=use_adapters, attn_taps=taps, value=value)
+        eng = self.engine(ids.shape[0] * (group or 1), ids.shape[1], n_new, padded=padded, sample=sampling is not None and not score,
+                          score=score, score_range=score_range, vocab_range=vocab_range, use_adapters=use_adapters, attn_taps=taps,
+                          value=value, group=group)
         if sampling is not None:
             eng.set_sampling(sampling)
         if score:
@@ -581,24 +611,28 @@ class PrismaticForConditionalGeneration(PrismaticPreTrainedModel):
 
     @torch.no_grad()
     def _run_beams(self, ids: torch.Tensor, pv: torch.Tensor, n_new: int, attention_mask: Optional[torch.Tensor], W: int, R: int,
-                   vocab_range, use_adapters: Optional[bool], value: Optional[str]) -> EngineResult:
+                   vocab_range, use_adapters: Optional[bool], value: Optional[str], share_prefill: bool = False) -> EngineResult:
         """Beam search of W beams for every prompt, the best R of each returned prompt-major: ids [B·R, n_new], wt
         [B·R, n_new, 2], values [B·R] (V(s) is the prompt's: the same for its R rows). The prompts are split over engine
         runs of max(1, 16 // W) prompts — a prompt's beams are never split, and every run stays within the 16 rows where a
-        sequence's result is its batch-1 result — so a prompt's beams do not depend on the prompts around it."""
+        sequence's result is its batch-1 result — so a prompt's beams do not depend on the prompts around it.
+        `share_prefill=True`: the same runs on the group=W engine — every prompt is prefilled once, not W times."""
         B = ids.shape[0]
         padded = attention_mask is not None and not bool(attention_mask.bool().all())
         per_run, parts = max(1, 16 // W), []
         for e0 in range(0, B, per_run):
             c = min(per_run, B - e0)
             eng = self.engine(c * W, ids.shape[1], n_new, padded=padded, vocab_range=vocab_range, use_adapters=use_adapters,
-                              value=value, beams=W)
+                              value=value, beams=W, group=W if share_prefill else None)
             if padded:
                 eng.set_padded_inputs(ids[e0:e0 + c], pv[e0:e0 + c], attention_mask[e0:e0 + c])
             else:
                 eng.set_inputs(ids[e0:e0 + c], pv[e0:e0 + c])
             eng.replay()
-            parts.append(eng.result(torch.clone))
+            r = eng.result(torch.clone)
+            if share_prefill and r.values is not None:      # one V(s) per prompt → per row, as the replicated engine hands it out
+                r = r._replace(values=r.values.repeat_interleave(W))
+            parts.append(r)
         best = lambda x: x.reshape((-1, W) + tuple(x.shape[1:]))[:, :R].reshape((-1,) + tuple(x.shape[1:]))
         return EngineResult(ids=torch.cat([best(p.ids) for p in parts]), wt=torch.cat([best(p.wt) for p in parts]),
                             values=None if value is None else torch.cat([best(p.values) for p in parts]))
@@ -614,6 +648,37 @@ def copy_runs(B: int, K: int) -> List[Tuple[int, int]]:
     to 16 keep "a sequence's result is its batch-1 result"."""
     per_run = max(1, 16 // B)
     return [(j0, min(per_run, K - j0)) for j0 in range(0, K, per_run)]
+
+
+def group_runs(B: int, K: int) -> List[Tuple[int, int, int, int]]:
+    """(first prompt b0, prompts nb, first copy j0, copies c) of the engine runs that cover K copies of B prompts with ONE
+    prefill per prompt and run (`share_prefill=True`): rows are prompt-major, row (b - b0)·c + (j - j0). K <= 16: a prompt's K
+    rows are never split, max(1, 16 // K) prompts per run. K > 16: the copies are cut into chunks of at most 16, each run of
+    them with its own prefill. No run exceeds 16 rows: "a sequence's result is its batch-1 result" holds in every one."""
+    runs = []
+    for j0 in range(0, K, 16):
+        c = min(16, K - j0)
+        per_run = max(1, 16 // c)
+        runs += [(b0, min(per_run, B - b0), j0, c) for b0 in range(0, B, per_run)]
+    return runs
+
+
+def group_sampling(T, k, p, seed, b0: int, nb: int, j0: int, c: int) -> SamplingParams:
+    """The resolved per-sequence settings [B] for prompts b0 … b0 + nb - 1 and copies j0 … j0 + c - 1, prompt-major [nb·c]:
+    copy j draws with `derive_seed(seed, j)` whatever the chunking; seed=None (a score has none): 0."""
+    rows = slice(b0, b0 + nb)
+    return SamplingParams(temperature=np.repeat(T[rows], c), top_k=np.repeat(k[rows], c), top_p=np.repeat(p[rows], c),
+                          seed=0 if seed is None else np.stack([derive_seed(seed[rows], j) for j in range(j0, j0 + c)], axis=1).reshape(-1))
+
+
+def stack_groups(parts: Sequence, runs: Sequence[Tuple[int, int, int, int]], B: int, K: int):
+    """Per-run arrays [nb·c, …] (prompt-major, `group_runs`; None: absent) → [B, K, …]."""
+    if parts[0] is None:
+        return None
+    out = np.empty((B, K) + tuple(parts[0].shape[1:]), dtype=parts[0].dtype)
+    for x, (b0, nb, j0, c) in zip(parts, runs):
+        out[b0:b0 + nb, j0:j0 + c] = np.asarray(x).reshape((nb, c) + tuple(x.shape[1:]))
+    return out
 
 
 def tile_sampling(T, k, p, seed, j0: int, c: int) -> SamplingParams:
@@ -719,7 +784,9 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         wt, values = _numpy(r.wt), _numpy(r.values)
         if R > 1:       # [B, R, …], best first; V(s) is the prompt's
             actions, tokens = np.asarray(actions).reshape(B, R, n), tokens.reshape(B, R, n)
-            wt, values = None if wt is None else wt.reshape(B, R, n, 2), None if values is None else values[::R].copy()
+            if values is not None and kwargs.get("group") is None:      # a group engine's values are the prompts' already
+                values = values[::R].copy()
+            wt = None if wt is None else wt.reshape(B, R, n, 2)
         return SimpleNamespace(actions=actions, tokens=tokens, wt=wt, values=values, attention=r.attention)
 
     def _action_prompt(self, input_ids: torch.LongTensor, m: Optional[torch.Tensor]):
@@ -746,8 +813,12 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
                        num_samples: int = 1, attention_mask: Optional[torch.Tensor] = None,
                        action_tokens_only: bool = False,
                        use_adapters: Optional[bool] = None, return_attention: Optional[str] = None, attention_layers=None,
-                       text_splits=None, return_values: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """`use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy).
+                       text_splits=None, return_values: Optional[str] = None,
+                       share_prefill: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`share_prefill=True` prefills every prompt once per engine run instead of once per copy (`OpenVLAEngine(group=)`,
+        runs by `group_runs`): the same arrays, bit for bit, for less work. Padded prompts, `return_attention`,
+        `return_values="token"` and `model.fp8` raise ValueError with it: nothing falls back silently.
+        `use_adapters`: see `engine` (None: under the attached adapters if any; False: the base policy).
         `return_values="action"` appends V(s) fp32 [B] — every copy of a sequence is in the same state, so one value per
         sequence, taken from copy 0; `"token"` appends [B, num_samples, n], the values along every copy's own tokens. Order:
         actions, tokens, logprobs, values, attention.
@@ -769,6 +840,20 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         T, k, p, seed = sampling.resolve(B)
         keys = list(unnorm_key) if isinstance(unnorm_key, (list, tuple)) else None
         level = self._value_level(return_values)
+        if share_prefill:
+            groups = group_runs(B, num_samples)
+            runs = [self._predict(input_ids[b0:b0 + nb], keys[b0:b0 + nb] if keys is not None else unnorm_key, action_tokens_only,
+                                  use_adapters, pixel_values=pixel_values[b0:b0 + nb],
+                                  attention_mask=None if attention_mask is None else attention_mask[b0:b0 + nb],
+                                  sampling=group_sampling(T, k, p, seed, b0, nb, j0, c), return_weights=True, return_values=level,
+                                  return_attention=return_attention, share_prefill=True, group=c)
+                    for b0, nb, j0, c in groups]
+            flat = lambda x: np.asarray(x).reshape((-1,) + tuple(np.shape(x)[-1:]))
+            first = [i for i, g in enumerate(groups) if g[2] == 0]       # V(s) is the prompt's: the runs of copy 0 cover every prompt
+            return present(stack_groups([flat(r.actions) for r in runs], groups, B, num_samples),
+                           stack_groups([flat(r.tokens) for r in runs], groups, B, num_samples),
+                           stack_groups([logprob(r.wt).reshape(flat(r.tokens).shape) for r in runs], groups, B, num_samples),
+                           None if level is None else np.concatenate([runs[i].values for i in first]))
         runs = [self._predict(input_ids.repeat(c, 1), keys * c if keys is not None else unnorm_key, action_tokens_only, use_adapters,
                               pixel_values=pixel_values.repeat(c, 1, 1, 1),
                               attention_mask=None if attention_mask is None else attention_mask.repeat(c, 1),
@@ -783,8 +868,9 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
                      unnorm_key: Union[str, Sequence[Optional[str]], None] = None, num_beams: int = 4,
                      num_return_sequences: Optional[int] = None, attention_mask: Optional[torch.Tensor] = None,
                      action_tokens_only: bool = False, use_adapters: Optional[bool] = None,
-                     return_values: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """The `num_return_sequences` (None: all `num_beams`) most likely whole actions that beam search of `num_beams` beams
+                     return_values: Optional[str] = None, share_prefill: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`share_prefill=True`: every prompt is prefilled once, not once per beam (see `sample_actions`); same arrays.
+        The `num_return_sequences` (None: all `num_beams`) most likely whole actions that beam search of `num_beams` beams
         finds for every prompt, best first, in the shapes of `sample_actions`: → (actions [B, R, n], token_ids int64
         [B, R, n], logprobs fp64 [B, R, n]). logprobs = `sampling.logprob` of the per-token weight pairs: every token's
         log-probability under the unwarped policy given the tokens before it (their sum is the action's joint
@@ -803,7 +889,12 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
             raise ValueError("beam_actions: a list of unnorm_keys needs one key per sequence, all of one action dimension")
         n = self.get_action_dim(keys[0] if keys is not None else unnorm_key)
         ids, m = self._action_prompt(input_ids.to(self.device), attention_mask)
-        r = self._run_beams(ids, pixel_values.to(self.device), n, m, W, R, vocab_range, use_adapters, level)
+        if share_prefill:
+            if m is not None and not bool(m.bool().all()):
+                raise ValueError("share_prefill=True: padded prompts put every row at its own position; the shared decode kernel has one")
+            if bool(getattr(self, "fp8", False)):
+                raise ValueError("share_prefill=True: model.fp8: the e4m3 prefill is not the path it is specified against")
+        r = self._run_beams(ids, pixel_values.to(self.device), n, m, W, R, vocab_range, use_adapters, level, share_prefill)
         tokens = r.ids.cpu().numpy()
         row_keys = [unnorm_key] * (B * R) if keys is None else [k for k in keys for _ in range(R)]
         actions = np.stack([np.asarray(self.actions_from_token_ids(tokens[i:i + 1], k)).reshape(-1) for i, k in enumerate(row_keys)])
@@ -815,8 +906,10 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
                       attention_mask: Optional[torch.Tensor] = None, return_bins: bool = False,
                       action_tokens_only: bool = False, use_adapters: Optional[bool] = None,
                       return_attention: Optional[str] = None, attention_layers=None, text_splits=None,
-                      return_values: Optional[str] = None):
-        """`return_values="action"` appends V(s) fp32 [B] (the state is the same for every candidate: candidate 0's);
+                      return_values: Optional[str] = None, share_prefill: bool = False):
+        """`share_prefill=True`: every prompt is prefilled once per engine run, not once per candidate (see `sample_actions`);
+        the same arrays, bit for bit.
+        `return_values="action"` appends V(s) fp32 [B] (the state is the same for every candidate: candidate 0's);
         `"token"` appends [B, K, n], the values along the given tokens. `return_attention=` (with `attention_layers=`,
         `text_splits=` [B, k]; see `generate`) appends the `ActionAttention` under the GIVEN actions, tensors [B, K, n, layers,
         H, ·]. Order: logprobs, then (wt, bin_wt) with `return_bins`, then the values, then the `ActionAttention`.
@@ -855,6 +948,19 @@ class OpenVLAForActionPrediction(PrismaticForConditionalGeneration):
         rng = (self.vocab_size - n_bins, n_bins) if return_bins else None
         ids, m = self._action_prompt(input_ids.to(self.device), attention_mask)      # the prompt as predict_action prepares it
         level = self._value_level(return_values)
+        if share_prefill:
+            groups = group_runs(B, K)
+            runs = [self._generate(ids[b0:b0 + nb], n, pixel_values=pixel_values[b0:b0 + nb],
+                                   attention_mask=None if m is None else m[b0:b0 + nb],
+                                   sampling=group_sampling(T, k, p, None, b0, nb, j0, c),
+                                   forced_ids=torch.from_numpy(np.ascontiguousarray(tok[b0:b0 + nb, j0:j0 + c])), score_range=rng,
+                                   vocab_range=self.action_token_range() if action_tokens_only else None, use_adapters=use_adapters,
+                                   return_values=level, return_attention=return_attention, share_prefill=True)
+                    for b0, nb, j0, c in groups]
+            wt = stack_groups([_numpy(r.wt) for r in runs], groups, B, K)
+            first = [i for i, g in enumerate(groups) if g[2] == 0]
+            return present(logprob(wt), wt if return_bins else None, stack_groups([_numpy(r.range_wt) for r in runs], groups, B, K),
+                           None if level is None else np.concatenate([_numpy(runs[i].values) for i in first]))
         runs = []
         for j0, c in copy_runs(B, K):
             forced = torch.from_numpy(np.ascontiguousarray(tok[:, j0:j0 + c].transpose(1, 0, 2)).reshape(c * B, n))

@@ -20,7 +20,7 @@ from ._lib import (AttnDesc, GemmDesc, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_KE
                    EPI_NONE, EPI_SWIGLU_BWD, EPI_SWIGLU_KEEP,
                    EPI_RES, EPI_SWIGLU)
 
-__all__ = ["Op", "gemm", "gemm_last_form", "gemm_form_name", "gemm_fp8", "linear_fp8", "Fp8Weight", "quantize_rows_fp8", "quantize_weight_fp8", "quantize_packed_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "attention_probs", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
+__all__ = ["Op", "gemm", "gemm_last_form", "gemm_form_name", "gemm_fp8", "linear_fp8", "Fp8Weight", "quantize_rows_fp8", "quantize_weight_fp8", "quantize_packed_weight_fp8", "pack_weight", "unpack_weight", "cross_entropy", "layernorm", "rmsnorm", "rmsnorm_skinny", "skinny_rows_supported", "attention", "attention_rope", "attention_decode", "attention_decode_rope", "attention_decode_rope_grouped", "attention_decode_rope_shared", "repeat_rows", "attention_probs", "gather_rows", "skinny_supported", "rope_kvcache", "embed_splice",
            "argmax", "sample", "score", "beam_step", "cache_table", "beam_reorder_kv", "im2col_patch14", "preprocess_u8", "resample_coeffs", "resize_bicubic_u8", "resize_u8", "crop_resize_bilinear_u8", "augment_frames_u8", "write_prefix_tokens", "fill_synth", "run_all",
            "EPI_NONE", "EPI_BIAS", "EPI_BIAS_GELU", "EPI_BIAS_RES", "EPI_RES", "EPI_SWIGLU", "EPI_F32", "EPI_F32_BF16R",
            "EPI_SWIGLU_KEEP", "EPI_BIAS_GELU_KEEP", "EPI_SWIGLU_BWD", "EPI_GELU_BWD"]
@@ -687,6 +687,55 @@ def attention_decode_rope_grouped(qkv: torch.Tensor, k_caches: Sequence[torch.Te
                    (D, head_dim, D), False, head_dim ** -0.5, None)
     return _op(name, (C.byref(d), cos.data_ptr(), sin.data_ptr(), G, kp, vp) + tail,
                (d, qkv, o, cos, sin, kp, vp, tab, list(k_caches), list(v_caches)) + held, run)
+
+
+def attention_decode_rope_shared(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_gen: torch.Tensor,
+                                 v_gen: torch.Tensor, o: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, *, group: int, H: int,
+                                 head_dim: int, prefix_len: int, pos: int, scale: Optional[float] = None,
+                                 gq: Optional[int] = None, run: bool = True) -> Op:
+    """One decode step's attention for rows that share a prompt (bl_attention_decode_rope_shared_bf16): qkv [R, 3*H*hd] is
+    the step's fused projection of R = P*group rows, row r belongs to prompt r // group. k_cache / v_cache [P, H, cache_len,
+    hd] hold the prompts' rows 0 .. prefix_len-1 and are only read; k_gen / v_gen [R, H, gen_len, hd] hold every row's own
+    generated tokens: rows 0 .. pos-prefix_len-1 are keys prefix_len .. pos-1, and the step's k', v are appended at row
+    pos - prefix_len. o [R, H*hd]. Per row the bits of attention_decode_rope on replicated caches. gq (2, 4, 8): the rows
+    per workgroup, None = the library's choice."""
+    fn = "attention_decode_rope_shared"
+    D = H * head_dim
+    _contig_bf16(fn, (qkv, "qkv"), (k_cache, "k_cache"), (v_cache, "v_cache"), (k_gen, "k_gen"), (v_gen, "v_gen"), (o, "o"),
+                 (cos, "cos"), (sin, "sin"))
+    if k_cache.dim() != 4 or tuple(v_cache.shape) != tuple(k_cache.shape) or tuple(k_cache.shape[1::2]) != (H, head_dim):
+        raise ValueError(f"{fn}: prompt caches must both be [P, {H}, cache_len, {head_dim}]")
+    P, cache_len = k_cache.shape[0], k_cache.shape[2]
+    R = P * int(group)
+    if not 1 <= group <= 16 or tuple(qkv.shape) != (R, 3 * D) or tuple(o.shape) != (R, D):
+        raise ValueError(f"{fn}: group in 1 .. 16, qkv [{R}, {3 * D}] and o [{R}, {D}] for {P} prompts of {group} rows")
+    if k_gen.dim() != 4 or tuple(v_gen.shape) != tuple(k_gen.shape) or (k_gen.shape[0], k_gen.shape[1], k_gen.shape[3]) != (R, H, head_dim):
+        raise ValueError(f"{fn}: gen caches must both be [{R}, {H}, gen_len, {head_dim}]")
+    gen_len = k_gen.shape[2]
+    if not 1 <= prefix_len <= cache_len or not prefix_len <= pos < prefix_len + gen_len or pos >= cos.shape[0]:
+        raise ValueError(f"{fn}: prefix_len {prefix_len} / pos {pos} outside the prompt cache ({cache_len} rows), the gen cache "
+                         f"({gen_len} rows) or the rope table")
+    scale = head_dim ** -0.5 if scale is None else scale
+    cs = (H * cache_len * head_dim, cache_len * head_dim, head_dim)
+    d = _attn_desc(qkv, k_cache, v_cache, o, R, H, 1, pos + 1, head_dim, (3 * D, head_dim, 3 * D), cs, cs, (D, head_dim, D),
+                   False, scale, None)
+    args = (C.byref(d), cos.data_ptr(), sin.data_ptr(), pos, int(group), prefix_len, k_gen.data_ptr(), v_gen.data_ptr(), gen_len)
+    keep = (d, qkv, k_cache, v_cache, k_gen, v_gen, o, cos, sin)
+    if gq is None:
+        return _op("bl_attention_decode_rope_shared_bf16", args, keep, run)
+    return _op("bl_attention_decode_rope_shared_gq_bf16", args + (int(gq),), keep, run)
+
+
+def repeat_rows(src: torch.Tensor, dst: torch.Tensor, group: int, run: bool = True) -> Op:
+    """dst[r * group + j] = src[r] (bl_repeat_rows_bf16): src [rows, W] with contiguous rows (any row stride), dst contiguous
+    [rows * group, W]. A pure 16-byte copy, no allocation: usable inside a captured graph."""
+    _bf16(src, "src"); _bf16(dst, "dst")
+    if src.dim() != 2 or src.stride(1) != 1 or group < 1 or tuple(dst.shape) != (src.shape[0] * group, src.shape[1]) or not dst.is_contiguous():
+        raise ValueError(f"repeat_rows: src [rows, W] with contiguous rows, dst contiguous [rows * {group}, W]; got "
+                         f"{tuple(src.shape)} stride {src.stride()} -> {tuple(dst.shape)}")
+    rows, Wd = src.shape
+    return _op("bl_repeat_rows_bf16", (src.data_ptr(), _rows(src, "src"), dst.data_ptr(), Wd, rows, Wd, int(group)), (src, dst), run,
+               nbytes=2.0 * rows * Wd * (1 + group))
 
 
 def gather_rows(src: torch.Tensor, row_index: torch.Tensor, dst: torch.Tensor, run: bool = True) -> Op:

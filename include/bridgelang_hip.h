@@ -265,6 +265,30 @@ int bl_attention_decode_rope_grouped_bf16(const bl_attn_desc* d, const bl_bf16* 
 int bl_attention_decode_rope_pos_grouped_bf16(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab,
                                               int32_t n_groups, bl_bf16* const* k_caches, bl_bf16* const* v_caches,
                                               const int32_t* const* rope_pos, int32_t cache_len, void* stream);
+/* bl_attention_decode_rope_bf16 for rows that SHARE a prompt (samples of one observation, candidates, beams), without a copy
+ * of the prompt's cache rows: d->q is the step's fused qkv [R, 3*H*128] of R = P*group rows (d->B = R), row r belongs to
+ * prompt p = r / group. d->k / d->v are the PROMPT caches [P, H, cache_len, 128] (strides d->k_* / d->v_*, batch stride per
+ * prompt), read only; k_gen / v_gen are contiguous [R, H, gen_len, 128] caches of the rows' own generated tokens. Row r's
+ * keys 0 … prefix_len-1 are prompt p's cache rows, keys prefix_len … pos-1 rows 0 … pos-prefix_len-1 of its own gen cache,
+ * and key `pos` is the step's new token, rotated at `pos` and appended to gen row pos - prefix_len. o [R, H*128]
+ * (d->o_*); d->Skv must equal pos + 1. Per row bit-identical to bl_attention_decode_rope_bf16 on caches that hold the
+ * prompt rows followed by the generated rows. One workgroup serves several rows of one (prompt, head) and loads each prompt
+ * row once for all of them. head_dim != 128, group outside 1 … 16, R % group != 0, prefix_len < 1, pos < prefix_len,
+ * pos - prefix_len >= gen_len, pos >= 2048 or a cache head stride that does not hold prefix_len rows: BL_E_SHAPE; a NULL
+ * pointer or a key mask in the descriptor (every row attends to all of its keys, at one common position): BL_E_ARG; nothing
+ * is launched on a rejection. */
+int bl_attention_decode_rope_shared_bf16(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab, int32_t pos,
+                                         int32_t group, int32_t prefix_len, bl_bf16* k_gen, bl_bf16* v_gen, int32_t gen_len,
+                                         void* stream);
+/* The same with the rows per workgroup given: gq in {2, 4, 8} (else BL_E_ARG). Every gq gives the same bits; the entry point
+ * above uses the one measured fastest (tools/bench_shared_prefill.py times all three). */
+int bl_attention_decode_rope_shared_gq_bf16(const bl_attn_desc* d, const bl_bf16* cos_tab, const bl_bf16* sin_tab, int32_t pos,
+                                            int32_t group, int32_t prefix_len, bl_bf16* k_gen, bl_bf16* v_gen, int32_t gen_len,
+                                            int32_t gq, void* stream);
+/* dst[r * group + j, :cols] = src[r, :cols] for r < rows, j < group: every bf16 row replicated group-fold (the step-0 residual
+ * rows of a shared prefill). 16-byte copies: cols, ld_src, ld_dst multiples of 8 (BL_E_SHAPE / BL_E_ALIGN). */
+int bl_repeat_rows_bf16(const bl_bf16* src, int64_t ld_src, bl_bf16* dst, int64_t ld_dst, int64_t rows, int32_t cols,
+                        int32_t group, void* stream);
 
 /* ---- Llama glue -------------------------------------------------------------------------------------------- */
 /* Half-split RoPE (HF apply_rotary_pos_emb) on the q and k thirds of a fused qkv buffer [B*S, 3*H*hd], bf16 cos/sin
