@@ -103,6 +103,10 @@ SIGNATURES = {
     "bl_attention_rope_bf16": (C.c_int, [C.POINTER(AttnDesc), _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
     "bl_attention_lse_bf16": (C.c_int, [C.POINTER(AttnDesc), _vp, _vp]),
     "bl_attention_backward_bf16": (C.c_int, [C.POINTER(AttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bl_attention_tree_lse_bf16": (C.c_int, [C.POINTER(AttnDesc), _i32, _i32, _vp, _vp]),
+    "bl_attention_tree_backward_bf16": (C.c_int, [C.POINTER(AttnDesc), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bl_rope_pos_bf16": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "bl_rope_pos_backward_bf16": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "bl_attention_decode_bf16": (C.c_int, [C.POINTER(AttnDesc), _vp]),
     "bl_attention_probs_f32": (C.c_int, [C.POINTER(AttnDesc), _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32,
                                          _vp]),

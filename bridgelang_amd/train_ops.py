@@ -407,6 +407,49 @@ def attention_backward(q, k, v, o, dout, lse, delta, dq, dk, dv, *, B, H, Sq, Sk
                flops=14.0 * B * H * Sq * Skv * head_dim * (0.5 if causal else 1.0))
 
 
+def attention_tree_lse(q, k, v, o, lse, *, B, H, S, prefix, branch, head_dim, q_strides, k_strides, v_strides, o_strides,
+                       scale=None, key_mask=None, run: bool = True) -> Op:
+    """Training forward over the shared-prompt layout (bl_attention_tree_lse_bf16): every batch element is one prompt row
+    prefix ‖ G branches of `branch` rows, S = prefix + G·branch; lse fp32 [B*H*pad32(S)]."""
+    assert _f32(lse, "lse").numel() >= B * H * ((S + 31) // 32 * 32)
+    G = (S - prefix) // branch if branch > 0 else 0      # a bad branch is the library's to refuse
+    d = _attn_desc(q, k, v, o, B, H, S, S, head_dim, q_strides, k_strides, v_strides, o_strides, True,
+                   head_dim ** -0.5 if scale is None else scale, key_mask)
+    return _op("bl_attention_tree_lse_bf16", (C.byref(d), prefix, branch, lse.data_ptr()), (d, q, k, v, o, lse, key_mask), run,
+               flops=4.0 * B * H * head_dim * (0.5 * prefix * prefix + G * branch * (prefix + 0.5 * branch)))
+
+
+def attention_tree_backward(q, k, v, o, dout, lse, delta, dq, dk, dv, *, B, H, S, prefix, branch, head_dim, q_strides, k_strides,
+                            v_strides, o_strides, scale=None, key_mask=None, run: bool = True) -> Op:
+    for t in (lse, delta):
+        assert _f32(t, "lse/delta").numel() >= B * H * ((S + 31) // 32 * 32)
+    G = (S - prefix) // branch if branch > 0 else 0      # a bad branch is the library's to refuse
+    d = _attn_desc(q, k, v, o, B, H, S, S, head_dim, q_strides, k_strides, v_strides, o_strides, True,
+                   head_dim ** -0.5 if scale is None else scale, key_mask)
+    return _op("bl_attention_tree_backward_bf16",
+               (C.byref(d), prefix, branch, _bf16(dout, "dout").data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                _bf16(dq, "dq").data_ptr(), _bf16(dk, "dk").data_ptr(), _bf16(dv, "dv").data_ptr()),
+               (d, q, k, v, o, dout, lse, delta, dq, dk, dv, key_mask), run,
+               flops=14.0 * B * H * head_dim * (0.5 * prefix * prefix + G * branch * (prefix + 0.5 * branch)))
+
+
+def _rope_pos_args(qkv, what: str, cos, sin, pos, rows: int, H: int, head_dim: int):
+    if pos.dtype != torch.int32 or not pos.is_contiguous() or pos.numel() != rows:
+        raise ValueError(f"rope_pos: pos int32 [{rows}] contiguous")
+    return (_bf16(qkv, what).data_ptr(), _rows(qkv, what), rows, H, head_dim, cos.data_ptr(), sin.data_ptr(), pos.data_ptr())
+
+
+def rope_pos(qkv, cos, sin, pos, *, rows: int, H: int, head_dim: int, run: bool = True) -> Op:
+    """`rope` with a position per row: pos int32 [rows] on the device (bl_rope_pos_bf16)."""
+    return _op("bl_rope_pos_bf16", _rope_pos_args(qkv, "qkv", cos, sin, pos, rows, H, head_dim), (qkv, cos, sin, pos), run,
+               nbytes=8.0 * rows * H * head_dim)
+
+
+def rope_pos_backward(dqkv, cos, sin, pos, *, rows: int, H: int, head_dim: int, run: bool = True) -> Op:
+    return _op("bl_rope_pos_backward_bf16", _rope_pos_args(dqkv, "dqkv", cos, sin, pos, rows, H, head_dim), (dqkv, cos, sin, pos),
+               run, nbytes=8.0 * rows * H * head_dim)
+
+
 def pack(w: torch.Tensor, out: torch.Tensor, run: bool = True) -> Op:
     """Row-major [N, K] → fragment-major packed (bl_pack_weight_bf16) as a replayable Op (weights after an optimizer
     step; the transposed activations of a wgrad GEMM)."""

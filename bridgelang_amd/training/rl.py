@@ -90,7 +90,8 @@ def policy_batch(prompt_ids, attention_mask, token_ids, logprobs, advantages, pa
     """The training batch of one sampled action per sequence. prompt_ids int64 [B, lp] right-padded with attention_mask
     [B, lp] (None: no padding); token_ids int64 [B, n] and logprobs [B, n] as `sample_actions` reports them (K samples per
     prompt: repeat the prompt rows and flatten to [B·K, n] first); advantages [B], one per sequence, broadcast over its n
-    tokens. Every sequence is laid out as
+    tokens. Repeated that way, the K sequences of a prompt are consecutive and equal up to the action tokens: the group order
+    `TrainStep(shared_prompt=K, branch_len=n)` takes (one image per prompt there). Every sequence is laid out as
 
         prompt ‖ 29871 (the empty token, unless the prompt ends with it) ‖ the n action tokens ‖ EOS
 

@@ -35,6 +35,7 @@ from .linears import Linears, Scratch, ScratchSet
 from .param_store import STAGES, ParamStore, no_decay, param_sharded_key, pool_of, trainable_names      # noqa: F401  (re-exported)
 from .policy_loss import GROUP_STAT_NAMES, IS_STAT_NAMES, STAT_NAMES, PolicyLossConfig
 from .preference_loss import PAIR_STAT_NAMES, PREF_STAT_NAMES, SEQ_STAT_NAMES, PreferenceLossConfig, check_pairs
+from . import shared_prompt as SP
 from .sharding import ShardComm, comm_order
 from .unit_pools import UnitPools
 from .value_head import ValueHead
@@ -53,7 +54,8 @@ class TrainStep:
                  fp8_wgrad: bool = False, loss: str = "ce", policy: Optional[PolicyLossConfig] = None,
                  refresh_adapted: bool = False, preference: Optional[PreferenceLossConfig] = None,
                  value: Optional[ValueLossConfig] = None, value_head: Optional[ValueHead] = None,
-                 distill: Optional[DistillLossConfig] = None):
+                 distill: Optional[DistillLossConfig] = None, shared_prompt: Optional[int] = None,
+                 branch_len: Optional[int] = None):
         """`lora`: a training.lora.LoraAdapters → stage "lora": the base model is frozen and only the adapters train.
         `refresh_adapted` (with `lora`): the re-pack plan that follows every optimizer step ends with the ONE batched merge
         launch of `lora.refresh_ops()`, so `lora.adapted_weights()` — the weights an inference engine of the model the adapters
@@ -103,7 +105,18 @@ class TrainStep:
         defaults if None) and fed by `set_distill_batch` after `set_batch`. The forward plan ends with bl_distill_loss_f32 in
         place of the cross-entropy op and the backward plan starts with bl_distill_loss_backward_f32; the teacher lives in
         a static fp32 buffer [B·S, count] in row layout, so a captured graph serves every batch. `token_range` as for the
-        policy loss; `distill_stats()` reports the step statistics. `policy`, `preference` and `value` do not go with it."""
+        policy loss; `distill_stats()` reports the step statistics. `policy`, `preference` and `value` do not go with it.
+        `shared_prompt=G` with `branch_len=nb` (loss "ce" or "policy", either ratio level, with or without the rollout
+        correction; every stage, `recompute`, eager and graph replay): the B sequences come in consecutive groups of G that
+        share their prompt — what `rl.policy_batch` emits for G samples per prompt — and the step runs each group as ONE row
+        of the layout of training/shared_prompt.py, prefix ‖ G branches of nb rows: the towers, the projector and every
+        decoder layer see P = B / G images and P·(P0 + G·nb) token rows instead of B and B·S. The decoder's rotary embedding
+        and attention are then bl_rope_pos_bf16 / bl_attention_tree_lse_bf16 and their backwards, and the loss kernels take
+        the branches as their groups (group_rows = nb); every other op is the replicated step's over fewer rows.
+        `set_batch` / `set_batch_frames` take ids / mask / labels [B, l] as ever and pixel values / frames [P, …], one per
+        prompt; everything per token that is passed or read [B, l] (`set_policy_batch`, `token_logprobs()`,
+        `token_weights()`, `action_stats()` [B]) keeps its shape and order. `preference`, `distill`, `value`, `fp8` and
+        world > 1 raise ValueError with it: follow-ups. Without it both plans are what they were."""
         if loss not in ("ce", "policy", "preference", "distill"):
             raise ValueError(f"loss must be 'ce', 'policy', 'preference' or 'distill', got {loss!r}")
         if distill is not None and loss != "distill":
@@ -120,6 +133,21 @@ class TrainStep:
             raise ValueError("`value_head` goes with `value` (a ValueLossConfig)")
         if value is not None and value_head is not None and value_head.dim != weights.dims.llm_dim:
             raise ValueError(f"value_head.dim {value_head.dim} is not the model's llm_dim {weights.dims.llm_dim}")
+        self.shared: Optional[SP.SharedPromptLayout] = None
+        if (shared_prompt is None) != (branch_len is None):
+            raise ValueError("shared_prompt (the group size G) and branch_len (the rows per branch) go together")
+        if shared_prompt is not None:
+            for what, on in (("loss='preference'", loss == "preference"), ("loss='distill'", loss == "distill"),
+                             ("value= (the critic)", value is not None), ("fp8=True", fp8),
+                             ("world > 1 / shard_params", world > 1 or shard_params or (store is not None and store.layout.world > 1))):
+                if on:
+                    raise ValueError(f"shared_prompt does not run with {what} yet: the shared-prompt step covers loss 'ce' and "
+                                     "'policy' on one GPU with bf16 GEMMs")
+            if weights.dims.head_dim != 128:
+                raise ValueError("shared_prompt: the tree attention kernels are built for head_dim 128")
+            self.shared = SP.SharedPromptLayout(int(batch), int(shared_prompt), int(branch_len), int(prompt_len), weights.dims.n_patches)
+            self.B_seq, self.L_seq = batch, prompt_len                      # what the caller passes and reads
+            batch, prompt_len = self.shared.P, self.shared.text_len         # what the plans run over: P rows of the layout
         self.value = value
         self.value_head = (value_head or ValueHead(weights.dims.llm_dim, weights.embed.device)) if value is not None else None
         self.loss_kind = loss
@@ -200,6 +228,15 @@ class TrainStep:
         self.input_ids = z(B, prompt_len, dtype=torch.int64)
         self.key_mask = torch.ones(B, S, dtype=torch.uint8, device=dev)
         self.targets = torch.full((Tn,), IGNORE_INDEX, dtype=torch.int64, device=dev)
+        self._group_rows = S                     # rows per group of the loss kernels: a sequence, or a branch
+        if self.shared is not None:
+            lay = self.shared
+            self._group_rows = lay.nb
+            self.pos_rows = torch.arange(S, dtype=torch.int32, device=dev).repeat(B)      # rotary position of every row
+            per = S // lay.nb                    # groups per prompt row; branch g is group P0 / nb + g of its prompt
+            self._branch_groups = (torch.arange(lay.P, device=dev)[:, None] * per + lay.P0 // lay.nb
+                                   + torch.arange(lay.G, device=dev)[None, :]).reshape(-1)
+            self._token_row = np.full((self.B_seq, 1), -1, dtype=np.int64)
         # ---- frozen vision front end: reuse the inference engine's tower plans (its LLM buffers are not allocated twice:
         #      prompt_len 1, no decode) ----
         from ..engine import OpenVLAEngine
@@ -251,8 +288,8 @@ class TrainStep:
             self.advantages, self.old_logprob, self.ref_logprob = (z(Tn, dtype=torch.float32) for _ in range(3))
             self.row_stats, self.stats = z(Tn, 8, dtype=torch.float32), z(8, dtype=torch.float32)
             self.row_loss, self.mean_cnt = self.row_stats[:, 3], self.stats[:2]
-            if self.policy.ratio_level == "action":      # one group per sequence: its S rows
-                self.group_stats = z(B, 4, dtype=torch.float32)
+            if self.policy.ratio_level == "action":      # one group per sequence: its S rows (shared prompt: per nb rows)
+                self.group_stats = z(Tn // self._group_rows, 4, dtype=torch.float32)
             if self.policy.rollout_is_cap is not None:   # the rollout correction: μ per row in, (λ, w) per row and 8 means out
                 self.behaviour_logprob = z(Tn, dtype=torch.float32)
                 self.is_rows, self.is_stats = z(Tn, 2, dtype=torch.float32), z(8, dtype=torch.float32)
@@ -397,7 +434,7 @@ class TrainStep:
         extra = dict(behaviour_logprob=self.behaviour_logprob, is_rows=self.is_rows, is_stats=self.is_stats) if corrected else {}
         return T.policy_loss(self.logits, self.targets, self.advantages, None if self_proximal else self.old_logprob,
                              self.ref_logprob if self.policy.kl_coef != 0.0 else None, self.row_stats, self.stats,
-                             self.policy, IGNORE_INDEX, run=False, group_rows=self.S,
+                             self.policy, IGNORE_INDEX, run=False, group_rows=self._group_rows,
                              group_stats=getattr(self, "group_stats", None), **extra)
 
     def _layer_forward(self, l: int, with_down: bool = True) -> List[Op]:
@@ -410,10 +447,16 @@ class TrainStep:
         st, so = (S * lq, hd, lq), (S * lo, hd, lo)
         x, xm, qkv = self.x[l], self.xm[l], self.qkv[l]
         plan = [ops.rmsnorm(x, lw.ln1, self.h1[l], d.rms_eps, run=False)] + self.lin.forward(sc, self.h1[l], lw.qkv_w, qkv, EPI_NONE)
-        plan += [T.rope(qkv, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, run=False),
-                 T.attention_lse(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.lse[l], B=B, H=H, Sq=S, Skv=S,
-                                 head_dim=hd, q_strides=st, k_strides=st, v_strides=st, o_strides=so,
-                                 causal=True, key_mask=self.key_mask, run=False)]
+        if self.shared is None:
+            plan += [T.rope(qkv, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, run=False),
+                     T.attention_lse(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.lse[l], B=B, H=H, Sq=S, Skv=S,
+                                     head_dim=hd, q_strides=st, k_strides=st, v_strides=st, o_strides=so,
+                                     causal=True, key_mask=self.key_mask, run=False)]
+        else:                                  # a prompt row: prefix ‖ branches, every row at its own rotary position
+            plan += [T.rope_pos(qkv, self.cos, self.sin, self.pos_rows, rows=B * S, H=H, head_dim=hd, run=False),
+                     T.attention_tree_lse(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.lse[l], B=B, H=H, S=S,
+                                          prefix=self.shared.P0, branch=self.shared.nb, head_dim=hd, q_strides=st, k_strides=st,
+                                          v_strides=st, o_strides=so, key_mask=self.key_mask, run=False)]
         plan += self.lin.forward(sc, self.ao[l], lw.o_w, xm, EPI_RES, res=x)
         plan += [ops.rmsnorm(xm, lw.ln2, self.h2[l], d.rms_eps, run=False)]
         plan += self.lin.forward_act(sc, self.h2[l], lw.gu_w, self.gu[l], self.act[l], "swiglu")
@@ -466,11 +509,19 @@ class TrainStep:
                                                sc.norm_ws, d.rms_eps, dres=dx, run=False))
                 body += self.lin.backward(sc, dx2, self.ao[l], lw.o_w, self.dao)
                 qkv, dq = self.qkv[l], self.dqkv
-                body.append(T.attention_backward(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.dao, self.lse[l], self.delta,
-                                                 dq, dq[:, D:], dq[:, 2 * D:], B=B, H=H, Sq=S, Skv=S, head_dim=hd,
-                                                 q_strides=strides, k_strides=strides, v_strides=strides,
-                                                 o_strides=so, causal=True, key_mask=self.key_mask, run=False))
-                body.append(T.rope_backward(dq, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, run=False))
+                if self.shared is None:
+                    body.append(T.attention_backward(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.dao, self.lse[l], self.delta,
+                                                     dq, dq[:, D:], dq[:, 2 * D:], B=B, H=H, Sq=S, Skv=S, head_dim=hd,
+                                                     q_strides=strides, k_strides=strides, v_strides=strides,
+                                                     o_strides=so, causal=True, key_mask=self.key_mask, run=False))
+                    body.append(T.rope_backward(dq, self.cos, self.sin, B=B, S=S, H=H, head_dim=hd, run=False))
+                else:
+                    body.append(T.attention_tree_backward(qkv, qkv[:, D:], qkv[:, 2 * D:], self.ao[l], self.dao, self.lse[l],
+                                                          self.delta, dq, dq[:, D:], dq[:, 2 * D:], B=B, H=H, S=S,
+                                                          prefix=self.shared.P0, branch=self.shared.nb, head_dim=hd,
+                                                          q_strides=strides, k_strides=strides, v_strides=strides, o_strides=so,
+                                                          key_mask=self.key_mask, run=False))
+                    body.append(T.rope_pos_backward(dq, self.cos, self.sin, self.pos_rows, rows=B * S, H=H, head_dim=hd, run=False))
                 body += self.lin.backward(sc, dq, self.h1[l], lw.qkv_w, self.dh)
             plan += self._seq(lseq, j, True, body)             # sharded: the flush reduce-scatters and frees the gradient slot
             self._ready.append((len(plan), lseq[j]))
@@ -715,6 +766,8 @@ class TrainStep:
         return self._image_processor
 
     def _set_text_batch(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], labels: torch.Tensor) -> None:
+        if self.shared is not None:
+            return self._set_text_batch_shared(input_ids, attention_mask, labels)
         dev, B, L, P, S = self.device, self.B, self.L, self.dims.n_patches, self.S
         b, l = input_ids.shape
         if b != B or l > L:
@@ -745,6 +798,35 @@ class TrainStep:
         if self.distill is not None:            # the teacher belongs to a batch too
             self._teacher_set = False
 
+    def _set_text_batch_shared(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], labels: torch.Tensor) -> None:
+        """`_set_text_batch` of the shared-prompt step: the batch [B, l] is laid out by training/shared_prompt.py::plan_batch
+        (which raises before anything here is written) and the static ids / key mask / targets / positions are filled."""
+        sb = SP.plan_batch(self.shared, input_ids, attention_mask, labels)
+        if self._row_cfg is not None and self._row_cfg.token_range is not None:
+            first, count = self._row_cfg.token_range
+            lab = sb.targets[sb.targets != IGNORE_INDEX]
+            outside = (lab < first) | (lab >= first + count)
+            if bool(outside.any()):
+                raise ValueError(f"labels: {int(outside.sum())} labelled token(s) outside {self.loss_kind}.token_range [{first}, {first + count}): "
+                                 "that action has probability 0 under the restricted policy — draw rollouts with "
+                                 "action_tokens_only=True")
+        if int(sb.pos.max()) >= self.cos.shape[0]:
+            raise ValueError(f"shared_prompt: position {int(sb.pos.max())} exceeds the model's {self.cos.shape[0]} (model_max_length)")
+        dev = self.device
+        self.input_ids.copy_(torch.from_numpy(sb.ids).to(dev))
+        self.key_mask.copy_(torch.from_numpy(sb.key_mask).to(dev))
+        self.targets.copy_(torch.from_numpy(sb.targets).to(dev))
+        self.pos_rows.copy_(torch.from_numpy(sb.pos).to(dev))
+        self._token_row = sb.token_row
+        if self._row_cfg is not None:
+            self._batch_len = input_ids.shape[1]
+
+    def _from_rows(self, rows: torch.Tensor) -> torch.Tensor:
+        """Per-row values [T] of the last forward → [B, l] aligned with the labels of the last `set_batch` (0 off them)."""
+        if self.shared is not None:
+            return SP.rows_to_tokens(self._token_row, rows)
+        return shift_from_rows(rows.view(self.B, self.S), self.dims.n_patches)[:, :self._batch_len]
+
     def set_policy_batch(self, advantages: torch.Tensor, old_logprobs: Optional[torch.Tensor], ref_logprobs: Optional[torch.Tensor] = None,
                          behaviour_logprobs: Optional[torch.Tensor] = None) -> None:
         """Per-token inputs of loss="policy", [B, l] aligned with the `labels` of the preceding `set_batch`: the advantage
@@ -771,7 +853,9 @@ class TrainStep:
         for name, src, dst in (("advantages", advantages, self.advantages), ("old_logprobs", old_logprobs, self.old_logprob),
                                ("ref_logprobs", ref_logprobs, self.ref_logprob),
                                ("behaviour_logprobs", behaviour_logprobs, getattr(self, "behaviour_logprob", None))):
-            if src is not None:
+            if src is not None and self.shared is not None:
+                dst.copy_(SP.tokens_to_rows(self._token_row, src, self.T, name).to(self.device))
+            elif src is not None:
                 tokens_to_rows(name, src, dst, self._batch_len, self.dims.n_patches, valid,
                                "on labelled positions — a token outside the rollout's top-k / top-p support scores -inf; draw "
                                "training rollouts with temperature only")
@@ -891,13 +975,16 @@ class TrainStep:
         as `token_logprobs()` is."""
         if self.policy is None or self.policy.rollout_is_cap is None:
             raise RuntimeError("token_weights needs TrainStep(loss='policy') with policy.rollout_is_cap")
-        return shift_from_rows(self.is_rows[:, 1].view(self.B, self.S), self.dims.n_patches)[:, :self._batch_len]
+        return self._from_rows(self.is_rows[:, 1])
 
     def action_stats(self) -> Dict[str, torch.Tensor]:
         """The per-sequence statistics of the last forward under policy.ratio_level="action" (policy_loss.GROUP_STAT_NAMES)
         as device tensors [B]: the action's log-ratio, its ratio, its number of labelled tokens and its log π."""
-        return self._stats("action_stats", self.policy is not None and self.policy.ratio_level == "action",
-                           "TrainStep(loss='policy') with policy.ratio_level='action'", GROUP_STAT_NAMES, "group_stats")
+        stats = self._stats("action_stats", self.policy is not None and self.policy.ratio_level == "action",
+                            "TrainStep(loss='policy') with policy.ratio_level='action'", GROUP_STAT_NAMES, "group_stats")
+        if self.shared is not None:               # the groups are runs of nb rows: a sequence's is its branch
+            stats = {name: t[self._branch_groups] for name, t in stats.items()}
+        return stats
 
     def preference_stats(self) -> Dict[str, torch.Tensor]:
         """The 8 step statistics of the last forward (preference_loss.PREF_STAT_NAMES) as device scalars."""
@@ -918,7 +1005,7 @@ class TrainStep:
         from the training forward itself."""
         if self._row_cfg is None:
             raise RuntimeError("token_logprobs needs TrainStep(loss='policy'), TrainStep(loss='preference') or TrainStep(loss='distill')")
-        return shift_from_rows(self.row_stats[:, 0].view(self.B, self.S), self.dims.n_patches)[:, :self._batch_len]
+        return self._from_rows(self.row_stats[:, 0])
 
     def _run_forked(self, main_ops: List[Op], side_ops: List[Op]) -> None:
         """main_ops on the current stream, side_ops on the vision side stream, joined at the end (fork / join with stream

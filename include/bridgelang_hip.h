@@ -208,6 +208,27 @@ int bl_attention_lse_bf16(const bl_attn_desc* d, float* lse, void* stream);
  * chunks against 128-row register blocks — same summation order, same bits. All strides multiples of 8. */
 int bl_attention_backward_bf16(const bl_attn_desc* d, const bl_bf16* dout, const float* lse, float* delta, bl_bf16* dq,
                                bl_bf16* dk, bl_bf16* dv, void* stream);
+/* Attention over a shared prompt and its branches (the shared-prompt training step), forward with lse and backward.
+ * d describes one row of the layout  prefix (rows [0, prefix)) | branch 0 (`branch` rows) | ... | branch G-1  per batch element:
+ * Sq == Skv == prefix + G*branch, head_dim 128, causal = 1, key_mask [B, Skv] or NULL. Key j is visible to query i iff
+ * key_mask[j] != 0, j <= i, and (j < prefix, or i >= prefix and (i - prefix) / branch == (j - prefix) / branch). The branches
+ * read the prefix K / V rows in place (no copy per branch); the backward sums every branch's contribution to the prefix rows
+ * of dk / dv in row order inside one wave (no atomics, no workspace; two calls give the same bits). Arithmetic contract, lse
+ * (base 2, +inf for a row with no visible key) and the aliasing rules of dq / dk / dv as bl_attention_lse_bf16 /
+ * bl_attention_backward_bf16. lse and delta (scratch) are fp32 [B*H*pad32(Sq)], 16-byte aligned, indexed
+ * (b*H + h) * pad32(Sq) + i; the pair is the tree kernels' own. Any Sq up to model_max_length. BL_E_ARG for prefix < 1 or
+ * branch < 1; BL_E_SHAPE for (Sq - prefix) % branch != 0, prefix > Sq, Skv != Sq, causal == 0, head_dim != 128 or a stride
+ * that is not a multiple of 8; nothing is launched then. */
+int bl_attention_tree_lse_bf16(const bl_attn_desc* d, int32_t prefix, int32_t branch, float* lse, void* stream);
+int bl_attention_tree_backward_bf16(const bl_attn_desc* d, int32_t prefix, int32_t branch, const bl_bf16* dout, const float* lse,
+                                    float* delta, bl_bf16* dq, bl_bf16* dk, bl_bf16* dv, void* stream);
+/* bl_rope_bf16 / bl_rope_backward_bf16 with a position per row: row r of the fused qkv (dqkv) rows [rows, ld] is rotated at
+ * position pos[r] (device int32 [rows], a static buffer of the caller; a negative entry counts as 0 and every entry must lie
+ * inside the tables). The same expressions, so with pos[r] = pos0 + r % S the same bits as those two. */
+int bl_rope_pos_bf16(bl_bf16* qkv, int64_t ld, int64_t rows, int32_t H, int32_t head_dim, const bl_bf16* cos_tab,
+                     const bl_bf16* sin_tab, const int32_t* pos, void* stream);
+int bl_rope_pos_backward_bf16(bl_bf16* dqkv, int64_t ld, int64_t rows, int32_t H, int32_t head_dim, const bl_bf16* cos_tab,
+                              const bl_bf16* sin_tab, const int32_t* pos, void* stream);
 /* Single-query decode attention over a KV cache; kv_len = number of valid keys (same for the whole batch). */
 int bl_attention_decode_bf16(const bl_attn_desc* d, void* stream);
 /* The attention probabilities themselves (what HF returns as `attentions`), read-only: P = softmax over the visible keys of
