@@ -30,6 +30,13 @@ beams would leave slots without a finite hypothesis at step 0.
 
 `vocab=(first, count)` means what it means everywhere in `sampling.py`: the same on the slice, ids in full-vocabulary
 numbering.
+
+The domain (tests/test_beam_edge_gpu.py holds the kernel to all of it, on fp32 logits that are not bf16-rounded): -inf
+logits are INSIDE the definition as long as every row maximum is finite — the candidate weighs 0 and scores -inf; +inf and
+NaN logits are outside. Scores are any fp32 <= 0 down to -1e30, and -inf for a dead beam; a prompt whose beams are ALL
+dead has only -inf candidates and its survivors are the first W flat indices. total_j runs from 2^30 (a peaked row:
+lz_j = log_spec(1) = 0) to 36 480 · 2^30 > 2^45 (an all-equal row of the widest width the kernel takes), so fp32(total_j)
+rounds a 46-bit integer.
 """
 from __future__ import annotations
 

@@ -43,6 +43,19 @@ the result is what the function returns on that slice — maximum, top-k, top-p,
 taken over the slice — with token ids reported in full-vocabulary numbering. Every token outside the range has
 probability 0 and is never read: it scores (0, total_kept), like a token that top-k removed. An OpenVLA action is one of
 256 bins carried by token ids vocab_size - 256 … vocab_size - 1, so the action policy is `vocab=(31744, 256)`.
+
+The domain (tests/test_sample_edge_gpu.py holds the kernels to all of it, on fp32 logits that are not bf16-rounded):
+  logits   -inf is INSIDE the definition as long as the row maximum is finite: z = -inf, the clamp at -87 gives the weight
+           rint(e^-87 · 2^30) = 0, so a masked token is never drawn and scores (0, total_kept). +inf and NaN are OUTSIDE
+           for T > 0 (l - max would be NaN); a greedy row is defined on both, see above.
+  T        0 (greedy), or any finite fp32 > 0: from 2^-100 (z overflows to -inf: only the maxima weigh) to 1e30 (z -> 0:
+           every finite logit weighs 2^30). (l - max) / T is the IEEE fp32 QUOTIENT, not l - max times a rounded 1 / T.
+  top_k    0 and every k >= n: off. 1 … n - 1: every tie at the k-th value stays; -0 and +0 are one value.
+  top_p    any fp32 in (0, 1) through rint(top_p · 2^24): 1e-6 keeps the first-ranked token alone, 1 - 2^-24 (p24 =
+           2^24 - 1) drops at most the lightest tail; zero weights are never kept or counted. >= 1: off.
+  n        the kernels take multiples of 4 from 4 to 36 480; an all-maximum row of that width sums to 36 480 · 2^30 > 2^45,
+           which the 70-bit top-p comparison and the uint64 running sums hold.
+  step     0 … 2^31 - 1 (the Philox counter's first word).
 """
 from __future__ import annotations
 

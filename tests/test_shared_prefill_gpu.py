@@ -40,14 +40,31 @@ def rope(dev):
 PREFIX_GEN = [(pl, g) for pl in (1, 63, 64, 65, 267, 314) for g in (0, 1, 5)] + [(315, 5), (320, 0), (316, 5), (321, 0), (300, 21)]
 
 
+# Long caches: pos = 2047 is the last position of the rope table, where 8 rows per workgroup hold 8 x 2048 scores + 8 x 4 x 128
+# partial sums = 80 KiB of LDS (the limit the launcher raises to 96 KiB); the others put 100 … 200 generated rows into
+# three or four 64-key groups, behind a streamed (1500) and a resident (1, 63) prefix
+LONG_PREFIX_GEN = [(2000, 47), (1500, 100), (1, 200), (63, 130)]
+
+
 @pytest.mark.parametrize("P,G", [(1, 1), (1, 16), (3, 5), (2, 3), (16, 1)])
 def test_kernel_equals_the_existing_kernel_on_replicated_caches(dev, rope, P, G):
+    assert {pl + g for pl, g in PREFIX_GEN} >= {320, 321}
+    _kernel_against_replicated_caches(dev, rope, P, G, PREFIX_GEN)
+
+
+@pytest.mark.parametrize("P,G", [(1, 8), (2, 3)])
+def test_kernel_equals_the_existing_kernel_on_long_caches(dev, rope, P, G):
+    assert max(pl + g for pl, g in LONG_PREFIX_GEN) == 2047 == rope[0].shape[0] - 1
+    assert (8 * 2048 + 8 * 4 * 128) * 4 > 64 * 1024 and all(g > 64 for pl, g in LONG_PREFIX_GEN[1:])
+    _kernel_against_replicated_caches(dev, rope, P, G, LONG_PREFIX_GEN)
+
+
+def _kernel_against_replicated_caches(dev, rope, P, G, prefix_gen):
     from bridgelang_amd import ops
     cos, sin = rope
     R = P * G
     gen = torch.Generator(device=dev).manual_seed(1000 * P + G)
-    assert {pl + g for pl, g in PREFIX_GEN} >= {320, 321}
-    for prefix_len, n_gen in PREFIX_GEN:
+    for prefix_len, n_gen in prefix_gen:
         pos = prefix_len + n_gen
         cache_len, gen_len, ref_len = (prefix_len + 63) // 64 * 64, n_gen + 2, (pos + 1 + 63) // 64 * 64
         qkv = _rand((R, 3 * D), gen, dev)
