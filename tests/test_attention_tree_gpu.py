@@ -8,9 +8,15 @@ dk / dv those of fused dqkv rows, as the training step lays them out; every buff
 must still hold their sentinel afterwards.
 
 Shapes: B = 2, H = 2, hd = 128 over prefix ∈ {1, 31, 33, 288} × branch ∈ {1, 7, 8} × G ∈ {1, 2, 8, 16} (totals from 2 to 416
-rows: both sides of 320, 64-row and 128-row block edges, 16-row tiles that hold two or sixteen branches), each with a key mask
-that hides the tail of the prefix of batch element 1, flat and peaked scores; one case with the last rows of every branch
-masked (short branches). With G = 1 the mask is plain causal and the results are held to the same bound.
+rows: 64-row query tiles and 128-row blocks that end inside a branch, 16-row tiles that hold two or sixteen branches), each
+with a key mask that hides the tail of the prefix of batch element 1, flat and peaked scores; one case with the last rows of
+every branch masked (short branches). With G = 1 the mask is plain causal and the results are held to the same bound.
+
+What this grid does not reach (tests/tree_paths.py is the host model of the kernels' tile schedule that counts it, and
+tests/test_tree_paths_cpu.py pins the counts): no 256-key chunk is ever skipped by a dq workgroup, the forward skips one chunk
+in one tile of one case, no dkv workgroup walks more than two 256-row chunks or starts past row 256, no branch is longer than
+8 rows, and no chunk or step is fully masked. tests/test_attention_tree_long_gpu.py runs those paths — past 512 rows, branches
+up to 300 rows, masks that hide whole chunks — with the helpers of this file and the same bounds.
 """
 import numpy as np
 import pytest
@@ -109,8 +115,10 @@ def _guards_intact(buf, what):
     assert bool((c[:GR] == SENT).all()) and bool((c[-GR:] == SENT).all()), f"{what}: guard rows were written"
 
 
-def run_tree(dev, q, k, v, mask, prefix, branch, do=None):
-    """The kernels over fused qkv rows with guard rows; CPU float [B, H, S, hd] results and lse / delta [B, H, S]."""
+def run_tree(dev, q, k, v, mask, prefix, branch, do=None, stat_fill=None):
+    """The kernels over fused qkv rows with guard rows; CPU float [B, H, S, hd] results and lse / delta [B, H, S]. `stat_fill`
+    (default: the sentinel) is what lse / delta hold before the call, their pad rows [S, pad32(S)) included; those come back
+    as lse_pad / delta_pad."""
     from bridgelang_amd import train_ops as T
     S, D = q.shape[2], H * HD
     qkv = _guarded(torch.cat([_rows(q), _rows(k), _rows(v)], dim=1), dev)
@@ -119,6 +127,8 @@ def run_tree(dev, q, k, v, mask, prefix, branch, do=None):
     pad = (S + 31) // 32 * 32
     PADG = 16        # guard floats round lse / delta (multiples of 4 keep the 16-byte alignment)
     lse = torch.full((B * H * pad + 2 * PADG,), float(SENT), device=dev)
+    if stat_fill is not None:
+        lse[PADG:PADG + B * H * pad] = stat_fill
     st, so = (S * 3 * D, HD, 3 * D), (S * D, HD, D)
     kw = dict(B=B, H=H, S=S, prefix=prefix, branch=branch, head_dim=HD, q_strides=st, k_strides=st, v_strides=st, o_strides=so,
               key_mask=None if mask is None else mask.to(dev))
@@ -129,13 +139,15 @@ def run_tree(dev, q, k, v, mask, prefix, branch, do=None):
     _guards_intact(o, "forward o")
     assert bool((lse[:PADG] == SENT).all()) and bool((lse[-PADG:] == SENT).all()), "forward: lse guards were written"
     out = dict(o=_heads(ob.cpu(), S), lse=lv.cpu().view(B, H, pad)[:, :, :S].clone(), o_bits=ob.cpu().view(torch.int16).clone(),
-               lse_bits=lv.cpu().view(torch.int32).view(B, H, pad)[:, :, :S].clone())
+               lse_bits=lv.cpu().view(torch.int32).view(B, H, pad)[:, :, :S].clone(), lse_pad=lv.cpu().view(B, H, pad)[:, :, S:].clone())
     if do is not None:
         g = _guarded(_rows(do), dev)
         dqkv = _guarded(torch.zeros(B * S, 3 * D), dev)
         db = dqkv[GR:GR + B * S]
         delta = torch.full((B * H * pad + 2 * PADG,), float(SENT), device=dev)
         dl = delta[PADG:PADG + B * H * pad]
+        if stat_fill is not None:
+            dl.fill_(stat_fill)
         T.attention_tree_backward(body[:, :D], body[:, D:2 * D], body[:, 2 * D:], ob, g[GR:GR + B * S], lv, dl,
                                   db[:, :D], db[:, D:2 * D], db[:, 2 * D:], **kw)
         torch.cuda.synchronize()
@@ -144,19 +156,27 @@ def run_tree(dev, q, k, v, mask, prefix, branch, do=None):
         assert bool((delta[:PADG] == SENT).all()) and bool((delta[-PADG:] == SENT).all()), "backward: delta guards were written"
         c = db.cpu()
         out.update(dq=_heads(c[:, :D].contiguous(), S), dk=_heads(c[:, D:2 * D].contiguous(), S), dv=_heads(c[:, 2 * D:].contiguous(), S),
-                   delta=dl.cpu().view(B, H, pad)[:, :, :S].clone(), d_bits=c.view(torch.int16).clone())
+                   delta=dl.cpu().view(B, H, pad)[:, :, :S].clone(), d_bits=c.view(torch.int16).clone(),
+                   delta_pad=dl.cpu().view(B, H, pad)[:, :, S:].clone())
     return out
 
 
-def check_case(dev, prefix, branch, G, mask, seed, peaked, what):
-    S, scale = prefix + G * branch, HD ** -0.5
+def case_inputs(prefix, branch, G, mask, seed, peaked):
+    """q, k, v (bf16-representable fp32 [B, H, S, hd]) and the per-batch visibility of one case, from its seed alone."""
+    S = prefix + G * branch
     q, k, v = (rand_bf16((B, H, S, HD), seed + i) for i in range(3))
     vis = _vis(prefix, branch, S, mask)
     if peaked:
         q = _peaked(q, k, vis)
+    return q, k, v, vis
+
+
+def check_case(dev, prefix, branch, G, mask, seed, peaked, what, stat_fill=None):
+    S, scale = prefix + G * branch, HD ** -0.5
+    q, k, v, vis = case_inputs(prefix, branch, G, mask, seed, peaked)
     rows = torch.ones(B, S, dtype=torch.bool) if mask is None else mask.bool()      # masked (padding) query rows are not specified
     do = rand_bf16((B, H, S, HD), seed + 4) * rows.view(B, 1, S, 1)
-    got = run_tree(dev, q, k, v, mask, prefix, branch, do)
+    got = run_tree(dev, q, k, v, mask, prefix, branch, do, stat_fill=stat_fill)
     ref = ref_forward(q, k, v, scale, vis)
     assert_attn_close(got["o"], ref["o"], ref["m_o"], C_O, f"tree fwd O {what}", rows)
     assert_lse_close(got["lse"], ref["lse2"], ref["mag_s"], f"tree fwd lse {what}", rows)
